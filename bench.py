@@ -1,6 +1,6 @@
 """Headline benchmark: ray-samples/s of the per-field NeRF train step on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json metric, SURVEY 8d "M1"): synthetic 4096-ray x 128-sample batch per GPU --
 F = 8 fields x R = 512 rays, S = 64 coarse + 64 depth-guided samples, Fourier(64, raw) + 2x64 MLP,
@@ -10,7 +10,10 @@ w.r.t. every field parameter, sparse per-field Adam.  Jitter is drawn in-kernel 
 resident in HBM before the timed region.  Weak scaling: every rank owns its own 8 fields (field-per-
 GPU sharding); the only collective is the 64-byte loss-sum all-reduce (RCCL over xGMI).
 
-Extra objects on the JSON line:
+A plain run sets up, runs W warm-up steps (after SPIN_UP untimed ones), times exactly K steps and prints the JSON
+line (`value`, `ms_per_step` = the K steps' time / K).  --dump-outputs DIR writes what the last timed step computed.
+--full adds, after and outside the timed steps, everything else the line can carry, e.g.:
+  ms_per_step_windows -- the headline as the median of 11+ windows of K steps (at least 6 s of timed work)
   roofline     -- dominant kernel (MFMA backward) : algorithmic flops / HIP-event time on the launch stream
   cpu_baseline -- the CPU oracle (oracle/ngm_oracle.py, a restatement pinned to the reference) timed on
                   this box's host cores on a bounded sample of the same workload (rank 0, N = 1 only)
@@ -240,6 +243,35 @@ def emit_line(d):
     except Exception:
         pass
     print(json.dumps(d), flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_outputs(out, r):
+    """What a caller of the timed iteration holds after its last step: the loss terms and the prediction it returns, and
+    the field parameters its sparse Adam step updated in place; host copies keyed by file-safe names."""
+    import re
+    arrays = {"loss_" + k: v for k, v in out.items() if isinstance(v, torch.Tensor)}
+    arrays.update({"prediction_" + k: v for k, v in out["prediction"]._asdict().items() if v is not None})
+    arrays.update({"param_" + k: v for k, v in r._model.all_fields_params.items()})
+    return {re.sub(r"[^0-9A-Za-z_]+", "_", k): v.detach().cpu() for k, v in arrays.items()}
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as path/<name>.npy (float64 stays float64, everything else float32).  Above
+    DUMP_LIMIT_BYTES in all, every array is cut to the same fraction of its elements, a fixed seeded sample in flat order."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.double() if v.dtype == torch.float64 else v.float() for k, v in arrays.items()}
+    total = sum(v.numel() * v.element_size() for v in arrays.values())
+    budget = DUMP_LIMIT_BYTES - 256 * len(arrays)            # room for the .npy headers
+    for k, v in arrays.items():
+        if total > budget:
+            keep = int(v.numel() * budget / total)
+            idx = torch.randperm(v.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(path, k + ".npy"), v.numpy())
 
 
 def shader_clock_under_load(step, n=1500, read=True):
@@ -544,13 +576,21 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--windows", type=int, default=11,
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: 11 timed windows and at least 6 s of timed work (median headline), "
+                         "the shader clock under load, per-kernel times and rooflines, the other matmul arithmetic, the aux_* "
+                         "workloads and the CPU baseline.  Without it the run times exactly --steps steps once")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (loss terms, prediction, updated field "
+                         "parameters; rank 0) as DIR/<name>.npy in float32 / float64, at most 64 MB in all")
+    ap.add_argument("--windows", type=int, default=None,
                     help="number of consecutive timed windows of --steps steps each (after ONE --warmup phase); the line's "
-                         "ms_per_step / value are the median window, all windows are listed in ms_per_step_windows")
-    ap.add_argument("--min-seconds", type=float, default=6.0,
+                         "ms_per_step / value are the median window, all windows are listed in ms_per_step_windows "
+                         "(default 1, with --full 11)")
+    ap.add_argument("--min-seconds", type=float, default=None,
                     help="keep adding timed windows of --steps steps (same protocol, median headline) until this much timed GPU "
                          "work has run, so that an external sampler (rocm-smi, the driver's gpu_busy) sees the load: 11 windows of "
-                         "20 steps are 55 ms.  0: exactly --windows windows")
+                         "20 steps are 55 ms.  0: exactly --windows windows (default 0, with --full 6)")
     ap.add_argument("--no-aux-default", action="store_true",
                     help="skip `aux_default` and `aux_render_image`: the reference's default iteration (32 fields x 512 rays x (8 + 16) samples, "
                          "hash 16 x 2 + 1 x 32 network: config/neural_graph_map.yaml)")
@@ -580,6 +620,10 @@ def main():
                     help="auxiliary strong-scaling measurement of a realistic mapping iteration (200 fields, 32 active per "
                          "iteration, sharded id %% world) instead of the headline line; see scene_sim()")
     args = ap.parse_args()
+    if args.windows is None:
+        args.windows = 11 if args.full else 1
+    if args.min_seconds is None:
+        args.min_seconds = 6.0 if args.full else 0.0
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: start the N ranks ourselves (one process per GPU, torchrun rendezvous on
@@ -651,13 +695,14 @@ def main():
 
     def window():
         """EXACTLY K steps between barrier + synchronize on both sides; max over ranks"""
+        nonlocal out
         torch.cuda.synchronize()
         if world > 1:
             torch.distributed.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for i in range(args.steps):
-            step(i)
+            out = step(i)
         torch.cuda.synchronize()
         if world > 1:
             torch.distributed.barrier()
@@ -669,9 +714,9 @@ def main():
             d = float(tt.item())
         return d
 
-    # measurement protocol: the contract's timed region (W warm-up steps, then exactly K steps) repeated as `--windows`
-    # consecutive windows; the headline is the MEDIAN window (one 20-step window is 5 ms: +-8 % between boxes and runs).
-    # --min-seconds keeps adding windows until that much timed work has run (lets an external sampler see the load).
+    # measurement protocol: the contract's timed region (W warm-up steps, then exactly K steps); --full repeats it as
+    # `--windows` consecutive windows and the headline is the MEDIAN window (one 20-step window is 5 ms: +-8 % between boxes
+    # and runs).  --min-seconds keeps adding windows until that much timed work has run (lets an external sampler see the load).
     wins = [window() for _ in range(max(1, args.windows))]
     while args.min_seconds > 0 and sum(wins) < args.min_seconds:
         wins.append(window())
@@ -682,8 +727,68 @@ def main():
             wins.append(window())
         wins = wins[:int(nw.item())]
     dt = sorted(wins)[len(wins) // 2] if len(wins) % 2 else 0.5 * (sorted(wins)[len(wins) // 2 - 1] + sorted(wins)[len(wins) // 2])
-    sclk = shader_clock_under_load(step, read=(rank == 0))
     loss = float(out["combined"])
+    if args.dump_outputs and rank == 0:       # before anything else runs: a replayed graph overwrites `out` in place
+        dump_outputs(args.dump_outputs, step_outputs(out, r))
+    # the arithmetic the library resolved `auto` to for THIS batch shape (not the host-side expectation), and the backward
+    # kernel of the measured path (read before the side measurement below runs the other one)
+    resolved = r.last_matmul("forward") or r.mlp_matmul
+    bwd_variant = L.ngm_debug_last_bwd_variant()
+    if args.variant == "hash" and bwd_variant == 5:
+        resolved_note = "hidden layer: fp32 MFMA in the fused forward, three-way bf16 split in the backward (k_hash_mlp_bwd)"
+    else:
+        resolved_note = None
+    res = None
+    if rank == 0:
+        n_local = F_PER_GPU * R * (S_C + S_G)
+        value = world * n_local * args.steps / dt
+        res = dict(metric="ray-samples/sec (train step: fwd+loss+bwd+Adam, 4096 rays x 128 samples per GPU)",
+                   value=value, unit="ray-samples/s", n_gpus=ranks_seen, steps=args.steps, warmup=args.warmup,
+                   ms_per_step=1e3 * dt / args.steps, higher_is_better=True, scaling="strong" if strong else "weak",
+                   vs_baseline=None, dtype=DTYPE_LABEL[resolved], data="synthetic")
+        if len(wins) > 1:
+            res["ms_per_step_windows"] = dict(n=len(wins), steps_each=args.steps, median=1e3 * dt / args.steps,
+                                              min=1e3 * min(wins) / args.steps, max=1e3 * max(wins) / args.steps,
+                                              first=1e3 * wins[0] / args.steps, timed_seconds=round(sum(wins), 4),
+                                              all=[round(1e3 * w / args.steps, 5) for w in wins[:64]],
+                                              all_note="the first 64 windows" if len(wins) > 64 else "every window",
+                                              headline="median window")
+        if resolved_note:
+            res["dtype"] = DTYPE_LABEL["f32"] + "; " + resolved_note
+    devs = [dev_index]
+    if world > 1:                                    # which GPU every rank really ran on (rank -> GPU binding evidence)
+        dv = torch.zeros(world, device=dev, dtype=torch.int64)
+        dv[rank] = dev_index
+        torch.distributed.all_reduce(dv)
+        devs = dv.tolist()
+    if rank == 0:
+        res["config"] = dict(workload=f"M1: {F_PER_GPU} fields x 512 rays x (64 coarse + 64 depth-guided) samples per GPU, "
+                                      + ("Fourier(64,raw)+2x64 MLP" if args.variant == "fourier" else
+                                         "permutohedral hash (16 levels x 2, 2^12 entries)+1x32 MLP [auxiliary variant]")
+                                      + ", nrgbd compositing, NRGBD intrinsics",
+                             fields_per_gpu=F_PER_GPU, rays_per_field=R, samples_per_ray=S_C + S_G,
+                             sharding=f"field-per-GPU x{world}", ranks_seen=ranks_seen, spin_up_steps=SPIN_UP,
+                             devices=sorted(set(devs)), jitter="in-kernel Philox",
+                             launch=("eager" if (not use_graph or getattr(replay, "graph", None) is None) else
+                                     "hipGraph replay" if r.process_group is None else
+                                     "1 hipGraph incl. the peer loss exchange" if r.peer_exchange is not None else
+                                     "2 hipGraphs + all-reduce"), final_loss=loss)
+    if args.full:
+        full_measurements(args, res, r, tgt, pos, quat, step, dt, rank, world, dev, strong, F_PER_GPU, use_graph, resolved,
+                          bwd_variant)
+    if rank == 0:
+        emit_line(res)
+    if torch.distributed.is_initialized():
+        torch.distributed.destroy_process_group()
+
+
+def full_measurements(args, res, r, tgt, pos, quat, step, dt, rank, world, dev, strong, F_PER_GPU, use_graph, resolved,
+                      bwd_variant):
+    """--full: everything the line carries beyond the headline, measured after and outside the timed region; fills `res`
+    (rank 0).  Every rank runs the same GPU work here (with a process group each iteration holds a collective)."""
+    from neural_graph_mapping_amd import _capi as K
+    L = K.lib()
+    sclk = shader_clock_under_load(step, read=(rank == 0))
 
     # per-kernel device time: HIP events recorded on the launch stream around every kernel launch
     # (C-ABI hooks).  Under hipGraph replay host-side event records are not part of the graph, so the
@@ -695,9 +800,6 @@ def main():
     torch.cuda.synchronize()
     kern = {}
     L.ngm_profile_enable(0)
-    bwd_variant = L.ngm_debug_last_bwd_variant()     # of the measured path (read before the side measurement below runs the other one)
-    # the arithmetic the library resolved `auto` to for THIS batch shape (not the host-side expectation)
-    resolved = r.last_matmul("forward") or r.mlp_matmul
     for name, kid in K.KERNEL_IDS.items():
         ms, n = C.c_double(0), C.c_int64(0)
         L.ngm_profile_read(kid, C.byref(ms), C.byref(n))
@@ -725,16 +827,6 @@ def main():
                     note=f"python bench.py --matmul {other} makes this the measured path")
         del r3, rep3
 
-    devs = [dev_index]
-    if world > 1:                                    # which GPU every rank really ran on (rank -> GPU binding evidence)
-        dv = torch.zeros(world, device=dev, dtype=torch.int64)
-        dv[rank] = dev_index
-        torch.distributed.all_reduce(dv)
-        devs = dv.tolist()
-    if args.variant == "hash" and bwd_variant == 5:
-        resolved_note = "hidden layer: fp32 MFMA in the fused forward, three-way bf16 split in the backward (k_hash_mlp_bwd)"
-    else:
-        resolved_note = None
     # auxiliary: the reference's DEFAULT network (hash 16x2 + 1x32 MLP) on the same batch, in the same run
     aux_hash = None
     if world == 1 and args.variant == "fourier" and not strong and not args.no_aux_hash:
@@ -756,29 +848,7 @@ def main():
         aux_m2 = dict(fourier=aux_m2_line(dev, "fourier", args.matmul), hash=aux_m2_line(dev, "hash", args.matmul))
     if rank == 0:
         n_local = F_PER_GPU * R * (S_C + S_G)
-        value = world * n_local * args.steps / dt
-        res = dict(metric="ray-samples/sec (train step: fwd+loss+bwd+Adam, 4096 rays x 128 samples per GPU)",
-                   value=value, unit="ray-samples/s", n_gpus=ranks_seen, steps=args.steps, warmup=args.warmup,
-                   ms_per_step=1e3 * dt / args.steps,
-                   ms_per_step_windows=dict(n=len(wins), steps_each=args.steps, median=1e3 * dt / args.steps,
-                                            min=1e3 * min(wins) / args.steps, max=1e3 * max(wins) / args.steps,
-                                            first=1e3 * wins[0] / args.steps, timed_seconds=round(sum(wins), 4),
-                                            all=[round(1e3 * w / args.steps, 5) for w in wins[:64]],
-                                            all_note="the first 64 windows" if len(wins) > 64 else "every window",
-                                            headline="median window"),
-                   sclk_mhz=sclk, higher_is_better=True, scaling="strong" if strong else "weak", vs_baseline=None,
-                   dtype=DTYPE_LABEL[resolved], data="synthetic",
-                   config=dict(workload=f"M1: {F_PER_GPU} fields x 512 rays x (64 coarse + 64 depth-guided) samples per GPU, "
-                                        + ("Fourier(64,raw)+2x64 MLP" if args.variant == "fourier" else
-                                           "permutohedral hash (16 levels x 2, 2^12 entries)+1x32 MLP [auxiliary variant]")
-                                        + ", nrgbd compositing, NRGBD intrinsics",
-                               fields_per_gpu=F_PER_GPU, rays_per_field=R, samples_per_ray=S_C + S_G,
-                               sharding=f"field-per-GPU x{world}", ranks_seen=ranks_seen, spin_up_steps=SPIN_UP,
-                               devices=sorted(set(devs)), jitter="in-kernel Philox",
-                               launch=("eager" if (not use_graph or getattr(replay, "graph", None) is None) else
-                                       "hipGraph replay" if r.process_group is None else
-                                       "1 hipGraph incl. the peer loss exchange" if r.peer_exchange is not None else
-                                       "2 hipGraphs + all-reduce"), final_loss=loss))
+        res["sclk_mhz"] = sclk
         fb, ff = kern.get("field_bwd"), kern.get("render_fwd")
         if fb and args.variant == "fourier":
             achieved = FLOP_BWD * n_local / (fb["avg_us"] * 1e-6) / 1e12
@@ -825,8 +895,6 @@ def main():
                                         "algorithmic MLP flops fwd 16 896 + bwd 33 792 per sample")
         if args.variant == "hash":
             res.update(hash_rooflines(kern, n_local))
-            if resolved_note:
-                res["dtype"] = DTYPE_LABEL["f32"] + "; " + resolved_note
         res["kernels_us"] = {k: round(v["avg_us"], 2) for k, v in kern.items()}
         if side:
             res["matmul_alternative"] = side
@@ -840,9 +908,6 @@ def main():
             res["aux_m2"] = aux_m2
         if world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline()
-        emit_line(res)
-    if torch.distributed.is_initialized():
-        torch.distributed.destroy_process_group()
 
 
 if __name__ == "__main__":

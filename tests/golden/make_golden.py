@@ -931,11 +931,40 @@ def g24_render_ijs_knn():
     save("g24_render_ijs_knn", **out, **arrays)
 
 
+def g25_oracle_fresh_seed():
+    """The reference's render + loss + gradients on a seed no other fixture uses (2 fields x 19 rays, 5 + 7 samples,
+    termination weight 0.3, perturbed parameters): what tests/test_oracle_vs_reference.py holds the oracle to."""
+    F, R, n_c, n_g, seed = 2, 19, 5, 7, 4242
+    cam = camera.Camera(**NRGBD_CAMERA)
+    gen = torch.Generator().manual_seed(seed)
+    pos = 0.5 * torch.randn(F, 3, generator=gen)
+    quat = rand_quats(F, gen)
+    cfg = make_config(num_samples_coarse=n_c, num_samples_depth_guided=n_g, termination_weight=0.3)
+    ngm = build_map(rm, cfg, F, pos, quat, seed=seed)
+    ngm._camera = cam
+    with torch.no_grad():
+        for k, v in ngm._model.all_fields_params.items():
+            if v.dim() > 1:
+                v.add_(0.05 * torch.randn(v.shape, generator=gen))
+    t = synth_target(F, R, cam, pos, gen)
+    fids = torch.arange(F)
+    torch.manual_seed(seed + 1)
+    pred = ngm._render_ijs(t["ijs"], t["c2ws"], cam, field_ids=fids, use_vmap=True, near_distances=t["near"],
+                           far_distances=t["far"], gt_distances=t["gt"])
+    u_c, u_g = draw_u(seed + 1, F, R, n_c, n_g)
+    loss = ngm._compute_losses(make_target(t, fids), pred)
+    loss["combined"].backward()
+    vp = {k: v for k, v in ngm._model.vmap_fields_params.items() if k != "_neus_sd"}
+    save("g25_oracle_fresh_seed", pos=pos, quat=quat, u_coarse=u_c, u_guided=u_g, rgbds=pred.rgbds, combined=loss["combined"],
+         **{"t::" + k: t[k] for k in ("ijs", "c2ws", "near", "far", "gt", "rgbds", "depth_mask", "term_mask", "term_probs")},
+         **{"p::" + k: v for k, v in vp.items()}, **{"grad::" + k: v.grad for k, v in vp.items()})
+
+
 if __name__ == "__main__":
     import sys
     cases = [g1_directions, g2_g3_sampling, g4_field_forward, g5_quadrature, g6_train, g7_adam, g8_knn, g9_render_image,
              g10_behind_camera, g11_target_sampler, g12_skip_modes, g13_training_run, g15_triplane, g16_target_sampler_sv, g17_extract_mesh, g18_train_l2, g19_skip_other_encodings, g20_train_nll,
-             g21_field_radius_override, g22_fields_2d, g23_weighted_bins, g24_render_ijs_knn]
+             g21_field_radius_override, g22_fields_2d, g23_weighted_bins, g24_render_ijs_knn, g25_oracle_fresh_seed]
     only = set(sys.argv[1:])            # e.g. `python make_golden.py g10_behind_camera` regenerates one group
     for fn in cases:
         if not only or fn.__name__ in only:

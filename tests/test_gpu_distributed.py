@@ -391,7 +391,7 @@ def test_bench_line_with_two_ranks_runs_to_the_end():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, NGM_BENCH_SHARE_GPU="1", NGM_DIST_BACKEND="gloo")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--windows", "2",
-                        "--min-seconds", "0", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=600, cwd=root)
+                        "--min-seconds", "0", "--no-cpu-baseline", "--full"], capture_output=True, text=True, env=env, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().split("\n")[-1])
     assert line["n_gpus"] == 2 and line["config"]["ranks_seen"] == 2 and line["steps"] == 3 and line["value"] > 0

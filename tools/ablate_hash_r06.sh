@@ -10,13 +10,13 @@
 # run:  gpurun -- 'bash tools/ablate_hash_r06.sh > gpurun_out/hash_ablation.txt 2>&1'
 cd $GRAFT_REPO_ROOT
 line() {   # $1 = library name, $2 = atomics mode
-  NGM_LIB_PATH=$PWD/neural_graph_mapping_amd/lib/libngm_$1.so timeout 600 python bench.py --no-cpu-baseline --min-seconds 0.4 --no-aux-hash --hash-atomics $2 2>/dev/null | python -c "
+  NGM_LIB_PATH=$PWD/neural_graph_mapping_amd/lib/libngm_$1.so timeout 600 python bench.py --full --no-cpu-baseline --min-seconds 0.4 --no-aux-hash --hash-atomics $2 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().split('\n')[-1])
 a=d.get('aux_default') or {}
 print('  aux_default', round(a.get('ms_per_step',0),4), a.get('kernels_us'))
 "
-  NGM_LIB_PATH=$PWD/neural_graph_mapping_amd/lib/libngm_$1.so timeout 600 python bench.py --variant hash --no-cpu-baseline --min-seconds 0.4 --hash-atomics $2 2>/dev/null | python -c "
+  NGM_LIB_PATH=$PWD/neural_graph_mapping_amd/lib/libngm_$1.so timeout 600 python bench.py --full --variant hash --no-cpu-baseline --min-seconds 0.4 --hash-atomics $2 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().split('\n')[-1])
 print('  M1-hash    ', round(d['ms_per_step'],4), d.get('kernels_us'), 'sclk', d.get('sclk_mhz'))

@@ -12,7 +12,7 @@ cd $GRAFT_REPO_ROOT
 for rep in 1 2; do
 for n in hip hcells nosimplex; do
   echo "== $n $rep"
-  NGM_LIB_PATH=$PWD/neural_graph_mapping_amd/lib/libngm_$n.so timeout 300 python bench.py --variant hash --no-cpu-baseline --min-seconds 0.5 2>/dev/null | python -c "
+  NGM_LIB_PATH=$PWD/neural_graph_mapping_amd/lib/libngm_$n.so timeout 300 python bench.py --full --variant hash --no-cpu-baseline --min-seconds 0.5 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().split('\n')[-1])
 print('M1-hash', round(d['ms_per_step'],4), d.get('kernels_us'))

@@ -5,8 +5,8 @@
 set -u
 O=$GRAFT_REPO_ROOT/gpurun_out/final; mkdir -p $O
 cd $GRAFT_REPO_ROOT
-python bench.py > $O/bench_line.json 2> $O/bench.err; tail -c 600 $O/bench_line.json
-( cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- python $GRAFT_REPO_ROOT/bench.py --steps 100 --warmup 10 --no-cpu-baseline > $O/bench_prof.log 2>&1 )
+python bench.py --full > $O/bench_line.json 2> $O/bench.err; tail -c 600 $O/bench_line.json
+( root=$PWD; cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- python "$root/bench.py" --full --steps 100 --warmup 10 --no-cpu-baseline > $O/bench_prof.log 2>&1 )
 NGM_MATMUL=auto NGM_CHECK=time bash tools/pmc_pass.sh fetch FETCH_SIZE
 NGM_MATMUL=auto NGM_CHECK=time bash tools/pmc_pass.sh write WRITE_SIZE
 python tools/pmc_traffic.py $(find gpurun_out/pmc_fetch -name "*counter_collection.csv" | head -1) $(find gpurun_out/pmc_write -name "*counter_collection.csv" | head -1) > $O/pmc_field_bwd.json
@@ -24,8 +24,8 @@ python tools/pmc_summary.py $(find gpurun_out/pmc_h1 gpurun_out/pmc_h2 gpurun_ou
 # HBM bytes + L2 hit rate of the hash variant's kernels (M1 batch) -> what bench.py puts into the hash rooflines' `traffic`
 bash tools/profile_hash.sh > $O/pmc_hash.log 2>&1; cp gpurun_out/pmc_hash.json $O/pmc_hash.json
 python tools/stage_bench.py --out $O/stage_bench.json > /dev/null 2>> $O/bench.err
-python bench.py --variant hash --no-cpu-baseline > $O/bench_line_hash.json 2>> $O/bench.err
-python bench.py --matmul f32 --no-cpu-baseline --no-aux-hash > $O/bench_line_f32.json 2>> $O/bench.err
+python bench.py --full --variant hash --no-cpu-baseline > $O/bench_line_hash.json 2>> $O/bench.err
+python bench.py --full --matmul f32 --no-cpu-baseline --no-aux-hash > $O/bench_line_f32.json 2>> $O/bench.err
 python bench.py --scene-sim > $O/scene_sim.json 2>> $O/bench.err
 python tools/eval_bench.py > $O/eval_bench.json 2>> $O/bench.err
 # per-kernel times of the image path (render_image 640 x 480 x 640): rocprofv3 kernel stats of five renders
