@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define NGM_ABI_VERSION 11 /* 11: ngm_field_eval_stash_bytes / ngm_field_eval_fwd_train / ngm_field_eval_bwd_stash (training forward of the point evaluation writes the activation stash, its backward is the fused step's kernel); 10: ngm_field_cfg.activation_stash / .hash_grad_atomics (per configuration, no process-wide switch), empty loss selections report NaN like the reference; 9: ngm_sample_rays_weighted; 8: ngm_peer_set_timeout (a time-out now also poisons the sums with NaN); 7: ngm_encode_bwd; 6: ngm_render_eval_knn; 5: ngm_encode_fwd, ngm_render_bwd_seeded_vars, *_nll loss modes (+ loss-sum slot 10), peer status bits */
+#define NGM_ABI_VERSION 11 /* 11 (+ addition, number unchanged: ngm_target_sample_mv_workspace / ngm_target_sample_mv and struct ngm_target_sample, the device-side training-target sampler; nothing existing changed); 11: ngm_field_eval_stash_bytes / ngm_field_eval_fwd_train / ngm_field_eval_bwd_stash (training forward of the point evaluation writes the activation stash, its backward is the fused step's kernel); 10: ngm_field_cfg.activation_stash / .hash_grad_atomics (per configuration, no process-wide switch), empty loss selections report NaN like the reference; 9: ngm_sample_rays_weighted; 8: ngm_peer_set_timeout (a time-out now also poisons the sums with NaN); 7: ngm_encode_bwd; 6: ngm_render_eval_knn; 5: ngm_encode_fwd, ngm_render_bwd_seeded_vars, *_nll loss modes (+ loss-sum slot 10), peer status bits */
 #define NGM_MAX_LAYERS 4 /* hidden layers; +1 output layer */
 #define NGM_NUM_LOSS_SUMS 16
 
@@ -487,6 +487,51 @@ int ngm_target_visibility(const ngm_keyframes* kf, int32_t F, const float* field
 int ngm_target_rays(const ngm_keyframes* kf, int32_t F, int32_t R, const float* field_pos, float radius,
                     const float* bbox, const int64_t* frame_cids, const float* u_xy,
                     const ngm_target_out* out, void* stream);
+
+/* ---- training-target sampler, whole, on the device (opt-in) ---------------------------------------
+ * _sample_target_mv (rm.py:1259-1459) with the random draws made on the device from Philox4x32-10 (NOT torch's stream):
+ * three launches, no host synchronisation, fixed output capacity, the number of surviving fields left in device memory --
+ * so a captured graph draws fresh targets at every replay.  Distribution as in the reference:
+ *   n_obs fields uniformly without replacement from current_field_ids (random order), n_rand uniformly without replacement
+ *   from the other fields of [0, num_fields); field order = the union sorted ascending if n_rand > 0, else the observed draw
+ *   order; 20 Gaussian sphere offsets, normalised; fields no keyframe sees are dropped (the others keep their order); per ray
+ *   a keyframe uniform among the field's visible ones, pixel uniforms inside its box.
+ * Keying (stream ids 0x54470001-4, distinct from the ray samplers' 0 / 1; Philox offset = iteration):
+ *   observed draw: key_j = (word 0 of block ctr=current_field_ids[j], stream ..01) << 32 | j, the n_obs smallest keys;
+ *   random draw:   key_f = (word 0 of block ctr=f, stream ..02) << 32 | f over fields not drawn above, the n_rand smallest;
+ *   offsets:       Box-Muller on blocks 0..14 of stream ..03 (exact-rounding arithmetic only, restated on the host);
+ *   ray k of field id g: block ctr=(g << 32 | k), stream ..04: keyframe = list[(word0 * count) >> 32], u_x / u_y = words 1 / 2
+ *   as 24-bit uniforms.  A ray depends on (seed, iteration, g, k) only: not on its row, F, the rank or the other fields.
+ * Sharding (world_size W, rank r): every rank draws the same set; only drawn fields with id % W == r get rows, in draw order.
+ * Precondition (not checked, as in the reference): current_field_ids duplicate-free, ids in [0, num_fields); ids outside
+ * that range are dropped.  capacity must be min(num_observed + num_random, #{id in [0, num_fields): id % W == r}) and
+ * num_observed + num_random <= NGM_TARGET_MAX_DRAW.  Every ngm_target_out array is (capacity, R, ...): rows past *count hold
+ * field_ids = -1, masks 0 and zeros (frame_cids / u_xy too). */
+#define NGM_TARGET_MAX_DRAW 2048
+typedef struct ngm_target_sample {
+  const int64_t* current_field_ids; /* (num_current)                                                     */
+  const float* field_positions;     /* (>= num_fields, 3) map field centres                               */
+  int32_t num_current, num_fields;
+  int32_t num_observed;             /* min(num_train_fields / 2, num_current)                              */
+  int32_t num_random;               /* min(num_train_fields - num_observed, num_fields - num_observed)     */
+  int32_t num_rays, capacity;       /* R; output rows                                                      */
+  int32_t world_size, rank;
+  float radius;                     /* _field_radius                                                       */
+  int32_t reserved0;
+  uint64_t seed;
+  int64_t iteration;                /* >= 0: this iteration; < 0: read *iteration_dev once and advance it by one */
+  int64_t* iteration_dev;
+  int64_t* field_ids;               /* out (capacity)                                                      */
+  int32_t* count;                   /* out (1): surviving fields                                           */
+  int64_t* subset_observed;         /* out (num_observed): positions in current_field_ids, draw order     */
+  int64_t* subset_random;           /* out (num_random): field ids, draw order                             */
+  float* offsets;                   /* out (20,3) normalised sphere offsets                                */
+  int64_t* frame_cids;              /* out (capacity,R) keyframe per ray                                   */
+  float* u_xy;                      /* out (capacity,R,2) pixel uniforms                                   */
+} ngm_target_sample;
+int64_t ngm_target_sample_mv_workspace(int32_t num_frames, int32_t num_current, int32_t num_fields, int32_t capacity);
+int ngm_target_sample_mv(const ngm_keyframes* kf, const ngm_target_sample* s, const ngm_target_out* out, void* workspace,
+                         int64_t workspace_bytes, void* stream);
 
 /* Device part of NeuralGraphMap._sample_target_sv (rm.py:1461-1583), the single-view variant (`update_mode: single_view`):
  * hit (F,N) u8 = the segment camera origin -> point n of the (subsampled) back-projected depth image passes through the

@@ -108,6 +108,42 @@ class TargetOut(C.Structure):
                 ("rgb_mask", C.c_void_p), ("depth_mask", C.c_void_p), ("term_probs", f32p), ("term_mask", C.c_void_p)]
 
 
+NGM_TARGET_MAX_DRAW = 2048                     # include/ngm_hip.h: fields one ngm_target_sample_mv call may draw
+
+
+class TargetSample(C.Structure):
+    _fields_ = [("current_field_ids", C.c_void_p), ("field_positions", f32p), ("num_current", C.c_int32),
+                ("num_fields", C.c_int32), ("num_observed", C.c_int32), ("num_random", C.c_int32), ("num_rays", C.c_int32),
+                ("capacity", C.c_int32), ("world_size", C.c_int32), ("rank", C.c_int32), ("radius", C.c_float),
+                ("reserved0", C.c_int32), ("seed", C.c_uint64), ("iteration", C.c_int64), ("iteration_dev", C.c_void_p),
+                ("field_ids", C.c_void_p), ("count", C.c_void_p), ("subset_observed", C.c_void_p),
+                ("subset_random", C.c_void_p), ("offsets", f32p), ("frame_cids", C.c_void_p), ("u_xy", f32p)]
+
+
+def target_sample_mv_plan(num_current, num_fields, num_train_fields, num_rays, world_size=1, rank=0):
+    """Host-side sizes of ngm_target_sample_mv, known before anything runs: (n_obs, n_rand, capacity) with
+    n_obs = min(T // 2, len(cur)), n_rand = min(T - n_obs, num_fields - n_obs) (rm.py:1280-1319) and capacity = the
+    rows of this rank: min(n_obs + n_rand, fields of [0, num_fields) with id % world_size == rank).  Raises on bad input."""
+    for name, v in (("num_current", num_current), ("num_fields", num_fields), ("num_train_fields", num_train_fields),
+                    ("num_rays_per_field", num_rays), ("world_size", world_size), ("rank", rank)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise TypeError(f"target_sample_mv: {name} must be an int, got {type(v).__name__}")
+    if num_rays < 1:
+        raise ValueError(f"target_sample_mv: num_rays_per_field must be >= 1, got {num_rays}")
+    if num_train_fields < 0 or num_current < 0 or num_fields < 0:
+        raise ValueError("target_sample_mv: num_train_fields, len(current_field_ids) and num_fields must be >= 0")
+    if num_current > num_fields:
+        raise ValueError(f"target_sample_mv: {num_current} current fields but only {num_fields} fields in the map")
+    if world_size < 1 or not 0 <= rank < world_size:
+        raise ValueError(f"target_sample_mv: need 0 <= rank < world_size, got rank={rank}, world_size={world_size}")
+    n_obs = min(num_train_fields // 2, num_current)
+    n_rand = max(min(num_train_fields - n_obs, num_fields - n_obs), 0)
+    if n_obs + n_rand > NGM_TARGET_MAX_DRAW:
+        raise ValueError(f"target_sample_mv: {n_obs + n_rand} fields drawn, at most {NGM_TARGET_MAX_DRAW} per call")
+    owned = (num_fields - rank + world_size - 1) // world_size if num_fields > rank else 0
+    return n_obs, n_rand, min(n_obs + n_rand, owned)
+
+
 _lib = None
 
 
@@ -199,6 +235,10 @@ def lib():
     L.ngm_target_sv_intersect.restype = C.c_int
     L.ngm_target_sv_rays.argtypes = [i32, i32, vp, f32, vp, vp, vp, i32, i32, f32, f32, f32, f32, P(TargetOut), vp]
     L.ngm_target_sv_rays.restype = C.c_int
+    L.ngm_target_sample_mv_workspace.argtypes = [i32, i32, i32, i32]
+    L.ngm_target_sample_mv_workspace.restype = i64
+    L.ngm_target_sample_mv.argtypes = [P(Keyframes), P(TargetSample), P(TargetOut), vp, i64, vp]
+    L.ngm_target_sample_mv.restype = C.c_int
     L.ngm_marching_cubes_workspace.argtypes = [i32, i32, i32]
     L.ngm_marching_cubes_workspace.restype = i64
     L.ngm_marching_cubes_count.argtypes = [vp, i32, i32, i32, f32, vp, vp, i64, vp]
@@ -226,6 +266,7 @@ EXPORTED = ["ngm_abi_version", "ngm_last_error", "ngm_device_info", "ngm_permuto
             "ngm_render_bwd", "ngm_render_bwd_adam", "ngm_render_bwd_seeded", "ngm_render_bwd_seeded_vars", "ngm_render_read_samples", "ngm_adam_sparse",
             "ngm_field_eval_knn", "ngm_field_eval_knn_workspace", "ngm_render_eval_knn", "ngm_render_eval_knn_workspace", "ngm_adam_sparse_multi", "ngm_step_advance", "ngm_profile_enable", "ngm_profile_reset", "ngm_profile_read",
             "ngm_debug_phase_cycles", "ngm_debug_fwd_phase_cycles", "ngm_debug_last_bwd_variant", "ngm_debug_last_matmul", "ngm_debug_last_fwd_one_tile", "ngm_debug_last_comp_fused", "ngm_debug_disable_fused_comp", "ngm_debug_stash_mode", "ngm_debug_last_stash_mode", "ngm_target_visibility", "ngm_target_rays", "ngm_target_sv_intersect", "ngm_target_sv_rays",
+            "ngm_target_sample_mv_workspace", "ngm_target_sample_mv",
             "ngm_peer_mailbox_bytes", "ngm_peer_alloc", "ngm_peer_free", "ngm_ipc_export", "ngm_ipc_open", "ngm_ipc_close", "ngm_loss_exchange", "ngm_peer_set_timeout",
             "ngm_marching_cubes_workspace", "ngm_marching_cubes_count", "ngm_marching_cubes_emit", "ngm_marching_cubes_tables"]
 

@@ -312,6 +312,38 @@ int ngm_target_rays(const ngm_keyframes* kf, int32_t F, int32_t R, const float* 
   return check_launch("ngm_target_rays");
 }
 
+int64_t ngm_target_sample_mv_workspace(int32_t num_frames, int32_t num_current, int32_t num_fields, int32_t capacity) {
+  if (num_frames < 1 || num_current < 0 || num_fields < 0 || capacity < 0 || capacity > NGM_TARGET_MAX_DRAW) return -1;
+  return ngm_target_sample_mv_bytes(num_frames, num_current, num_fields, capacity);
+}
+int ngm_target_sample_mv(const ngm_keyframes* kf, const ngm_target_sample* s, const ngm_target_out* out, void* workspace,
+                         int64_t workspace_bytes, void* stream) {
+  int e = check_keyframes(kf);
+  if (e) return e;
+  if (!s || !out) return fail(NGM_E_INVALID, "ngm_target_sample_mv: NULL argument");
+  if (s->num_current < 0 || s->num_fields < 0 || s->num_rays < 1 || s->world_size < 1 || s->rank < 0 || s->rank >= s->world_size)
+    return fail(NGM_E_INVALID, "ngm_target_sample_mv: bad sizes (num_rays >= 1, 0 <= rank < world_size)");
+  if (s->num_observed < 0 || s->num_observed > s->num_current || s->num_random < 0 || s->num_random > s->num_fields - s->num_observed)
+    return fail(NGM_E_INVALID, "ngm_target_sample_mv: num_observed <= num_current and num_random <= num_fields - num_observed");
+  const int64_t n_all = (int64_t)s->num_observed + s->num_random;
+  if (n_all > NGM_TARGET_MAX_DRAW) return fail(NGM_E_UNSUPPORTED, "ngm_target_sample_mv: more than NGM_TARGET_MAX_DRAW fields drawn");
+  const int64_t owned = s->num_fields > s->rank ? ((int64_t)s->num_fields - s->rank + s->world_size - 1) / s->world_size : 0;
+  if (s->capacity != (n_all < owned ? n_all : owned))
+    return fail(NGM_E_INVALID, "ngm_target_sample_mv: capacity must be min(num_observed + num_random, fields of this rank)");
+  if ((s->num_current > 0 && !s->current_field_ids) || (s->num_fields > 0 && !s->field_positions) || !s->count || !s->field_ids ||
+      (s->num_observed > 0 && !s->subset_observed) || (s->num_random > 0 && !s->subset_random) || !s->offsets || !s->frame_cids ||
+      !s->u_xy || (s->iteration < 0 && !s->iteration_dev))
+    return fail(NGM_E_INVALID, "ngm_target_sample_mv: NULL array (iteration < 0 needs iteration_dev)");
+  if (!out->ijs || !out->near || !out->far || !out->gt || !out->rgbds || !out->rgb_mask || !out->depth_mask || !out->term_probs ||
+      !out->term_mask)
+    return fail(NGM_E_INVALID, "ngm_target_sample_mv: NULL output array");
+  if ((int64_t)s->capacity * s->num_rays > INT32_MAX) return fail(NGM_E_UNSUPPORTED, "ngm_target_sample_mv: capacity x num_rays >= 2^31");
+  const int64_t need = ngm_target_sample_mv_bytes(kf->num_frames, s->num_current, s->num_fields, s->capacity);
+  if (!workspace || workspace_bytes < need) return fail(NGM_E_WORKSPACE, "ngm_target_sample_mv: workspace too small");
+  ngm_launch_target_sample_mv(*kf, *s, *out, workspace, (hipStream_t)stream);
+  return check_launch("ngm_target_sample_mv");
+}
+
 int ngm_target_sv_intersect(int32_t F, int64_t N, const float* field_pos_cam, const float* points_cam, float radius, uint8_t* hit,
                             void* stream) {
   if (F < 0 || N < 0 || radius < 0.f || (F > 0 && N > 0 && (!field_pos_cam || !points_cam || !hit)))

@@ -216,6 +216,9 @@ int ngm_launch_target_sv_rays(int F, int R, const float* pos_c, float radius, co
                               hipStream_t st);
 int ngm_launch_target_rays(const ngm_keyframes& kf, int F, int R, const float* field_pos, float radius, const float* bbox,
                            const int64_t* frame_cids, const float* u_xy, const ngm_target_out& o, hipStream_t st);
+int64_t ngm_target_sample_mv_bytes(int num_frames, int num_current, int num_fields, int capacity);
+int ngm_launch_target_sample_mv(const ngm_keyframes& kf, const ngm_target_sample& s, const ngm_target_out& o, void* workspace,
+                                hipStream_t st);
 
 // flat parameter vector layout of one field: [enc_w][w0][b0]...[wL][bL]
 __host__ __device__ static inline int64_t ngm_param_offsets(const ngm_field_cfg* fc, int64_t* enc_off, int64_t* w_off, int64_t* b_off) {

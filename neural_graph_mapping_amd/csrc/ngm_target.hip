@@ -24,17 +24,15 @@ __device__ __forceinline__ Cam3 world_to_cam(const float* T, float px, float py,
   return c;
 }
 
-__global__ void k_target_visibility(ngm_keyframes kf, int F, const float* __restrict__ field_pos, int num_offsets,
-                                    const float* __restrict__ offsets, float radius, uint8_t* __restrict__ kf_mask,
-                                    float* __restrict__ bbox) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= F * kf.num_frames) return;
-  const int f = idx / kf.num_frames, c = idx - f * kf.num_frames;
+// One (field, keyframe) pair of rm.py:1321-1392: does keyframe c see the field at (px, py, pz)?  *box = the projected sphere
+// samples' 2-D bounding box, clamped to the image.  Shared by k_target_visibility and the device sampler's k_tsmv_visibility,
+// so the two give the same bits by construction.
+__device__ __forceinline__ bool target_visibility_one(const ngm_keyframes& kf, int c, float px, float py, float pz, int num_offsets,
+                                                      const float* __restrict__ offsets, float radius, float4* box) {
   const float* T = kf.c2ws + 16 * (int64_t)c;
   const float* img = kf.rgbd + kf.frame_to_store[c] * (int64_t)kf.height * kf.width * 4;
   // Camera.project_points(points, "opengl") with the default pixel centre 0.5 (camera.py:119-154,176-180)
   const float cxp = kf.cx + 0.5f, cyp = kf.cy + 0.5f;
-  const float px = field_pos[3 * f], py = field_pos[3 * f + 1], pz = field_pos[3 * f + 2];
   bool in_front = false, in_front_depth = false, in_frustum = false;
   float mnx = INFINITY, mny = INFINITY, mxx = -INFINITY, mxy = -INFINITY;
   for (int s = 0; s < num_offsets; ++s) {
@@ -52,21 +50,28 @@ __global__ void k_target_visibility(ngm_keyframes kf, int F, const float* __rest
     in_frustum |= valid;
     mnx = fminf(mnx, X); mny = fminf(mny, Y); mxx = fmaxf(mxx, X); mxy = fmaxf(mxy, Y);
   }
-  kf_mask[idx] = (in_front && in_front_depth && in_frustum) ? 1 : 0;
   // boxes are stored clamped to the image as the reference does before gathering them (rm.py:1388-1392)
-  reinterpret_cast<float4*>(bbox)[idx] = make_float4(fmaxf(mnx, 0.f), fmaxf(mny, 0.f), fminf(mxx, (float)kf.width),
-                                                     fminf(mxy, (float)kf.height));
+  *box = make_float4(fmaxf(mnx, 0.f), fmaxf(mny, 0.f), fminf(mxx, (float)kf.width), fminf(mxy, (float)kf.height));
+  return in_front && in_front_depth && in_frustum;
 }
 
-__global__ void k_target_rays(ngm_keyframes kf, int F, int R, const float* __restrict__ field_pos, float radius,
-                              const float* __restrict__ bbox, const int64_t* __restrict__ frame_cids,
-                              const float* __restrict__ u_xy, ngm_target_out o) {
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (int64_t)F * R) return;
-  const int f = (int)(idx / R);
-  const int64_t c = frame_cids[idx];
-  const float4 bb = reinterpret_cast<const float4*>(bbox)[(int64_t)f * kf.num_frames + c];
-  const float ux = u_xy[2 * idx], uy = u_xy[2 * idx + 1];
+__global__ void k_target_visibility(ngm_keyframes kf, int F, const float* __restrict__ field_pos, int num_offsets,
+                                    const float* __restrict__ offsets, float radius, uint8_t* __restrict__ kf_mask,
+                                    float* __restrict__ bbox) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= F * kf.num_frames) return;
+  const int f = idx / kf.num_frames, c = idx - f * kf.num_frames;
+  float4 box;
+  const bool seen = target_visibility_one(kf, c, field_pos[3 * f], field_pos[3 * f + 1], field_pos[3 * f + 2], num_offsets, offsets,
+                                          radius, &box);
+  kf_mask[idx] = seen ? 1 : 0;
+  reinterpret_cast<float4*>(bbox)[idx] = box;
+}
+
+// One ray of rm.py:1394-1459: keyframe c, pixel uniforms (ux, uy) inside the box bb -> output row `idx` of o.  Shared by
+// k_target_rays and the device sampler's k_tsmv_rays.
+__device__ __forceinline__ void target_ray_one(const ngm_keyframes& kf, float fpx, float fpy, float fpz, float radius, float4 bb,
+                                               int64_t c, float ux, float uy, const ngm_target_out& o, int64_t idx) {
   const float x = (bb.z - bb.x) * ux + bb.x, y = (bb.w - bb.y) * uy + bb.y;          // rm.py:1400-1402
   int j = min((int)x, kf.width - 1), i = min((int)y, kf.height - 1);                 // rm.py:1403-1407
   // (a negative index can only come from a keyframe that does not see the field; torch would wrap it around)
@@ -78,7 +83,7 @@ __global__ void k_target_rays(ngm_keyframes kf, int F, int R, const float* __res
     dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2]; dst[3] = src[3];
   }
   o.ijs[2 * idx] = i; o.ijs[2 * idx + 1] = j;
-  const Cam3 pc = world_to_cam(T, field_pos[3 * f], field_pos[3 * f + 1], field_pos[3 * f + 2]);
+  const Cam3 pc = world_to_cam(T, fpx, fpy, fpz);
   // ijs_to_directions, OpenGL (camera.py:186-203) and the OpenCV z component for depth_to_distance (:339-340)
   const float dx = ((float)j - kf.cx) / kf.fx, dy = ((float)i - kf.cy) / kf.fy;
   const float nrm = fmaxf(sqrtf(dx * dx + dy * dy + 1.0f), 1e-12f);
@@ -94,6 +99,18 @@ __global__ void k_target_rays(ngm_keyframes kf, int F, int R, const float* __res
   o.depth_mask[idx] = (gt > nearv && gt < farv && vd) ? 1 : 0;
   o.term_probs[idx] = (gt < farv) ? 1.0f : 0.0f;
   o.term_mask[idx] = (gt > nearv && vd) ? 1 : 0;
+}
+
+__global__ void k_target_rays(ngm_keyframes kf, int F, int R, const float* __restrict__ field_pos, float radius,
+                              const float* __restrict__ bbox, const int64_t* __restrict__ frame_cids,
+                              const float* __restrict__ u_xy, ngm_target_out o) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (int64_t)F * R) return;
+  const int f = (int)(idx / R);
+  const int64_t c = frame_cids[idx];
+  const float4 bb = reinterpret_cast<const float4*>(bbox)[(int64_t)f * kf.num_frames + c];
+  target_ray_one(kf, field_pos[3 * f], field_pos[3 * f + 1], field_pos[3 * f + 2], radius, bb, c, u_xy[2 * idx], u_xy[2 * idx + 1], o,
+                 idx);
 }
 
 // ---- single-view variant (NeuralGraphMap._sample_target_sv, rm.py:1461-1583) ------------------------------------
@@ -166,5 +183,345 @@ int ngm_launch_target_rays(const ngm_keyframes& kf, int F, int R, const float* f
   const int64_t n = (int64_t)F * R;
   hipLaunchKernelGGL(k_target_rays, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, kf, F, R, field_pos, radius, bbox,
                      frame_cids, u_xy, o);
+  return 0;
+}
+
+// ---- the whole sampler on the device (ngm_target_sample_mv, include/ngm_hip.h) -----------------------------------------
+// Three launches, no host synchronisation:
+//   k_tsmv_draw       one workgroup: iteration (explicit or read from the device counter, which it advances), both field
+//                     subsets (k smallest of unique 64-bit keys by an MSB-first radix select), their union, the owner filter,
+//                     the 20 sphere offsets, the field centres gathered from the map
+//   k_tsmv_visibility one thread per (slot, keyframe): target_visibility_one + a "some keyframe sees it" flag per slot
+//   k_tsmv_rays       one workgroup per (slot, ray chunk): the slot's output row (scan over the flags), the field's visible
+//                     keyframes in ascending frame id (ballot + prefix, in LDS; a workspace list past TSMV_LDS_FRAMES), the
+//                     ray draws and target_ray_one; invisible slots write the padding rows
+constexpr uint32_t TSMV_STREAM_OBS = 0x54470001u, TSMV_STREAM_RAND = 0x54470002u, TSMV_STREAM_OFFSETS = 0x54470003u,
+                   TSMV_STREAM_RAYS = 0x54470004u;
+constexpr uint64_t TSMV_EXCLUDED = ~0ull;        // never a real key: the low word of one is a position / field id < 2^31
+constexpr int TSMV_DRAW_THREADS = 1024, TSMV_RAY_THREADS = 256, TSMV_LDS_FRAMES = 2048, TSMV_NUM_OFFSETS = 20;
+
+struct tsmv_ws {
+  int64_t* hdr;        // [0] iteration of this call, [1] owned fields drawn (slots in use)
+  uint64_t* keys;      // max(num_current, num_fields)
+  int64_t* slot_ids;   // capacity
+  float* slot_pos;     // capacity x 3
+  int* flags;          // capacity: some keyframe sees the slot's field
+  float* offsets;      // 20 x 3
+  uint8_t* kf_mask;    // capacity x num_frames
+  float4* bbox;        // capacity x num_frames
+  int* list;           // capacity x num_frames visible-keyframe lists, only when num_frames > TSMV_LDS_FRAMES
+};
+
+static int64_t tsmv_layout(int num_frames, int num_current, int num_fields, int capacity, char* base, tsmv_ws* w) {
+  int64_t off = 0;
+  auto take = [&](int64_t bytes) { char* p = base ? base + off : nullptr; off += (bytes + 255) / 256 * 256; return p; };
+  const int64_t pairs = (int64_t)capacity * num_frames;
+  tsmv_ws t;
+  t.hdr = (int64_t*)take(2 * sizeof(int64_t));
+  t.keys = (uint64_t*)take((int64_t)(num_current > num_fields ? num_current : num_fields) * sizeof(uint64_t));
+  t.slot_ids = (int64_t*)take((int64_t)capacity * sizeof(int64_t));
+  t.slot_pos = (float*)take((int64_t)capacity * 3 * sizeof(float));
+  t.flags = (int*)take((int64_t)capacity * sizeof(int));
+  t.offsets = (float*)take(TSMV_NUM_OFFSETS * 3 * sizeof(float));
+  t.kf_mask = (uint8_t*)take(pairs);
+  t.bbox = (float4*)take(pairs * sizeof(float4));
+  t.list = num_frames > TSMV_LDS_FRAMES ? (int*)take(pairs * sizeof(int)) : nullptr;
+  if (w) *w = t;
+  return off;
+}
+
+// Exact-rounding stand-ins for logf / sincosf (only +, -, *, / and bit operations, fp contraction off): the host restates the
+// offsets bit for bit with numpy float32 (tests/test_gpu_target_device.py).  Series truncation errors < 1e-7.
+__device__ __forceinline__ float tsmv_log(float u) {                     // u > 0, normal
+  const uint32_t b = __float_as_uint(u);
+  const float e = (float)((int)((b >> 23) & 255u) - 127);
+  const float m = __uint_as_float((b & 0x7FFFFFu) | 0x3F800000u);        // [1, 2)
+  const float s = (m - 1.0f) / (m + 1.0f), z = s * s;                    // log m = 2 atanh(s), s in [0, 1/3)
+  float p = 0.0769230798f;                                                // 1/13
+  p = p * z + 0.0909090936f; p = p * z + 0.111111112f; p = p * z + 0.142857149f; p = p * z + 0.200000003f;
+  p = p * z + 0.333333343f; p = p * z + 1.0f;
+  return e * 0.693147182f + 2.0f * s * p;
+}
+__device__ __forceinline__ void tsmv_sincos_2pi(float u, float* sn, float* cs) {   // u in [0, 1): sin / cos of 2 pi u
+  const float u4 = u * 4.0f;
+  const int q = (int)u4;
+  const float ph = (u4 - (float)q) * 1.57079637f, z = ph * ph;           // [0, pi/2)
+  float ps = 1.60590444e-10f;                                             // 1/13!
+  ps = ps * z - 2.50521079e-08f; ps = ps * z + 2.75573188e-06f; ps = ps * z - 1.98412701e-04f; ps = ps * z + 8.33333377e-03f;
+  ps = ps * z - 0.166666672f; ps = ps * z + 1.0f;
+  float pc = 2.08767570e-09f;                                             // 1/12!
+  pc = pc * z - 2.75573188e-07f; pc = pc * z + 2.48015876e-05f; pc = pc * z - 1.38888892e-03f; pc = pc * z + 4.16666679e-02f;
+  pc = pc * z - 0.5f; pc = pc * z + 1.0f;
+  const float s = ph * ps, c = pc;
+  *sn = q == 0 ? s : q == 1 ? c : q == 2 ? -s : -c;
+  *cs = q == 0 ? c : q == 1 ? -s : q == 2 ? -c : s;
+}
+
+// The k smallest of keys[0..n) (TSMV_EXCLUDED skipped, the others unique), ascending, into out[0..k).  MSB-first radix select
+// over 8-bit digits until the bin that holds the k-th key holds exactly the keys still wanted; then every key whose digits so
+// far are <= the prefix is in, and a rank sort over the k orders them.  Block-uniform arguments; all threads must call.
+__device__ void tsmv_k_smallest(const uint64_t* keys, int n, int k, uint64_t* out, uint64_t* scratch, int* hist, int* st) {
+  const int tid = threadIdx.x, nt = blockDim.x;
+  if (k <= 0) return;
+  int shift = 64, rem = k;
+  uint64_t prefix = 0;
+  for (;;) {
+    shift -= 8;
+    for (int b = tid; b < 256; b += nt) hist[b] = 0;
+    __syncthreads();
+    for (int i = tid; i < n; i += nt) {
+      const uint64_t key = keys[i];
+      if (key == TSMV_EXCLUDED || (shift < 56 && (key >> (shift + 8)) != prefix)) continue;
+      atomicAdd(&hist[(key >> shift) & 255u], 1);
+    }
+    __syncthreads();
+    if (tid == 0) {
+      int cum = 0, b = 0;
+      for (; b < 255; ++b) {
+        if (cum + hist[b] >= rem) break;
+        cum += hist[b];
+      }
+      st[0] = b; st[1] = rem - cum; st[2] = hist[b] == rem - cum;
+    }
+    __syncthreads();
+    prefix = (prefix << 8) | (uint64_t)st[0];
+    rem = st[1];
+    const bool done = st[2] != 0 || shift == 0;
+    __syncthreads();
+    if (done) break;
+  }
+  if (tid == 0) st[3] = 0;
+  __syncthreads();
+  for (int i = tid; i < n; i += nt) {
+    const uint64_t key = keys[i];
+    if (key != TSMV_EXCLUDED && (key >> shift) <= prefix) {
+      const int p = atomicAdd(&st[3], 1);
+      if (p < k) scratch[p] = key;
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < k; i += nt) {
+    const uint64_t v = scratch[i];
+    int r = 0;
+    for (int j = 0; j < k; ++j) {
+      const uint64_t u = scratch[j];
+      r += (u < v || (u == v && j < i)) ? 1 : 0;
+    }
+    out[r] = v;
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(TSMV_DRAW_THREADS) void k_tsmv_draw(ngm_target_sample s, tsmv_ws w) {
+  __shared__ uint64_t sel[NGM_TARGET_MAX_DRAW], scratch[NGM_TARGET_MAX_DRAW];
+  __shared__ int64_t drawn[NGM_TARGET_MAX_DRAW];
+  __shared__ int hist[256], st[4];
+  __shared__ int64_t s_iter;
+  __shared__ int s_own;
+  __shared__ float normals[3 * TSMV_NUM_OFFSETS];
+  const int tid = threadIdx.x, nt = blockDim.x;
+  if (tid == 0) {
+    const int64_t it = s.iteration >= 0 ? s.iteration : *s.iteration_dev;
+    s_iter = it;
+    w.hdr[0] = it;
+  }
+  __syncthreads();
+  const uint64_t it = (uint64_t)s_iter;
+  if (tid == 0 && s.iteration < 0) *s.iteration_dev = (int64_t)it + 1;          // after the barrier: every read is done
+  const int n_obs = s.num_observed, n_rand = s.num_random, n_all = n_obs + n_rand;
+  // 1. observed fields: the n_obs smallest of (philox(id) << 32 | position), in key order = random order
+  for (int j = tid; j < s.num_current; j += nt) {
+    uint32_t q[4];
+    philox_block(s.seed, it, (uint64_t)s.current_field_ids[j], TSMV_STREAM_OBS, q);
+    w.keys[j] = ((uint64_t)q[0] << 32) | (uint32_t)j;
+  }
+  __syncthreads();
+  tsmv_k_smallest(w.keys, s.num_current, n_obs, sel, scratch, hist, st);
+  for (int i = tid; i < n_obs; i += nt) {
+    const int64_t j = (int64_t)(sel[i] & 0xFFFFFFFFull);       // < num_current: the select returns exactly n_obs keys
+    s.subset_observed[i] = j;
+    drawn[i] = j < s.num_current ? s.current_field_ids[j] : -1;
+  }
+  __syncthreads();
+  // 2. random fields: the n_rand smallest of (philox(f) << 32 | f) over the fields not drawn in 1.
+  if (n_rand > 0) {
+    for (int f = tid; f < s.num_fields; f += nt) {
+      uint32_t q[4];
+      philox_block(s.seed, it, (uint64_t)f, TSMV_STREAM_RAND, q);
+      w.keys[f] = ((uint64_t)q[0] << 32) | (uint32_t)f;
+    }
+    __syncthreads();
+    for (int i = tid; i < n_obs; i += nt) {
+      const int64_t id = drawn[i];
+      if (id >= 0 && id < s.num_fields) w.keys[id] = TSMV_EXCLUDED;
+    }
+    __syncthreads();
+    tsmv_k_smallest(w.keys, s.num_fields, n_rand, sel, scratch, hist, st);
+    for (int i = tid; i < n_rand; i += nt) {
+      const int64_t id = (int64_t)(sel[i] & 0xFFFFFFFFull);
+      s.subset_random[i] = id;
+      drawn[n_obs + i] = id;
+    }
+    __syncthreads();
+    // 3. the union sorted ascending (torch.unique)
+    for (int i = tid; i < n_all; i += nt) {
+      const int64_t v = drawn[i];
+      int r = 0;
+      for (int j = 0; j < n_all; ++j) {
+        const int64_t u = drawn[j];
+        r += (u < v || (u == v && j < i)) ? 1 : 0;
+      }
+      sel[r] = (uint64_t)v;
+    }
+    __syncthreads();
+    for (int i = tid; i < n_all; i += nt) drawn[i] = (int64_t)sel[i];
+    __syncthreads();
+  }
+  // 4. owner filter, order kept (ids outside [0, num_fields) dropped)
+  if (tid == 0) {
+    int n = 0;
+    for (int i = 0; i < n_all; ++i) {
+      const int64_t id = drawn[i];
+      if (id >= 0 && id < s.num_fields && id % s.world_size == s.rank && n < s.capacity) scratch[n++] = (uint64_t)id;
+    }
+    s_own = n;
+    w.hdr[1] = n;
+    if (s.capacity == 0) *s.count = 0;                 // no k_tsmv_rays launch then
+  }
+  __syncthreads();
+  const int n_own = s_own;
+  for (int i = tid; i < s.capacity; i += nt) {
+    w.flags[i] = 0;
+    if (i < n_own) {
+      const int64_t id = (int64_t)scratch[i];
+      w.slot_ids[i] = id;
+      w.slot_pos[3 * i] = s.field_positions[3 * id];
+      w.slot_pos[3 * i + 1] = s.field_positions[3 * id + 1];
+      w.slot_pos[3 * i + 2] = s.field_positions[3 * id + 2];
+    }
+  }
+  // 5. sphere offsets: Box-Muller on 15 blocks (two pairs each), u1 = odd / 2^24 in (0, 1), then normalised
+  if (tid < 3 * TSMV_NUM_OFFSETS / 2) {
+    uint32_t q[4];
+    philox_block(s.seed, it, (uint64_t)(tid >> 1), TSMV_STREAM_OFFSETS, q);
+    const int h = 2 * (tid & 1);
+    const float u1 = (float)((q[h] >> 9) * 2u + 1u) * (1.0f / 16777216.0f);
+    const float u2 = philox_word_uniform(q[h + 1]);
+    const float r = sqrtf(-2.0f * tsmv_log(u1));
+    float sn, cs;
+    tsmv_sincos_2pi(u2, &sn, &cs);
+    normals[2 * tid] = r * cs;
+    normals[2 * tid + 1] = r * sn;
+  }
+  __syncthreads();
+  if (tid < TSMV_NUM_OFFSETS) {
+    const float x = normals[3 * tid], y = normals[3 * tid + 1], z = normals[3 * tid + 2];
+    const float n = sqrtf((x * x + y * y) + z * z);
+    const float ox = x / n, oy = y / n, oz = z / n;
+    w.offsets[3 * tid] = ox; w.offsets[3 * tid + 1] = oy; w.offsets[3 * tid + 2] = oz;
+    s.offsets[3 * tid] = ox; s.offsets[3 * tid + 1] = oy; s.offsets[3 * tid + 2] = oz;
+  }
+}
+
+__global__ void k_tsmv_visibility(ngm_keyframes kf, int capacity, float radius, tsmv_ws w) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (int64_t)capacity * kf.num_frames) return;
+  const int slot = (int)(idx / kf.num_frames), c = (int)(idx - (int64_t)slot * kf.num_frames);
+  if (slot >= (int)w.hdr[1]) return;
+  float4 box;
+  const bool seen = target_visibility_one(kf, c, w.slot_pos[3 * slot], w.slot_pos[3 * slot + 1], w.slot_pos[3 * slot + 2],
+                                          TSMV_NUM_OFFSETS, w.offsets, radius, &box);
+  w.kf_mask[idx] = seen ? 1 : 0;
+  w.bbox[idx] = box;
+  if (seen) w.flags[slot] = 1;                       // every writer stores the same 1 (flags zeroed by k_tsmv_draw)
+}
+
+__global__ __launch_bounds__(TSMV_RAY_THREADS) void k_tsmv_rays(ngm_keyframes kf, ngm_target_sample s, ngm_target_out o, tsmv_ws w) {
+  __shared__ int list[TSMV_LDS_FRAMES];
+  __shared__ int red[2], wave_cnt[TSMV_RAY_THREADS / 64];
+  const int slot = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int n_own = (int)w.hdr[1];
+  const uint64_t it = (uint64_t)w.hdr[0];
+  if (tid < 2) red[tid] = 0;
+  __syncthreads();
+  // output row: visible slots in order first (rows 0..count-1), then the others (padding rows count..capacity-1)
+  int before = 0, total = 0;
+  for (int i = tid; i < n_own; i += TSMV_RAY_THREADS) {
+    const int f = w.flags[i];
+    total += f;
+    before += i < slot ? f : 0;
+  }
+  if (total) atomicAdd(&red[1], total);
+  if (before) atomicAdd(&red[0], before);
+  __syncthreads();
+  const int count = red[1], vb = red[0];
+  const bool vis = slot < n_own && w.flags[slot] != 0;
+  const int row = vis ? vb : count + (slot - vb);
+  const int R = s.num_rays, k = blockIdx.x * TSMV_RAY_THREADS + tid;
+  if (blockIdx.x == 0 && tid == 0) {
+    s.field_ids[row] = vis ? w.slot_ids[slot] : -1;
+    if (slot == 0) *s.count = count;
+  }
+  if (!vis) {
+    if (k < R) {
+      const int64_t idx = (int64_t)row * R + k;
+      if (o.c2ws) {
+        float4* dst = reinterpret_cast<float4*>(o.c2ws + 16 * idx);
+        dst[0] = dst[1] = dst[2] = dst[3] = make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+      o.ijs[2 * idx] = 0; o.ijs[2 * idx + 1] = 0;
+      o.near[idx] = 0.f; o.far[idx] = 0.f; o.gt[idx] = 0.f;
+      reinterpret_cast<float4*>(o.rgbds)[idx] = make_float4(0.f, 0.f, 0.f, 0.f);
+      o.rgb_mask[idx] = 0; o.depth_mask[idx] = 0; o.term_probs[idx] = 0.f; o.term_mask[idx] = 0;
+      s.frame_cids[idx] = 0; s.u_xy[2 * idx] = 0.f; s.u_xy[2 * idx + 1] = 0.f;
+    }
+    return;
+  }
+  // the field's visible keyframes in ascending frame id (every block of the slot writes the same global list when it is used)
+  const int Nc = kf.num_frames;
+  int* lst = Nc <= TSMV_LDS_FRAMES ? list : w.list + (int64_t)slot * Nc;
+  const uint8_t* m = w.kf_mask + (int64_t)slot * Nc;
+  int base = 0;
+  for (int c0 = 0; c0 < Nc; c0 += TSMV_RAY_THREADS) {
+    const int c = c0 + tid;
+    const bool on = c < Nc && m[c] != 0;
+    const uint64_t bal = __ballot(on);
+    if (lane == 0) wave_cnt[wv] = __popcll(bal);
+    __syncthreads();
+    int off = base, tot = 0;
+    for (int q = 0; q < TSMV_RAY_THREADS / 64; ++q) {
+      off += q < wv ? wave_cnt[q] : 0;
+      tot += wave_cnt[q];
+    }
+    if (on) lst[off + __popcll(bal & ((1ull << lane) - 1ull))] = c;
+    base += tot;
+    __syncthreads();
+  }
+  if (k >= R) return;
+  const int64_t id = w.slot_ids[slot];
+  uint32_t q[4];
+  philox_block(s.seed, it, ((uint64_t)(uint32_t)id << 32) | (uint32_t)k, TSMV_STREAM_RAYS, q);
+  const int c = lst[(int)(((uint64_t)q[0] * (uint64_t)base) >> 32)];
+  const float ux = philox_word_uniform(q[1]), uy = philox_word_uniform(q[2]);
+  const int64_t idx = (int64_t)row * R + k;
+  s.frame_cids[idx] = c;
+  s.u_xy[2 * idx] = ux; s.u_xy[2 * idx + 1] = uy;
+  target_ray_one(kf, w.slot_pos[3 * slot], w.slot_pos[3 * slot + 1], w.slot_pos[3 * slot + 2], s.radius,
+                 w.bbox[(int64_t)slot * Nc + c], (int64_t)c, ux, uy, o, idx);
+}
+
+int64_t ngm_target_sample_mv_bytes(int num_frames, int num_current, int num_fields, int capacity) {
+  return tsmv_layout(num_frames, num_current, num_fields, capacity, nullptr, nullptr);
+}
+int ngm_launch_target_sample_mv(const ngm_keyframes& kf, const ngm_target_sample& s, const ngm_target_out& o, void* workspace,
+                                hipStream_t st) {
+  tsmv_ws w;
+  tsmv_layout(kf.num_frames, s.num_current, s.num_fields, s.capacity, (char*)workspace, &w);
+  hipLaunchKernelGGL(k_tsmv_draw, dim3(1), dim3(TSMV_DRAW_THREADS), 0, st, s, w);
+  if (s.capacity == 0) return 0;
+  const int64_t pairs = (int64_t)s.capacity * kf.num_frames;
+  hipLaunchKernelGGL(k_tsmv_visibility, dim3((unsigned)((pairs + 127) / 128)), dim3(128), 0, st, kf, s.capacity, s.radius, w);
+  hipLaunchKernelGGL(k_tsmv_rays, dim3((unsigned)((s.num_rays + TSMV_RAY_THREADS - 1) / TSMV_RAY_THREADS), (unsigned)s.capacity),
+                     dim3(TSMV_RAY_THREADS), 0, st, kf, s, o, w);
   return 0;
 }

@@ -1005,3 +1005,97 @@ def target_sv_rays(pos_c, radius, pts_ijs, segments, image, fx, fy, cx, cy):
     for k in ("rgb_mask", "depth_mask", "term_mask"):
         o[k] = o[k].bool()
     return o
+
+
+# ------------------------------------------------------------------------------------------------
+# training-target sampler, whole, on the device (include/ngm_hip.h ngm_target_sample_mv)
+# ------------------------------------------------------------------------------------------------
+TARGET_SAMPLE_MV_OUT = ("ijs", "c2ws", "near", "far", "gt", "field_ids", "rgbds", "rgb_mask", "depth_mask", "term_probs",
+                        "term_mask", "count", "subset_observed", "subset_random", "offsets", "frame_cids", "u_xy")
+
+
+def _target_sample_mv_shapes(n_obs, n_rand, cap, R):
+    """(shape, dtype) of every output of torch.ops.ngm355.target_sample_mv, in TARGET_SAMPLE_MV_OUT order"""
+    f32, i64, b = torch.float32, torch.int64, torch.bool
+    return [((cap, R, 2), i64), ((cap, R, 4, 4), f32), ((cap, R), f32), ((cap, R), f32), ((cap, R), f32), ((cap,), i64),
+            ((cap, R, 4), f32), ((cap, R), b), ((cap, R), b), ((cap, R), f32), ((cap, R), b), ((1,), torch.int32),
+            ((n_obs,), i64), ((n_rand,), i64), ((20, 3), f32), ((cap, R), i64), ((cap, R, 2), f32)]
+
+
+@_op("target_sample_mv", mutates_args=("iteration_dev",))
+def _target_sample_mv_op(current_field_ids: torch.Tensor, c2ws: torch.Tensor, rgbd_store: torch.Tensor,
+                         frame_to_store: torch.Tensor, field_positions: torch.Tensor, iteration_dev: Optional[torch.Tensor],
+                         intrinsics: List[float], radius: float, num_fields: int, num_train_fields: int, num_rays: int,
+                         seed: int, iteration: int, world_size: int, rank: int) -> List[torch.Tensor]:
+    """TARGET_SAMPLE_MV_OUT, every per-field array at the host-known capacity (rows past count: padding)"""
+    n_obs, n_rand, cap = K.target_sample_mv_plan(current_field_ids.shape[0], num_fields, num_train_fields, num_rays, world_size, rank)
+    dev = field_positions.device
+    outs = [torch.empty(shape, dtype=dt, device=dev) for shape, dt in _target_sample_mv_shapes(n_obs, n_rand, cap, num_rays)]
+    o = dict(zip(TARGET_SAMPLE_MV_OUT, outs))
+    kf = keyframes_struct(c2ws, rgbd_store, frame_to_store, *intrinsics)
+    ws_bytes = K.lib().ngm_target_sample_mv_workspace(kf.num_frames, current_field_ids.shape[0], num_fields, cap)
+    if ws_bytes < 0:
+        raise K.NgmError("ngm_target_sample_mv_workspace: bad sizes")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    s = K.TargetSample(_ptr(current_field_ids), _ptr(field_positions), current_field_ids.shape[0], num_fields, n_obs, n_rand,
+                       num_rays, cap, world_size, rank, float(radius), 0, int(seed), int(iteration), _ptr(iteration_dev))
+    for k in ("field_ids", "count", "subset_observed", "subset_random", "offsets", "frame_cids", "u_xy"):
+        setattr(s, k, o[k].data_ptr())
+    out = K.TargetOut()
+    for k in ("ijs", "c2ws", "near", "far", "gt", "rgbds", "rgb_mask", "depth_mask", "term_probs", "term_mask"):
+        setattr(out, k, o[k].data_ptr())
+    K.check(K.lib().ngm_target_sample_mv(C.byref(kf), C.byref(s), C.byref(out), _ptr(ws), ws_bytes, _stream()),
+            "ngm_target_sample_mv")
+    return outs
+
+
+@_target_sample_mv_op.register_fake
+def _(current_field_ids, c2ws, rgbd_store, frame_to_store, field_positions, iteration_dev, intrinsics, radius, num_fields,
+      num_train_fields, num_rays, seed, iteration, world_size, rank):
+    n_obs, n_rand, cap = K.target_sample_mv_plan(current_field_ids.shape[0], num_fields, num_train_fields, num_rays, world_size, rank)
+    return [torch.empty(shape, dtype=dt, device=field_positions.device)
+            for shape, dt in _target_sample_mv_shapes(n_obs, n_rand, cap, num_rays)]
+
+
+def _check_target_sample_mv(current_field_ids, c2ws, rgbd_store, frame_to_store, field_positions, iteration_dev, num_fields):
+    def need(cond, msg, exc=ValueError):
+        if not cond:
+            raise exc("target_sample_mv: " + msg)
+    for name, t, dt in (("current_field_ids", current_field_ids, torch.int64), ("c2ws", c2ws, torch.float32),
+                        ("rgbd_store", rgbd_store, torch.float32), ("frame_to_store", frame_to_store, torch.int64),
+                        ("field_positions", field_positions, torch.float32)):
+        need(isinstance(t, torch.Tensor), f"{name} must be a tensor", TypeError)
+        need(t.dtype == dt, f"{name} must be {dt}, got {t.dtype}", TypeError)
+        need(t.is_contiguous(), f"{name} must be contiguous")
+    need(current_field_ids.dim() == 1, f"current_field_ids must be 1-D, got shape {tuple(current_field_ids.shape)}")
+    need(c2ws.dim() == 3 and tuple(c2ws.shape[1:]) == (4, 4) and c2ws.shape[0] >= 1, f"c2ws must be (Nc>=1, 4, 4), got {tuple(c2ws.shape)}")
+    need(rgbd_store.dim() == 4 and rgbd_store.shape[3] == 4, f"rgbd_store must be (N, H, W, 4), got {tuple(rgbd_store.shape)}")
+    need(tuple(frame_to_store.shape) == (c2ws.shape[0],), f"frame_to_store must be ({c2ws.shape[0]},), got {tuple(frame_to_store.shape)}")
+    need(field_positions.dim() == 2 and field_positions.shape[1] == 3 and field_positions.shape[0] >= num_fields,
+         f"field_positions must be (>= num_fields = {num_fields}, 3), got {tuple(field_positions.shape)}")
+    if iteration_dev is not None:
+        need(isinstance(iteration_dev, torch.Tensor) and iteration_dev.dtype == torch.int64 and iteration_dev.numel() == 1,
+             "iteration_dev must be a one-element int64 tensor", TypeError)
+
+
+def target_sample_mv(current_field_ids, c2ws, rgbd_store, frame_to_store, field_positions, fx, fy, cx, cy, radius, num_fields,
+                     num_train_fields, num_rays_per_field, seed=0, iteration=None, iteration_dev=None, world_size=1, rank=0):
+    """_sample_target_mv (rm.py:1259-1459) with the draws on the device, three launches, no host synchronisation
+    (torch.ops.ngm355.target_sample_mv).  iteration=None: iteration_dev (one-element int64 device tensor) is read and
+    advanced by one inside the call; an int uses that iteration and leaves iteration_dev alone.  Returns a dict keyed by
+    TARGET_SAMPLE_MV_OUT; per-field arrays have K.target_sample_mv_plan(...)[2] rows, `count` (int32, device) of them valid."""
+    _check_target_sample_mv(current_field_ids, c2ws, rgbd_store, frame_to_store, field_positions, iteration_dev, int(num_fields))
+    K.target_sample_mv_plan(current_field_ids.shape[0], int(num_fields), int(num_train_fields), int(num_rays_per_field),
+                            int(world_size), int(rank))
+    if iteration is None and iteration_dev is None:
+        raise ValueError("target_sample_mv: iteration=None needs iteration_dev (the device counter)")
+    if iteration is not None and int(iteration) < 0:
+        raise ValueError(f"target_sample_mv: iteration must be >= 0, got {iteration}")
+    if not 0 <= int(seed) < 2 ** 63:
+        raise ValueError(f"target_sample_mv: seed must be in [0, 2^63), got {seed}")
+    _require_gpu(current_field_ids, c2ws, rgbd_store, frame_to_store, field_positions, iteration_dev)
+    outs = torch.ops.ngm355.target_sample_mv(current_field_ids, c2ws, rgbd_store, frame_to_store, field_positions, iteration_dev,
+                                             [float(fx), float(fy), float(cx), float(cy)], float(radius), int(num_fields),
+                                             int(num_train_fields), int(num_rays_per_field), int(seed),
+                                             -1 if iteration is None else int(iteration), int(world_size), int(rank))
+    return dict(zip(TARGET_SAMPLE_MV_OUT, outs))

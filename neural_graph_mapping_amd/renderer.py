@@ -23,6 +23,29 @@ Prediction = namedtuple("Prediction", ["rgbds", "color_vars", "depth_vars", "ter
                                        "tsdf_residuals"])
 
 
+class DeviceTarget(namedtuple("DeviceTarget", Target._fields + ("count", "subset_observed", "subset_random", "offsets",
+                                                                "frame_cids", "u_xy", "world_size"))):
+    """What NeuralGraphRenderer.sample_target_mv_device returns: the fields of Target at a fixed, host-known capacity
+    (Fcap, R, ...), `count` = a device int32 tensor (1,) holding the number of surviving fields (rows count..Fcap-1 are
+    padding: field_ids -1, masks 0, zeros elsewhere), plus the draws that produced them."""
+    __slots__ = ()
+
+    def materialize(self) -> Target:
+        """The usual Target, sliced to `count`: reading `count` is the one host synchronisation."""
+        n = int(self.count.item())
+        return Target(*(getattr(self, k)[:n] for k in Target._fields))
+
+    def draws(self) -> dict:
+        """The draws in the conventions of sample_target_mv(draws=...) (subset_observed: positions in current_field_ids,
+        subset_random: field ids, offsets: already normalised, frame_cids / u_xy of the surviving fields): replaying them
+        there reproduces this target.  Single process only (a rank's rows do not hold the other ranks' fields)."""
+        if self.world_size != 1:
+            raise ValueError("DeviceTarget.draws(): a sharded target holds only its own rank's fields")
+        n = int(self.count.item())
+        return dict(subset_observed=self.subset_observed, subset_random=self.subset_random, offsets=self.offsets,
+                    frame_cids=self.frame_cids[:n], u_xy=self.u_xy[:n])
+
+
 class Camera:
     """Pinhole intrinsics with the reference's pixel-centre convention (camera.py:15-116)."""
 
@@ -146,6 +169,7 @@ class NeuralGraphRenderer:
         self.peer_check_interval = 256     # iterations between PeerExchange.check() calls (a device synchronisation each)
         self._peer_calls = 0
         self.field_draw_generator = None   # torch.Generator of sample_target_mv(field_draw="balanced_by_owner"), see there
+        self._target_iter_dev = None       # sample_target_mv_device's iteration counter (device int64, advanced by each call)
 
     def last_matmul(self, kernel: str = "forward") -> Optional[str]:
         """The arithmetic the library resolved `mlp_matmul` to in the LAST launch of the fused forward ("forward"), the
@@ -583,6 +607,45 @@ class NeuralGraphRenderer:
         return Target(ijs=o["ijs"], c2ws=o["c2ws"], near_distances=o["near"], far_distances=o["far"],
                       gt_distances=o["gt"], field_ids=field_ids, rgbds=o["rgbds"], rgb_mask=o["rgb_mask"],
                       depth_mask=o["depth_mask"], term_probs=o["term_probs"], term_mask=o["term_mask"])
+
+    @torch.no_grad()
+    def sample_target_mv_device(self, current_field_ids, c_c2w, nc_rgbd, frame_cid_to_ncid, num_train_fields, num_rays_per_field,
+                                num_fields=None, camera: Optional[Camera] = None, seed: int = 0, iteration: Optional[int] = None,
+                                world_size: int = 1, rank: int = 0) -> DeviceTarget:
+        """sample_target_mv with every draw made on the device (ngm_target_sample_mv: three kernels, no host synchronisation,
+        no data-dependent shapes), so it can be captured in a graph.  Same distribution as the reference's sampler, NOT the
+        same random numbers: the draws come from Philox4x32-10 keyed by (seed, iteration) -- the field draw and offsets by
+        those alone, ray k of field g by (seed, iteration, g, k) -- not from torch's generator.
+        iteration=None: a device counter owned by this renderer is read and advanced by the call (a graph replay draws the
+        next iteration's targets); an int uses that iteration and leaves the counter alone.
+        world_size / rank: every rank draws the same fields; rows are made only for drawn fields with id % world_size == rank
+        (distributed.field_owner), in draw order, bit for bit the single-process rows of those fields.
+        Precondition (not checked: that would synchronise): current_field_ids is duplicate-free, ids in [0, num_fields), as
+        the reference's is.  Returns a DeviceTarget; .materialize() gives the Target for optimization_iteration."""
+        cam = camera or self._camera
+        dev = self._device
+        num_fields = self._global_map_dict["num"] if num_fields is None else num_fields
+        cur = current_field_ids if current_field_ids.device == torch.device(dev) else current_field_ids.to(dev)
+        if cur.dtype != torch.int64:
+            cur = cur.long()
+        counter = None
+        if iteration is None:
+            if self._target_iter_dev is None:
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("sample_target_mv_device: call it once outside the graph capture first (or pass "
+                                       "iteration=...): the device iteration counter must exist before the capture")
+                self._target_iter_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+            counter = self._target_iter_dev
+        fx, fy, cx, cy, _ = cam.get_pinhole_camera_parameters(0.0)
+        o = ops.target_sample_mv(cur.contiguous(), c_c2w.contiguous(), nc_rgbd.contiguous(), frame_cid_to_ncid.contiguous(),
+                                 self._global_map_dict["positions"].contiguous(), fx, fy, cx, cy, self._field_radius + 0.0,
+                                 int(num_fields), int(num_train_fields), int(num_rays_per_field), seed=seed, iteration=iteration,
+                                 iteration_dev=counter, world_size=world_size, rank=rank)
+        return DeviceTarget(ijs=o["ijs"], c2ws=o["c2ws"], near_distances=o["near"], far_distances=o["far"], gt_distances=o["gt"],
+                            field_ids=o["field_ids"], rgbds=o["rgbds"], rgb_mask=o["rgb_mask"], depth_mask=o["depth_mask"],
+                            term_probs=o["term_probs"], term_mask=o["term_mask"], count=o["count"],
+                            subset_observed=o["subset_observed"], subset_random=o["subset_random"], offsets=o["offsets"],
+                            frame_cids=o["frame_cids"], u_xy=o["u_xy"], world_size=int(world_size))
 
     def sample_target_sv(self, rgbd_image, c2w, active_field_ids, num_train_fields, num_rays_per_field,
                          camera: Optional[Camera] = None, draws: Optional[dict] = None, num_points: int = 50000) -> Target:
