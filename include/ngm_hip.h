@@ -595,7 +595,7 @@ int ngm_profile_read(int32_t kernel_id, double* total_ms, int64_t* launches);
 /* Debug: with NGM_PHASE_TIMING set in the environment the backward kernel's first wave records its
  * s_memtime cycles per phase (prologue, inputs, encode, forward, output layer, staging, wgrad, dgrad,
  * encoding grads, relu mask, -, epilogue, total); this copies the 16 counters of the last launch. */
-int ngm_debug_phase_cycles(unsigned long long* out528);   /* 16 slots (-DNGM_PHASE_TIMING) + 8 x 64 timeline entries (-DNGM_BWD_TIMELINE) */
+int ngm_debug_phase_cycles(unsigned long long* out528);   /* 16 slots (-DNGM_PHASE_TIMING) + 8 x 64 words the backward leaves zero */
 /* Same for the fused forward (library built with -DNGM_PHASE_TIMING): slots = prologue, ray setup, sampler, step head,
  * encoding, hidden layers, activation stash stores, output layer, compositing, variance pass, ray outputs, block
  * reduction, -, -, total shader cycles, total 100 MHz ticks; then the event timeline of the 8 waves of that workgroup. */
@@ -616,16 +616,16 @@ int ngm_debug_last_matmul(int which);
 int ngm_debug_last_fwd_one_tile(void);
 /* Debug: 1 when the last ngm_render_bwd / ngm_render_bwd_adam ran the compositing backward inside k_field_bwd_b3 (loss
  * seeds, pointwise geometry modes; no k_stash_bwd launch, the forward's colour / geometry stash stays intact), 0 when
- * k_stash_bwd ran.  Environment: NGM_NO_FUSED_COMP=1 forces the separate kernel. */
+ * k_stash_bwd ran.  ngm_debug_disable_fused_comp(1) forces the separate kernel. */
 int ngm_debug_last_comp_fused(void);
 int ngm_debug_disable_fused_comp(int on);
 /* DEVELOPER override of ngm_field_cfg.activation_stash for A/B timing of one library on one box (tools/): 0 / 1 force that
- * mode for every configuration of the process, -1 queries, -2 removes the override (environment NGM_STASH=full|half does
- * the same at load time).  The product path never calls it: the renderer sets ngm_field_cfg.activation_stash.
+ * mode for every configuration of the process, -1 queries, -2 removes the override.  The product path never calls it: the
+ * renderer sets ngm_field_cfg.activation_stash.
  * Returns the override in force before the call (-1: none). */
 int ngm_debug_stash_mode(int mode);
 int ngm_debug_last_stash_mode(void);   /* the stash the last MLP backward actually read: 0 / 1 as above, -1 none (recompute kernels) */
-  /* 1 = always launch k_stash_bwd (as NGM_NO_FUSED_COMP=1); returns the previous setting */
+  /* 1 = always launch k_stash_bwd; returns the previous setting */
 
 /* ---- one-shot exchange of the loss sums between the ranks of one node ---------------
  * Replaces torch.distributed.all_reduce (RCCL) on the 16 floats between ngm_render_fwd and ngm_render_bwd* by ONE small

@@ -104,11 +104,6 @@ static int g_last_bwd_variant = -1;   // 0: 32-sample tiles, 1: 16-sample tiles 
 static int g_no_fused_comp = 0;       // ngm_debug_disable_fused_comp
 static int g_last_stash_mode = -1;    // FieldBwdArgs::act_half of the last MLP backward that read an activation stash
 static int g_last_comp_fused = 0;     // the last training backward did the compositing backward inside k_field_bwd_b3 (no k_stash_bwd launch)
-// true when launch_bwd_any's first candidate is k_field_bwd_b3 (no experiment switch in the way)
-static bool bwd_b3_is_default() {
-  static const bool off = getenv("NGM_BWD32") != nullptr || getenv("NGM_NO_BWD_B3") != nullptr;
-  return !off;
-}
 // Which targets the LAST forward on a workspace wrote its per-ray loss seeds for (host-side bookkeeping by pointer identity:
 // the fused compositing backward trusts off_rayseed only when the forward that filled this workspace ran with the same
 // targets; a forward without targets, or with other targets, leaves the backward on k_stash_bwd, which derives the seeds
@@ -145,29 +140,31 @@ static bool forward_wrote_seeds_for(const void* ws, const void* rgbds) {
 }
 
 static int launch_bwd_any(FieldBwdArgs& a, int blocks, hipStream_t st) {
-  static const bool force32 = getenv("NGM_BWD32") != nullptr;
   static const bool timing = getenv("NGM_PHASE_TIMING") != nullptr;
   a.debug_cycles = nullptr;
   if (timing) {
     if (!g_debug_cycles) { (void)hipMalloc(&g_debug_cycles, NGM_FWD_DEBUG_WORDS * 8); (void)hipMemset(g_debug_cycles, 0, NGM_FWD_DEBUG_WORDS * 8); }
     a.debug_cycles = g_debug_cycles;
   }
-  // order of preference: stashed activations (no forward recompute) -> 16-sample-tile recompute ->
-  // 32-sample-tile recompute
-  static const bool no_b3 = getenv("NGM_NO_BWD_B3") != nullptr;
+  // In order of preference, the first kernel that takes the problem (the others return NGM_E_UNSUPPORTED):
+  // bf16-split tiles on the activation stash -> hash encoding + 1x32 MLP on its encoding stash -> 16-sample tiles on the
+  // stash -> 16-sample-tile recompute -> 32-sample-tile recompute.
   int e = NGM_E_UNSUPPORTED;
+  auto next = [&](int variant, int (*launch)(const FieldBwdArgs&, int, hipStream_t)) {
+    if (e == NGM_E_UNSUPPORTED) { e = launch(a, blocks, st); g_last_bwd_variant = variant; }
+  };
   g_last_stash_mode = a.act ? a.act_half : -1;
-  if (e == NGM_E_UNSUPPORTED && !force32 && !no_b3 && a.act) { e = ngm_launch_field_bwd_b3(a, blocks, st); g_last_bwd_variant = 3; }
+  if (a.act) next(3, ngm_launch_field_bwd_b3);
   if (a.act_half && e == NGM_E_UNSUPPORTED) {                   // no other kernel reads a half stash: never fall through
     snprintf(g_err, sizeof(g_err), "render_bwd: the forward stashed one hidden layer (split path) but k_field_bwd_b3 does not take this problem");
     return NGM_E_INVALID;
   }
-  if (e == NGM_E_UNSUPPORTED && !force32 && !no_b3 && a.act) { e = ngm_launch_hash_mlp_bwd(a, blocks, st); g_last_bwd_variant = 5; }
+  if (a.act) next(5, ngm_launch_hash_mlp_bwd);
   g_last_comp_fused = (a.fused_comp && e == 0) ? 1 : 0;
-  if (a.fused_comp && e) return e;                              // no other kernel composites: never fall through
-  if (e == NGM_E_UNSUPPORTED && !force32 && a.act) { e = ngm_launch_field_bwd16s(a, blocks, st); g_last_bwd_variant = 2; }
-  if (e == NGM_E_UNSUPPORTED && !force32) { e = ngm_launch_field_bwd16(a, blocks, st); g_last_bwd_variant = 1; }
-  if (e == NGM_E_UNSUPPORTED) { e = ngm_launch_field_bwd(a, blocks, st); g_last_bwd_variant = 0; }
+  if (a.fused_comp) return e;                                   // no other kernel composites: never fall through
+  if (a.act) next(2, ngm_launch_field_bwd16s);
+  next(1, ngm_launch_field_bwd16);
+  next(0, ngm_launch_field_bwd);
   return e;
 }
 static int check_launch(const char* what) {
@@ -603,7 +600,7 @@ int ngm_field_eval_bwd(const ngm_field_cfg* fcfg, const ngm_params* params, int3
 // the backward is the fused step's kernel, k_field_bwd_b3, in point mode.
 static int act_stash_kind(const ngm_field_cfg* fc);
 static bool field_eval_stash_applies(const ngm_field_cfg* fc, int32_t F, int64_t P) {
-  if (act_stash_kind(fc) != 1 || !bwd_b3_is_default()) return false;
+  if (act_stash_kind(fc) != 1) return false;
   FieldBwdArgs probe;
   memset(&probe, 0, sizeof(probe));
   probe.fc = *fc; probe.F = F; probe.P = P;
@@ -746,30 +743,18 @@ static int act_stash_kind(const ngm_field_cfg* fc) {
   return (fc->skip_mode == NGM_SKIP_NO && th == 4 && ti == 4 && fc->num_layers >= 1 && fc->num_layers <= 2) ? 1 : 0;
 }
 
-#ifndef NGM_STASH_DEFAULT
-#define NGM_STASH_DEFAULT 0
-#endif
 // Half stash (round 5): with two hidden layers on the split path the forward stashes layer 0's output only and
 // k_field_bwd_b3<.., HS> recomputes the output layer's input from it on the matrix pipe: 256 instead of 512 bytes of stash per
 // sample each way.  Decided from the field configuration and the samples per field alone, so that ngm_render_fwd and
 // ngm_render_bwd* (which see the same fcfg and rays) agree; the forward's choice is also recorded per workspace.
-// NGM_FULL_STASH=1: both layers, as before (A/B, and what every other backward kernel reads).
-// NGM_STASH=full | half | planes overrides the default (A/B on one box); NGM_FULL_STASH=1 = NGM_STASH=full.
 // ABI 10: the mode is ngm_field_cfg.activation_stash; the override below is a developer A/B switch only (tools/)
 static int g_stash_override = -1;      // ngm_debug_stash_mode
 static int stash_pref(const ngm_field_cfg* fc) {
   if (g_stash_override >= 0) return g_stash_override;
-  static const int env = [] {
-    const char* e = getenv("NGM_STASH");
-    if (getenv("NGM_FULL_STASH")) return 0;
-    if (!e) return -1;
-    return !strcmp(e, "full") ? 0 : !strcmp(e, "half") ? 1 : -1;
-  }();
-  if (env >= 0) return env;
-  return fc->activation_stash == NGM_STASH_HALF ? 1 : NGM_STASH_DEFAULT;
+  return fc->activation_stash == NGM_STASH_HALF ? 1 : 0;
 }
 static bool half_stash_applies(const ngm_field_cfg* fc, int64_t P) {
-  if (stash_pref(fc) == 0 || !bwd_b3_is_default() || fc->num_layers != 2 || act_stash_kind(fc) != 1) return false;
+  if (stash_pref(fc) == 0 || fc->num_layers != 2 || act_stash_kind(fc) != 1) return false;
   FieldBwdArgs probe;
   memset(&probe, 0, sizeof(probe));
   probe.fc = *fc; probe.P = P; probe.act = reinterpret_cast<const float*>(1);
@@ -999,25 +984,24 @@ static int render_bwd_common(const ngm_field_cfg* fcfg, const ngm_render_cfg* rc
     a.act_half = a.act ? (rec < 0 ? p.stash_mode : rec) : 0;
   }
   // Compositing backward inside the MLP backward (k_field_bwd_b3<FC>, k_hash_mlp_bwd<FC>): loss seeds, pointwise geometry
-  // modes, and a kernel that implements it about to be chosen.  Otherwise k_stash_bwd runs first and leaves
-  // dL/d(raw outputs) in place of the forward's stash.  NGM_NO_FUSED_COMP=1: never.
-  static const bool no_fuse_env = getenv("NGM_NO_FUSED_COMP") != nullptr;
-  const bool no_fuse = no_fuse_env || g_no_fused_comp;
+  // modes, and a kernel that takes the problem with the fused fields set (launch_bwd_any tries the same two first).  Otherwise
+  // k_stash_bwd runs first and leaves dL/d(raw outputs) in place of the forward's stash.  ngm_debug_disable_fused_comp: never.
   const bool pointwise = rcfg->geometry_mode != NGM_GEO_NEUS && rcfg->geometry_mode != NGM_GEO_DENSITY;
   // the variance-weighted loss modes (gradients through the rendered variances) are k_stash_bwd's
   const bool nll_loss = rcfg->photometric_mode == NGM_PHOTO_GAUSSIAN_NLL || rcfg->depth_mode != NGM_DEPTH_HUBER;
   if (nll_loss && sb.seed_mode == 0 && (!sb.pred.color_vars || !sb.pred.depth_vars))
     return fail(NGM_E_INVALID, "render_bwd: the *_nll loss modes need pred.color_vars and pred.depth_vars");
-  bool fuse = !no_fuse && !nll_loss && sb.seed_mode == 0 && pointwise && bwd_b3_is_default() && a.P < (1 << 24) &&
-              forward_wrote_seeds_for(workspace, sb.tg.rgbds) && (ngm_field_bwd_b3_applies(a) || ngm_hash_mlp_bwd_applies(a));
+  FieldBwdArgs af = a;
+  af.fused_comp = 1; af.rc = sb.rc;
+  af.rayseed = reinterpret_cast<const float*>(ws + p.off_rayseed);
+  af.loss_sums = sb.loss_sums; af.loss_partials = sb.loss_partials; af.n_partials = sb.n_partials;
+  af.sums_out = sb.sums_out; af.loss_out = sb.loss_out; af.counter = sb.counter;
+  // (hash encoding: k_hash_mlp_bwd writes the positions k_hash_grad needs into a.hash_xyz itself)
+  const bool fuse = !g_no_fused_comp && !nll_loss && sb.seed_mode == 0 && pointwise && a.P < (1 << 24) &&
+                    forward_wrote_seeds_for(workspace, sb.tg.rgbds) && (ngm_field_bwd_b3_applies(af) || ngm_hash_mlp_bwd_applies(af));
   int e = 0;
-  const FieldBwdArgs a_plain = a;            // for the fall-back below: the launch records before the fused fields are set
   if (fuse) {
-    a.fused_comp = 1; a.rc = sb.rc;
-    a.rayseed = reinterpret_cast<const float*>(ws + p.off_rayseed);
-    a.loss_sums = sb.loss_sums; a.loss_partials = sb.loss_partials; a.n_partials = sb.n_partials;
-    a.sums_out = sb.sums_out; a.loss_out = sb.loss_out; a.counter = sb.counter;
-    // (hash encoding: k_hash_mlp_bwd writes the positions k_hash_grad needs into a.hash_xyz itself)
+    a = af;
   } else {
     sb.xyz_out = a.hash_xyz;                 // positions for the table-gradient kernel (hash encoding)
     a.hash_xyz_ready = a.hash_xyz != nullptr;
@@ -1032,20 +1016,6 @@ static int render_bwd_common(const ngm_field_cfg* fcfg, const ngm_render_cfg* rc
   e = prep_lattice_grad(fcfg, grads, rays->F, a, st);
   if (e) return e;
   e = launch_bwd_any(a, a.blocks_per_field * a.F, st);
-  if (e == NGM_E_UNSUPPORTED && fuse) {
-    // the fused kernel declined after all (its own LDS / shape checks): composite in k_stash_bwd, then any MLP backward
-    fuse = false;
-    a = a_plain;
-    sb.xyz_out = a.hash_xyz;
-    a.hash_xyz_ready = a.hash_xyz != nullptr;
-    e = ngm_launch_stash_bwd(sb, st);
-    if (e) return fail(e, "render_bwd: unsupported geometry mode");
-    e = check_launch("ngm_stash_bwd");
-    if (e) return e;
-    e = prep_lattice_grad(fcfg, grads, rays->F, a, st);
-    if (e) return e;
-    e = launch_bwd_any(a, a.blocks_per_field * a.F, st);
-  }
   if (e) return fail(e, "render_bwd: no kernel for this (D,H,L)");
   e = check_launch("ngm_field_bwd");
   if (e) return e;

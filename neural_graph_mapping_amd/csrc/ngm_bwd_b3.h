@@ -3,23 +3,6 @@
 #pragma once
 #include "ngm_bwd16.h"
 
-// -DNGM_DMAWAIT_TIMING: only the clocks spent in the tile-start DMA wait (slot 2) and the kernel total (slot 12)
-#ifdef NGM_DMAWAIT_TIMING
-#undef TICK_DECL
-#undef TICK
-#undef TICK_REPORT
-#define TICK_DECL unsigned long long tw_ = 0, tl_ = 0; const unsigned long long ts_ = __builtin_readcyclecounter()
-#define TICK(k)                                                                  \
-  do {                                                                           \
-    if ((k) == 10) tl_ = __builtin_readcyclecounter();                           \
-    if ((k) == 2) tw_ += __builtin_readcyclecounter() - tl_;                     \
-  } while (0)
-#define TICK_REPORT                                                                                \
-  if (a.debug_cycles && blockIdx.x == gridDim.x / 2 && threadIdx.x == 64) {                        \
-    for (int k = 0; k < 13; ++k) a.debug_cycles[k] = 0;                                            \
-    a.debug_cycles[2] = tw_; a.debug_cycles[12] = __builtin_readcyclecounter() - ts_;              \
-  }
-#endif
 #define B3B_WAVES 4
 #define B3B_THREADS 256
 #define HT 2048                 // floats of one 32 x 64 activation tile
@@ -83,10 +66,10 @@ __device__ __forceinline__ void dma16_x4(const char* sb, uint32_t voff, uint32_t
       "s_mov_b32 %0, m0\n\t"
       "s_mov_b32 m0, %3\n\t"
       "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, %2 " NGM_DMA_HINT "\n\t"
-      "global_load_lds_dwordx4 %1, %2 offset:1024 " NGM_DMA_HINT "\n\t"
-      "global_load_lds_dwordx4 %1, %2 offset:2048 " NGM_DMA_HINT "\n\t"
-      "global_load_lds_dwordx4 %1, %2 offset:3072 " NGM_DMA_HINT "\n\t"
+      "global_load_lds_dwordx4 %1, %2 nt\n\t"
+      "global_load_lds_dwordx4 %1, %2 offset:1024 nt\n\t"
+      "global_load_lds_dwordx4 %1, %2 offset:2048 nt\n\t"
+      "global_load_lds_dwordx4 %1, %2 offset:3072 nt\n\t"
       "s_mov_b32 m0, %0"
       : "=&s"(keep)
       : "v"(voff), "s"(sb), "s"(lds_base)

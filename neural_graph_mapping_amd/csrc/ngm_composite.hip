@@ -887,8 +887,7 @@ int ngm_launch_composite_bwd(const CompositeArgs& a, hipStream_t st) {
   int rpw;
   const int blocks = comp_grid(a.N, a.S, &rpw);
   const int gm = a.rc.geometry_mode;
-  static const bool no_whole = getenv("NGM_NO_WHOLE_COMP_BWD") != nullptr;       // A/B and test knob: the generic kernel
-  if (!no_whole && a.S % 64 == 0 && a.S <= 512 && (gm == NGM_GEO_NRGBD || gm == NGM_GEO_OCCUPANCY) && !comp_packed_host(a) &&
+  if (a.S % 64 == 0 && a.S <= 512 && (gm == NGM_GEO_NRGBD || gm == NGM_GEO_OCCUPANCY) && !comp_packed_host(a) &&
       a.colors && a.geoms && a.depths) {
 #define NGM_CBW(N_) hipLaunchKernelGGL((k_composite_bwd_whole<N_>), dim3(std::max(blocks, 1)), dim3(NGM_BLOCK), 0, st, a, rpw)
     switch (a.S / 64) { case 1: NGM_CBW(1); break; case 2: NGM_CBW(2); break; case 3: NGM_CBW(3); break; case 4: NGM_CBW(4); break;

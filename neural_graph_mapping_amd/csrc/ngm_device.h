@@ -184,31 +184,10 @@ __device__ __forceinline__ float ngm_relu(float y) {
   return r;
 }
 
-// Two sines per instruction stream: the same routine as ngm_sinf on a float2, so that the 13 arithmetic steps
-// compile to packed-fp32 instructions (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32: two lanes' worth of fp32 per
-// issue slot on gfx950); only the sign flip stays per element.  Element-wise identical to ngm_sinf.
+// Packed-fp32 helpers: two lanes' worth of fp32 per issue slot on gfx950 (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32).
 typedef float ngm_v2f __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ ngm_v2f ngm_splat2(float v) { return ngm_v2f{v, v}; }
 __device__ __forceinline__ ngm_v2f ngm_fma2(ngm_v2f a, ngm_v2f b, ngm_v2f c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ ngm_v2f ngm_sinf2(ngm_v2f x) {
-  const ngm_v2f magic = ngm_splat2(12582912.0f);
-  const ngm_v2f n = ngm_fma2(x, ngm_splat2(0.3183098861837907f), magic);
-  const ngm_v2f k = n - magic;
-  ngm_v2f r = ngm_fma2(k, ngm_splat2(-3.140625f), x);
-  r = ngm_fma2(k, ngm_splat2(-9.670257568359375e-4f), r);
-  r = ngm_fma2(k, ngm_splat2(-6.2771141529083251953e-7f), r);
-  const ngm_v2f z = r * r;
-  ngm_v2f p = ngm_splat2(-2.3846690373585197e-08f);
-  p = ngm_fma2(p, z, ngm_splat2(2.7522618610619714e-06f));
-  p = ngm_fma2(p, z, ngm_splat2(-1.9840804033395678e-04f));
-  p = ngm_fma2(p, z, ngm_splat2(8.33333049561397e-03f));
-  p = ngm_fma2(p, z, ngm_splat2(-1.6666666606465025e-01f));
-  const ngm_v2f s = ngm_fma2(r * z, p, r);
-  ngm_v2f o;
-  o.x = __uint_as_float(__float_as_uint(s.x) ^ (__float_as_uint(n.x) << 31));
-  o.y = __uint_as_float(__float_as_uint(s.y) ^ (__float_as_uint(n.y) << 31));
-  return o;
-}
 
 // ------------------------------------------------------------------------------------------------
 // Write-through (sc1) stores for data one kernel hands to the NEXT launch (round 6).  A consumer workgroup lands on any XCD;

@@ -194,26 +194,19 @@ template <int MI>
 __device__ __forceinline__ void encode_pair_sin(const float* sm_encw, int hi, ngm_v2f x, ngm_v2f y, ngm_v2f z,
                                                 f32x16 (&E0)[MI], f32x16 (&E1)[MI]) {
   const float4* tab = reinterpret_cast<const float4*>(sm_encw);
-#ifndef NGM_FWD_POLYSIN
   const ngm_v2f xr = x * ngm_splat2(0.15915494309189535f), yr = y * ngm_splat2(0.15915494309189535f),
                 zr = z * ngm_splat2(0.15915494309189535f);
-#endif
 #pragma unroll
   for (int mi = 0; mi < MI; ++mi) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const float4 w = tab[32 * mi + frow(r, 0) + 4 * hi];
-#ifndef NGM_FWD_POLYSIN  // default: v_sin_f32 on the argument in revolutions (position pre-scaled by 1/(2 pi)); measured
-      // parity error of the fused forward against the oracle is unchanged (7e-7 vs 1e-6 abs at sigma 4, 1.8e-6 vs 3.2e-6
-      // at sigma 25: the fp32 evaluation order dominates, not the sine) and the kernel is 5 us faster.
-      // -DNGM_FWD_POLYSIN restores the 1.2e-7 polynomial (ngm_sinf2).
+      // v_sin_f32 on the argument in revolutions (position pre-scaled by 1/(2 pi)); against the 1.2e-7 polynomial it replaced,
+      // the measured parity error of the fused forward against the oracle is unchanged (7e-7 vs 1e-6 abs at sigma 4, 1.8e-6
+      // vs 3.2e-6 at sigma 25: the fp32 evaluation order dominates, not the sine) and the kernel is 5 us faster.
       const ngm_v2f rev = ngm_fma2(ngm_splat2(w.z), zr, ngm_fma2(ngm_splat2(w.y), yr, ngm_splat2(w.x) * xr));
       ngm_v2f v = {__builtin_amdgcn_sinf(__builtin_amdgcn_fractf(rev.x)), __builtin_amdgcn_sinf(__builtin_amdgcn_fractf(rev.y))};
       const ngm_v2f arg = {r == 0 ? x.x : r == 1 ? y.x : z.x, r == 0 ? x.y : r == 1 ? y.y : z.y};   // raw rows only
-#else
-      const ngm_v2f arg = ngm_fma2(ngm_splat2(w.z), z, ngm_fma2(ngm_splat2(w.y), y, ngm_splat2(w.x) * x));
-      ngm_v2f v = ngm_sinf2(arg);
-#endif
       if (mi == 0 && r < 3) { const bool raw = (w.w == NGM_FK_RAW); v.x = raw ? arg.x : v.x; v.y = raw ? arg.y : v.y; }
       E0[mi][r] = v.x; E1[mi][r] = v.y;
       if ((r & 3) == 3) __builtin_amdgcn_sched_barrier(0);
@@ -585,39 +578,13 @@ __device__ __forceinline__ void b3_split(float x, uint32_t& h, uint32_t& m, uint
 // two bf16 (upper halves of even / odd) -> one packed word, even element in the low half
 __device__ __forceinline__ uint32_t b3_pack(uint32_t even, uint32_t odd) { return __builtin_amdgcn_perm(odd, even, 0x07060302u); }
 
-// One pair of values -> the three packed words (even element in the low half).  Three forms of the same exact
-// arithmetic (bit-identical planes for normal numbers, tools/micro/dot2c_split.hip):
-//   default       h = x & 0xffff0000, r = x - h, ... : 4 VALU per element + 3 v_perm per pair
-//   NGM_SPLIT_DOT2C  the packed hi pair is formed FIRST (one v_perm straight from the fp32 registers), and each residual is
-//                 one v_dot2c_f32_bf16 (gfx950): r0 = x0 + hp.lo * (-1) + hp.hi * 0 -- exact, since r is representable --
-//                 2 VALU per element + 3 v_perm per pair
-//   NGM_SPLIT_PK  the two residual subtractions of a pair as one v_pk_add_f32
+// One pair of values -> the three packed words (even element in the low half): h = x & 0xffff0000, r = x - h, ... :
+// 4 VALU per element + 3 v_perm per pair
 __device__ __forceinline__ void b3_split2(float x0, float x1, uint32_t& hp, uint32_t& mp, uint32_t& lp) {
-#if defined(NGM_SPLIT_DOT2C)
-  typedef __bf16 bf2_ __attribute__((ext_vector_type(2)));
-  uint32_t clo = 0x0000bf80u, chi = 0xbf800000u;        // (-1, 0) and (0, -1) as (low, high) bf16
-#if NGM_SPLIT_DOT2C == 1
-  asm("" : "+v"(clo)); asm("" : "+v"(chi));             // keep them in registers (no inline-constant folding)
-#endif
-  hp = b3_pack(__float_as_uint(x0), __float_as_uint(x1));
-  const float r0 = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf2_, hp), __builtin_bit_cast(bf2_, clo), x0, false);
-  const float r1 = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf2_, hp), __builtin_bit_cast(bf2_, chi), x1, false);
-  mp = b3_pack(__float_as_uint(r0), __float_as_uint(r1));
-  const float q0 = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf2_, mp), __builtin_bit_cast(bf2_, clo), r0, false);
-  const float q1 = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf2_, mp), __builtin_bit_cast(bf2_, chi), r1, false);
-  lp = b3_pack(__float_as_uint(q0), __float_as_uint(q1));
-#elif defined(NGM_SPLIT_PK)
-  const uint32_t h0 = __float_as_uint(x0) & 0xffff0000u, h1 = __float_as_uint(x1) & 0xffff0000u;
-  const ngm_v2f r = ngm_v2f{x0, x1} - ngm_v2f{__uint_as_float(h0), __uint_as_float(h1)};
-  const uint32_t m0 = __float_as_uint(r.x) & 0xffff0000u, m1 = __float_as_uint(r.y) & 0xffff0000u;
-  const ngm_v2f q = r - ngm_v2f{__uint_as_float(m0), __uint_as_float(m1)};
-  hp = b3_pack(h0, h1); mp = b3_pack(m0, m1); lp = b3_pack(__float_as_uint(q.x), __float_as_uint(q.y));
-#else
   uint32_t h0, m0, l0, h1, m1, l1;
   b3_split(x0, h0, m0, l0);
   b3_split(x1, h1, m1, l1);
   hp = b3_pack(h0, h1); mp = b3_pack(m0, m1); lp = b3_pack(l0, l1);
-#endif
 }
 
 __device__ __forceinline__ void b3_split8(const float (&x)[8], ngm_bf16x8& H, ngm_bf16x8& M, ngm_bf16x8& Lo) {
@@ -630,16 +597,10 @@ __device__ __forceinline__ void b3_split8(const float (&x)[8], ngm_bf16x8& H, ng
   ngm_u32x4 h4, m4, l4;
 #pragma unroll
   for (int p = 0; p < 4; ++p) {
-#if defined(NGM_SPLIT_DOT2C) || defined(NGM_SPLIT_PK)
-    uint32_t hp, mp, lp;
-    b3_split2(x[2 * p], x[2 * p + 1], hp, mp, lp);
-    h4[p] = hp; m4[p] = mp; l4[p] = lp;
-#else
     uint32_t h0, m0, l0, h1, m1, l1;
     b3_split(x[2 * p], h0, m0, l0);
     b3_split(x[2 * p + 1], h1, m1, l1);
     h4[p] = b3_pack(h0, h1); m4[p] = b3_pack(m0, m1); l4[p] = b3_pack(l0, l1);
-#endif
   }
   H = __builtin_bit_cast(ngm_bf16x8, h4); M = __builtin_bit_cast(ngm_bf16x8, m4); Lo = __builtin_bit_cast(ngm_bf16x8, l4);
 }
@@ -842,12 +803,7 @@ __device__ __forceinline__ void act_store(const ActStash& st, int layer, int lan
           typedef float v4f __attribute__((ext_vector_type(4)));
           const v4f val = {H[nt][m][4 * g4], H[nt][m][4 * g4 + 1], H[nt][m][4 * g4 + 2], H[nt][m][4 * g4 + 3]};
           const int pos = r ^ ((2 * g4 + hi) & 7);                       // chunk = 8 m + 2 g4 + hi
-#ifdef NGM_STASH_NT    // rounds 1-5: non-temporal stores (the lines stay in the writing XCD's L2 until evicted, dirty)
-          constexpr bool wt_ = false;
-#else
-          constexpr bool wt_ = WT;
-#endif
-          if constexpr (!wt_) {
+          if constexpr (!WT) {
             __builtin_nontemporal_store(val, reinterpret_cast<v4f*>(p + (8 * m + 2 * g4) * 128 + 4 * pos));
           } else {
           // Round 6: WRITE-THROUGH stores (sc1).  The stash is read once, by the NEXT kernel, from whichever XCD its workgroup
@@ -855,7 +811,7 @@ __device__ __forceinline__ void act_store(const ActStash& st, int layer, int lan
           // transfers are served by the memory side directly.  Same-box A/B at the M1 batch: forward 82.3 -> 80.8 us,
           // BACKWARD 142.5 -> 138.9 us, step 0.2324 -> 0.2266 ms (MI355X_MICROARCH.md, "publish-large": write-through wins for
           // tens of KB per workgroup handed to another kernel).
-          asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(reinterpret_cast<v4f*>(p + (8 * m + 2 * g4) * 128 + 4 * pos)), "v"(val));
+          ngm_store_wt(reinterpret_cast<v4f*>(p + (8 * m + 2 * g4) * 128 + 4 * pos), val);
           }
         }
     }

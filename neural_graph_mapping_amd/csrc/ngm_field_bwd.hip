@@ -835,7 +835,7 @@ __device__ __forceinline__ float hash_acc_value(typename HashAcc<FLT>::T v) {
   if constexpr (FLT) return v;
   else return (float)((double)(long long)v * (1.0 / 1099511627776.0));
 }
-// NL = levels per workgroup.  NL = 2 (round 6 experiment, NGM_HASH_PAIR=1; NOT the default: 2 us slower): a workgroup of 1024
+// NL = levels per workgroup.  NL = 2 (round 6 experiment, not launched: 2 us slower): a workgroup of 1024
 // threads owns the level PAIR (l, L - 1 - l) of its (field, chunk) with both tables in LDS (2 x 64 KB): the position of a
 // sample is read once for two levels (384 -> 256 B per sample over the 16 levels) and a thread carries two independent
 // simplex searches.  Measured equal-to-slower than one level per workgroup: the loop is not bound by its loads.
@@ -1086,18 +1086,13 @@ int ngm_launch_hash_grad(const FieldBwdArgs& fb, hipStream_t st, bool* adam_appl
   a.gtab = fb.lattice_grad; a.gstride = fb.lattice_grad_stride;
   const int T = 1 << fb.fc.log2_hashmap_size;
   const bool flt = fb.fc.hash_grad_atomics == NGM_HASH_ATOMICS_FLOAT;
-  const size_t lds1 = (size_t)2 * T * (flt ? sizeof(float) : sizeof(unsigned long long));
-  if (lds1 > 150 * 1024) return NGM_E_UNSUPPORTED;
-  // level pairs (k_hash_grad<., 2>): both tables of a pair in one workgroup's LDS.  NGM_HASH_PAIR=0: one level per workgroup
-  // (the round-5 kernel; A/B inside one library)
-  static const bool pair_on = getenv("NGM_HASH_PAIR") != nullptr && atoi(getenv("NGM_HASH_PAIR")) == 1;
-  const bool pair = pair_on && (fb.fc.nr_levels & 1) == 0 && 2 * lds1 <= 150 * 1024;
-  const size_t lds = pair ? 2 * lds1 : lds1;
-  const int units = (int)fb.F * (pair ? fb.fc.nr_levels / 2 : fb.fc.nr_levels);      // (field, level) or (field, level pair)
+  const size_t lds = (size_t)2 * T * (flt ? sizeof(float) : sizeof(unsigned long long));
+  if (lds > 150 * 1024) return NGM_E_UNSUPPORTED;
+  const int units = (int)fb.F * fb.fc.nr_levels;      // (field, level)
+  constexpr int NT = 512;                              // threads per workgroup (table gradient and the riding MLP reduction)
   // One level per workgroup: 2 blocks per CU = exactly what is resident at a time (64 KB of LDS each), one round: with the
   // coarse / fine level pairing of the block decoding the CUs finish together (M1 hash batch, kernel time: 4 chunks 99 us,
-  // 6: 100, 8: 102, 5: 115; before the pairing 4 chunks cost 118 -- two coarse levels on one CU).  Level pairs: one
-  // 1024-thread workgroup per CU.
+  // 6: 100, 8: 102, 5: 115; before the pairing 4 chunks cost 118 -- two coarse levels on one CU).
   int ncu = 256;
   {
     int dev = 0;
@@ -1107,14 +1102,12 @@ int ngm_launch_hash_grad(const FieldBwdArgs& fb, hipStream_t st, bool* adam_appl
       cached = prop.multiProcessorCount;
     if (cached) ncu = cached;
   }
-  const int slots = pair ? ncu : 2 * ncu;
+  const int slots = 2 * ncu;
   int chunks = (int)((slots + (int64_t)units - 1) / (int64_t)units);
   const int64_t max_chunks = (fb.P + 4095) / 4096;
   if (chunks > max_chunks) chunks = (int)max_chunks;
   if (chunks < 1) chunks = 1;
   if (chunks > 8) chunks = 8;
-  static const char* env_chunks = getenv("NGM_HASH_CHUNKS");      // experiment knob (1..8)
-  if (env_chunks && atoi(env_chunks) >= 1 && atoi(env_chunks) <= 8 && atoi(env_chunks) <= max_chunks) chunks = atoi(env_chunks);
   a.chunks = chunks; a.per_chunk = (fb.P + chunks - 1) / chunks;
   a.part = fb.hash_part;
   a.ad_param = nullptr; a.ad_lp = nullptr; a.ad_lp_dt = 0;
@@ -1132,29 +1125,24 @@ int ngm_launch_hash_grad(const FieldBwdArgs& fb, hipStream_t st, bool* adam_appl
     }
   }
   a.hash_blocks = chunks * units;
-  static const bool no_ride = getenv("NGM_NO_REDUCE_RIDE") != nullptr;          // developer A/B switch
-  if (mlp_reduce && !no_ride) {
+  if (mlp_reduce) {
     if (build_grad_reduce(*mlp_reduce, a.mlp)) return NGM_E_INVALID;
-    const int nt = (pair || (getenv("NGM_HASH_THREADS") != nullptr && atoi(getenv("NGM_HASH_THREADS")) == 1024)) ? 1024 : 512;
-    a.mlp_bx = (int)((a.mlp.ptot + nt - 1) / nt);
+    a.mlp_bx = (int)((a.mlp.ptot + NT - 1) / NT);
     if (mlp_reduced) *mlp_reduced = true;
   }
   const int grid_x = a.hash_blocks + a.mlp_bx * (int)fb.F;
   {
     NgmProfScope prof_(NGM_K_HASH_GRAD, st);
-#define NGM_HG(FLT_, NL_, NT_)                                                                                                  \
-    do {                                                                                                                        \
-      (void)hipFuncSetAttribute((const void*)k_hash_grad<FLT_, NL_, NT_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-      hipLaunchKernelGGL((k_hash_grad<FLT_, NL_, NT_>), dim3(grid_x), dim3(NT_), lds, st, a);                                    \
+#define NGM_HG(FLT_)                                                                                                          \
+    do {                                                                                                                      \
+      (void)hipFuncSetAttribute((const void*)k_hash_grad<FLT_, 1, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+      hipLaunchKernelGGL((k_hash_grad<FLT_, 1, NT>), dim3(grid_x), dim3(NT), lds, st, a);                                    \
     } while (0)
     // Round 6 A/B on one box (profiles/r06_hash_ablation.txt), M1 hash batch at 2397 MHz: one level per workgroup, 512 threads
     // (two resident workgroups = 4 waves per SIMD) 76.7 us; 1024 threads (8 waves per SIMD) 84.9 us; level pairs 78.8 us.  More
     // waves do not help (the LDS atomic unit is shared by them), sharing the position load does not either (the loop is bound
-    // by its own instructions, not by the loads).  NGM_HASH_THREADS=1024 / NGM_HASH_PAIR=1 reproduce the comparison.
-    static const bool wide = getenv("NGM_HASH_THREADS") != nullptr && atoi(getenv("NGM_HASH_THREADS")) == 1024;
-    if (pair) { if (flt) NGM_HG(true, 2, 1024); else NGM_HG(false, 2, 1024); }
-    else if (wide) { if (flt) NGM_HG(true, 1, 1024); else NGM_HG(false, 1, 1024); }
-    else { if (flt) NGM_HG(true, 1, 512); else NGM_HG(false, 1, 512); }
+    // by its own instructions, not by the loads).
+    if (flt) NGM_HG(true); else NGM_HG(false);
 #undef NGM_HG
   }
   if (chunks > 1) {        // one chunk: k_hash_grad wrote the gradient table and applied the update itself

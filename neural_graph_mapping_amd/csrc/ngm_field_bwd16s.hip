@@ -72,20 +72,6 @@ __device__ __forceinline__ void load16b(const float* buf, int lane, f32x4 (&V)[4
   }
 }
 
-// Weight-gradient accumulate with the accumulator pinned to the AGPR half of the register file.  The
-// 2 x 64 accumulator registers live for the whole kernel; left to the allocator (VGPR-form MFMA, one
-// 256-register pool) it spills a third of them inside the tile loop, every spill store serialised
-// behind its MFMA.  "+a" makes them AGPRs: 128 AGPRs for the accumulators, 128 VGPRs for the rest.
-// No software wait states are needed: an accumulator is only consumed as SrcC of the same opcode
-// (back-to-back accumulate) and by the epilogue, a barrier away.
-__device__ __forceinline__ void mfma16_agpr(f32x4& acc, float a, float b) {
-#ifndef NGM_S_AGPRFORM
-  acc = mfma16(a, b, acc);
-#else
-  asm("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
-#endif
-}
-
 // Data-gradient MFMAs in explicit VGPR form.  Once a function uses AGPRs hipcc selects the AGPR form for
 // every builtin MFMA, and dX's 16 destination registers would then compete with the 128 accumulator
 // AGPRs (it spilled 64 of them per tile).  The compiler cannot see into the asm, so the MFMA -> VALU read
@@ -157,7 +143,7 @@ __device__ __forceinline__ void wgrad16b(const float* __restrict__ dbuf, const f
 #pragma unroll
     for (int mo = 0; mo < 4; ++mo)
 #pragma unroll
-      for (int mi = 0; mi < 4; ++mi) mfma16_agpr(acc[mo][mi], av[t & 1][mo], bv[t & 1][mi]);
+      for (int mi = 0; mi < 4; ++mi) acc[mo][mi] = mfma16(av[t & 1][mo], bv[t & 1][mi], acc[mo][mi]);
     __builtin_amdgcn_sched_barrier(0);
   }
 }
@@ -209,33 +195,10 @@ __device__ __forceinline__ void issue_act(const char* sbase, uint32_t gb, uint32
   }
 }
 
-#ifndef NGM_OLDER_SHARE
-#define NGM_OLDER_SHARE 18u     // 32nds of a workgroup's tiles that go to its four older waves (see the tile lists below)
-#endif
-
-// per-wave event timeline of the middle workgroup (debug builds, -DNGM_BWD_TIMELINE; a.debug_cycles must hold
-// 16 + 8 * 64 words): entry, after the prologue barrier, every tile start, loop end, kernel end
-#ifdef NGM_BWD_TIMELINE
-#define BTL_DECL                                                                                                    \
-  unsigned long long* btl = (a.debug_cycles && blockIdx.x == gridDim.x / 2 && (threadIdx.x & 63) == 0)              \
-                                ? a.debug_cycles + 16 + 64 * (threadIdx.x >> 6) : nullptr;                        \
-  int btl_n = 0;                                                                                                    \
-  const unsigned long long btl_t0 = __builtin_readcyclecounter()
-#define BTL(k)                                                                                                      \
-  do {                                                                                                              \
-    if (btl && btl_n < 64) btl[btl_n] = ((unsigned long long)(k) << 48) | (__builtin_readcyclecounter() - btl_t0);  \
-    ++btl_n;                                                                                                        \
-  } while (0)
-#else
-#define BTL_DECL
-#define BTL(k)
-#endif
-
 // ------------------------------------------------------------------------------------------------
 template <int L, bool NEED_COS, bool ENC_GRAD>
 __global__ __launch_bounds__(B16_THREADS) void k_field_bwd16s(FieldBwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  BTL_DECL;
   using LY = Lds16s<L>;
   using LW = typename LY::W;
   constexpr int BLK = LW::BLK;
@@ -271,10 +234,11 @@ __global__ __launch_bounds__(B16_THREADS) void k_field_bwd16s(FieldBwdArgs a) {
   const uint32_t beg = (uint32_t)chunk * (uint32_t)a.per_block, end = (uint32_t)min(a.P, (int64_t)beg + a.per_block);
   // Tile lists.  The SIMD's arbiter favours its older wave (waves 0-3 of the workgroup): with an even split those
   // finished ~2 of 16 tiles ahead of waves 4-7, which then ran their last tiles alone, without a partner to hide
-  // LDS / DMA latency behind (wave timeline, -DNGM_BWD_TIMELINE).  So the older waves take NGM_OLDER_SHARE/32 = 18/32 of the tiles (17: 180.6 us, 18: 178.6, 19: 180.5):
+  // LDS / DMA latency behind (wave timeline).  So the older waves take older_share/32 = 18/32 of the tiles (17: 180.6 us, 18: 178.6, 19: 180.5):
   // tiles [0, nA) go round-robin to waves 0-3, tiles [nA, T) to waves 4-7.  Static, hence deterministic.
+  constexpr uint32_t older_share = 18u;
   const uint32_t T = (end - beg + 15u) >> 4;
-  uint32_t nA = ((T * NGM_OLDER_SHARE + 31u) / 32u + 3u) & ~3u;
+  uint32_t nA = ((T * older_share + 31u) / 32u + 3u) & ~3u;
   if (nA > T) nA = T;
   const bool older = wave < 4;
   const uint32_t first = beg + 16u * (older ? (uint32_t)wave : nA + (uint32_t)(wave - 4));
@@ -312,14 +276,12 @@ __global__ __launch_bounds__(B16_THREADS) void k_field_bwd16s(FieldBwdArgs a) {
     stage.commit(sm, a.fc);
   }
   __syncthreads();
-  BTL(1);
   TICK_DECL;
   TICK(0);
   for (uint32_t base = first; base < lend; base += TSTRIDE) {
     const uint32_t n = base + j, nxt = base + TSTRIDE;
     const bool valid = n < end, more = nxt < lend;
     // ---- inputs and the last hidden activation tile (landed while the previous tile was differentiated)
-    BTL(2);
     TICK(10);   // loop back-edge
     DMA_WAIT(0);
     TICK(3);    // wait for inputs + last hidden tile
@@ -430,9 +392,7 @@ __global__ __launch_bounds__(B16_THREADS) void k_field_bwd16s(FieldBwdArgs a) {
   }
   DMA_WAIT(0);
   TICK(10);
-  BTL(3);
   __syncthreads();
-  BTL(4);
 #ifdef NGM_ABLS_NOEPI   // timing ablation: keep the accumulators alive with one store, skip the reduction
   {
     float keep = dbh[0] + dwo[0] + dwo[1] + dwo[2] + dwo[3] + dwf[0] + dwf[1] + dwf[2] + dbo[0] + dbo[1] + dbo[2] + dbo[3];
@@ -450,7 +410,6 @@ __global__ __launch_bounds__(B16_THREADS) void k_field_bwd16s(FieldBwdArgs a) {
   constexpr int EPI = (L == 2) ? 16 : 8;                     // 2 rounds for either depth
   static_assert(LW::WTOTAL + B16_WAVES * LY::WAVE_TOTAL >= B16_WAVES * EPI * 256, "epilogue staging does not fit");
   bwd16_epilogue<4, 4, L, ENC_GRAD, EPI>(a, sm, acc0, accH, dbh, dwo, dwf, dbo);
-  BTL(5);
   TICK(11);
   TICK_REPORT
 }

@@ -475,7 +475,6 @@ __global__ __launch_bounds__(B3B_THREADS) void k_field_bwd_b3(FieldBwdArgs a) {
         // lane = output feature, registers = samples: the "lane = feature" layout the rest of this phase works in.  Same block
         // structure as a data gradient (row splits of k-block k + 1 under the MFMAs of k-block k).
         const ngm_u32x4* fwdP = planes + LY::fwd_slot() * 3 * PLANE_G;
-#ifndef NGM_HS_NO_EARLY_ENC
         // ... with the ENCODING of this tile in the shadows of its 48 MFMAs: sine (and, Fourier, cosine) of the tile's 32 x 64
         // (sample, feature) pairs need only the positions, the recompute only the H1 rows -- two independent streams, and this
         // kernel instance has the registers to keep the 32 + 32 results until layer 0 wants them (the full-stash kernel does not:
@@ -485,16 +484,6 @@ __global__ __launch_bounds__(B3B_THREADS) void k_field_bwd_b3(FieldBwdArgs a) {
           const float4 encw[2] = {cenc[i], cenc[32 + i]};
           recompute_with_encoding<NEED_COS, ENC_GRAD>(fwdP, H1b, pb_c, encw, lane, Hc, Eb, Cb);
         }
-#else
-        {
-          RowRegs Rh;
-          PlaneRegs Wf;
-          load_rows(H1b, lane, Rh);
-          load_planes(fwdP, 0, lane, Wf);
-          __builtin_amdgcn_sched_barrier(0);
-          dgrad_b3(fwdP, Rh, Wf, lane, Hc);
-        }
-#endif
         // layer 1's input columns (weight gradient operand, ReLU mask of layer 0) and the d_out rows: in flight under the bias / ReLU
 #pragma unroll
         for (int m = 0; m < 2; ++m)
@@ -631,11 +620,7 @@ __global__ __launch_bounds__(B3B_THREADS) void k_field_bwd_b3(FieldBwdArgs a) {
     TICK(8);
     const float4 encw[2] = {cenc[i], cenc[32 + i]};
     float4 ppa[2][8];                // both blocks' positions up front: the second block's read latency hides under the first's arithmetic
-#ifndef NGM_HS_NO_EARLY_ENC
     constexpr bool EARLY = HS;       // the encoding was evaluated under the recompute's MFMAs
-#else
-    constexpr bool EARLY = false;
-#endif
     if constexpr (!EARLY || ENC_GRAD) {
 #pragma unroll
       for (int b = 0; b < 2; ++b)
@@ -887,8 +872,8 @@ template <int L, bool HS>
 static int launch_bwd_b3(const FieldBwdArgs& a, int blocks, hipStream_t st) {
 #define NGM_LBB3(NC, EG)                                                                                              \
   do {                                                                                                                \
+    static_assert(LdsB3b<L, EG, HS>::TOTAL * sizeof(float) <= 160 * 1024, "k_field_bwd_b3: LDS over 160 KiB");       \
     const size_t lds = (size_t)LdsB3b<L, EG, HS>::TOTAL * sizeof(float);                                              \
-    if (lds > 160 * 1024) return NGM_E_UNSUPPORTED;                                                                   \
     if (a.fused_comp) {                                                                                               \
       (void)hipFuncSetAttribute((const void*)k_field_bwd_b3<L, NC, EG, true, HS>, hipFuncAttributeMaxDynamicSharedMemorySize, \
                                 (int)lds);                                                                            \

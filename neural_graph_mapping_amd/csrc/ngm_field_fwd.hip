@@ -490,18 +490,10 @@ __global__ __launch_bounds__(512) void k_render_fwd(RenderFwdArgs a) {
         wl.wbuf[idx] = w; wl.cbuf[0][idx] = c0; wl.cbuf[1][idx] = c1; wl.cbuf[2][idx] = c2;
         if (a.stashA) {
           const int64_t gs = ((int64_t)f * R + rb) * S + idx;
-          typedef float v4f __attribute__((ext_vector_type(4)));
-          typedef float v2f __attribute__((ext_vector_type(2)));
-          const v4f sa = {c0, c1, c2, geom};
-          const v2f sb = {t, T_excl};
-#ifdef NGM_STASH_NT      // rounds 1-5: non-temporal
-          __builtin_nontemporal_store(sa, reinterpret_cast<v4f*>(a.stashA + gs));   // read once, by the next kernel
-          __builtin_nontemporal_store(sb, reinterpret_cast<v2f*>(a.stashB + gs));
-#else                    // round 6: written through (sc1), like the activation stash (ngm_field.h act_store): the backward reads these
-                         // rows from another CU, most often another XCD -- M1 backward 141.4 -> 137.7 us, k_hash_mlp_bwd 37.3 -> 33.8 us
-          asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(reinterpret_cast<v4f*>(a.stashA + gs)), "v"(sa));
-          asm volatile("global_store_dwordx2 %0, %1, off sc1" ::"v"(reinterpret_cast<v2f*>(a.stashB + gs)), "v"(sb));
-#endif
+          // written through (sc1), like the activation stash (ngm_field.h act_store): the backward reads these rows from another
+          // CU, most often another XCD -- M1 backward 141.4 -> 137.7 us, k_hash_mlp_bwd 37.3 -> 33.8 us
+          ngm_store_wt(reinterpret_cast<ngm_v4f_*>(a.stashA + gs), ngm_v4f_{c0, c1, c2, geom});
+          ngm_store_wt(reinterpret_cast<ngm_v2f_*>(a.stashB + gs), ngm_v2f_{t, T_excl});
         }
       }
       float sc[5] = {w * c0, w * c1, w * c2, w * depth, w};      // five segmented sums over the same rays: one fused scan
@@ -513,10 +505,6 @@ __global__ __launch_bounds__(512) void k_render_fwd(RenderFwdArgs a) {
         ra[0] += s0; ra[1] += s1; ra[2] += s2; ra[3] += s3; ra[4] += s4;
       }
   };
-#ifdef NGM_FWD_STAGGER   // experiment: offset the second wave of every SIMD by a fraction of a step so that its matrix
-  // phases meet the first wave's VALU phases instead of its matrix phases (NGM_FWD_STAGGER x 64 clocks)
-  if (wave >= nwaves / 2) __builtin_amdgcn_s_sleep(NGM_FWD_STAGGER);
-#endif
   for (int rb = r_beg; rb < r_end; rb += BR) {
     const int nb = min(BR, r_end - rb);
     const int nsamp = nb * S;

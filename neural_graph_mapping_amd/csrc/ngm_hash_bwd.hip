@@ -477,12 +477,13 @@ bool ngm_hash_mlp_bwd_applies(const FieldBwdArgs& a) {
       a.fc.matmul_mode == NGM_MATMUL_F32 || a.fc.num_layers != 1 || a.fc.dim_enc > 32 || a.fc.dim_hidden > 32 || a.fc.dim_enc <= 16 ||
       a.fc.dim_out != 4 || !a.hash_dE)
     return false;
+  // fused compositing: the loss seeds, and whole 32-sample tiles per wave; else the positions from k_stash_bwd
+  if (a.fused_comp ? (!a.rayseed || !a.hash_xyz || a.per_block % (HB_WAVES * 32)) : !a.hash_xyz_ready) return false;
   return (a.P + 64) * 128 < ((int64_t)1 << 32);     // 32-bit byte offsets inside a field
 }
 // returns NGM_E_UNSUPPORTED when this kernel does not apply (caller falls back to k_field_bwd16)
 int ngm_launch_hash_mlp_bwd(const FieldBwdArgs& a, int blocks, hipStream_t st) {
   if (!ngm_hash_mlp_bwd_applies(a)) return NGM_E_UNSUPPORTED;
-  if (a.fused_comp ? (!a.rayseed || !a.hash_xyz || a.per_block % (HB_WAVES * 32)) : !a.hash_xyz_ready) return NGM_E_UNSUPPORTED;
   NgmProfScope prof_(NGM_K_FIELD_BWD, st);
   const size_t lds = (size_t)LdsHB::TOTAL * sizeof(float);
   if (a.fused_comp) {

@@ -31,26 +31,18 @@
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); \
   } while (0)
 
-#ifndef KNN_TILE
-#define KNN_TILE 512
-#endif
+constexpr int KNN_TILE = 512;
 #define KNN_MAXK 8
 // copies of the per-field pair counters: 4096 workgroups flushing their histograms into ~100 addresses serialise on the
 // device-scope atomics; sixteen copies, summed by k_knn_offsets
-#ifndef KNN_COUNT_REPL
-#define KNN_COUNT_REPL 16
-#endif
-#ifndef KNN_ASSIGN_MAX_WG
-#define KNN_ASSIGN_MAX_WG 4096
-#endif
+constexpr int KNN_COUNT_REPL = 16;
+constexpr int KNN_ASSIGN_MAX_WG = 4096;
 // the candidate lists are kept per SUB-cell (edge c / KNN_SUB) of the grid extended by one ring: a list holds the centres within
 // the mask radius of its box, and a box of half the edge sees half as many (13 instead of 26 on a cover-grid map) -- the
 // assignment walks its list for every point near a field
 #define KNN_SUB 2
 #define KNN_NEAR_PER_FIELD (27 * KNN_SUB * KNN_SUB * KNN_SUB)   // a centre is listed by sub-cells of its own and the 26 adjacent cells only
-#ifndef KNN_EVAL_B3_THREADS
-#define KNN_EVAL_B3_THREADS 512
-#endif
+constexpr int KNN_EVAL_B3_THREADS = 512;
 #define CQ_MAXS_EVAL 1024      // samples per ray the quadrature kernel takes (CQ_MAXS of ngm_composite.hip)
 
 struct KnnArgs {
@@ -520,9 +512,7 @@ __global__ void k_knn_offsets(KnnArgs a) {
 // Counting-sort scatter in two levels: every workgroup ranks its SC_ITEMS * 256 pairs per field with LDS atomics,
 // reserves one contiguous range per field with ONE global atomic, then writes.  (One global atomic per pair on the
 // per-field cursor serialised badly -- neighbouring pixels hit the same field -- and took 80 % of render_image.)
-#ifndef SC_ITEMS
-#define SC_ITEMS 32
-#endif
+constexpr int SC_ITEMS = 32;
 __global__ __launch_bounds__(256) void k_knn_scatter(KnnArgs a) {
   extern __shared__ int sc_lds[];
   int* hist = sc_lds;            // NF: pairs of this workgroup per field, then the reserved global base

@@ -110,7 +110,7 @@ struct FieldBwdArgs {
   float* sums_out; float* loss_out; unsigned long long* counter;   // as StashBwdArgs
 };
 bool ngm_field_bwd_b3_applies(const FieldBwdArgs& a);   // would ngm_launch_field_bwd_b3 take this problem
-bool ngm_hash_mlp_bwd_applies(const FieldBwdArgs& a);   // would ngm_launch_hash_mlp_bwd (given positions, or fused_comp)
+bool ngm_hash_mlp_bwd_applies(const FieldBwdArgs& a);   // would ngm_launch_hash_mlp_bwd take this problem
 struct GradReduceArgs;
 // mlp_reduce (optional): the MLP's gradient reduction (+ Adam) to run as extra workgroups of the same launch; *mlp_reduced tells
 // the caller that it did (no ngm_launch_grad_reduce needed then)
