@@ -1,11 +1,13 @@
 """End-to-end smoke of the drop-in path on one MI355X: keyframe store -> training-target sampler -> fused
 training step (forward, losses, backward, sparse Adam) -> kNN-blended render -> PSNR.
 
-    python examples/fit_synthetic.py [--iters 300]
+    python examples/fit_synthetic.py [--iters 300] [--device-iteration]
 
 A synthetic RGB-D "scan" of a textured wall with a sphere in front of it is observed from a few keyframes; fields
 on a grid in front of the cameras are trained exactly as NeuralGraphMap._optimization_iteration would
 (rm.py:1123-1221), with every tensor operation of the hot path running in the HIP kernels.
+--device-iteration trains through NeuralGraphRenderer.capture_training instead: targets drawn on the device and consumed at
+their fixed capacity, sampler + training step replayed as one captured graph per iteration (no host synchronisation).
 """
 import argparse
 import math
@@ -54,7 +56,14 @@ def synth_keyframe(c2w):
     return torch.cat([rgb, depth[..., None]], -1)
 
 
-def main(iters=300, device="cuda:0", quiet=False):
+def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0):
+    """loop: "torch" -- sample_target_mv (torch draws) -> optimization_iteration, the reference's loop;
+    "device" -- capture_training: one graph replay per iteration;
+    "materialize" -- the same device-drawn targets and jitter stream as "device" (sampler seed 0, iteration i; jitter
+    seed `jitter_seed`), but sliced to their count on the host every iteration (DeviceTarget.materialize: one
+    synchronisation, a data-dependent batch shape)."""
+    if loop not in ("torch", "device", "materialize"):
+        raise ValueError(loop)
     torch.manual_seed(0)
     dev = torch.device(device)
     cam = Rr.Camera(W, H, FOC, FOC, (W - 1) / 2, (H - 1) / 2, pixel_center=0.0)
@@ -87,9 +96,16 @@ def main(iters=300, device="cuda:0", quiet=False):
     cur = torch.arange(NF, device=dev)
 
     losses = []
+    step = r.capture_training(cur, c2ws, store, cid, 32, 256, seed=jitter_seed, camera=cam) if loop == "device" else None
     for it in range(iters):
-        tgt = r.sample_target_mv(cur, c2ws, store, cid, num_train_fields=32, num_rays_per_field=256, camera=cam)
-        out = r.optimization_iteration(tgt, seed=it)
+        if loop == "device":
+            out = step()
+        elif loop == "materialize":
+            tgt = r.sample_target_mv_device(cur, c2ws, store, cid, 32, 256, camera=cam, seed=0, iteration=it).materialize()
+            out = r.optimization_iteration(tgt, seed=jitter_seed)
+        else:
+            tgt = r.sample_target_mv(cur, c2ws, store, cid, num_train_fields=32, num_rays_per_field=256, camera=cam)
+            out = r.optimization_iteration(tgt, seed=it)
         if it % 25 == 0 or it == iters - 1:
             losses.append(float(out["combined"]))
             if not quiet:
@@ -112,5 +128,7 @@ def main(iters=300, device="cuda:0", quiet=False):
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=300)
+    ap.add_argument("--device-iteration", action="store_true",
+                    help="train through capture_training: device-drawn targets, one captured graph per iteration")
     a = ap.parse_args()
-    main(a.iters)
+    main(a.iters, loop="device" if a.device_iteration else "torch")

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define NGM_ABI_VERSION 11 /* 11 (+ addition, number unchanged: ngm_target_sample_mv_workspace / ngm_target_sample_mv and struct ngm_target_sample, the device-side training-target sampler; nothing existing changed); 11: ngm_field_eval_stash_bytes / ngm_field_eval_fwd_train / ngm_field_eval_bwd_stash (training forward of the point evaluation writes the activation stash, its backward is the fused step's kernel); 10: ngm_field_cfg.activation_stash / .hash_grad_atomics (per configuration, no process-wide switch), empty loss selections report NaN like the reference; 9: ngm_sample_rays_weighted; 8: ngm_peer_set_timeout (a time-out now also poisons the sums with NaN); 7: ngm_encode_bwd; 6: ngm_render_eval_knn; 5: ngm_encode_fwd, ngm_render_bwd_seeded_vars, *_nll loss modes (+ loss-sum slot 10), peer status bits */
+#define NGM_ABI_VERSION 11 /* 11 (+ addition, number unchanged: ngm_render_fwd_counted / ngm_render_bwd_counted / ngm_render_bwd_adam_counted, the training step launched at a capacity with the number of active rows in device memory; nothing existing changed); 11 (+ addition, number unchanged: ngm_target_sample_mv_workspace / ngm_target_sample_mv and struct ngm_target_sample, the device-side training-target sampler; nothing existing changed); 11: ngm_field_eval_stash_bytes / ngm_field_eval_fwd_train / ngm_field_eval_bwd_stash (training forward of the point evaluation writes the activation stash, its backward is the fused step's kernel); 10: ngm_field_cfg.activation_stash / .hash_grad_atomics (per configuration, no process-wide switch), empty loss selections report NaN like the reference; 9: ngm_sample_rays_weighted; 8: ngm_peer_set_timeout (a time-out now also poisons the sums with NaN); 7: ngm_encode_bwd; 6: ngm_render_eval_knn; 5: ngm_encode_fwd, ngm_render_bwd_seeded_vars, *_nll loss modes (+ loss-sum slot 10), peer status bits */
 #define NGM_MAX_LAYERS 4 /* hidden layers; +1 output layer */
 #define NGM_NUM_LOSS_SUMS 16
 
@@ -419,6 +419,40 @@ int ngm_render_bwd_adam(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg, c
                         int32_t num_mlp_tensors, const ngm_adam_tensor* lattice_tensor, const int64_t* field_index,
                         int64_t step, int64_t* step_dev, float lr, float beta1, float beta2, float eps,
                         float weight_decay, float* loss_values, void* workspace, int64_t workspace_bytes, void* stream);
+/* ---- counted step: the training step launched at a CAPACITY, the number of active rows in device memory -------------
+ * ngm_render_fwd / ngm_render_bwd / ngm_render_bwd_adam with one more argument: num_active, a DEVICE int32 (for instance
+ * ngm_target_out.count of ngm_target_sample_mv) with 0 <= *num_active <= rays->F.  Plans, workspace size
+ * (ngm_render_workspace(fcfg, rcfg, rays->F, R, 1)) and validation are those of the un-suffixed call with the same rays->F;
+ * no kernel launch depends on the count, so the sequence can be captured in a graph whose replays see a new count each.
+ * Rows 0 .. *num_active - 1 are the batch.  For rows f >= *num_active:
+ *   - nothing of theirs is READ: not params->field_index[f] / rays->pose_index[f] / the Adam field_index[f], not their rays,
+ *     targets or masks -- the result of the call is bitwise independent of what those rows hold;
+ *   - nothing of theirs is WRITTEN: prediction rows, gradient rows (hash `lattice` rows included), parameter / Adam moment /
+ *     reduced-precision rows stay as they were (gradient and prediction rows >= *num_active are therefore unspecified
+ *     leftovers of earlier calls); no parameter row other than field_index[0 .. *num_active - 1] changes;
+ *   - they contribute exactly nothing to the loss sums and counts.
+ * Bookkeeping happens once per call whatever the count: loss_sums / loss_values written, the philox_offset_autoinc counter
+ * (and with it the Adam step it doubles as) advanced.  *num_active == 0 is a legal call: zero sums, hence the loss values of
+ * empty selections (NaN terms, as the reference's empty .mean()), no parameter touched.  *num_active == rays->F computes
+ * bit for bit what the un-suffixed call computes.
+ * num_active == NULL: NGM_E_INVALID.  The neus geometry mode, the triplane encoding (both run launches over all F rows)
+ * and the *_nll loss modes: NGM_E_UNSUPPORTED.  These two checks come before every other and read only fcfg and rcfg. */
+int ngm_render_fwd_counted(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg,
+                           const ngm_params* params, const ngm_rays* rays, const ngm_targets* targets,
+                           const ngm_prediction* pred, float* loss_sums, void* workspace,
+                           int64_t workspace_bytes, void* stream, const int32_t* num_active);
+int ngm_render_bwd_counted(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg,
+                           const ngm_params* params, const ngm_rays* rays, const ngm_targets* targets,
+                           const ngm_prediction* pred, const float* loss_sums, const ngm_grads* grads,
+                           float* loss_out, void* workspace, int64_t workspace_bytes, void* stream,
+                           const int32_t* num_active);
+int ngm_render_bwd_adam_counted(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg, const ngm_params* params,
+                                const ngm_rays* rays, const ngm_targets* targets, const ngm_prediction* pred,
+                                const float* loss_sums, const ngm_grads* grads, const ngm_adam_tensor* mlp_tensors,
+                                int32_t num_mlp_tensors, const ngm_adam_tensor* lattice_tensor, const int64_t* field_index,
+                                int64_t step, int64_t* step_dev, float lr, float beta1, float beta2, float eps,
+                                float weight_decay, float* loss_values, void* workspace, int64_t workspace_bytes, void* stream,
+                                const int32_t* num_active);
 /* ++*step_dev, ++*philox_offset_dev on the stream (either may be NULL): end-of-iteration bookkeeping
  * for graph-captured training loops. */
 int ngm_step_advance(int64_t* step_dev, uint64_t* philox_offset_dev, void* stream);

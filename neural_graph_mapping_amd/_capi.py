@@ -204,6 +204,11 @@ def lib():
                                       P(Grads), P(AdamTensor), i32, P(AdamTensor), vp, i64, vp, f32, f32, f32, f32, f32,
                                       vp, vp, i64, vp]
     L.ngm_render_bwd_adam.restype = C.c_int
+    # the counted step: the same calls with a device int32 count of active rows as last argument
+    for name in ("ngm_render_fwd", "ngm_render_bwd", "ngm_render_bwd_adam"):
+        counted = getattr(L, name + "_counted")
+        counted.argtypes = list(getattr(L, name).argtypes) + [vp]
+        counted.restype = C.c_int
     L.ngm_render_read_samples.argtypes = [P(FieldCfg), P(RenderCfg), i32, i32, i32, vp, vp, vp, vp]
     L.ngm_adam_sparse.argtypes = [vp, vp, vp, i64, vp, i64, vp, i32, i64, i64, f32, f32, f32, f32, f32, vp]
     L.ngm_adam_sparse_multi.argtypes = [P(AdamTensor), i32, vp, i32, i64, vp, f32, f32, f32, f32, f32, i32, vp, vp]
@@ -267,6 +272,7 @@ EXPORTED = ["ngm_abi_version", "ngm_last_error", "ngm_device_info", "ngm_permuto
             "ngm_field_eval_knn", "ngm_field_eval_knn_workspace", "ngm_render_eval_knn", "ngm_render_eval_knn_workspace", "ngm_adam_sparse_multi", "ngm_step_advance", "ngm_profile_enable", "ngm_profile_reset", "ngm_profile_read",
             "ngm_debug_phase_cycles", "ngm_debug_fwd_phase_cycles", "ngm_debug_last_bwd_variant", "ngm_debug_last_matmul", "ngm_debug_last_fwd_one_tile", "ngm_debug_last_comp_fused", "ngm_debug_disable_fused_comp", "ngm_debug_stash_mode", "ngm_debug_last_stash_mode", "ngm_target_visibility", "ngm_target_rays", "ngm_target_sv_intersect", "ngm_target_sv_rays",
             "ngm_target_sample_mv_workspace", "ngm_target_sample_mv",
+            "ngm_render_fwd_counted", "ngm_render_bwd_counted", "ngm_render_bwd_adam_counted",
             "ngm_peer_mailbox_bytes", "ngm_peer_alloc", "ngm_peer_free", "ngm_ipc_export", "ngm_ipc_open", "ngm_ipc_close", "ngm_loss_exchange", "ngm_peer_set_timeout",
             "ngm_marching_cubes_workspace", "ngm_marching_cubes_count", "ngm_marching_cubes_emit", "ngm_marching_cubes_tables"]
 

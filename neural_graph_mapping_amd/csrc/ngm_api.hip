@@ -22,7 +22,7 @@ int ngm_launch_adam(float* param, float* m, float* v, int64_t stride, const floa
                     float eps, float wd, hipStream_t st);
 int ngm_launch_adam_multi(const ngm_adam_tensor* tensors, int n, const int64_t* field_index, int F, int64_t step,
                           const int64_t* step_dev, float lr, float beta1, float beta2, float eps, float wd,
-                          int64_t* advance_step, uint64_t* advance_offset, hipStream_t st);
+                          int64_t* advance_step, uint64_t* advance_offset, hipStream_t st, const int32_t* num_active = nullptr);
 int ngm_launch_step_advance(int64_t* step_dev, uint64_t* off_dev, hipStream_t st);
 int64_t ngm_mc_workspace_bytes(int nx, int ny, int nz);
 int ngm_launch_mc_count(const float* vol, int nx, int ny, int nz, float iso, int64_t* counts, void* workspace,
@@ -891,9 +891,30 @@ static int check_render(const ngm_field_cfg* fc, const ngm_render_cfg* rc, const
   return NGM_OK;
 }
 
-int ngm_render_fwd(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg, const ngm_params* params, const ngm_rays* rays,
-                   const ngm_targets* targets, const ngm_prediction* pred, float* loss_sums, void* workspace,
-                   int64_t workspace_bytes, void* stream) {
+// The counted step (ngm_render_*_counted): launched at the capacity rays->F, every kernel learns the number of active rows
+// from device memory.  Outside it: the configurations that run extra launches over all F rows (neus: neighbour stencil +
+// ngm_launch_neus_sd_grad; triplane: accumulator memset + ngm_launch_tri_finish) and the variance-weighted loss modes.
+// These two checks come first and read nothing but the two configurations.
+static int check_counted(const char* who, const ngm_field_cfg* fc, const ngm_render_cfg* rc, const int32_t* num_active) {
+  char msg[256];
+  if (!num_active) {
+    snprintf(msg, sizeof(msg), "%s: num_active is NULL (the un-suffixed entry point is the call for all F rows)", who);
+    return fail(NGM_E_INVALID, msg);
+  }
+  const char* why = nullptr;
+  if (rc && rc->geometry_mode == NGM_GEO_NEUS) why = "the neus geometry mode";
+  else if (fc && fc->encoding == NGM_ENC_TRIPLANE) why = "the triplane encoding";
+  else if (rc && (rc->photometric_mode == NGM_PHOTO_GAUSSIAN_NLL || rc->depth_mode != NGM_DEPTH_HUBER)) why = "the *_nll loss modes";
+  if (why) {
+    snprintf(msg, sizeof(msg), "%s: %s is outside the counted step (it launches over all F rows): slice the batch to its count and call the un-suffixed entry point", who, why);
+    return fail(NGM_E_UNSUPPORTED, msg);
+  }
+  return NGM_OK;
+}
+
+static int render_fwd_impl(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg, const ngm_params* params, const ngm_rays* rays,
+                           const ngm_targets* targets, const ngm_prediction* pred, float* loss_sums, void* workspace,
+                           int64_t workspace_bytes, void* stream, const int32_t* num_active) {
   int e = check_render(fcfg, rcfg, params, rays);
   if (e) return e;
   if (!pred) return fail(NGM_E_INVALID, "render_fwd: pred is NULL");
@@ -916,6 +937,7 @@ int ngm_render_fwd(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg, const 
     a.neus_sd = params->neus_sd; a.neus_sd_stride = params->neus_sd_stride;
   }
   a.has_targets = has_tg ? 1 : 0;
+  a.num_active = num_active;
   if (has_tg) a.tg = *targets;
   a.S = p.S; a.rays_per_block = p.rays_per_block; a.waves_per_block = p.waves_fwd; a.maxs = p.maxs;
   if (save) {
@@ -946,15 +968,29 @@ int ngm_render_fwd(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg, const 
   }
   return e;
 }
+int ngm_render_fwd(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg, const ngm_params* params, const ngm_rays* rays,
+                   const ngm_targets* targets, const ngm_prediction* pred, float* loss_sums, void* workspace,
+                   int64_t workspace_bytes, void* stream) {
+  return render_fwd_impl(fcfg, rcfg, params, rays, targets, pred, loss_sums, workspace, workspace_bytes, stream, nullptr);
+}
+int ngm_render_fwd_counted(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg, const ngm_params* params, const ngm_rays* rays,
+                           const ngm_targets* targets, const ngm_prediction* pred, float* loss_sums, void* workspace,
+                           int64_t workspace_bytes, void* stream, const int32_t* num_active) {
+  const int e = check_counted("ngm_render_fwd_counted", fcfg, rcfg, num_active);
+  if (e) return e;
+  return render_fwd_impl(fcfg, rcfg, params, rays, targets, pred, loss_sums, workspace, workspace_bytes, stream, num_active);
+}
 
 static int render_bwd_common(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg, const ngm_params* params,
                              const ngm_rays* rays, StashBwdArgs& sb, const ngm_grads* grads, void* workspace,
                              int64_t workspace_bytes, hipStream_t st, const GradAdam* adam = nullptr,
-                             const GradAdam* lattice_adam = nullptr, bool* lattice_adam_applied = nullptr) {
+                             const GradAdam* lattice_adam = nullptr, bool* lattice_adam_applied = nullptr,
+                             const int32_t* num_active = nullptr) {
   const RenderPlan p = plan_render(fcfg, rcfg, rays->F, rays->R, rays->gt != nullptr, true);
   if (!workspace || workspace_bytes < p.total) return fail(NGM_E_WORKSPACE, "render_bwd: workspace too small");
   char* ws = reinterpret_cast<char*>(align_up((int64_t)workspace, 256));
   sb.rc = *rcfg; sb.F = rays->F; sb.R = rays->R; sb.S = p.S;
+  sb.num_active = num_active;
   if (!rays->gt) sb.rc.w_freespace = sb.rc.w_tsdf = 0.f;       // no gt: the reference forms no free-space / TSDF terms (rm.py:624, 632)
   sb.stashA = reinterpret_cast<float4*>(ws + p.off_stashA);
   sb.stashB = reinterpret_cast<const float2*>(ws + p.off_stashB);
@@ -974,6 +1010,7 @@ static int render_bwd_common(const ngm_field_cfg* fcfg, const ngm_render_cfg* rc
   FieldBwdArgs a;
   memset(&a, 0, sizeof(a));
   a.fc = *fcfg; a.pr = *params; a.F = rays->F; a.P = (int64_t)rays->R * p.S; a.S = p.S;
+  a.num_active = num_active;
   carve_hash_scratch(fcfg, rays->F, a.P, ws + p.off_hash, a);
   a.per_block = p.per_block_bwd; a.blocks_per_field = p.blocks_per_field_bwd;
   a.raytab = sb.raytab; a.stashB = sb.stashB; a.d_out = neus ? sb.d_out : sb.stashA;
@@ -1023,6 +1060,7 @@ static int render_bwd_common(const ngm_field_cfg* fcfg, const ngm_render_cfg* rc
   GradReduceArgs g;
   memset(&g.adam, 0, sizeof(g.adam));
   if (adam) g.adam = *adam;
+  g.num_active = num_active;
   g.fc = *fcfg; g.gr = *grads; g.F = rays->F; g.blocks_per_field = a.blocks_per_field; g.partials = a.partials; g.p_pad = a.p_pad;
   bool mlp_reduced = false;
   if (fcfg->encoding == NGM_ENC_PERMUTO) {
@@ -1039,9 +1077,9 @@ static int render_bwd_common(const ngm_field_cfg* fcfg, const ngm_render_cfg* rc
   return check_launch("ngm_grad_reduce");
 }
 
-int ngm_render_bwd(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg, const ngm_params* params, const ngm_rays* rays,
-                   const ngm_targets* targets, const ngm_prediction* pred, const float* loss_sums, const ngm_grads* grads,
-                   float* loss_out, void* workspace, int64_t workspace_bytes, void* stream) {
+static int render_bwd_impl(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg, const ngm_params* params, const ngm_rays* rays,
+                           const ngm_targets* targets, const ngm_prediction* pred, const float* loss_sums, const ngm_grads* grads,
+                           float* loss_out, void* workspace, int64_t workspace_bytes, void* stream, const int32_t* num_active) {
   int e = check_render(fcfg, rcfg, params, rays);
   if (e) return e;
   if (!targets || !targets->rgbds || !targets->depth_mask || !pred || !pred->rgbds || !pred->term_probs || !grads)
@@ -1050,14 +1088,30 @@ int ngm_render_bwd(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg, const 
   memset(&sb, 0, sizeof(sb));
   sb.seed_mode = 0; sb.tg = *targets; sb.pred = *pred; sb.loss_sums = loss_sums;
   sb.loss_out = loss_out;      // written by the compositing-backward kernel (no separate launch)
-  return render_bwd_common(fcfg, rcfg, params, rays, sb, grads, workspace, workspace_bytes, (hipStream_t)stream);
+  return render_bwd_common(fcfg, rcfg, params, rays, sb, grads, workspace, workspace_bytes, (hipStream_t)stream, nullptr, nullptr,
+                           nullptr, num_active);
+}
+int ngm_render_bwd(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg, const ngm_params* params, const ngm_rays* rays,
+                   const ngm_targets* targets, const ngm_prediction* pred, const float* loss_sums, const ngm_grads* grads,
+                   float* loss_out, void* workspace, int64_t workspace_bytes, void* stream) {
+  return render_bwd_impl(fcfg, rcfg, params, rays, targets, pred, loss_sums, grads, loss_out, workspace, workspace_bytes, stream,
+                         nullptr);
+}
+int ngm_render_bwd_counted(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg, const ngm_params* params, const ngm_rays* rays,
+                           const ngm_targets* targets, const ngm_prediction* pred, const float* loss_sums, const ngm_grads* grads,
+                           float* loss_out, void* workspace, int64_t workspace_bytes, void* stream, const int32_t* num_active) {
+  const int e = check_counted("ngm_render_bwd_counted", fcfg, rcfg, num_active);
+  if (e) return e;
+  return render_bwd_impl(fcfg, rcfg, params, rays, targets, pred, loss_sums, grads, loss_out, workspace, workspace_bytes, stream,
+                         num_active);
 }
 
-int ngm_render_bwd_adam(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg, const ngm_params* params, const ngm_rays* rays,
-                        const ngm_targets* targets, const ngm_prediction* pred, const float* loss_sums, const ngm_grads* grads,
-                        const ngm_adam_tensor* mlp_tensors, int32_t num_mlp_tensors, const ngm_adam_tensor* lattice_tensor,
-                        const int64_t* field_index, int64_t step, int64_t* step_dev, float lr, float beta1, float beta2,
-                        float eps, float weight_decay, float* loss_out, void* workspace, int64_t workspace_bytes, void* stream) {
+static int render_bwd_adam_impl(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg, const ngm_params* params, const ngm_rays* rays,
+                                const ngm_targets* targets, const ngm_prediction* pred, const float* loss_sums, const ngm_grads* grads,
+                                const ngm_adam_tensor* mlp_tensors, int32_t num_mlp_tensors, const ngm_adam_tensor* lattice_tensor,
+                                const int64_t* field_index, int64_t step, int64_t* step_dev, float lr, float beta1, float beta2,
+                                float eps, float weight_decay, float* loss_out, void* workspace, int64_t workspace_bytes,
+                                void* stream, const int32_t* num_active) {
   int e = check_render(fcfg, rcfg, params, rays);
   if (e) return e;
   if (!targets || !targets->rgbds || !targets->depth_mask || !pred || !pred->rgbds || !pred->term_probs || !grads ||
@@ -1078,14 +1132,35 @@ int ngm_render_bwd_adam(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg, c
   lad.tensors = lattice_tensor; lad.num = lattice_tensor ? 1 : 0;
   bool lattice_done = false;
   e = render_bwd_common(fcfg, rcfg, params, rays, sb, grads, workspace, workspace_bytes, (hipStream_t)stream, &ad,
-                        lattice_tensor ? &lad : nullptr, &lattice_done);
+                        lattice_tensor ? &lad : nullptr, &lattice_done, num_active);
   if (e) return e;
   if (lattice_tensor && !lattice_done) {   // unaligned tables: k_hash_reduce left the update to a plain Adam launch
     ngm_launch_adam_multi(lattice_tensor, 1, field_index, rays->F, step, step_dev, lr, beta1, beta2, eps, weight_decay,
-                          nullptr, nullptr, (hipStream_t)stream);
+                          nullptr, nullptr, (hipStream_t)stream, num_active);
     e = check_launch("ngm_adam_sparse_multi");
   }
   return e;
+}
+int ngm_render_bwd_adam(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg, const ngm_params* params, const ngm_rays* rays,
+                        const ngm_targets* targets, const ngm_prediction* pred, const float* loss_sums, const ngm_grads* grads,
+                        const ngm_adam_tensor* mlp_tensors, int32_t num_mlp_tensors, const ngm_adam_tensor* lattice_tensor,
+                        const int64_t* field_index, int64_t step, int64_t* step_dev, float lr, float beta1, float beta2,
+                        float eps, float weight_decay, float* loss_out, void* workspace, int64_t workspace_bytes, void* stream) {
+  return render_bwd_adam_impl(fcfg, rcfg, params, rays, targets, pred, loss_sums, grads, mlp_tensors, num_mlp_tensors, lattice_tensor,
+                              field_index, step, step_dev, lr, beta1, beta2, eps, weight_decay, loss_out, workspace, workspace_bytes,
+                              stream, nullptr);
+}
+int ngm_render_bwd_adam_counted(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg, const ngm_params* params, const ngm_rays* rays,
+                                const ngm_targets* targets, const ngm_prediction* pred, const float* loss_sums, const ngm_grads* grads,
+                                const ngm_adam_tensor* mlp_tensors, int32_t num_mlp_tensors, const ngm_adam_tensor* lattice_tensor,
+                                const int64_t* field_index, int64_t step, int64_t* step_dev, float lr, float beta1, float beta2,
+                                float eps, float weight_decay, float* loss_out, void* workspace, int64_t workspace_bytes,
+                                void* stream, const int32_t* num_active) {
+  const int e = check_counted("ngm_render_bwd_adam_counted", fcfg, rcfg, num_active);
+  if (e) return e;
+  return render_bwd_adam_impl(fcfg, rcfg, params, rays, targets, pred, loss_sums, grads, mlp_tensors, num_mlp_tensors, lattice_tensor,
+                              field_index, step, step_dev, lr, beta1, beta2, eps, weight_decay, loss_out, workspace, workspace_bytes,
+                              stream, num_active);
 }
 
 int ngm_render_bwd_seeded(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg, const ngm_params* params,

@@ -101,6 +101,27 @@ struct FieldStreams {
   uint32_t par;           // parity of the field's first global sample index
 };
 
+// Counted step (FieldBwdArgs::num_active), workgroup of a row f >= *num_active of a kernel with the fused compositing backward:
+// it has no sample to work on, but block 0 owns the loss bookkeeping of the call (global sums copy, iteration counter, loss
+// scalars) and is such a workgroup when the count is 0.  Every forward workgroup then left a zero partial, so the sums are
+// zero in any order; with all-reduced sums (loss_sums) the other ranks' values are reported.  Called by the whole workgroup
+// before any barrier; the caller returns right after.
+__device__ __forceinline__ void ngm_counted_idle_bookkeeping(const FieldBwdArgs& a) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  float s[NGM_NUM_LOSS_SUMS];
+#pragma unroll
+  for (int i = 0; i < NGM_NUM_LOSS_SUMS; ++i) s[i] = a.loss_partials ? 0.f : a.loss_sums[i];
+  if (a.loss_partials)
+    for (int b = 0; b < a.n_partials; ++b)
+#pragma unroll
+      for (int i = 0; i < NGM_NUM_LOSS_SUMS; ++i) s[i] += a.loss_partials[(int64_t)b * NGM_NUM_LOSS_SUMS + i];
+  if (a.sums_out)
+#pragma unroll
+    for (int i = 0; i < NGM_NUM_LOSS_SUMS; ++i) a.sums_out[i] = s[i];
+  if (a.loss_partials && a.counter) *a.counter += 1ull;
+  if (a.loss_out) loss_values_from_sums(a.rc, s, a.loss_out);
+}
+
 // Fused compositing backward (k_field_bwd_b3<FC>, k_hash_mlp_bwd<FC>): a wave walks its tiles back to front carrying the
 // suffix value Q of the per-ray recursion Q_{k-1} = a_k o_k + (1 - o_k) Q_k.  Its range ends with a tile, not necessarily with
 // a ray: this returns Q at the range's upper end, i.e. the recursion over the m samples of the cut ray that lie BEYOND `end`

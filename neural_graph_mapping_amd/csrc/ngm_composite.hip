@@ -907,7 +907,9 @@ int ngm_launch_composite_bwd(const CompositeArgs& a, hipStream_t st) {
 // ================================================================================================
 __global__ __launch_bounds__(NGM_BLOCK) void k_stash_bwd(StashBwdArgs a, int rays_per_wave) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t N = (int64_t)a.F * a.R;
+  // counted step: the rays of the active rows only (rows are whole ray blocks, active rows first); a wave beyond them has
+  // no step to walk but still takes part in the loss bookkeeping below
+  const int64_t N = (int64_t)(a.num_active ? min(*a.num_active, a.F) : a.F) * a.R;
   const int64_t gw = (int64_t)blockIdx.x * NGM_WAVES_PER_BLOCK + wave;
   const int64_t r_beg = min(N, gw * rays_per_wave), r_end = min(N, r_beg + rays_per_wave);
   const int S = a.S;
@@ -1280,22 +1282,26 @@ struct AdamMultiK {
   float lr, beta1, beta2, eps, wd;
   int64_t* advance_step;      // non-NULL: ++*advance_step once every block has read it
   uint64_t* advance_offset;   // non-NULL: ++*advance_offset likewise (Philox offset of the next iteration)
+  const int32_t* num_active;  // counted step: rows f >= *num_active are left alone (NULL: all rows)
 };
 __device__ unsigned int g_adam_blocks_done = 0;
 __global__ void k_adam_multi(AdamMultiK a) {
   const ngm_adam_tensor& t = a.t[blockIdx.z];
   const int f = blockIdx.y;
-  const int64_t row = a.field_index ? a.field_index[f] : f;
+  // counted step: a padding row updates nothing and does not read field_index[f]; it still counts itself below
+  const bool active = !a.num_active || f < *a.num_active;
+  const int64_t row = (active && a.field_index) ? a.field_index[f] : f;
   const double step = (double)(a.step_dev ? *a.step_dev : a.step);
   float lr_bc1 = 0.f, inv_sqrt_bc2 = 0.f;
-  if ((int64_t)blockIdx.x * blockDim.x < t.numel) {     // the grid is sized for the largest tensor
+  if (active && (int64_t)blockIdx.x * blockDim.x < t.numel) {     // the grid is sized for the largest tensor
     lr_bc1 = (float)((double)a.lr / (1.0 - pow((double)a.beta1, step)));
     inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)a.beta2, step)));
   }
   const bool vec = ((t.numel | t.stride | t.grad_stride) & 3) == 0 &&
                    ((reinterpret_cast<uintptr_t>(t.param) | reinterpret_cast<uintptr_t>(t.grad) |
                      reinterpret_cast<uintptr_t>(t.exp_avg) | reinterpret_cast<uintptr_t>(t.exp_avg_sq)) & 15) == 0;
-  if (vec) {                                   // 16-byte accesses (the hash tables: 128 Ki floats per field)
+  if (!active) {
+  } else if (vec) {                            // 16-byte accesses (the hash tables: 128 Ki floats per field)
     const int64_t n4 = t.numel >> 2;
     float4* P4 = reinterpret_cast<float4*>(t.param + row * t.stride);
     float4* M4 = reinterpret_cast<float4*>(t.exp_avg + row * t.stride);
@@ -1348,9 +1354,10 @@ __global__ void k_adam_multi(AdamMultiK a) {
 }
 int ngm_launch_adam_multi(const ngm_adam_tensor* tensors, int n, const int64_t* field_index, int F, int64_t step,
                           const int64_t* step_dev, float lr, float beta1, float beta2, float eps, float wd,
-                          int64_t* advance_step, uint64_t* advance_offset, hipStream_t st) {
+                          int64_t* advance_step, uint64_t* advance_offset, hipStream_t st, const int32_t* num_active) {
   NgmProfScope prof_(NGM_K_ADAM, st);
   AdamMultiK a;
+  a.num_active = num_active;
   int64_t mx = 1;
   for (int i = 0; i < n; ++i) { a.t[i] = tensors[i]; mx = std::max<int64_t>(mx, tensors[i].numel); }
   a.n = n; a.field_index = field_index; a.step_dev = step_dev; a.step = step;

@@ -194,6 +194,7 @@ __global__ __launch_bounds__(NGM_BLOCK) void k_field_bwd(FieldBwdArgs a) {
   using BL = BwdLds<MI, MH, L, CAT>;
   constexpr int MC = CAT ? MH + MI : MH;       // input tiles of the layers after the first (concat: hidden ++ encoding)
   const int f = blockIdx.x % a.F, chunk = blockIdx.x / a.F;
+  if (a.num_active && f >= *a.num_active) return;      // counted step: a padding row -- nothing of it is read or written
   const int64_t row = a.pr.field_index ? a.pr.field_index[f] : f;
   {
     FieldStage<MI, MH, L, CAT> fstage;       // every parameter load in flight at once, then the permuting LDS writes
@@ -540,13 +541,20 @@ struct GradReduceK {
   // fused sparse Adam (seg[k].param != NULL): torch.optim.Adam with L2-coupled weight decay, as k_adam_multi
   const int64_t* field_index; const int64_t* step_dev; int64_t step;
   float lr, beta1, beta2, eps, wd;
+  const int32_t* num_active;      // counted step: rows f >= *num_active keep their gradient / parameter / moment rows (NULL: all F)
 };
 
 // 64 parameters x 4 interleaved quarter-sums of the per-workgroup partials per block (the quarters are
 // combined in a fixed order -> deterministic); 4x the loads in flight of a one-thread-per-parameter loop.
+// COUNTED: the counted step's instance (GradReduceK::num_active != NULL), chosen by the launcher -- the kernel is a latency chain
+// and a run-time test of the pointer in front of it cost the plain step 0.2-0.6 us
+template <bool COUNTED>
 __global__ void __launch_bounds__(256) k_grad_reduce(GradReduceK a) {
   __shared__ float part[4][64];
   const int f = blockIdx.y, q = threadIdx.x >> 6, l = threadIdx.x & 63;
+  if constexpr (COUNTED) {
+    if (f >= *a.num_active) return;      // counted step: padding row (workgroup-uniform, before the barrier)
+  }
   const int64_t p = (int64_t)blockIdx.x * 64 + l;
   // The kernel is a latency chain (a few KB per workgroup): everything that does not depend on the sums is issued FIRST --
   // the parameter / moment loads of the quarter that will apply the update, the bias corrections (two fp64 pow) -- and the
@@ -628,8 +636,12 @@ __global__ void __launch_bounds__(256) k_grad_reduce(GradReduceK a) {
 // summed in exactly the order of k_grad_reduce -- quarter i = p_i + p_(i+4), then ((q0 + q1) + q2) + q3 -- so the bits are the same.
 // One parameter p of field f: its partials summed in exactly k_grad_reduce's order -- quarter i = partials i, i + 4, i + 8, ... in
 // that order, then ((q0 + q1) + q2) + q3 -- and the sparse Adam update.  <= 8 partials: all in flight together.
+template <bool COUNTED>
 __device__ __forceinline__ void grad_reduce_one(const GradReduceK& a, int f, int64_t p) {
   if (p >= a.ptot) return;
+  if constexpr (COUNTED) {
+    if (f >= *a.num_active) return;      // counted step: padding row
+  }
   int seg = -1;
   for (int k = 0; k < a.nseg; ++k)
     if (p >= a.seg[k].off && p < a.seg[k].off + a.seg[k].size) { seg = k; break; }
@@ -685,12 +697,14 @@ __device__ __forceinline__ void grad_reduce_one(const GradReduceK& a, int f, int
     if (a.seg[seg].lp) ngm_stp(a.seg[seg].lp, so, pn, a.seg[seg].lp_dt);
   }
 }
+template <bool COUNTED>
 __global__ void __launch_bounds__(256) k_grad_reduce_flat(GradReduceK a) {
-  grad_reduce_one(a, blockIdx.y, (int64_t)blockIdx.x * 256 + threadIdx.x);
+  grad_reduce_one<COUNTED>(a, blockIdx.y, (int64_t)blockIdx.x * 256 + threadIdx.x);
 }
 
 static int build_grad_reduce(const GradReduceArgs& g, GradReduceK& k) {
   k.F = g.F; k.blocks_per_field = g.blocks_per_field; k.partials = g.partials; k.p_pad = g.p_pad;
+  k.num_active = g.num_active;
   int64_t enc_off, w_off[NGM_MAX_LAYERS + 1], b_off[NGM_MAX_LAYERS + 1];
   k.ptot = ngm_param_offsets(&g.fc, &enc_off, w_off, b_off);
   int n = 0;
@@ -726,11 +740,13 @@ int ngm_launch_grad_reduce(const GradReduceArgs& g, hipStream_t st) {
   if (rc) return rc;
   if (k.blocks_per_field <= 8) {
     dim3 grid((unsigned)((k.ptot + 255) / 256), (unsigned)g.F);
-    hipLaunchKernelGGL(k_grad_reduce_flat, grid, dim3(256), 0, st, k);
+    if (k.num_active) hipLaunchKernelGGL(k_grad_reduce_flat<true>, grid, dim3(256), 0, st, k);
+    else hipLaunchKernelGGL(k_grad_reduce_flat<false>, grid, dim3(256), 0, st, k);
     return 0;
   }
   dim3 grid((unsigned)((k.ptot + 63) / 64), (unsigned)g.F);
-  hipLaunchKernelGGL(k_grad_reduce, grid, dim3(256), 0, st, k);
+  if (k.num_active) hipLaunchKernelGGL(k_grad_reduce<true>, grid, dim3(256), 0, st, k);
+  else hipLaunchKernelGGL(k_grad_reduce<false>, grid, dim3(256), 0, st, k);
   return 0;
 }
 
@@ -821,6 +837,7 @@ struct HashGradArgs {
   // it was 8 us of latency chain + boundary in a 195 us iteration.  mlp_bx = 0: none.
   int hash_blocks, mlp_bx;
   GradReduceK mlp;
+  const int32_t* num_active;      // counted step: (field, level, chunk) workgroups of rows f >= *num_active do nothing (NULL: all F)
 };
 
 // FLT = false (NGM_HASH_ATOMICS_EXACT, the default): Q23.40 fixed point in LDS -- integer LDS atomics run at full bank rate
@@ -846,7 +863,9 @@ __global__ __launch_bounds__(NT) void k_hash_grad(HashGradArgs a) {
   acc_t* tab = reinterpret_cast<acc_t*>(tab_raw);
   if ((int)blockIdx.x >= a.hash_blocks) {          // the MLP reduction riding along: one thread per parameter (grad_reduce_one)
     const int id = (int)blockIdx.x - a.hash_blocks;
-    grad_reduce_one(a.mlp, id / a.mlp_bx, (int64_t)(id % a.mlp_bx) * blockDim.x + threadIdx.x);
+    // (the riding reduction tests the pointer at run time: this branch is a handful of workgroups behind the table work)
+    if (a.mlp.num_active) grad_reduce_one<true>(a.mlp, id / a.mlp_bx, (int64_t)(id % a.mlp_bx) * blockDim.x + threadIdx.x);
+    else grad_reduce_one<false>(a.mlp, id / a.mlp_bx, (int64_t)(id % a.mlp_bx) * blockDim.x + threadIdx.x);
     return;
   }
   int chunk, f, level[NL];
@@ -873,6 +892,7 @@ __global__ __launch_bounds__(NT) void k_hash_grad(HashGradArgs a) {
     }
   }
   const int T = 1 << a.fc.log2_hashmap_size;
+  if (a.num_active && f >= *a.num_active) return;      // counted step: padding row (workgroup-uniform, before any barrier)
   const int64_t row = a.pr.field_index ? a.pr.field_index[f] : f;
   for (int i = threadIdx.x; i < NL * 2 * T; i += blockDim.x) tab[i] = acc_t(0);
   // Adam's bias corrections (two double-precision pow) once per workgroup, up front, by one thread -- not by every thread in
@@ -1043,6 +1063,7 @@ __global__ void k_hash_reduce(HashGradArgs a) {
   const int level = blockIdx.y, f = blockIdx.z;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;          // float4 index
   if (i >= T / 2) return;
+  if (a.num_active && f >= *a.num_active) return;      // counted step: padding row
   const float4* src = reinterpret_cast<const float4*>(a.part + ((int64_t)f * a.fc.nr_levels + level) * a.chunks * 2 * T);
   float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
   for (int c = 0; c < a.chunks; ++c) {
@@ -1084,6 +1105,7 @@ int ngm_launch_hash_grad(const FieldBwdArgs& fb, hipStream_t st, bool* adam_appl
   if (mlp_reduced) *mlp_reduced = false;
   a.fc = fb.fc; a.pr = fb.pr; a.F = fb.F; a.P = fb.P; a.dE = fb.hash_dE; a.xyz = fb.hash_xyz;
   a.gtab = fb.lattice_grad; a.gstride = fb.lattice_grad_stride;
+  a.num_active = fb.num_active;
   const int T = 1 << fb.fc.log2_hashmap_size;
   const bool flt = fb.fc.hash_grad_atomics == NGM_HASH_ATOMICS_FLOAT;
   const size_t lds = (size_t)2 * T * (flt ? sizeof(float) : sizeof(unsigned long long));

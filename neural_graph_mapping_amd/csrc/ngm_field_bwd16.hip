@@ -67,6 +67,7 @@ __global__ __launch_bounds__(B16_THREADS) void k_field_bwd16(FieldBwdArgs a) {
   using LY = Lds16<TI, TH, L>;
   constexpr int BLK = LY::BLK;
   const int f = blockIdx.x % a.F, chunk = blockIdx.x / a.F;
+  if (a.num_active && f >= *a.num_active) return;      // counted step: a padding row -- nothing of it is read or written
   const int64_t row = a.pr.field_index ? a.pr.field_index[f] : f;
   {
     FieldStage16<TI, TH, L> stage;      // every parameter load in flight at once, then the permuting LDS writes

@@ -203,6 +203,7 @@ __global__ __launch_bounds__(B16_THREADS) void k_field_bwd16s(FieldBwdArgs a) {
   using LW = typename LY::W;
   constexpr int BLK = LW::BLK;
   const int f = blockIdx.x % a.F, chunk = blockIdx.x / a.F;
+  if (a.num_active && f >= *a.num_active) return;      // counted step: a padding row -- nothing of it is read or written
   const int64_t row = a.pr.field_index ? a.pr.field_index[f] : f;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int j = lane & 15, q = lane >> 4;

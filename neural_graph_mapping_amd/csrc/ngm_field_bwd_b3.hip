@@ -124,7 +124,9 @@ __device__ __forceinline__ void recompute_with_encoding(const ngm_u32x4* __restr
 // and carries the suffix value Q of the per-ray recursion Q_{k-1} = a_k o_k + (1 - o_k) Q_k from tile to tile.
 // HS: half stash (FieldBwdArgs::act_half, L = 2): only layer 0's output was stashed; the output layer's input is recomputed
 // from it per tile (LdsB3b).
-template <int L, bool NEED_COS, bool ENC_GRAD, bool FC = false, bool HS = false>
+// COUNTED: the instance of the counted step (FieldBwdArgs::num_active != NULL).  A template parameter, chosen by the launcher:
+// as a run-time pointer test in the one instance it cost the plain step 0.6-3.7 us of this kernel at equal register usage.
+template <int L, bool NEED_COS, bool ENC_GRAD, bool FC = false, bool HS = false, bool COUNTED = false>
 __global__ __launch_bounds__(B3B_THREADS) void k_field_bwd_b3(FieldBwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   using LY = LdsB3b<L, ENC_GRAD, HS>;
@@ -136,6 +138,12 @@ __global__ __launch_bounds__(B3B_THREADS) void k_field_bwd_b3(FieldBwdArgs a) {
 #define PTK(i)
 #endif
   const int f = blockIdx.x % a.F, chunk = blockIdx.x / a.F;
+  if constexpr (COUNTED) {
+    if (f >= *a.num_active) {      // counted step: a padding row -- nothing of it is read or written
+      if constexpr (FC) ngm_counted_idle_bookkeeping(a);
+      return;
+    }
+  }
   const int64_t row = a.pr.field_index ? a.pr.field_index[f] : f;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i = lane & 31, hi = lane >> 5;
@@ -874,20 +882,25 @@ static int launch_bwd_b3(const FieldBwdArgs& a, int blocks, hipStream_t st) {
   do {                                                                                                                \
     static_assert(LdsB3b<L, EG, HS>::TOTAL * sizeof(float) <= 160 * 1024, "k_field_bwd_b3: LDS over 160 KiB");       \
     const size_t lds = (size_t)LdsB3b<L, EG, HS>::TOTAL * sizeof(float);                                              \
-    if (a.fused_comp) {                                                                                               \
-      (void)hipFuncSetAttribute((const void*)k_field_bwd_b3<L, NC, EG, true, HS>, hipFuncAttributeMaxDynamicSharedMemorySize, \
+    if (a.fused_comp) NGM_LBB3_ONE(NC, EG, true); else NGM_LBB3_ONE(NC, EG, false);                                    \
+  } while (0)
+#define NGM_LBB3_ONE(NC, EG, FC_)                                                                                     \
+  do {                                                                                                                \
+    if (a.num_active) {                                                                                               \
+      (void)hipFuncSetAttribute((const void*)k_field_bwd_b3<L, NC, EG, FC_, HS, true>, hipFuncAttributeMaxDynamicSharedMemorySize, \
                                 (int)lds);                                                                            \
-      hipLaunchKernelGGL((k_field_bwd_b3<L, NC, EG, true, HS>), dim3(blocks), dim3(B3B_THREADS), lds, st, a);         \
+      hipLaunchKernelGGL((k_field_bwd_b3<L, NC, EG, FC_, HS, true>), dim3(blocks), dim3(B3B_THREADS), lds, st, a);    \
     } else {                                                                                                          \
-      (void)hipFuncSetAttribute((const void*)k_field_bwd_b3<L, NC, EG, false, HS>, hipFuncAttributeMaxDynamicSharedMemorySize, \
+      (void)hipFuncSetAttribute((const void*)k_field_bwd_b3<L, NC, EG, FC_, HS>, hipFuncAttributeMaxDynamicSharedMemorySize, \
                                 (int)lds);                                                                            \
-      hipLaunchKernelGGL((k_field_bwd_b3<L, NC, EG, false, HS>), dim3(blocks), dim3(B3B_THREADS), lds, st, a);        \
+      hipLaunchKernelGGL((k_field_bwd_b3<L, NC, EG, FC_, HS>), dim3(blocks), dim3(B3B_THREADS), lds, st, a);          \
     }                                                                                                                 \
   } while (0)
   if (a.fc.encoding == NGM_ENC_FOURIER) NGM_LBB3(false, true);
   else if (a.fc.encoding == NGM_ENC_NERF) NGM_LBB3(true, false);
   else NGM_LBB3(false, false);
 #undef NGM_LBB3
+#undef NGM_LBB3_ONE
   return 0;
 }
 

@@ -323,13 +323,22 @@ __device__ __forceinline__ int fdiv_idx(int idx, float inv_s, int S) {
 // HALF (round 6): the instance for batches of at most 32 samples per wave (a rank of an 8-GPU run: one 24-sample ray per wave):
 // the wave step evaluates ONE 32-sample tile (eval_32) where the batch allows it.  A separate instance, chosen by the launcher,
 // so that the default instance's code and register allocation stay what they were (in-line it cost the M1 forward 0.9 us).
-template <int MI, int MH, int L, bool NEED_COS, int HASH, int SKIP, bool B3 = false, bool NEUS = false, bool HALF = false>
+// COUNTED: the instance of the counted step (RenderFwdArgs::num_active != NULL), chosen by the launcher like HALF and for the same
+// reason: as a run-time test in the one instance it cost the plain M1 forward 0.6-0.8 us.
+template <int MI, int MH, int L, bool NEED_COS, int HASH, int SKIP, bool B3 = false, bool NEUS = false, bool HALF = false, bool COUNTED = false>
 __global__ __launch_bounds__(512) void k_render_fwd(RenderFwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   using LY = FieldLds<MI, MH, L, SKIP == 2>;
   const int F = a.rays.F, R = a.rays.R;
   const int f = blockIdx.x % F, chunk = blockIdx.x / F;
-  const int64_t row = a.pr.field_index ? a.pr.field_index[f] : f;
+  // Counted step: a row at or beyond the device count is padding.  Its workgroup SKIPS instead of leaving: an empty ray range
+  // (below), so nothing of the row is read (field_index[f] and pose_index[f] included: parameter row 0 and pose 0 are staged in
+  // their place and never used) or written, and the loss reduction at the end leaves the zero partial the backward's sum over
+  // ALL forward workgroups needs.  (An early `return` here changed the register allocation of every instance -- the split-path
+  // instance went from 17 to 41 spilled VGPRs; this form compiles to the resource usage of the kernel without it.)  Neus and
+  // the triplane encoding are outside the counted step: no COUNTED instance of them is launched.
+  const bool idle = COUNTED && f >= *a.num_active;
+  const int64_t row = idle ? 0 : (a.pr.field_index ? a.pr.field_index[f] : f);
 #ifdef NGM_PHASE_TIMING
   // timeline of every wave of the middle block: 16 summary slots, then 64 log entries per wave
   PhaseClock pclk;
@@ -353,13 +362,13 @@ __global__ __launch_bounds__(512) void k_render_fwd(RenderFwdArgs a) {
 
   float div, off;
   scale_consts(a.fc.scale_mode, a.fc.field_radius, &div, &off);
-  const int64_t pf = a.rays.pose_index ? a.rays.pose_index[f] : f;
+  const int64_t pf = idle ? 0 : (a.rays.pose_index ? a.rays.pose_index[f] : f);
   const float px = a.rays.field_pos[3 * pf], py = a.rays.field_pos[3 * pf + 1], pz = a.rays.field_pos[3 * pf + 2];
   const float qw = a.rays.field_quat[4 * pf], qx = a.rays.field_quat[4 * pf + 1], qy = a.rays.field_quat[4 * pf + 2],
               qz = a.rays.field_quat[4 * pf + 3];
 
   // this wave's rays [r_beg, r_end) inside field f
-  const int blk_beg = chunk * a.rays_per_block, blk_end = min(R, blk_beg + a.rays_per_block);
+  const int blk_beg = chunk * a.rays_per_block, blk_end = idle ? blk_beg : min(R, blk_beg + a.rays_per_block);
   const int per_wave = (blk_end - blk_beg + nwaves - 1) / nwaves;
   const int r_beg = min(blk_end, blk_beg + wave * per_wave), r_end = min(blk_end, r_beg + per_wave);
   const int BR = max(1, min(RF_BRMAX, a.maxs / S));
@@ -771,6 +780,30 @@ static int launch_points(const PointsFwdArgs& a, int blocks, hipStream_t st) {
   else NGM_LAUNCH_VARIANT(k_field_points_fwd, false, 0, blocks, blk, 0, 0);
   return 0;
 }
+// one instance of k_render_fwd: the COUNTED twin when the call carries a device count (never for the triplane encoding)
+template <int MI, int MH, int L, bool NC, int HS, int SK, bool B3, bool HALF>
+static void launch_render_inst(const RenderFwdArgs& a, int blocks, dim3 blk, size_t lds, hipStream_t st) {
+  if constexpr (HS != 2) {
+    if (a.num_active) {
+      (void)hipFuncSetAttribute((const void*)k_render_fwd<MI, MH, L, NC, HS, SK, B3, false, HALF, true>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipLaunchKernelGGL((k_render_fwd<MI, MH, L, NC, HS, SK, B3, false, HALF, true>), dim3(blocks), blk, lds, st, a);
+      return;
+    }
+  }
+  (void)hipFuncSetAttribute((const void*)k_render_fwd<MI, MH, L, NC, HS, SK, B3, false, HALF>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL((k_render_fwd<MI, MH, L, NC, HS, SK, B3, false, HALF>), dim3(blocks), blk, lds, st, a);
+}
+#define NGM_RENDER_VARIANT(NC, HS)                                                                                        \
+  do {                                                                                                                   \
+    if (a.fc.skip_mode == NGM_SKIP_ADD)                                                                                  \
+      launch_render_inst<MI, MH, L, NC, HS, 1, false, false>(a, blocks, blk, (FieldLds<MI, MH, L, false>::TOTAL + wave_lds) * sizeof(float), st); \
+    else if (a.fc.skip_mode == NGM_SKIP_CONCAT)                                                                          \
+      launch_render_inst<MI, MH, L, NC, HS, 2, false, false>(a, blocks, blk, (FieldLds<MI, MH, L, true>::TOTAL + wave_lds) * sizeof(float), st);  \
+    else                                                                                                                 \
+      launch_render_inst<MI, MH, L, NC, HS, 0, false, false>(a, blocks, blk, (FieldLds<MI, MH, L, false>::TOTAL + wave_lds) * sizeof(float), st); \
+  } while (0)
 template <int MI, int MH, int L>
 static int launch_render(const RenderFwdArgs& a, int blocks, hipStream_t st) {
   const size_t wave_lds = (size_t)a.waves_per_block * RenderWaveLds::floats(a.maxs);
@@ -799,14 +832,10 @@ static int launch_render(const RenderFwdArgs& a, int blocks, hipStream_t st) {
         static const bool no_half = getenv("NGM_NO_HALF_STEP") != nullptr;          // developer A/B switch
         g_ngm_last_fwd_one_tile = (per_wave * a.S <= 32 && !no_half) ? 1 : 0;
         if (per_wave * a.S <= 32 && !no_half) {
-          (void)hipFuncSetAttribute((const void*)k_render_fwd<MI, MH, L, false, 0, 0, true, false, true>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-          hipLaunchKernelGGL((k_render_fwd<MI, MH, L, false, 0, 0, true, false, true>), dim3(blocks), blk, lds, st, a);
+          launch_render_inst<MI, MH, L, false, 0, 0, true, true>(a, blocks, blk, lds, st);
           return 0;
         }
-        (void)hipFuncSetAttribute((const void*)k_render_fwd<MI, MH, L, false, 0, 0, true>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((k_render_fwd<MI, MH, L, false, 0, 0, true>), dim3(blocks), blk, lds, st, a);
+        launch_render_inst<MI, MH, L, false, 0, 0, true, false>(a, blocks, blk, lds, st);
         return 0;
       }
     }
@@ -819,17 +848,15 @@ static int launch_render(const RenderFwdArgs& a, int blocks, hipStream_t st) {
       static const bool no_half = getenv("NGM_NO_HALF_STEP") != nullptr;
       if (per_wave * a.S <= 32 && !no_half && a.fc.skip_mode == NGM_SKIP_NO) {
         const size_t lds_ = (FieldLds<MI, MH, L>::TOTAL + wave_lds) * sizeof(float);
-        (void)hipFuncSetAttribute((const void*)k_render_fwd<MI, MH, L, false, 1, 0, false, false, true>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_);
-        hipLaunchKernelGGL((k_render_fwd<MI, MH, L, false, 1, 0, false, false, true>), dim3(blocks), blk, lds_, st, a);
+        launch_render_inst<MI, MH, L, false, 1, 0, false, true>(a, blocks, blk, lds_, st);
         g_ngm_last_fwd_one_tile = 1;
         return 0;
       }
-      NGM_LAUNCH_VARIANT(k_render_fwd, false, 1, blocks, blk, 0, wave_lds);
+      NGM_RENDER_VARIANT(false, 1);
     }
     else return NGM_E_UNSUPPORTED;
-  } else if (a.fc.encoding == NGM_ENC_TRIPLANE) NGM_LAUNCH_VARIANT(k_render_fwd, false, 2, blocks, blk, 0, wave_lds); else if (a.fc.encoding == NGM_ENC_NERF) NGM_LAUNCH_VARIANT(k_render_fwd, true, 0, blocks, blk, 0, wave_lds);
-  else NGM_LAUNCH_VARIANT(k_render_fwd, false, 0, blocks, blk, 0, wave_lds);
+  } else if (a.fc.encoding == NGM_ENC_TRIPLANE) NGM_RENDER_VARIANT(false, 2); else if (a.fc.encoding == NGM_ENC_NERF) NGM_RENDER_VARIANT(true, 0);
+  else NGM_RENDER_VARIANT(false, 0);
   return 0;
 }
 

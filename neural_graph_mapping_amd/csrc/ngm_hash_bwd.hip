@@ -63,6 +63,10 @@ __global__ __launch_bounds__(HB_THREADS) void k_hash_mlp_bwd(FieldBwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   using LY = LdsHB;
   const int f = blockIdx.x % a.F, chunk = blockIdx.x / a.F;
+  if (a.num_active && f >= *a.num_active) {      // counted step: a padding row -- nothing of it is read or written
+    if constexpr (FC) ngm_counted_idle_bookkeeping(a);
+    return;
+  }
   const int64_t row = a.pr.field_index ? a.pr.field_index[f] : f;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i = lane & 31, hi = lane >> 5;

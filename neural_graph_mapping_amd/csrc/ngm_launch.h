@@ -51,6 +51,9 @@ struct RenderFwdArgs {
   const float* neus_sd;   // neus: "_neus_sd" (N,) rows like the other parameters (field_index), else NULL
   int64_t neus_sd_stride;
   unsigned long long* debug_cycles;   // optional (NGM_PHASE_TIMING): per-phase shader-clock cycles of one wave
+  // counted step (ngm_render_fwd_counted): device count of active rows, 0 <= *num_active <= rays.F; a workgroup of row
+  // f >= *num_active reads and writes nothing of that row and leaves a zero loss partial in its slot.  NULL: all rays.F rows.
+  const int32_t* num_active;
 };
 
 // backward of the field MLP for flat samples of each field
@@ -63,6 +66,9 @@ struct GradAdam {
   int64_t step; const int64_t* step_dev;
   float lr, beta1, beta2, eps, wd;
 };
+// Counted step: `num_active` (device, NULL = all F rows) in the argument records below.  Workgroups of rows f >= *num_active
+// leave before their first read through field_index and write nothing; the loss bookkeeping of block 0 (fused compositing
+// backward, k_stash_bwd) happens whatever the count (ngm_counted_idle_bookkeeping, ngm_bwd16.h).
 struct FieldBwdArgs {
   ngm_field_cfg fc;
   ngm_params pr;
@@ -108,6 +114,7 @@ struct FieldBwdArgs {
   const float* loss_sums;             // global (all-reduced) sums, or NULL -> loss_partials
   const float* loss_partials; int n_partials;
   float* sums_out; float* loss_out; unsigned long long* counter;   // as StashBwdArgs
+  const int32_t* num_active;          // counted step: device count of active rows (NULL: all F)
 };
 bool ngm_field_bwd_b3_applies(const FieldBwdArgs& a);   // would ngm_launch_field_bwd_b3 take this problem
 bool ngm_hash_mlp_bwd_applies(const FieldBwdArgs& a);   // would ngm_launch_hash_mlp_bwd take this problem
@@ -125,6 +132,7 @@ struct GradReduceArgs {
   const float* partials;
   int64_t p_pad;
   GradAdam adam;
+  const int32_t* num_active = nullptr; // counted step: rows f >= *num_active keep their gradient and parameter rows (NULL: all F)
 };
 
 // composite (quadrature) standalone + stash variants
@@ -177,6 +185,7 @@ struct StashBwdArgs {
   float* sums_out;            // (16) optional copy of the reduced sums
   unsigned long long* counter;// optional iteration counter to advance (what k_loss_reduce does otherwise)
   float4* xyz_out;            // (F*R*S) optional: scaled field-local sample positions for k_hash_grad (permutohedral encoding)
+  const int32_t* num_active;  // counted step: only the rays of rows f < *num_active are walked (NULL: all F)
 };
 
 // which arithmetic the last launch of each forward-type kernel resolved to (ngm_debug_last_matmul): 0 = the fused render

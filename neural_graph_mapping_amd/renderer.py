@@ -27,7 +27,9 @@ class DeviceTarget(namedtuple("DeviceTarget", Target._fields + ("count", "subset
                                                                 "frame_cids", "u_xy", "world_size"))):
     """What NeuralGraphRenderer.sample_target_mv_device returns: the fields of Target at a fixed, host-known capacity
     (Fcap, R, ...), `count` = a device int32 tensor (1,) holding the number of surviving fields (rows count..Fcap-1 are
-    padding: field_ids -1, masks 0, zeros elsewhere), plus the draws that produced them."""
+    padding: field_ids -1, masks 0, zeros elsewhere), plus the draws that produced them.
+    NeuralGraphRenderer.optimization_iteration / capture_iteration take it as it is (the counted step: launched at Fcap,
+    the kernels read `count` on the device); materialize() is only needed by consumers that want data-dependent shapes."""
     __slots__ = ()
 
     def materialize(self) -> Target:
@@ -170,6 +172,7 @@ class NeuralGraphRenderer:
         self._peer_calls = 0
         self.field_draw_generator = None   # torch.Generator of sample_target_mv(field_draw="balanced_by_owner"), see there
         self._target_iter_dev = None       # sample_target_mv_device's iteration counter (device int64, advanced by each call)
+        self._warned_counted_fallback = False
 
     def last_matmul(self, kernel: str = "forward") -> Optional[str]:
         """The arithmetic the library resolved `mlp_matmul` to in the LAST launch of the fused forward ("forward"), the
@@ -798,7 +801,19 @@ class NeuralGraphRenderer:
         sparse Adam on the touched fields.  Returns the loss dict (device scalars) and, with
         update=False, also the gradients.  Every launch is asynchronous on the current stream and the
         sequence is hipGraph-capturable (device-side step / jitter counters, no allocation after the
-        first call with a given batch shape)."""
+        first call with a given batch shape).
+
+        A DeviceTarget (sample_target_mv_device) is consumed as it is -- the counted step: every launch is sized for the
+        capacity Fcap and the kernels read `target.count` on the device, so nothing here synchronises or depends on the
+        count, and one captured graph serves every count in [0, Fcap].  Rows >= count are never read (their field_ids of
+        -1 included) and never written: `prediction` rows and, with update=False, gradient rows >= count are unspecified
+        (leftovers of earlier calls).  count == 0 is an iteration like _idle_iteration's: zero sums, NaN loss terms, no
+        parameter touched, counters advanced; with a process group / peer_exchange the loss exchange is entered by every
+        rank whatever its count.  Configurations outside the counted step (geometry mode neus, triplane encoding, *_nll
+        loss modes) fall back to target.materialize() with a one-time RuntimeWarning (it synchronises) -- under graph
+        capture they raise instead."""
+        if isinstance(target, DeviceTarget):
+            return self._counted_iteration(target, u_coarse, u_guided, seed, update)
         if self._rc_train.geometry_mode == K.GEO["neus"] and not self._neus_fused():
             return self.optimization_iteration_staged(target, u_coarse, u_guided, seed, update)
         if target.ijs.shape[0] == 0:
@@ -807,6 +822,40 @@ class NeuralGraphRenderer:
         if self.process_group is not None:
             # the only cross-GPU exchange of the path: global loss sums / counts (64 bytes)
             self._exchange(ctx["w"]["sums"])
+        return self._iteration_backward(ctx, update)
+
+    def counted_step_unsupported(self) -> Optional[str]:
+        """Why this renderer's configuration is outside the counted step (None: it is inside).  The library draws the same
+        line (ngm_render_*_counted: NGM_E_UNSUPPORTED): neus and the triplane encoding run launches over all F rows, the
+        *_nll loss modes are left out."""
+        rc, fc = self._rc_train, self._fc
+        if rc.geometry_mode == K.GEO["neus"]:
+            return "geometry mode 'neus'"
+        if fc.encoding == K.ENC["triplane"]:
+            return "the triplane encoding"
+        if rc.photometric_mode == K.PHOTO["gaussian_nll"] or rc.depth_mode != K.DEPTH["huber"]:
+            return "the *_nll loss modes"
+        return None
+
+    def _counted_iteration(self, target: "DeviceTarget", u_coarse=None, u_guided=None, seed=0, update=True) -> dict:
+        """optimization_iteration on a DeviceTarget: the fused step at capacity with the device count (never materialize(),
+        never a read of `count`), or the warned fallback for configurations outside the counted step."""
+        why = self.counted_step_unsupported()
+        if why is not None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"optimization_iteration(DeviceTarget): {why} is outside the counted step and the "
+                                   "fallback (DeviceTarget.materialize()) synchronises: it cannot be captured")
+            if not self._warned_counted_fallback:
+                self._warned_counted_fallback = True
+                warnings.warn(f"optimization_iteration(DeviceTarget): {why} is outside the counted step; falling back to "
+                              "DeviceTarget.materialize(), which synchronises with the host every iteration",
+                              RuntimeWarning, stacklevel=3)
+            return self.optimization_iteration(target.materialize(), u_coarse, u_guided, seed, update)
+        if target.ijs.shape[0] == 0:                      # capacity 0 is known on the host (a rank that owns no field at all)
+            return self._idle_iteration(update)
+        ctx = self._iteration_forward(target, u_coarse, u_guided, seed, advance=update, count=target.count)
+        if self.process_group is not None:
+            self._exchange(ctx["w"]["sums"])                # entered by every rank, whatever its own count
         return self._iteration_backward(ctx, update)
 
     def check_exchange(self):
@@ -858,10 +907,12 @@ class NeuralGraphRenderer:
         loss["prediction"] = None
         return loss
 
-    def _iteration_forward(self, target: Target, u_coarse=None, u_guided=None, seed=0, advance=True) -> dict:
+    def _iteration_forward(self, target: Target, u_coarse=None, u_guided=None, seed=0, advance=True, count=None) -> dict:
         """First half of the iteration: fused forward + local loss sums (everything before the all-reduce).
         One device counter counts the iterations: the forward adds it to the Philox offset, the loss-reduction kernel
-        advances it (advance=True) and Adam then reads it as its step -- no launch of its own for the bookkeeping."""
+        advances it (advance=True) and Adam then reads it as its step -- no launch of its own for the bookkeeping.
+        count (device int32 (1,)): the counted step -- `target` holds that many rows followed by padding; the padded
+        field_ids go to the kernels as they are (rows >= count are not read)."""
         L = K.lib()
         fc, rc = self._fc, self._rc_train
         fids = target.field_ids
@@ -895,10 +946,17 @@ class NeuralGraphRenderer:
         # single GPU: nothing happens between forward and backward, so the loss partials are reduced by the backward
         # itself (deferred reduction, one launch less); with a process group the sums are needed here for the all-reduce
         defer = self.process_group is None
-        K.check(L.ngm_render_fwd(C.byref(fc), C.byref(rc), C.byref(ps), C.byref(rays), C.byref(tg), C.byref(pred),
-                                 None if defer else w["sums"].data_ptr(), w["ws"].data_ptr(), w["wsb"], st), "ngm_render_fwd")
+        if count is not None:
+            if count.dtype != torch.int32 or count.numel() != 1 or not count.is_cuda:
+                raise TypeError("count must be a device int32 tensor of one element")
+            K.check(L.ngm_render_fwd_counted(C.byref(fc), C.byref(rc), C.byref(ps), C.byref(rays), C.byref(tg), C.byref(pred),
+                                             None if defer else w["sums"].data_ptr(), w["ws"].data_ptr(), w["wsb"], st,
+                                             count.data_ptr()), "ngm_render_fwd_counted")
+        else:
+            K.check(L.ngm_render_fwd(C.byref(fc), C.byref(rc), C.byref(ps), C.byref(rays), C.byref(tg), C.byref(pred),
+                                     None if defer else w["sums"].data_ptr(), w["ws"].data_ptr(), w["wsb"], st), "ngm_render_fwd")
         return dict(fc=fc, rc=rc, ps=ps, rays=rays, tg=tg, pred=pred, w=w, F=F, fids=fids, allp=allp, lp=lp, defer=defer,
-                    neus=neus, keep=(keep, dm, tm, rgbds_t, target))
+                    neus=neus, count=count, keep=(keep, dm, tm, rgbds_t, target))
 
     def _iteration_backward(self, ctx: dict, update=True) -> dict:
         """Second half: compositing + MLP backward with the (global) loss sums, sparse Adam, counters."""
@@ -913,7 +971,22 @@ class NeuralGraphRenderer:
             grads["_neus_sd"] = torch.zeros(F, device=self._device)
             gs.neus_sd = grads["_neus_sd"].data_ptr()
         sums_ptr = None if ctx.get("defer") else w["sums"].data_ptr()
-        if update:
+        count = ctx.get("count")
+        if count is not None:
+            # the counted step (neus / triplane never get here: their extra launches below run over all F rows)
+            if update:
+                self._step += 1
+                arr, n_mlp, lat = ops.adam_tensor_arrays(fc, allp, self._optim_state, grads, ctx.get("lp"))
+                K.check(L.ngm_render_bwd_adam_counted(
+                    C.byref(fc), C.byref(rc), C.byref(ps), C.byref(rays), C.byref(tg), C.byref(pred), sums_ptr, C.byref(gs), arr,
+                    n_mlp, lat, ops._ptr(fids), int(self._step), ops._ptr(self._step_dev), self._learning_rate, 0.9, 0.999,
+                    self._adam_eps, self._adam_weight_decay, w["loss"].data_ptr(), w["ws"].data_ptr(), w["wsb"], st,
+                    count.data_ptr()), "ngm_render_bwd_adam_counted")
+            else:
+                K.check(L.ngm_render_bwd_counted(C.byref(fc), C.byref(rc), C.byref(ps), C.byref(rays), C.byref(tg), C.byref(pred),
+                                                 sums_ptr, C.byref(gs), w["loss"].data_ptr(), w["ws"].data_ptr(), w["wsb"],
+                                                 st, count.data_ptr()), "ngm_render_bwd_counted")
+        elif update:
             # backward + sparse Adam in one call: the gradient-reduction kernel applies the update of the MLP tensors
             # itself (rm.py:1183-1221); the device counter already holds the new step (the loss reduction advanced it)
             self._step += 1                                  # one counter for all fields (rm.py:380-385)
@@ -957,10 +1030,18 @@ class NeuralGraphRenderer:
         replays it.  Tensors of `target` are read in place at every replay; the Adam step counter and the Philox
         jitter offset live on the device and advance inside the graph.  With a process group the iteration becomes
         two graphs (before / after the loss all-reduce) and the 64-byte collective is issued between the replays --
-        unless `peer_exchange` is set: then the exchange is a kernel of the ONE captured graph."""
+        unless `peer_exchange` is set: then the exchange is a kernel of the ONE captured graph.
+        A DeviceTarget is captured as the counted step: the one graph serves every active count up to its capacity."""
         if self._rc_train.geometry_mode == K.GEO["neus"] and not self._neus_fused():
             raise NotImplementedError("capture_iteration: the staged (neus) iteration allocates under autograd; call "
                                       "optimization_iteration directly")
+        count = None
+        if isinstance(target, DeviceTarget):
+            why = self.counted_step_unsupported()
+            if why is not None:
+                raise RuntimeError(f"capture_iteration(DeviceTarget): {why} is outside the counted step; capture a "
+                                   "materialised Target instead")
+            count = target.count
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -987,7 +1068,7 @@ class NeuralGraphRenderer:
         try:
             g1, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
             with torch.cuda.graph(g1, capture_error_mode="thread_local"):
-                ctx = self._iteration_forward(target, u_coarse, u_guided, seed, advance=True)
+                ctx = self._iteration_forward(target, u_coarse, u_guided, seed, advance=True, count=count)
             with torch.cuda.graph(g2, pool=g1.pool(), capture_error_mode="thread_local"):
                 out = self._iteration_backward(ctx, True)
         except RuntimeError as err:
@@ -1014,3 +1095,119 @@ class NeuralGraphRenderer:
             return out
         replay2.graph = (g1, g2)
         return replay2
+
+    def capture_training(self, current_field_ids, c_c2w, nc_rgbd, frame_cid_to_ncid, num_train_fields, num_rays_per_field,
+                         seed=0, camera: Optional[Camera] = None, world_size: int = 1, rank: int = 0):
+        """The whole training iteration as ONE captured graph: sample_target_mv_device(iteration=None) followed by the
+        counted optimization_iteration on its DeviceTarget -- sampler, forward, losses, backward and sparse Adam, with no
+        host synchronisation and no data-dependent shape.  Returns a callable; every call replays the graph, i.e. draws the
+        NEXT iteration's targets (the renderer's device iteration counter advances inside the graph) and trains on them,
+        and returns the loss dict of device scalars.  `.target` is the static DeviceTarget the replays overwrite, `.graph`
+        the torch.cuda.CUDAGraph -- or the pair (before / after the loss all-reduce) with a process group and no
+        `peer_exchange`, as capture_iteration builds it; None if the runtime refused that capture (plain launches then).
+
+        The input tensors and the field poses are READ IN PLACE at every replay: update their contents freely (new
+        keyframes in the same store, moved fields), but the graph is valid only while their shapes and storage, the
+        number of fields and the stacked parameter tensors are unchanged (add_fields / load_model need a new capture).
+        Shapes, data pointers and `num` are checked on the host at every replay (no synchronisation); the inputs must be
+        contiguous device tensors (current_field_ids / frame_cid_to_ncid int64), since a copy made here would be the
+        one the graph keeps reading.
+
+        Every rank must own at least one field of the map (a capacity of 0 rows raises ValueError: nothing to capture).
+
+        Before the capture the sampler and the counted step run once with update=False (allocations, the device
+        counters); the iteration counter is put back afterwards, so the first replay is the iteration the counter named
+        when this was called, and nothing has been trained yet."""
+        why = self.counted_step_unsupported()
+        if why is not None:
+            raise RuntimeError(f"capture_training: {why} is outside the counted step (optimization_iteration would fall "
+                               "back to DeviceTarget.materialize(), which synchronises)")
+        dev = torch.device(self._device)
+        named = dict(current_field_ids=current_field_ids, c_c2w=c_c2w, nc_rgbd=nc_rgbd, frame_cid_to_ncid=frame_cid_to_ncid)
+        for n, t in named.items():
+            if not t.is_cuda or not t.is_contiguous():
+                raise ValueError(f"capture_training: {n} must be a contiguous device tensor (it is read in place at every replay)")
+        for n in ("current_field_ids", "frame_cid_to_ncid"):
+            if named[n].dtype != torch.int64:
+                raise TypeError(f"capture_training: {n} must be int64")
+        num_fields = self._global_map_dict["num"]
+
+        def watched():
+            ts = dict(named, positions=self._global_map_dict["positions"], orientations=self._global_map_dict["orientations"])
+            ts.update({"param " + n: v for n, v in self._model.all_fields_params.items()})
+            return {n: (t.data_ptr(), tuple(t.shape)) for n, t in ts.items()}
+        for n in ("positions", "orientations"):
+            if not self._global_map_dict[n].is_contiguous():
+                raise ValueError(f"capture_training: the field {n} must be contiguous (read in place at every replay)")
+
+        def sample():
+            return self.sample_target_mv_device(current_field_ids, c_c2w, nc_rgbd, frame_cid_to_ncid, num_train_fields,
+                                                num_rays_per_field, num_fields=num_fields, camera=camera, seed=seed,
+                                                iteration=None, world_size=world_size, rank=rank)
+        # once outside the capture, on a side stream: creates the device counters, the workspace and the gradient buffers
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            it0 = None if self._target_iter_dev is None else self._target_iter_dev.clone()
+            probe = sample()
+            if probe.ijs.shape[0] == 0:
+                raise ValueError("capture_training: this rank's capacity is 0 (it owns none of the fields that can be drawn: "
+                                 "fewer fields than ranks); there is no step to capture -- call optimization_iteration, "
+                                 "which runs the idle iteration for such a rank")
+            self.optimization_iteration(probe, seed=seed, update=False)
+            if it0 is None:
+                self._target_iter_dev.zero_()
+            else:
+                self._target_iter_dev.copy_(it0)
+        torch.cuda.current_stream().wait_stream(s)
+        step0 = self._step
+        two = self.process_group is not None and self.peer_exchange is None
+        if not two:
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                target = sample()
+                out = self.optimization_iteration(target, seed=seed)
+            self._step = step0                                # the capture pass records, it does not execute
+            graphs = graph
+        else:
+            try:
+                g1, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g1, capture_error_mode="thread_local"):
+                    target = sample()
+                    ctx = self._iteration_forward(target, None, None, seed, advance=True, count=target.count)
+                with torch.cuda.graph(g2, pool=g1.pool(), capture_error_mode="thread_local"):
+                    out = self._iteration_backward(ctx, True)
+            except RuntimeError as err:
+                self._step = step0
+                torch.cuda.synchronize()
+                warnings.warn(f"capture_training: graph capture refused ({err}); falling back to plain launches",
+                              RuntimeWarning, stacklevel=2)
+
+                def eager():
+                    eager.target = sample()
+                    return self.optimization_iteration(eager.target, seed=seed)
+                eager.graph, eager.target, eager.capture_error = None, None, str(err)
+                return eager
+            self._step = step0
+            graphs = (g1, g2)
+            sums, group = ctx["w"]["sums"], self.process_group
+        seen = watched()
+
+        def replay():
+            now = watched()
+            if now != seen or self._global_map_dict["num"] != num_fields:
+                changed = sorted(n for n in now if now[n] != seen.get(n)) or ["number of fields"]
+                raise RuntimeError(f"capture_training: {changed} changed shape or storage since the capture; the graph "
+                                   "reads the captured addresses -- capture again")
+            if two:
+                g1.replay()
+                torch.distributed.all_reduce(sums, group=group)
+                g2.replay()
+            else:
+                graph.replay()
+                if self.peer_exchange is not None:
+                    self._count_exchange()
+            self._step += 1
+            return out
+        replay.graph, replay.target = graphs, target
+        return replay
