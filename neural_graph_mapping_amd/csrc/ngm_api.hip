@@ -17,12 +17,10 @@ int ngm_launch_loss_reduce(const float* partials, int nblocks, float* sums, uint
 int ngm_launch_neus_sd_grad(const float* d_isd_rays, int F, int R, const float* neus_sd, int64_t sd_stride,
                             const int64_t* field_index, float* d_sd, hipStream_t st);
 int ngm_launch_read_stash(const float4* sa, const float2* sb, int64_t n, float* geoms, float* dists, hipStream_t st);
-int ngm_launch_adam(float* param, float* m, float* v, int64_t stride, const float* grad, int64_t gstride,
-                    const int64_t* field_index, int F, int64_t numel, int64_t step, float lr, float beta1, float beta2,
-                    float eps, float wd, hipStream_t st);
-int ngm_launch_adam_multi(const ngm_adam_tensor* tensors, int n, const int64_t* field_index, int F, int64_t step,
-                          const int64_t* step_dev, float lr, float beta1, float beta2, float eps, float wd,
-                          int64_t* advance_step, uint64_t* advance_offset, hipStream_t st, const int32_t* num_active = nullptr);
+int ngm_launch_adam(float* param, float* m, float* v, int64_t stride, const float* grad, int64_t gstride, int F, int64_t numel,
+                    const AdamHyper& h, hipStream_t st);
+int ngm_launch_adam_multi(const ngm_adam_tensor* tensors, int n, int F, const AdamHyper& h, int64_t* advance_step,
+                          uint64_t* advance_offset, hipStream_t st, const int32_t* num_active = nullptr);
 int ngm_launch_step_advance(int64_t* step_dev, uint64_t* off_dev, hipStream_t st);
 int64_t ngm_mc_workspace_bytes(int nx, int ny, int nz);
 int ngm_launch_mc_count(const float* vol, int nx, int ny, int nz, float iso, int64_t* counts, void* workspace,
@@ -1124,8 +1122,8 @@ static int render_bwd_adam_impl(const ngm_field_cfg* fcfg, const ngm_render_cfg*
   sb.seed_mode = 0; sb.tg = *targets; sb.pred = *pred; sb.loss_sums = loss_sums;
   sb.loss_out = loss_out;
   GradAdam ad;
-  ad.tensors = mlp_tensors; ad.num = num_mlp_tensors; ad.field_index = field_index; ad.step = step; ad.step_dev = step_dev;
-  ad.lr = lr; ad.beta1 = beta1; ad.beta2 = beta2; ad.eps = eps; ad.wd = weight_decay;
+  ad.tensors = mlp_tensors; ad.num = num_mlp_tensors;
+  ad.hyper = AdamHyper{field_index, step_dev, step, lr, beta1, beta2, eps, weight_decay};
   if (lattice_tensor && (!lattice_tensor->param || !lattice_tensor->exp_avg || !lattice_tensor->exp_avg_sq || !lattice_tensor->grad))
     return fail(NGM_E_INVALID, "render_bwd_adam: NULL lattice tensor");
   GradAdam lad = ad;
@@ -1135,8 +1133,7 @@ static int render_bwd_adam_impl(const ngm_field_cfg* fcfg, const ngm_render_cfg*
                         lattice_tensor ? &lad : nullptr, &lattice_done, num_active);
   if (e) return e;
   if (lattice_tensor && !lattice_done) {   // unaligned tables: k_hash_reduce left the update to a plain Adam launch
-    ngm_launch_adam_multi(lattice_tensor, 1, field_index, rays->F, step, step_dev, lr, beta1, beta2, eps, weight_decay,
-                          nullptr, nullptr, (hipStream_t)stream, num_active);
+    ngm_launch_adam_multi(lattice_tensor, 1, rays->F, ad.hyper, nullptr, nullptr, (hipStream_t)stream, num_active);
     e = check_launch("ngm_adam_sparse_multi");
   }
   return e;
@@ -1212,8 +1209,8 @@ int ngm_adam_sparse(float* param, float* exp_avg, float* exp_avg_sq, int64_t str
                     float lr, float beta1, float beta2, float eps, float weight_decay, void* stream) {
   if (!param || !exp_avg || !exp_avg_sq || !grad || F < 1 || numel_per_field < 1 || step < 1)
     return fail(NGM_E_INVALID, "ngm_adam_sparse: bad argument");
-  ngm_launch_adam(param, exp_avg, exp_avg_sq, stride, grad, grad_stride, field_index, F, numel_per_field, step, lr, beta1,
-                  beta2, eps, weight_decay, (hipStream_t)stream);
+  ngm_launch_adam(param, exp_avg, exp_avg_sq, stride, grad, grad_stride, F, numel_per_field,
+                  AdamHyper{field_index, nullptr, step, lr, beta1, beta2, eps, weight_decay}, (hipStream_t)stream);
   return check_launch("ngm_adam_sparse");
 }
 
@@ -1225,7 +1222,7 @@ int ngm_adam_sparse_multi(const ngm_adam_tensor* tensors, int32_t num_tensors, c
   for (int i = 0; i < num_tensors; ++i)
     if (!tensors[i].param || !tensors[i].exp_avg || !tensors[i].exp_avg_sq || !tensors[i].grad || tensors[i].numel < 1)
       return fail(NGM_E_INVALID, "ngm_adam_sparse_multi: NULL tensor");
-  ngm_launch_adam_multi(tensors, num_tensors, field_index, F, step, step_dev, lr, beta1, beta2, eps, weight_decay,
+  ngm_launch_adam_multi(tensors, num_tensors, F, AdamHyper{field_index, step_dev, step, lr, beta1, beta2, eps, weight_decay},
                         (advance_step_dev && step_dev) ? step_dev : nullptr, advance_philox_offset_dev, (hipStream_t)stream);
   return check_launch("ngm_adam_sparse_multi");
 }

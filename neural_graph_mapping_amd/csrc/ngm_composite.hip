@@ -1252,23 +1252,20 @@ __global__ void k_adam_sparse(float* param, float* m, float* v, int64_t stride, 
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < numel; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t o = row * stride + i;
     const float p = param[o];
-    const float g = grad[(int64_t)f * gstride + i] + wd * p;
-    const float mn = beta1 * m[o] + (1.0f - beta1) * g;
-    const float vn = beta2 * v[o] + (1.0f - beta2) * g * g;
-    m[o] = mn; v[o] = vn;
-    const float denom = sqrtf(vn) * inv_sqrt_bc2 + eps;
-    param[o] = p - lr_bc1 * (mn / denom);
+    float m0 = m[o], v0 = v[o];
+    const AdamCoef c = {lr_bc1, inv_sqrt_bc2};
+    const float pn = adam_update(p, m0, v0, grad[(int64_t)f * gstride + i], c, beta1, beta2, eps, wd);
+    m[o] = m0; v[o] = v0;
+    param[o] = pn;
   }
 }
-int ngm_launch_adam(float* param, float* m, float* v, int64_t stride, const float* grad, int64_t gstride,
-                    const int64_t* field_index, int F, int64_t numel, int64_t step, float lr, float beta1, float beta2,
-                    float eps, float wd, hipStream_t st) {
+int ngm_launch_adam(float* param, float* m, float* v, int64_t stride, const float* grad, int64_t gstride, int F, int64_t numel,
+                    const AdamHyper& h, hipStream_t st) {
   NgmProfScope prof_(NGM_K_ADAM, st);
-  const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-  const float lr_bc1 = (float)((double)lr / bc1), inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+  const AdamCoef c = adam_coef(h.lr, h.beta1, h.beta2, (double)h.step);      // this site's coefficients come from the host
   dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>((numel + 255) / 256, 64)), (unsigned)F);
-  hipLaunchKernelGGL(k_adam_sparse, grid, dim3(256), 0, st, param, m, v, stride, grad, gstride, field_index, F, numel,
-                     lr_bc1, inv_sqrt_bc2, beta1, beta2, eps, wd);
+  hipLaunchKernelGGL(k_adam_sparse, grid, dim3(256), 0, st, param, m, v, stride, grad, gstride, h.field_index, F, numel,
+                     c.lr_bc1, c.inv_sqrt_bc2, h.beta1, h.beta2, h.eps, h.wd);
   return 0;
 }
 
@@ -1276,10 +1273,7 @@ int ngm_launch_adam(float* param, float* m, float* v, int64_t stride, const floa
 struct AdamMultiK {
   ngm_adam_tensor t[2 * (NGM_MAX_LAYERS + 1) + 2];
   int n;
-  const int64_t* field_index;
-  const int64_t* step_dev;
-  int64_t step;
-  float lr, beta1, beta2, eps, wd;
+  AdamHyper hyper;
   int64_t* advance_step;      // non-NULL: ++*advance_step once every block has read it
   uint64_t* advance_offset;   // non-NULL: ++*advance_offset likewise (Philox offset of the next iteration)
   const int32_t* num_active;  // counted step: rows f >= *num_active are left alone (NULL: all rows)
@@ -1290,13 +1284,11 @@ __global__ void k_adam_multi(AdamMultiK a) {
   const int f = blockIdx.y;
   // counted step: a padding row updates nothing and does not read field_index[f]; it still counts itself below
   const bool active = !a.num_active || f < *a.num_active;
-  const int64_t row = (active && a.field_index) ? a.field_index[f] : f;
-  const double step = (double)(a.step_dev ? *a.step_dev : a.step);
-  float lr_bc1 = 0.f, inv_sqrt_bc2 = 0.f;
-  if (active && (int64_t)blockIdx.x * blockDim.x < t.numel) {     // the grid is sized for the largest tensor
-    lr_bc1 = (float)((double)a.lr / (1.0 - pow((double)a.beta1, step)));
-    inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)a.beta2, step)));
-  }
+  const int64_t row = (active && a.hyper.field_index) ? a.hyper.field_index[f] : f;
+  const double step = (double)(a.hyper.step_dev ? *a.hyper.step_dev : a.hyper.step);
+  AdamCoef co = {0.f, 0.f};
+  if (active && (int64_t)blockIdx.x * blockDim.x < t.numel)      // the grid is sized for the largest tensor
+    co = adam_coef(a.hyper.lr, a.hyper.beta1, a.hyper.beta2, step);
   const bool vec = ((t.numel | t.stride | t.grad_stride) & 3) == 0 &&
                    ((reinterpret_cast<uintptr_t>(t.param) | reinterpret_cast<uintptr_t>(t.grad) |
                      reinterpret_cast<uintptr_t>(t.exp_avg) | reinterpret_cast<uintptr_t>(t.exp_avg_sq)) & 15) == 0;
@@ -1310,30 +1302,24 @@ __global__ void k_adam_multi(AdamMultiK a) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
       float4 p = P4[i], m = M4[i], v = V4[i];
       const float4 g4 = G4[i];
-      float* pp = &p.x; float* pm = &m.x; float* pv = &v.x; const float* pg = &g4.x;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const float g = pg[c] + a.wd * pp[c];
-        const float mn = a.beta1 * pm[c] + (1.0f - a.beta1) * g;
-        const float vn = a.beta2 * pv[c] + (1.0f - a.beta2) * g * g;
-        pm[c] = mn; pv[c] = vn;
-        pp[c] = pp[c] - lr_bc1 * (mn / (sqrtf(vn) * inv_sqrt_bc2 + a.eps));
-      }
+      adam_update4(p, m, v, g4, co, a.hyper.beta1, a.hyper.beta2, a.hyper.eps, a.hyper.wd);
       M4[i] = m; V4[i] = v; P4[i] = p;
       if (t.param_lp) {
 #pragma unroll
-        for (int c = 0; c < 4; ++c) ngm_stp(t.param_lp, row * t.stride + 4 * i + c, pp[c], t.lp_dtype);
+        for (int c = 0; c < 4; ++c) ngm_stp(t.param_lp, row * t.stride + 4 * i + c, (&p.x)[c], t.lp_dtype);
       }
     }
   } else
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < t.numel; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t o = row * t.stride + i;
+    // adam_update's lines written out: calling it here changes which product of exp_avg's sum is fused into the FMA, and so
+    // this branch's bits (profiles/r09_adam_unify.md)
     const float p = t.param[o];
-    const float g = t.grad[(int64_t)f * t.grad_stride + i] + a.wd * p;
-    const float mn = a.beta1 * t.exp_avg[o] + (1.0f - a.beta1) * g;
-    const float vn = a.beta2 * t.exp_avg_sq[o] + (1.0f - a.beta2) * g * g;
+    const float g = t.grad[(int64_t)f * t.grad_stride + i] + a.hyper.wd * p;
+    const float mn = a.hyper.beta1 * t.exp_avg[o] + (1.0f - a.hyper.beta1) * g;
+    const float vn = a.hyper.beta2 * t.exp_avg_sq[o] + (1.0f - a.hyper.beta2) * g * g;
     t.exp_avg[o] = mn; t.exp_avg_sq[o] = vn;
-    const float pn = p - lr_bc1 * (mn / (sqrtf(vn) * inv_sqrt_bc2 + a.eps));
+    const float pn = p - co.lr_bc1 * (mn / (sqrtf(vn) * co.inv_sqrt_bc2 + a.hyper.eps));
     t.param[o] = pn;
     if (t.param_lp) ngm_stp(t.param_lp, o, pn, t.lp_dtype);
   }
@@ -1352,16 +1338,14 @@ __global__ void k_adam_multi(AdamMultiK a) {
     }
   }
 }
-int ngm_launch_adam_multi(const ngm_adam_tensor* tensors, int n, const int64_t* field_index, int F, int64_t step,
-                          const int64_t* step_dev, float lr, float beta1, float beta2, float eps, float wd,
-                          int64_t* advance_step, uint64_t* advance_offset, hipStream_t st, const int32_t* num_active) {
+int ngm_launch_adam_multi(const ngm_adam_tensor* tensors, int n, int F, const AdamHyper& h, int64_t* advance_step,
+                          uint64_t* advance_offset, hipStream_t st, const int32_t* num_active) {
   NgmProfScope prof_(NGM_K_ADAM, st);
   AdamMultiK a;
   a.num_active = num_active;
   int64_t mx = 1;
   for (int i = 0; i < n; ++i) { a.t[i] = tensors[i]; mx = std::max<int64_t>(mx, tensors[i].numel); }
-  a.n = n; a.field_index = field_index; a.step_dev = step_dev; a.step = step;
-  a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = wd;
+  a.n = n; a.hyper = h;
   a.advance_step = advance_step; a.advance_offset = advance_offset;
   // blocks per (field, tensor): enough to put the large tensors (hash tables) on every CU
   const int64_t want = std::max<int64_t>(1, (4 * 256 + (int64_t)F - 1) / F);

@@ -538,9 +538,7 @@ struct GradReduceK {
   const float* partials;
   int64_t p_pad, ptot;
   GradSeg seg[2 * (NGM_MAX_LAYERS + 1) + 1];
-  // fused sparse Adam (seg[k].param != NULL): torch.optim.Adam with L2-coupled weight decay, as k_adam_multi
-  const int64_t* field_index; const int64_t* step_dev; int64_t step;
-  float lr, beta1, beta2, eps, wd;
+  AdamHyper hyper;                // fused sparse Adam (seg[k].param != NULL)
   const int32_t* num_active;      // counted step: rows f >= *num_active keep their gradient / parameter / moment rows (NULL: all F)
 };
 
@@ -561,13 +559,14 @@ __global__ void __launch_bounds__(256) k_grad_reduce(GradReduceK a) {
   // partial sums keep up to eight loads in flight per thread (they used to go four at a time, the Adam loads behind them).
   int seg = -1;
   int64_t so = 0;
-  float pv = 0.f, m0 = 0.f, v0 = 0.f, lr_bc1 = 0.f, inv_sqrt_bc2 = 1.f;
+  float pv = 0.f, m0 = 0.f, v0 = 0.f;
+  AdamCoef co = {0.f, 1.f};
   const bool adam = q == 0 && p < a.ptot;
   if (adam) {
     for (int k = 0; k < a.nseg; ++k)
       if (p >= a.seg[k].off && p < a.seg[k].off + a.seg[k].size) { seg = k; break; }
     if (seg >= 0 && a.seg[seg].param) {
-      const int64_t row = a.field_index ? a.field_index[f] : f;
+      const int64_t row = a.hyper.field_index ? a.hyper.field_index[f] : f;
       so = row * a.seg[seg].pstride + (p - a.seg[seg].off);
       pv = a.seg[seg].param[so]; m0 = a.seg[seg].m[so]; v0 = a.seg[seg].v[so];
     }
@@ -585,9 +584,8 @@ __global__ void __launch_bounds__(256) k_grad_reduce(GradReduceK a) {
     for (int j = 0; j < 8; ++j) v8[j] = src[(c + 4 * j) * cs];
   }
   if (adam && seg >= 0 && a.seg[seg].param) {
-    const double step = (double)(a.step_dev ? *a.step_dev : a.step);
-    lr_bc1 = (float)((double)a.lr / (1.0 - pow((double)a.beta1, step)));
-    inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)a.beta2, step)));
+    const double step = (double)(a.hyper.step_dev ? *a.hyper.step_dev : a.hyper.step);
+    co = adam_coef(a.hyper.lr, a.hyper.beta1, a.hyper.beta2, step);
   }
   float s = 0.f;
   if (pre) {
@@ -619,12 +617,9 @@ __global__ void __launch_bounds__(256) k_grad_reduce(GradReduceK a) {
   if (a.seg[seg].dst) a.seg[seg].dst[(int64_t)f * a.seg[seg].stride + i] = s;
   if (a.seg[seg].param) {
     // the update of rm.py:1183-1221 on row field_index[f], straight from the reduced gradient (no second launch, no
-    // gradient round trip); same arithmetic as k_adam_multi
-    const float g = s + a.wd * pv;
-    const float mn = a.beta1 * m0 + (1.0f - a.beta1) * g;
-    const float vn = a.beta2 * v0 + (1.0f - a.beta2) * g * g;
-    a.seg[seg].m[so] = mn; a.seg[seg].v[so] = vn;
-    const float pn = pv - lr_bc1 * (mn / (sqrtf(vn) * inv_sqrt_bc2 + a.eps));
+    // gradient round trip)
+    const float pn = adam_update(pv, m0, v0, s, co, a.hyper.beta1, a.hyper.beta2, a.hyper.eps, a.hyper.wd);
+    a.seg[seg].m[so] = m0; a.seg[seg].v[so] = v0;
     a.seg[seg].param[so] = pn;
     if (a.seg[seg].lp) ngm_stp(a.seg[seg].lp, so, pn, a.seg[seg].lp_dt);      // the reduced-precision copy the kernels read
   }
@@ -632,10 +627,9 @@ __global__ void __launch_bounds__(256) k_grad_reduce(GradReduceK a) {
 
 // Few partials per field (<= 8: 32 and more active fields on the chip): the four-quarter split above leaves each quarter
 // two loads and launches four times the workgroups the work needs (32 fields x 137 = 4 384 of them for the 64 + 2 x 64
-// network: 18.7 us, more than twice the 8-field launch).  Here a thread owns ONE parameter: its <= 8 partials in flight together,
-// summed in exactly the order of k_grad_reduce -- quarter i = p_i + p_(i+4), then ((q0 + q1) + q2) + q3 -- so the bits are the same.
-// One parameter p of field f: its partials summed in exactly k_grad_reduce's order -- quarter i = partials i, i + 4, i + 8, ... in
-// that order, then ((q0 + q1) + q2) + q3 -- and the sparse Adam update.  <= 8 partials: all in flight together.
+// network: 18.7 us, more than twice the 8-field launch).  Here a thread owns ONE parameter p of field f: its partials summed in
+// exactly k_grad_reduce's order -- quarter i = partials i, i + 4, i + 8, ... in that order, then ((q0 + q1) + q2) + q3, so the bits
+// are the same -- and the sparse Adam update.  <= 8 partials: all in flight together.
 template <bool COUNTED>
 __device__ __forceinline__ void grad_reduce_one(const GradReduceK& a, int f, int64_t p) {
   if (p >= a.ptot) return;
@@ -649,7 +643,7 @@ __device__ __forceinline__ void grad_reduce_one(const GradReduceK& a, int f, int
   float pv = 0.f, m0 = 0.f, v0 = 0.f;
   const bool adam = seg >= 0 && a.seg[seg].param;
   if (adam) {
-    const int64_t row = a.field_index ? a.field_index[f] : f;
+    const int64_t row = a.hyper.field_index ? a.hyper.field_index[f] : f;
     so = row * a.seg[seg].pstride + (p - a.seg[seg].off);
     pv = a.seg[seg].param[so]; m0 = a.seg[seg].m[so]; v0 = a.seg[seg].v[so];
   }
@@ -677,22 +671,18 @@ __device__ __forceinline__ void grad_reduce_one(const GradReduceK& a, int f, int
         if (c0 + u < a.blocks_per_field) q[u & 3] += v[u];
     }
   }
-  float lr_bc1 = 0.f, inv_sqrt_bc2 = 1.f;
+  AdamCoef co = {0.f, 1.f};
   if (adam) {
-    const double step = (double)(a.step_dev ? *a.step_dev : a.step);
-    lr_bc1 = (float)((double)a.lr / (1.0 - pow((double)a.beta1, step)));
-    inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)a.beta2, step)));
+    const double step = (double)(a.hyper.step_dev ? *a.hyper.step_dev : a.hyper.step);
+    co = adam_coef(a.hyper.lr, a.hyper.beta1, a.hyper.beta2, step);
   }
   const float s = ((q[0] + q[1]) + q[2]) + q[3];
   if (seg < 0) return;
   const int64_t i = p - a.seg[seg].off;
   if (a.seg[seg].dst) a.seg[seg].dst[(int64_t)f * a.seg[seg].stride + i] = s;
   if (adam) {
-    const float g = s + a.wd * pv;
-    const float mn = a.beta1 * m0 + (1.0f - a.beta1) * g;
-    const float vn = a.beta2 * v0 + (1.0f - a.beta2) * g * g;
-    a.seg[seg].m[so] = mn; a.seg[seg].v[so] = vn;
-    const float pn = pv - lr_bc1 * (mn / (sqrtf(vn) * inv_sqrt_bc2 + a.eps));
+    const float pn = adam_update(pv, m0, v0, s, co, a.hyper.beta1, a.hyper.beta2, a.hyper.eps, a.hyper.wd);
+    a.seg[seg].m[so] = m0; a.seg[seg].v[so] = v0;
     a.seg[seg].param[so] = pn;
     if (a.seg[seg].lp) ngm_stp(a.seg[seg].lp, so, pn, a.seg[seg].lp_dt);
   }
@@ -719,7 +709,7 @@ static int build_grad_reduce(const GradReduceArgs& g, GradReduceK& k) {
     k.seg[n++] = GradSeg{b_off[l], (int64_t)dout, g.gr.b[l], g.gr.b_stride[l], nullptr, nullptr, nullptr, 0, nullptr, 0};
   }
   k.nseg = n;
-  k.field_index = nullptr; k.step_dev = nullptr; k.step = 1; k.lr = k.beta1 = k.beta2 = k.eps = k.wd = 0.f;
+  k.hyper = AdamHyper{nullptr, nullptr, 1, 0.f, 0.f, 0.f, 0.f, 0.f};
   if (g.adam.tensors) {
     if (g.adam.num != n) return NGM_E_INVALID;
     for (int i = 0; i < n; ++i) {
@@ -728,8 +718,7 @@ static int build_grad_reduce(const GradReduceArgs& g, GradReduceK& k) {
       k.seg[i].param = t.param; k.seg[i].m = t.exp_avg; k.seg[i].v = t.exp_avg_sq; k.seg[i].pstride = t.stride;
       k.seg[i].lp = t.param_lp; k.seg[i].lp_dt = t.lp_dtype;
     }
-    k.field_index = g.adam.field_index; k.step_dev = g.adam.step_dev; k.step = g.adam.step;
-    k.lr = g.adam.lr; k.beta1 = g.adam.beta1; k.beta2 = g.adam.beta2; k.eps = g.adam.eps; k.wd = g.adam.wd;
+    k.hyper = g.adam.hyper;
   }
   return 0;
 }
@@ -828,10 +817,9 @@ struct HashGradArgs {
   const float2* dE; const float4* xyz;
   float* gtab; int64_t gstride;
   float* part;     // [F][L][chunks][2T] per-workgroup partial tables (plain stores, reduced in fixed order)
-  // optional fused sparse Adam on the tables (ad_param != NULL), as k_adam_multi
+  // optional fused sparse Adam on the tables (ad_param != NULL)
   float* ad_param; float* ad_m; float* ad_v; int64_t ad_stride; void* ad_lp; int ad_lp_dt;
-  const int64_t* ad_field_index; const int64_t* ad_step_dev; int64_t ad_step;
-  float ad_lr, ad_beta1, ad_beta2, ad_eps, ad_wd;
+  AdamHyper hyper;
   // Round 6: the MLP's gradient reduction + Adam (k_grad_reduce's work, a few KB per field) rides along as extra workgroups
   // behind the hash_blocks table workgroups: it depends on the MLP backward only, like this kernel, and as a launch of its own
   // it was 8 us of latency chain + boundary in a 195 us iteration.  mlp_bx = 0: none.
@@ -897,11 +885,10 @@ __global__ __launch_bounds__(NT) void k_hash_grad(HashGradArgs a) {
   for (int i = threadIdx.x; i < NL * 2 * T; i += blockDim.x) tab[i] = acc_t(0);
   // Adam's bias corrections (two double-precision pow) once per workgroup, up front, by one thread -- not by every thread in
   // the epilogue; read back after the barrier that ends the sample loop
-  __shared__ float adam_c[2];
+  __shared__ AdamCoef adam_c;
   if (a.chunks == 1 && a.ad_param && threadIdx.x == 0) {
-    const double step = (double)(a.ad_step_dev ? *a.ad_step_dev : a.ad_step);
-    adam_c[0] = (float)((double)a.ad_lr / (1.0 - pow((double)a.ad_beta1, step)));
-    adam_c[1] = (float)(1.0 / sqrt(1.0 - pow((double)a.ad_beta2, step)));
+    const double step = (double)(a.hyper.step_dev ? *a.hyper.step_dev : a.hyper.step);
+    adam_c = adam_coef(a.hyper.lr, a.hyper.beta1, a.hyper.beta2, step);
   }
   float lp[NL][8];
 #pragma unroll
@@ -1015,11 +1002,11 @@ __global__ __launch_bounds__(NT) void k_hash_grad(HashGradArgs a) {
       // (2 x 32 KB per level and field), no k_hash_reduce launch.  (The reference's default iteration: 32 fields x 16 levels =
       // one chunk per level; the M1 batch has 4 chunks per level and keeps the reduction kernel.)
       float* gdst = a.gtab + (int64_t)f * a.gstride + (int64_t)lv * T * 2;
-      float lr_bc1 = 0.f, inv_sqrt_bc2 = 1.f;
+      AdamCoef co = {0.f, 1.f};
       int64_t prow = 0;
       if (a.ad_param) {
-        lr_bc1 = adam_c[0]; inv_sqrt_bc2 = adam_c[1];
-        prow = (a.ad_field_index ? a.ad_field_index[f] : f) * a.ad_stride + (int64_t)lv * T * 2;
+        co = adam_c;
+        prow = (a.hyper.field_index ? a.hyper.field_index[f] : f) * a.ad_stride + (int64_t)lv * T * 2;
       }
       for (int i4 = threadIdx.x; i4 < T / 2; i4 += blockDim.x) {            // float4 = two entries x two features
         const int e0 = 2 * i4;
@@ -1029,24 +1016,16 @@ __global__ __launch_bounds__(NT) void k_hash_grad(HashGradArgs a) {
         s4.z = hash_acc_value<FLT>(tq[e0 + 1]);
         s4.w = hash_acc_value<FLT>(tq[T + e0 + 1]);
         reinterpret_cast<float4*>(gdst)[i4] = s4;
-        if (a.ad_param) {                                                     // same arithmetic as k_hash_reduce / k_adam_multi
+        if (a.ad_param) {
           const int64_t o4 = prow / 4 + i4;                                   // tables are 16-byte aligned rows (checked by the launcher)
           float4 p = reinterpret_cast<float4*>(a.ad_param)[o4], m = reinterpret_cast<float4*>(a.ad_m)[o4],
                  v = reinterpret_cast<float4*>(a.ad_v)[o4];
-          float* pp = &p.x; float* pm = &m.x; float* pv = &v.x; const float* pg = &s4.x;
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            const float g = pg[c] + a.ad_wd * pp[c];
-            const float mn = a.ad_beta1 * pm[c] + (1.0f - a.ad_beta1) * g;
-            const float vn = a.ad_beta2 * pv[c] + (1.0f - a.ad_beta2) * g * g;
-            pm[c] = mn; pv[c] = vn;
-            pp[c] = pp[c] - lr_bc1 * (mn / (sqrtf(vn) * inv_sqrt_bc2 + a.ad_eps));
-          }
+          adam_update4(p, m, v, s4, co, a.hyper.beta1, a.hyper.beta2, a.hyper.eps, a.hyper.wd);
           reinterpret_cast<float4*>(a.ad_m)[o4] = m; reinterpret_cast<float4*>(a.ad_v)[o4] = v;
           reinterpret_cast<float4*>(a.ad_param)[o4] = p;      // (written through: no measurable difference, round 6)
           if (a.ad_lp) {
 #pragma unroll
-            for (int c = 0; c < 4; ++c) ngm_stp(a.ad_lp, 4 * o4 + c, pp[c], a.ad_lp_dt);
+            for (int c = 0; c < 4; ++c) ngm_stp(a.ad_lp, 4 * o4 + c, (&p.x)[c], a.ad_lp_dt);
           }
         }
       }
@@ -1072,27 +1051,18 @@ __global__ void k_hash_reduce(HashGradArgs a) {
   }
   reinterpret_cast<float4*>(a.gtab + (int64_t)f * a.gstride + (int64_t)level * T * 2)[i] = s;
   if (a.ad_param) {
-    const double step = (double)(a.ad_step_dev ? *a.ad_step_dev : a.ad_step);
-    const float lr_bc1 = (float)((double)a.ad_lr / (1.0 - pow((double)a.ad_beta1, step)));
-    const float inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)a.ad_beta2, step)));
-    const int64_t row = a.ad_field_index ? a.ad_field_index[f] : f;
+    const double step = (double)(a.hyper.step_dev ? *a.hyper.step_dev : a.hyper.step);
+    const AdamCoef co = adam_coef(a.hyper.lr, a.hyper.beta1, a.hyper.beta2, step);
+    const int64_t row = a.hyper.field_index ? a.hyper.field_index[f] : f;
     const int64_t o4 = (row * a.ad_stride + (int64_t)level * T * 2) / 4 + i;       // tables are 16-byte aligned rows
     float4 p = reinterpret_cast<float4*>(a.ad_param)[o4], m = reinterpret_cast<float4*>(a.ad_m)[o4],
            v = reinterpret_cast<float4*>(a.ad_v)[o4];
-    float* pp = &p.x; float* pm = &m.x; float* pv = &v.x; const float* pg = &s.x;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const float g = pg[c] + a.ad_wd * pp[c];
-      const float mn = a.ad_beta1 * pm[c] + (1.0f - a.ad_beta1) * g;
-      const float vn = a.ad_beta2 * pv[c] + (1.0f - a.ad_beta2) * g * g;
-      pm[c] = mn; pv[c] = vn;
-      pp[c] = pp[c] - lr_bc1 * (mn / (sqrtf(vn) * inv_sqrt_bc2 + a.ad_eps));
-    }
+    adam_update4(p, m, v, s, co, a.hyper.beta1, a.hyper.beta2, a.hyper.eps, a.hyper.wd);
     reinterpret_cast<float4*>(a.ad_m)[o4] = m; reinterpret_cast<float4*>(a.ad_v)[o4] = v;
     reinterpret_cast<float4*>(a.ad_param)[o4] = p;
     if (a.ad_lp) {
 #pragma unroll
-      for (int c = 0; c < 4; ++c) ngm_stp(a.ad_lp, 4 * o4 + c, pp[c], a.ad_lp_dt);
+      for (int c = 0; c < 4; ++c) ngm_stp(a.ad_lp, 4 * o4 + c, (&p.x)[c], a.ad_lp_dt);
     }
   }
 }
@@ -1141,9 +1111,7 @@ int ngm_launch_hash_grad(const FieldBwdArgs& fb, hipStream_t st, bool* adam_appl
         ((reinterpret_cast<uintptr_t>(t.param) | reinterpret_cast<uintptr_t>(t.exp_avg) | reinterpret_cast<uintptr_t>(t.exp_avg_sq)) & 15) == 0) {
       a.ad_param = t.param; a.ad_m = t.exp_avg; a.ad_v = t.exp_avg_sq; a.ad_stride = t.stride;
       a.ad_lp = t.param_lp; a.ad_lp_dt = t.lp_dtype;
-      a.ad_field_index = fb.lattice_adam.field_index; a.ad_step_dev = fb.lattice_adam.step_dev; a.ad_step = fb.lattice_adam.step;
-      a.ad_lr = fb.lattice_adam.lr; a.ad_beta1 = fb.lattice_adam.beta1; a.ad_beta2 = fb.lattice_adam.beta2;
-      a.ad_eps = fb.lattice_adam.eps; a.ad_wd = fb.lattice_adam.wd;
+      a.hyper = fb.lattice_adam.hyper;
     }
   }
   a.hash_blocks = chunks * units;

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/ngm_hip.h"
+#include "ngm_adam.h"
 
 #ifndef NGM_BLOCK
 #define NGM_WAVE 64
@@ -62,9 +63,7 @@ struct RenderFwdArgs {
 struct GradAdam {
   const ngm_adam_tensor* tensors;    // host array, num == number of segments; NULL: reduction only
   int num;
-  const int64_t* field_index;
-  int64_t step; const int64_t* step_dev;
-  float lr, beta1, beta2, eps, wd;
+  AdamHyper hyper;
 };
 // Counted step: `num_active` (device, NULL = all F rows) in the argument records below.  Workgroups of rows f >= *num_active
 // leave before their first read through field_index and write nothing; the loss bookkeeping of block 0 (fused compositing

@@ -1,6 +1,7 @@
-"""Every copy of the sparse per-field Adam update against ONE float64 reference (tests/_adam_host.py), one update at a time,
-past step one and from non-zero moments, at 4x the reference's fp32 error bound (BAR; tests/test_adam_host_cpu.py shows that
-seven plausible faults break it).  The six sites:
+"""Every site of the one sparse per-field Adam update (csrc/ngm_adam.h; k_adam_multi's scalar branch writes the same lines
+out) against ONE float64 reference (tests/_adam_host.py), one update at a time, past step one and from non-zero moments, at
+4x the reference's fp32 error bound (BAR; tests/test_adam_host_cpu.py shows that seven plausible faults break it).  The six
+sites:
 
     1  k_adam_sparse                      ops.adam_sparse_ (bias corrections on the host)
     2  k_adam_multi, float4 and scalar    ngm_adam_sparse_multi; the renderer's triplane planes and `_neus_sd`
