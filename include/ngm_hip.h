@@ -25,7 +25,18 @@ extern "C" {
 #endif
 
 #define NGM_ABI_VERSION 11 /* 11 (+ addition, number unchanged: ngm_render_fwd_counted / ngm_render_bwd_counted / ngm_render_bwd_adam_counted, the training step launched at a capacity with the number of active rows in device memory; nothing existing changed); 11 (+ addition, number unchanged: ngm_target_sample_mv_workspace / ngm_target_sample_mv and struct ngm_target_sample, the device-side training-target sampler; nothing existing changed); 11: ngm_field_eval_stash_bytes / ngm_field_eval_fwd_train / ngm_field_eval_bwd_stash (training forward of the point evaluation writes the activation stash, its backward is the fused step's kernel); 10: ngm_field_cfg.activation_stash / .hash_grad_atomics (per configuration, no process-wide switch), empty loss selections report NaN like the reference; 9: ngm_sample_rays_weighted; 8: ngm_peer_set_timeout (a time-out now also poisons the sums with NaN); 7: ngm_encode_bwd; 6: ngm_render_eval_knn; 5: ngm_encode_fwd, ngm_render_bwd_seeded_vars, *_nll loss modes (+ loss-sum slot 10), peer status bits */
-#define NGM_MAX_LAYERS 4 /* hidden layers; +1 output layer */
+/* Array bound of the per-layer pointers below (hidden layers; +1 output layer).  NOT the depth every entry point takes -- the
+ * kernels are compiled per depth L = num_layers and padded width class (dim_enc and dim_hidden both <= 32, or both 33..64):
+ *   L = 1, 2   every entry point, both width classes (forward, backward, fused step, kNN evaluation)
+ *   L = 3      forward only and 33..64-wide only: ngm_field_eval_fwd, ngm_render_fwd (no targets' backward), ngm_field_eval_knn,
+ *              ngm_render_eval_knn; always exact-fp32 MFMA (NGM_MATMUL_AUTO resolves to it, an explicit NGM_MATMUL_BF16X3 is
+ *              refused by the fused forward).  Every backward entry point (ngm_field_eval_bwd, ngm_render_bwd*, the *_adam and
+ *              *_seeded forms) returns NGM_E_UNSUPPORTED before its first launch: workspace, gradients, parameters, Adam state
+ *              and the device-side iteration counter are left as they were.
+ *   L = 3 at <= 32 units, L = 4   nothing: refused by the configuration check of every entry point (NGM_E_UNSUPPORTED), the
+ *              standalone encoding stages excepted (ngm_encode_fwd / ngm_encode_bwd never run the hidden layers).
+ * tests/_config_matrix.py holds the table these lines are tested against. */
+#define NGM_MAX_LAYERS 4
 #define NGM_NUM_LOSS_SUMS 16
 
 enum ngm_status {

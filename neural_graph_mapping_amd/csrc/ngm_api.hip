@@ -195,10 +195,16 @@ static int64_t field_lds_floats(const ngm_field_cfg* fc) {
   return t + MC * 32 * 4 + 8;
 }
 
-static int check_field_cfg(const ngm_field_cfg* fc) {
+// mlp = false: the standalone encoding stages (ngm_encode_fwd / ngm_encode_bwd), which never run the hidden layers
+static int check_field_cfg(const ngm_field_cfg* fc, bool mlp = true) {
   if (!fc) return fail(NGM_E_INVALID, "field cfg is NULL");
   if (fc->dim_out != 4) return fail(NGM_E_UNSUPPORTED, "dim_out must be 4 (r,g,b,geometry)");
   if (fc->num_layers < 1 || fc->num_layers > NGM_MAX_LAYERS) return fail(NGM_E_UNSUPPORTED, "num_layers out of range");
+  // depths no launcher has a kernel for (include/ngm_hip.h, NGM_MAX_LAYERS): refused here, before any launch
+  if (mlp && fc->num_layers > 3)
+    return fail(NGM_E_UNSUPPORTED, "num_layers = 4: no entry point has a kernel for four hidden layers (1-2: everything; 3: forward only, 33..64-wide)");
+  if (mlp && fc->num_layers == 3 && (fc->dim_enc <= 32 || fc->dim_hidden <= 32))
+    return fail(NGM_E_UNSUPPORTED, "num_layers = 3 needs dim_enc and dim_hidden in 33..64: no entry point has a three-layer kernel for layers of 32 units or fewer");
   if (fc->encoding == NGM_ENC_PERMUTO) {
     if (fc->nr_feat_per_level != 2 || fc->nr_levels < 1 || fc->nr_levels > 16 || fc->dim_enc != 2 * fc->nr_levels)
       return fail(NGM_E_UNSUPPORTED, "permutohedral encoding: nr_feat_per_level must be 2, nr_levels <= 16, no concat_points");
@@ -226,6 +232,14 @@ static int check_field_cfg(const ngm_field_cfg* fc) {
     return fail(NGM_E_INVALID, "activation_stash: NGM_STASH_FULL / NGM_STASH_HALF (ABI 10: is the struct the caller built 276 bytes?)");
   if (fc->hash_grad_atomics != NGM_HASH_ATOMICS_EXACT && fc->hash_grad_atomics != NGM_HASH_ATOMICS_FLOAT)
     return fail(NGM_E_INVALID, "hash_grad_atomics: NGM_HASH_ATOMICS_EXACT / NGM_HASH_ATOMICS_FLOAT");
+  return NGM_OK;
+}
+// The backward kernels (k_field_bwd*, k_hash_mlp_bwd) are compiled for one and two hidden layers.  Checked by every backward
+// entry point before its first launch: a refusal leaves the workspace, the gradient tensors, the parameters and the
+// device-side iteration counter as they were.
+static int check_bwd_cfg(const ngm_field_cfg* fc) {
+  if (fc->num_layers > 2)
+    return fail(NGM_E_UNSUPPORTED, "num_layers = 3 is forward only (point evaluation, fused render forward, kNN evaluation): no backward kernel");
   return NGM_OK;
 }
 static int check_params(const ngm_field_cfg* fc, const ngm_params* pr) {
@@ -447,7 +461,7 @@ int ngm_field_eval_fwd(const ngm_field_cfg* fcfg, const ngm_params* params, int3
 
 int ngm_encode_fwd(const ngm_field_cfg* fcfg, const ngm_params* params, int32_t F, int64_t P, const float* points,
                    const float* field_pos, const float* field_quat, float* out, void* stream) {
-  int rc = check_field_cfg(fcfg);
+  int rc = check_field_cfg(fcfg, false);
   if (rc) return rc;
   rc = check_params(fcfg, params);
   if (rc) return rc;
@@ -472,7 +486,7 @@ int64_t ngm_encode_bwd_workspace(const ngm_field_cfg* fcfg, int32_t F, int64_t P
 int ngm_encode_bwd(const ngm_field_cfg* fcfg, const ngm_params* params, int32_t F, int64_t P, const float* points,
                    const float* field_pos, const float* field_quat, const float* d_enc, const ngm_grads* grads, void* workspace,
                    int64_t workspace_bytes, void* stream) {
-  int rc = check_field_cfg(fcfg);
+  int rc = check_field_cfg(fcfg, false);
   if (rc) return rc;
   rc = check_params(fcfg, params);
   if (rc) return rc;
@@ -558,6 +572,8 @@ int ngm_field_eval_bwd(const ngm_field_cfg* fcfg, const ngm_params* params, int3
                        const float* field_pos, const float* field_quat, const float* d_out, const ngm_grads* grads,
                        void* workspace, int64_t workspace_bytes, void* stream) {
   int rc = check_field_cfg(fcfg);
+  if (rc) return rc;
+  rc = check_bwd_cfg(fcfg);
   if (rc) return rc;
   rc = check_params(fcfg, params);
   if (rc) return rc;
@@ -849,7 +865,9 @@ static RenderPlan plan_render(const ngm_field_cfg* fc, const ngm_render_cfg* rc,
 }
 
 int64_t ngm_render_workspace(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg, int32_t F, int32_t R, int32_t train) {
-  if (check_field_cfg(fcfg) || !rcfg || F < 1 || R < 1) return NGM_E_INVALID;
+  const int e = check_field_cfg(fcfg);                 // NGM_E_UNSUPPORTED for a configuration no kernel takes
+  if (e) return e;
+  if (!rcfg || F < 1 || R < 1) return NGM_E_INVALID;
   // sized for the guided case (S_c + S_g), the larger of the two
   return plan_render(fcfg, rcfg, F, R, true, train != 0).total;
 }
@@ -1080,6 +1098,8 @@ static int render_bwd_impl(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg
                            float* loss_out, void* workspace, int64_t workspace_bytes, void* stream, const int32_t* num_active) {
   int e = check_render(fcfg, rcfg, params, rays);
   if (e) return e;
+  e = check_bwd_cfg(fcfg);
+  if (e) return e;
   if (!targets || !targets->rgbds || !targets->depth_mask || !pred || !pred->rgbds || !pred->term_probs || !grads)
     return fail(NGM_E_INVALID, "render_bwd: NULL argument");
   StashBwdArgs sb;
@@ -1111,6 +1131,8 @@ static int render_bwd_adam_impl(const ngm_field_cfg* fcfg, const ngm_render_cfg*
                                 float eps, float weight_decay, float* loss_out, void* workspace, int64_t workspace_bytes,
                                 void* stream, const int32_t* num_active) {
   int e = check_render(fcfg, rcfg, params, rays);
+  if (e) return e;
+  e = check_bwd_cfg(fcfg);
   if (e) return e;
   if (!targets || !targets->rgbds || !targets->depth_mask || !pred || !pred->rgbds || !pred->term_probs || !grads ||
       !mlp_tensors || num_mlp_tensors < 1 || (step < 1 && !step_dev))
@@ -1165,6 +1187,8 @@ int ngm_render_bwd_seeded(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg,
                           const ngm_grads* grads, void* workspace, int64_t workspace_bytes, void* stream) {
   int e = check_render(fcfg, rcfg, params, rays);
   if (e) return e;
+  e = check_bwd_cfg(fcfg);
+  if (e) return e;
   if (!d_rgbds || !grads) return fail(NGM_E_INVALID, "render_bwd_seeded: NULL argument");
   StashBwdArgs sb;
   memset(&sb, 0, sizeof(sb));
@@ -1177,6 +1201,8 @@ int ngm_render_bwd_seeded_vars(const ngm_field_cfg* fcfg, const ngm_render_cfg* 
                                const float* d_depth_vars, const float* d_term, const float* d_geom_samples,
                                const ngm_grads* grads, void* workspace, int64_t workspace_bytes, void* stream) {
   int e = check_render(fcfg, rcfg, params, rays);
+  if (e) return e;
+  e = check_bwd_cfg(fcfg);
   if (e) return e;
   if (!d_rgbds || !grads) return fail(NGM_E_INVALID, "render_bwd_seeded_vars: NULL argument");
   if ((d_color_vars || d_depth_vars) && (!pred || !pred->rgbds || !pred->term_probs))

@@ -753,12 +753,13 @@ def render_ijs_fused(fc: K.FieldCfg, rc: K.RenderCfg, params: Dict[str, torch.Te
     save = bool(gt is not None or (torch.is_grad_enabled() and any(t.requires_grad for t in plist)))
     if c2ws.dim() != 2 and c2ws.numel() != ijs.shape[0] * ijs.shape[1] * 16:
         c2ws = c2ws.expand(ijs.shape[0], ijs.shape[1], 4, 4)
+    wsb = int(K.lib().ngm_render_workspace(C.byref(fc), C.byref(rc), ijs.shape[0], ijs.shape[1], 1)) if save else 0
+    if wsb < 0:                                            # a configuration the library refuses: its status and message
+        K.check(wsb, "ngm_render_workspace")
     out = torch.ops.ngm355.render_ijs(cfg_blob(fc), cfg_blob(rc), ijs.contiguous(), _f32c(c2ws), _f32c(near), _f32c(far),
                                       _f32c(gt), _f32c(pos), _f32c(quat), _f32c(u_coarse), _f32c(u_guided), int(seed),
                                       float(near_const), float(far_const), save,
-                                      rc.num_samples_coarse + (rc.num_samples_guided if gt is not None else 0),
-                                      int(K.lib().ngm_render_workspace(C.byref(fc), C.byref(rc), ijs.shape[0], ijs.shape[1], 1)) if save else 0,
-                                      plist)
+                                      rc.num_samples_coarse + (rc.num_samples_guided if gt is not None else 0), wsb, plist)
     rgbds, cvars, dvars, term, geoms, dists, _ = out
     # color_vars / depth_vars stay in the graph: a loss that reads them (losses.py's *_nll modes) seeds them, and the backward
     # then runs ngm_render_bwd_seeded_vars; a loss that does not leaves their gradients None (set_materialize_grads(False))

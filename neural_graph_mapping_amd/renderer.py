@@ -787,6 +787,8 @@ class NeuralGraphRenderer:
         key = (F, R)
         if key not in self._ws_cache:
             wsb = K.lib().ngm_render_workspace(C.byref(self._fc), C.byref(self._rc_train), F, R, 1)
+            if wsb < 0:                                    # a configuration the library refuses: its status and message
+                K.check(int(wsb), "ngm_render_workspace")
             dev = self._device
             self._ws_cache[key] = dict(
                 ws=torch.empty(wsb, device=dev, dtype=torch.uint8), wsb=wsb,
@@ -975,13 +977,13 @@ class NeuralGraphRenderer:
         if count is not None:
             # the counted step (neus / triplane never get here: their extra launches below run over all F rows)
             if update:
-                self._step += 1
                 arr, n_mlp, lat = ops.adam_tensor_arrays(fc, allp, self._optim_state, grads, ctx.get("lp"))
                 K.check(L.ngm_render_bwd_adam_counted(
                     C.byref(fc), C.byref(rc), C.byref(ps), C.byref(rays), C.byref(tg), C.byref(pred), sums_ptr, C.byref(gs), arr,
-                    n_mlp, lat, ops._ptr(fids), int(self._step), ops._ptr(self._step_dev), self._learning_rate, 0.9, 0.999,
+                    n_mlp, lat, ops._ptr(fids), int(self._step) + 1, ops._ptr(self._step_dev), self._learning_rate, 0.9, 0.999,
                     self._adam_eps, self._adam_weight_decay, w["loss"].data_ptr(), w["ws"].data_ptr(), w["wsb"], st,
                     count.data_ptr()), "ngm_render_bwd_adam_counted")
+                self._step += 1                                  # after the call: a refused step is no step
             else:
                 K.check(L.ngm_render_bwd_counted(C.byref(fc), C.byref(rc), C.byref(ps), C.byref(rays), C.byref(tg), C.byref(pred),
                                                  sums_ptr, C.byref(gs), w["loss"].data_ptr(), w["ws"].data_ptr(), w["wsb"],
@@ -989,13 +991,13 @@ class NeuralGraphRenderer:
         elif update:
             # backward + sparse Adam in one call: the gradient-reduction kernel applies the update of the MLP tensors
             # itself (rm.py:1183-1221); the device counter already holds the new step (the loss reduction advanced it)
-            self._step += 1                                  # one counter for all fields (rm.py:380-385)
             arr, n_mlp, lat = ops.adam_tensor_arrays(fc, allp, self._optim_state, grads, ctx.get("lp"))
             K.check(L.ngm_render_bwd_adam(C.byref(fc), C.byref(rc), C.byref(ps), C.byref(rays), C.byref(tg), C.byref(pred),
-                                          sums_ptr, C.byref(gs), arr, n_mlp, lat, ops._ptr(fids), int(self._step),
+                                          sums_ptr, C.byref(gs), arr, n_mlp, lat, ops._ptr(fids), int(self._step) + 1,
                                           ops._ptr(self._step_dev), self._learning_rate, 0.9, 0.999, self._adam_eps,
                                           self._adam_weight_decay, w["loss"].data_ptr(), w["ws"].data_ptr(), w["wsb"], st),
                     "ngm_render_bwd_adam")
+            self._step += 1                                  # one counter for all fields (rm.py:380-385); a refused step is no step
             if fc.encoding == K.ENC["triplane"]:      # the feature planes: gradient from the fixed-point scatter, same sparse Adam
                 n = "_encoding.plane_coef"
                 pl, stt, gp = allp[n], self._optim_state[n], grads[n]

@@ -111,12 +111,11 @@ def away_from_relu_boundaries(q, pos, quat, params, fs, margin=1e-5, tries=20):
     g = torch.Generator().manual_seed(99)
     for _ in range(tries):
         x = O.world_to_field(q.double(), pos.double(), quat.double(), 1.0, "unit_cube")
-        h = O.encode(x, p64, fs)
+        pres = []
+        O.field_mlp(O.encode(x, p64, fs), p64, fs, pre_out=pres)       # (skip connections included)
         bad = torch.zeros(q.shape[:2], dtype=torch.bool)
-        for i in range(fs.num_layers):
-            pre = torch.einsum("fpi,foi->fpo", h, p64[f"_linears.{i}.weight"]) + p64[f"_linears.{i}.bias"].unsqueeze(-2)
+        for pre in pres:
             bad |= (pre.abs() < margin).any(-1)
-            h = torch.relu(pre)
         if not bad.any():
             return q
         q = q.clone()
@@ -148,10 +147,22 @@ CASES = {
 }
 
 
+class NoEncoding(M.PositionalEncoding):
+    """NGM_ENC_NONE as an encoding module: the raw local coordinates, no parameters (the config-matrix tests' `none` entries)"""
+
+    def get_out_dim(self) -> int:
+        return 3
+
+    def spec(self):
+        return dict(encoding="none")
+
+
 def make_renderer(fkw, ckw, num_fields, params=None):
     if fkw["encoding"] == "fourier":
         et = "neural_graph_mapping.positional_encodings.PositionalEncodingFourier"
         ek = dict(dim_in=3, dim_out=fkw["dim_enc"], mu=0.0, sigma=4.0, raw_coords=True)
+    elif fkw["encoding"] == "none":
+        et, ek = NoEncoding, {}
     elif fkw["encoding"] == "permuto":
         et = "neural_graph_mapping.positional_encodings.PermutohedralEncoding"
         ek = dict(pos_dim=3, log2_hashmap_size=fkw.get("log2_hashmap_size", 12), nr_levels=fkw.get("nr_levels", 16),
@@ -166,7 +177,7 @@ def make_renderer(fkw, ckw, num_fields, params=None):
         ek = dict(dim_in=3, num_octaves=fkw["num_octaves"], start_octave=0)
     model = M.NeuralFieldSet(dim_points=3, field_type="neural_graph_mapping.models.NeuralField", field_kwargs=dict(
         encoding_type=et, encoding_kwargs=ek, num_layers=fkw["num_layers"], dim_out=4, neus_initial_sd=1.0,
-        skip_mode=fkw.get("skip_mode", "no")), num_knn=2,
+        dim_mlp_out=fkw.get("dim_hidden"), skip_mode=fkw.get("skip_mode", "no")), num_knn=2,
         distance_factor=10.0, outside_value=1.0, field_radius=float(ckw.get("field_radius", 1.0)), scale_mode="unit_cube",
         weight_dtype=fkw.get("weight_dtype")).to(DEV)                 # one radius for model and map, like the shipped YAML's anchor
     cfg = dict(geometry_mode="nrgbd", geometry_factor=20.0, color_factor=1.0, truncation_distance=0.1, field_radius=1.0,
@@ -319,6 +330,104 @@ def ragged_case(F, R, n_c, n_g, fkw, geometry_mode="nrgbd", geometry_factor=20.0
     loss["combined"].backward()        # NaN value or not: the oracle's backward is finite (an empty mean has an empty gradient)
     for k in po:
         grad_close(res["grads"][k], po[k].grad, grad_tol, k)
+
+
+# ------------------------------------------------------------------------------------------------ the configuration matrix
+# (tests/_config_matrix.py; shared by test_gpu_config_matrix.py and its CPU companion: every reference is computed once)
+_MATRIX_CACHE = {}
+NEUS_SD = torch.tensor([0.4, 0.8, -1.5])
+
+
+def matrix_is_hash(entry):
+    return entry["fkw"]["encoding"] == "permuto"
+
+
+def matrix_step_case(entry, shape):
+    """One fused-step problem of a matrix entry, like `ragged_case`: targets, kink-free jitter (only where the step is expected
+    to run: a refused step compares no gradient), the oracle's prediction and gradients in fp64 (stored as fp32).  Cached."""
+    key = ("step", entry["name"], shape)
+    if key in _MATRIX_CACHE:
+        return _MATRIX_CACHE[key]
+    from _config_matrix import runs
+    F, R, n_c, n_g = shape
+    fkw, seed = entry["fkw"], R + 101 * entry["seed"]
+    torch.manual_seed(F * 1000 + R + entry["seed"])
+    neus = entry["geometry"] == "neus"
+    gkw = dict(termination_weight=0.3, geometry_mode=entry["geometry"], geometry_factor=5.0 if neus else 20.0)
+    pos, quat, t = synth_target(F, R, seed=seed)
+    fs = O.FieldSpec(**fkw)
+    rs = O.RenderSpec(num_samples_coarse=n_c, num_samples_depth_guided=n_g, **gkw)
+    params = O.init_params(fs, F, seed=seed, sigma=3.0)
+    params[f"_linears.{fkw['num_layers']}.weight"] *= 2.0
+    u_c, u_g = torch.rand(F, R, n_c), torch.rand(F, R, n_g)
+    sd = NEUS_SD[:F].clone() if neus else None
+    isd = None if sd is None else 1.0 / sd.abs()
+    trains = any(runs(o) for o in entry["step"].values())
+    n0 = len(KINK)
+    if trains:
+        # hash: the sweep's band (test_cfg2_hash_network_random_shapes_vs_oracle: two fp32 evaluations of a hash encoding
+        # differ by ~5e-4, so do the pre-activations); the cap on neutralised rays stays the default 15 %
+        u_c, u_g, t = kink_free_draws(t, pos, quat, params, fs, rs, u_c, u_g, margin=2e-3 if matrix_is_hash(entry) else 5e-5,
+                                      neus_isds=isd)
+    d = lambda x: x.double() if torch.is_tensor(x) and x.is_floating_point() else x          # the reference runs in fp64
+    t64 = {k: d(v) for k, v in t.items()}
+    kink = KINK[n0:]                  # kept with the case (it is built once, by whichever test asks first): the GPU test reports it
+    del KINK[n0:]
+    po = {k: v.double().requires_grad_(k not in K.NO_GRAD_PARAMS) for k, v in params.items()}
+    pred = O.render_ijs(t["ijs"], t64["c2ws"], NRGBD, d(pos), d(quat), po, fs, rs, t64["near"], t64["far"], t64["gt"], d(u_c),
+                        d(u_g), neus_isds=None if isd is None else d(isd).view(-1, 1, 1))
+    grads = None
+    if trains:
+        loss = O.compute_losses(pred, t64["rgbds"], t["depth_mask"], t["term_mask"], t64["term_probs"], rs)
+        loss["combined"].backward()
+        grads = {k: v.grad.float() for k, v in po.items() if v.grad is not None}
+    pred = {k: (v.detach().float() if torch.is_tensor(v) else v) for k, v in pred.items()}
+    case = dict(F=F, R=R, n_c=n_c, n_g=n_g, fs=fs, rs=rs, pos=pos, quat=quat, t=t, params=params, u_c=u_c, u_g=u_g, sd=sd,
+                pred=pred, grads=grads, kink=kink, ckw=dict(num_samples_coarse=n_c, num_samples_depth_guided=n_g, **gkw))
+    _MATRIX_CACHE[key] = case
+    return case
+
+
+def matrix_points_case(entry, P, F=3):
+    """Point evaluation of a matrix entry: posed fields, query points off the ReLU kinks, the oracle's output and parameter
+    gradients for a fixed d_out, all in fp64.  Cached."""
+    key = ("points", entry["name"], P)
+    if key in _MATRIX_CACHE:
+        return _MATRIX_CACHE[key]
+    fkw = entry["fkw"]
+    g = torch.Generator().manual_seed(1000 + P + entry["seed"])
+    fs = O.FieldSpec(**fkw)
+    params = O.init_params(fs, F, seed=5 + entry["seed"], sigma=3.0)
+    pos = torch.randn(F, 3, generator=g)
+    quat = torch.nn.functional.normalize(torch.randn(F, 4, generator=g), dim=-1)
+    q = pos[:, None] + 0.5 * torch.randn(F, P, 3, generator=g)
+    q = away_from_relu_boundaries(q, pos, quat, params, fs, margin=2e-3 if matrix_is_hash(entry) else 1e-5)
+    d_out = torch.randn(F, P, 4, generator=g)
+    po = {k: v.double().requires_grad_(k not in K.NO_GRAD_PARAMS) for k, v in params.items()}
+    out = O.field_set_forward_vmap(q.double(), pos.double(), quat.double(), po, fs)
+    (out * d_out.double()).sum().backward()
+    case = dict(F=F, P=P, fs=fs, params=params, pos=pos, quat=quat, q=q, d_out=d_out, out=out.detach().float(),
+                grads={k: v.grad.float() for k, v in po.items() if v.grad is not None})
+    _MATRIX_CACHE[key] = case
+    return case
+
+
+def matrix_knn_case(entry, NF=7, K_=3, P=500):
+    """kNN-blended evaluation of a matrix entry against the oracle in fp64.  Cached."""
+    key = ("knn", entry["name"])
+    if key in _MATRIX_CACHE:
+        return _MATRIX_CACHE[key]
+    g = torch.Generator().manual_seed(77 + entry["seed"])
+    fs = O.FieldSpec(**entry["fkw"])
+    params = O.init_params(fs, NF, seed=NF + entry["seed"], sigma=3.0)
+    pos = torch.rand(NF, 3, generator=g) * 3
+    quat = torch.nn.functional.normalize(torch.randn(NF, 4, generator=g), dim=-1)
+    pts = torch.rand(P, 3, generator=g) * 4 - 0.5
+    ref = O.field_set_forward_knn(pts.double(), pos.double(), quat.double(), {k: v.double() for k, v in params.items()}, fs,
+                                  num_knn=K_, distance_factor=10.0, outside_value=1.0)
+    case = dict(NF=NF, K=K_, P=P, fs=fs, params=params, pos=pos, quat=quat, pts=pts, ref=ref.float())
+    _MATRIX_CACHE[key] = case
+    return case
 
 
 from _philox_host import host_philox_draws, host_philox_uniform  # noqa: E402,F401  (numpy-only: also imported by the CPU tests)
