@@ -663,14 +663,22 @@ int ngm_debug_last_fwd_one_tile(void);
  * seeds, pointwise geometry modes; no k_stash_bwd launch, the forward's colour / geometry stash stays intact), 0 when
  * k_stash_bwd ran.  ngm_debug_disable_fused_comp(1) forces the separate kernel. */
 int ngm_debug_last_comp_fused(void);
-int ngm_debug_disable_fused_comp(int on);
+int ngm_debug_disable_fused_comp(int on);   /* 1 = always launch k_stash_bwd; returns the previous setting */
 /* DEVELOPER override of ngm_field_cfg.activation_stash for A/B timing of one library on one box (tools/): 0 / 1 force that
  * mode for every configuration of the process, -1 queries, -2 removes the override.  The product path never calls it: the
  * renderer sets ngm_field_cfg.activation_stash.
  * Returns the override in force before the call (-1: none). */
 int ngm_debug_stash_mode(int mode);
 int ngm_debug_last_stash_mode(void);   /* the stash the last MLP backward actually read: 0 / 1 as above, -1 none (recompute kernels) */
-  /* 1 = always launch k_stash_bwd; returns the previous setting */
+/* Debug: the MLP backward plan of a call with these arguments, without launching anything (no GPU needed).  rcfg != NULL: the
+ * fused step on F fields x n rays (guided: the rays carry gt distances; seeds_written: the forward on the workspace ran with the
+ * backward's targets, no per-workspace stash record); rcfg == NULL: the point evaluation on F x n points (stash_offered:
+ * ngm_field_eval_bwd_stash rather than ngm_field_eval_bwd).  out5 = backward variant (ngm_debug_last_bwd_variant), compositing
+ * fused, stash kind (0 none, 1 hidden activations, 2 hash encoding), stash layers, and the arithmetic the fused forward resolves
+ * to (NGM_MATMUL_F32 / NGM_MATMUL_BF16X3; -1 in point mode).  Returns the plan's refusal (NGM_E_UNSUPPORTED / NGM_E_INVALID,
+ * message in ngm_last_error) where the backward would refuse. */
+int ngm_debug_plan_bwd(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg, int32_t F, int64_t n, int32_t guided,
+                       int32_t stash_offered, int32_t seeds_written, int32_t* out5);
 
 /* ---- one-shot exchange of the loss sums between the ranks of one node ---------------
  * Replaces torch.distributed.all_reduce (RCCL) on the 16 floats between ngm_render_fwd and ngm_render_bwd* by ONE small

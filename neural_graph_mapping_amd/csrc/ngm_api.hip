@@ -39,10 +39,11 @@ int ngm_launch_render_eval_knn(const ngm_field_cfg* fc, const ngm_render_cfg* rc
                                void* workspace, int64_t workspace_bytes, hipStream_t st);
 
 #include <mutex>
+#include <unordered_map>
 #include <vector>
 
 static thread_local char g_err[512] = "";
-static int prep_lattice_grad(const ngm_field_cfg* fc, const ngm_grads* grads, int F, FieldBwdArgs& a, hipStream_t st);
+static int check_enc_grads(const ngm_field_cfg* fc, const ngm_grads* grads, FieldBwdArgs& a);
 
 // ---- profiling hooks ----------------------------------------------------------------------------
 namespace {
@@ -93,21 +94,16 @@ static int fail(int code, const char* msg) {
   snprintf(g_err, sizeof(g_err), "%s", msg);
   return code;
 }
-// prefer the 8-wave / 16-sample-tile backward; fall back to the 4-wave / 32-sample-tile kernel
 #define NGM_FWD_DEBUG_WORDS (16 + 8 * 64)   // 16 summary slots + 8 waves x 64 timeline entries
 static unsigned long long* g_debug_cycles = nullptr;
 int g_ngm_last_matmul[3] = {-1, -1, -1};   // ngm_launch.h
 int g_ngm_last_fwd_one_tile = 0;
-static int g_last_bwd_variant = -1;   // 0: 32-sample tiles, 1: 16-sample tiles (recompute), 2: 16-sample tiles + activation stash, 3: bf16-split tiles + stash, 5: hash encoding + 1x32 MLP on the bf16 split
 static int g_no_fused_comp = 0;       // ngm_debug_disable_fused_comp
-static int g_last_stash_mode = -1;    // FieldBwdArgs::act_half of the last MLP backward that read an activation stash
-static int g_last_comp_fused = 0;     // the last training backward did the compositing backward inside k_field_bwd_b3 (no k_stash_bwd launch)
+static int g_stash_override = -1;     // ngm_debug_stash_mode
 // Which targets the LAST forward on a workspace wrote its per-ray loss seeds for (host-side bookkeeping by pointer identity:
 // the fused compositing backward trusts off_rayseed only when the forward that filled this workspace ran with the same
 // targets; a forward without targets, or with other targets, leaves the backward on k_stash_bwd, which derives the seeds
 // from targets + prediction itself).
-#include <mutex>
-#include <unordered_map>
 static std::mutex g_seed_mu;
 static std::unordered_map<const void*, const void*> g_seed_targets;       // workspace -> targets.rgbds of the forward that wrote the seeds
 static std::unordered_map<const void*, int> g_ws_act_layers;              // workspace -> hidden layers the last training forward stashed (0: all)
@@ -137,34 +133,6 @@ static bool forward_wrote_seeds_for(const void* ws, const void* rgbds) {
   return it != g_seed_targets.end() && it->second == rgbds;
 }
 
-static int launch_bwd_any(FieldBwdArgs& a, int blocks, hipStream_t st) {
-  static const bool timing = getenv("NGM_PHASE_TIMING") != nullptr;
-  a.debug_cycles = nullptr;
-  if (timing) {
-    if (!g_debug_cycles) { (void)hipMalloc(&g_debug_cycles, NGM_FWD_DEBUG_WORDS * 8); (void)hipMemset(g_debug_cycles, 0, NGM_FWD_DEBUG_WORDS * 8); }
-    a.debug_cycles = g_debug_cycles;
-  }
-  // In order of preference, the first kernel that takes the problem (the others return NGM_E_UNSUPPORTED):
-  // bf16-split tiles on the activation stash -> hash encoding + 1x32 MLP on its encoding stash -> 16-sample tiles on the
-  // stash -> 16-sample-tile recompute -> 32-sample-tile recompute.
-  int e = NGM_E_UNSUPPORTED;
-  auto next = [&](int variant, int (*launch)(const FieldBwdArgs&, int, hipStream_t)) {
-    if (e == NGM_E_UNSUPPORTED) { e = launch(a, blocks, st); g_last_bwd_variant = variant; }
-  };
-  g_last_stash_mode = a.act ? a.act_half : -1;
-  if (a.act) next(3, ngm_launch_field_bwd_b3);
-  if (a.act_half && e == NGM_E_UNSUPPORTED) {                   // no other kernel reads a half stash: never fall through
-    snprintf(g_err, sizeof(g_err), "render_bwd: the forward stashed one hidden layer (split path) but k_field_bwd_b3 does not take this problem");
-    return NGM_E_INVALID;
-  }
-  if (a.act) next(5, ngm_launch_hash_mlp_bwd);
-  g_last_comp_fused = (a.fused_comp && e == 0) ? 1 : 0;
-  if (a.fused_comp) return e;                                   // no other kernel composites: never fall through
-  if (a.act) next(2, ngm_launch_field_bwd16s);
-  next(1, ngm_launch_field_bwd16);
-  next(0, ngm_launch_field_bwd);
-  return e;
-}
 static int check_launch(const char* what) {
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
@@ -193,6 +161,116 @@ static int64_t field_lds_floats(const ngm_field_cfg* fc) {
   int64_t t = MI * 32 * 4;
   for (int l = 0; l < fc->num_layers; ++l) t += MH * (l == 0 ? MI : MC) * 16 * 2 * 33 + MH * 32;
   return t + MC * 32 * 4 + 8;
+}
+
+// ---- the MLP backward plan -----------------------------------------------------------------------------------------------------
+// Which kernel a backward runs (variant: 0 k_field_bwd, 1 k_field_bwd16, 2 k_field_bwd16s, 3 k_field_bwd_b3, 5 k_hash_mlp_bwd),
+// which stash the forward writes for it and whether the compositing backward rides inside it are ONE decision, taken by
+// plan_mlp_bwd from plain values.  Forward and backward ask it before anything is carved or launched: a stash is written exactly
+// when a kernel reads it, and a refusal leaves workspace, gradients, parameters and counters as they were.
+struct BwdAsk {
+  const ngm_render_cfg* rc = nullptr;   // ray mode; NULL: point mode
+  int F = 1;
+  int64_t P = 0;                        // samples per field
+  bool seeded = false;                  // ray mode: explicit seeds (ngm_render_bwd_seeded*), not the loss
+  bool stash_offered = false;           // point mode: the caller holds a stash for the forward to write / the backward to read
+  int rec_layers = -1;                  // per-workspace record forward_stash_layers: 0 every hidden layer, 1 layer 0 only, -1 none
+  bool seeds_written = false;           // per-workspace record forward_wrote_seeds_for these targets
+};
+struct BwdPlan {
+  int status; const char* why;          // NGM_OK, or the refusal (NGM_E_UNSUPPORTED / NGM_E_INVALID) and its message
+  int stash_kind;                       // 0: none; 1: post-ReLU hidden activations (64 floats per sample and layer); 2: the hash
+                                        // encoding itself (32 features per sample: no simplex search, no table gathers)
+  int stash_layers, half;               // layers in the stash: every hidden layer, or (half) layer 0 of two; kind 2: 1
+  int variant, fused_comp;
+  int64_t per_block; int blocks_per_field;
+};
+static BwdPlan g_last_bwd = {NGM_OK, nullptr, 0, 0, 0, -1, 0, 0, 0};   // the last plan that launched (ngm_debug_last_*)
+
+// unit: samples a workgroup's range is a multiple of -- whole 32-sample tiles for each of its waves (4 waves: 128; the
+// hash network's 8-wave backward: 256)
+static void plan_bwd(int F, int64_t P, int64_t* per_block, int* bpf, int64_t unit = 32 * NGM_WAVES_PER_BLOCK) {
+  const int ncu = num_cus();
+  int64_t b = (ncu + F - 1) / F;
+  int64_t per = align_up((P + b - 1) / b, unit);
+  if (per < unit) per = unit;
+  *per_block = per;
+  *bpf = (int)((P + per - 1) / per);
+}
+// The only reader of the three process switches: NGM_NO_ACT_STASH=1 (recompute everywhere; saves the stash's workspace),
+// ngm_debug_stash_mode (developer A/B override of ngm_field_cfg.activation_stash) and ngm_debug_disable_fused_comp.
+static BwdPlan plan_mlp_bwd(const ngm_field_cfg* fc, const BwdAsk& q) {
+  static const bool no_stash = getenv("NGM_NO_ACT_STASH") != nullptr;
+  BwdPlan p;
+  memset(&p, 0, sizeof(p));
+  p.variant = -1;
+  const bool ray = q.rc != nullptr;
+  const int L = fc->num_layers, ti = (fc->dim_enc + 15) / 16, th = (fc->dim_hidden + 15) / 16;
+  plan_bwd(q.F, q.P, &p.per_block, &p.blocks_per_field, ray && fc->encoding == NGM_ENC_PERMUTO ? 256 : 128);
+  BwdProblem pr = {!ray, q.P, p.per_block, 0, false, false};
+  // The stash.  Its consumers are skip-less (with a skip connection the stashed activation no longer tells the ReLU mask); the
+  // triplane backward recomputes (it needs the taps anyway).  Point mode: only k_field_bwd_b3 reads one.
+  if (!no_stash && fc->skip_mode == NGM_SKIP_NO && fc->encoding != NGM_ENC_TRIPLANE) {
+    if (fc->encoding == NGM_ENC_PERMUTO) pr.stash_kind = (ti == 2 && fc->dim_hidden <= 32) ? 2 : 0;
+    else pr.stash_kind = (ti == 4 && th == 4 && L <= 2) ? 1 : 0;
+    if (!ray && !(pr.stash_kind == 1 && q.stash_offered && ngm_field_bwd_b3_takes(*fc, pr))) pr.stash_kind = 0;
+  }
+  // Half stash: with two hidden layers on the split path the forward stashes layer 0's output only and k_field_bwd_b3<.., HS>
+  // recomputes the output layer's input from it: 256 instead of 512 bytes of stash per sample each way.  What the forward on
+  // this workspace recorded wins over the configuration the backward was handed.
+  if (pr.stash_kind && q.rec_layers >= 0) pr.half = q.rec_layers != 0;
+  else if (ray && pr.stash_kind == 1 && L == 2 && (g_stash_override >= 0 ? g_stash_override : fc->activation_stash == NGM_STASH_HALF)) {
+    pr.half = true;
+    pr.half = ngm_field_bwd_b3_takes(*fc, pr);
+  }
+  p.stash_kind = pr.stash_kind; p.half = pr.half;
+  p.stash_layers = pr.stash_kind == 1 ? (pr.half ? 1 : L) : pr.stash_kind == 2 ? 1 : 0;
+  auto refuse = [&](int status, const char* why) { p.status = status; p.why = why; return p; };
+  if (L > 2)
+    return refuse(NGM_E_UNSUPPORTED, "num_layers = 3 is forward only (point evaluation, fused render forward, kNN evaluation): no backward kernel");
+  // Compositing backward inside the MLP backward: the loss (not explicit seeds) in a pointwise geometry mode, per-ray seeds
+  // the forward wrote for these targets, ray indices that fit 24 bits, and a stash kernel that takes the fused problem.  The
+  // variance-weighted loss modes (gradients through the rendered variances) are k_stash_bwd's.
+  const bool may_fuse = ray && !g_no_fused_comp && !q.seeded && q.seeds_written && q.P < (1 << 24) &&
+                        q.rc->geometry_mode != NGM_GEO_NEUS && q.rc->geometry_mode != NGM_GEO_DENSITY &&             // pointwise
+                        q.rc->photometric_mode != NGM_PHOTO_GAUSSIAN_NLL && q.rc->depth_mode == NGM_DEPTH_HUBER;      // no *_nll
+  // In order of preference: bf16-split tiles on the activation stash -> hash encoding + 1x32 MLP on its encoding stash (both
+  // fused if they may) -> 16-sample tiles on the stash -> 16-sample-tile recompute -> 32-sample-tile recompute.
+  auto stash_kernel = [&](bool fused) {
+    pr.fused_comp = fused;
+    return ngm_field_bwd_b3_takes(*fc, pr) ? 3 : ngm_hash_mlp_bwd_takes(*fc, pr) ? 5 : -1;
+  };
+  if (pr.stash_kind) {
+    if (may_fuse) p.variant = stash_kernel(true);
+    p.fused_comp = p.variant >= 0;
+    if (p.variant < 0) p.variant = stash_kernel(false);
+    if (pr.half && p.variant != 3)                       // no other kernel reads a half stash
+      return refuse(NGM_E_INVALID, "render_bwd: the forward stashed one hidden layer (split path) but k_field_bwd_b3 does not take this problem");
+    if (p.variant < 0 && ngm_field_bwd16s_takes(*fc, pr)) p.variant = 2;
+  }
+  if (p.variant < 0 && ngm_field_bwd16_takes(*fc, pr)) p.variant = 1;
+  if (p.variant < 0 && ngm_field_bwd_takes(*fc, pr)) p.variant = 0;
+  if (p.variant < 0) return refuse(NGM_E_UNSUPPORTED, "no MLP backward kernel for this (D,H,L)");
+  return p;
+}
+static int launch_mlp_bwd(const BwdPlan& p, FieldBwdArgs& a, hipStream_t st) {
+  static const bool timing = getenv("NGM_PHASE_TIMING") != nullptr;
+  a.debug_cycles = nullptr;
+  if (timing) {
+    if (!g_debug_cycles) { (void)hipMalloc(&g_debug_cycles, NGM_FWD_DEBUG_WORDS * 8); (void)hipMemset(g_debug_cycles, 0, NGM_FWD_DEBUG_WORDS * 8); }
+    a.debug_cycles = g_debug_cycles;
+  }
+  g_last_bwd = p;
+  const int blocks = a.blocks_per_field * a.F;
+  int e = NGM_E_INVALID;
+  switch (p.variant) {
+    case 3: e = ngm_launch_field_bwd_b3(a, blocks, st); break;
+    case 5: e = ngm_launch_hash_mlp_bwd(a, blocks, st); break;
+    case 2: e = ngm_launch_field_bwd16s(a, blocks, st); break;
+    case 1: e = ngm_launch_field_bwd16(a, blocks, st); break;
+    case 0: e = ngm_launch_field_bwd(a, blocks, st); break;
+  }
+  return e ? fail(e, "MLP backward: the launcher does not take the planned problem (internal error)") : check_launch("ngm_field_bwd");
 }
 
 // mlp = false: the standalone encoding stages (ngm_encode_fwd / ngm_encode_bwd), which never run the hidden layers
@@ -232,14 +310,6 @@ static int check_field_cfg(const ngm_field_cfg* fc, bool mlp = true) {
     return fail(NGM_E_INVALID, "activation_stash: NGM_STASH_FULL / NGM_STASH_HALF (ABI 10: is the struct the caller built 276 bytes?)");
   if (fc->hash_grad_atomics != NGM_HASH_ATOMICS_EXACT && fc->hash_grad_atomics != NGM_HASH_ATOMICS_FLOAT)
     return fail(NGM_E_INVALID, "hash_grad_atomics: NGM_HASH_ATOMICS_EXACT / NGM_HASH_ATOMICS_FLOAT");
-  return NGM_OK;
-}
-// The backward kernels (k_field_bwd*, k_hash_mlp_bwd) are compiled for one and two hidden layers.  Checked by every backward
-// entry point before its first launch: a refusal leaves the workspace, the gradient tensors, the parameters and the
-// device-side iteration counter as they were.
-static int check_bwd_cfg(const ngm_field_cfg* fc) {
-  if (fc->num_layers > 2)
-    return fail(NGM_E_UNSUPPORTED, "num_layers = 3 is forward only (point evaluation, fused render forward, kNN evaluation): no backward kernel");
   return NGM_OK;
 }
 static int check_params(const ngm_field_cfg* fc, const ngm_params* pr) {
@@ -373,10 +443,10 @@ int ngm_target_sv_rays(int32_t F, int32_t R, const float* field_pos_cam, float r
   return check_launch("ngm_target_sv_rays");
 }
 
-int ngm_debug_last_bwd_variant(void) { return g_last_bwd_variant; }
+int ngm_debug_last_bwd_variant(void) { return g_last_bwd.variant; }
 int ngm_debug_last_matmul(int which) { return (which >= 0 && which < 3) ? g_ngm_last_matmul[which] : -1; }
 int ngm_debug_last_fwd_one_tile(void) { return g_ngm_last_fwd_one_tile; }
-int ngm_debug_last_comp_fused(void) { return g_last_comp_fused; }
+int ngm_debug_last_comp_fused(void) { return g_last_bwd.fused_comp; }
 int ngm_debug_disable_fused_comp(int on) { const int old = g_no_fused_comp; g_no_fused_comp = on ? 1 : 0; return old; }
 
 static unsigned long long* g_debug_cycles_fwd = nullptr;
@@ -437,28 +507,6 @@ int ngm_sample_rays_weighted(const ngm_render_cfg* cfg, const ngm_rays* rays, in
 }
 
 // ------------------------------------------------------------------------------------------------
-int ngm_field_eval_fwd(const ngm_field_cfg* fcfg, const ngm_params* params, int32_t F, int64_t P, const float* points,
-                       const float* field_pos, const float* field_quat, float* out, void* stream) {
-  int rc = check_field_cfg(fcfg);
-  if (rc) return rc;
-  rc = check_params(fcfg, params);
-  if (rc) return rc;
-  if (!points || !out || F < 1 || P < 0) return fail(NGM_E_INVALID, "ngm_field_eval_fwd: bad argument");
-  if ((field_pos == nullptr) != (field_quat == nullptr)) return fail(NGM_E_INVALID, "pos/quat must both be given");
-  if (P == 0) return NGM_OK;
-  PointsFwdArgs a;
-  memset(&a, 0, sizeof(a));
-  a.fc = *fcfg; a.pr = *params; a.F = F; a.P = P; a.points = points; a.pos = field_pos; a.quat = field_quat; a.out = out;
-  const int ncu = num_cus();
-  int64_t bpf = (ncu + F - 1) / F;                         // workgroups per field
-  int64_t per = align_up((P + bpf - 1) / bpf, NGM_BLOCK);
-  bpf = (P + per - 1) / per;
-  a.per_block = per;
-  rc = ngm_launch_points_fwd(a, (int)(bpf * F), (hipStream_t)stream);
-  if (rc) return fail(rc, "ngm_field_eval_fwd: no kernel for this (D,H,L)");
-  return check_launch("ngm_field_eval_fwd");
-}
-
 int ngm_encode_fwd(const ngm_field_cfg* fcfg, const ngm_params* params, int32_t F, int64_t P, const float* points,
                    const float* field_pos, const float* field_quat, float* out, void* stream) {
   int rc = check_field_cfg(fcfg, false);
@@ -527,16 +575,6 @@ int ngm_encode_bwd(const ngm_field_cfg* fcfg, const ngm_params* params, int32_t 
   return check_launch("ngm_encode_bwd");
 }
 
-// unit: samples a workgroup's range is a multiple of -- whole 32-sample tiles for each of its waves (4 waves: 128; the
-// hash network's 8-wave backward: 256)
-static void plan_bwd(int F, int64_t P, int64_t* per_block, int* bpf, int64_t unit = 32 * NGM_WAVES_PER_BLOCK) {
-  const int ncu = num_cus();
-  int64_t b = (ncu + F - 1) / F;
-  int64_t per = align_up((P + b - 1) / b, unit);
-  if (per < unit) per = unit;
-  *per_block = per;
-  *bpf = (int)((P + per - 1) / per);
-}
 // permutohedral backward scratch: dL/dE per sample and level (8 B) + scaled local position (16 B)
 static int64_t tri_numel(const ngm_field_cfg* fc) {       // floats of one field's planes (3, C, res, res)
   const int64_t C = fc->tri_mode == NGM_TRI_CONCAT ? fc->dim_enc / 3 : fc->dim_enc;
@@ -549,7 +587,6 @@ static int64_t hash_scratch_bytes(const ngm_field_cfg* fc, int F, int64_t P) {
   return align_up((int64_t)fc->nr_levels * F * P * 8, 256) + align_up((int64_t)F * P * 16, 256) + align_up(part, 256);
 }
 static void carve_hash_scratch(const ngm_field_cfg* fc, int F, int64_t P, char* base, FieldBwdArgs& a) {
-  a.hash_dE = nullptr; a.hash_xyz = nullptr; a.hash_part = nullptr; a.tri_acc = nullptr; a.tri_numel = 0;
   if (fc->encoding == NGM_ENC_TRIPLANE) { a.tri_acc = reinterpret_cast<long long*>(base); a.tri_numel = tri_numel(fc); return; }
   if (fc->encoding != NGM_ENC_PERMUTO) return;
   a.hash_dE = reinterpret_cast<float2*>(base);
@@ -568,34 +605,92 @@ int64_t ngm_field_eval_bwd_workspace(const ngm_field_cfg* fcfg, int32_t F, int64
   return align_up((int64_t)F * bpf * param_pad(fcfg) * 4 + 256, 256) + hash_scratch_bytes(fcfg, F, P) + 256;
 }
 
-int ngm_field_eval_bwd(const ngm_field_cfg* fcfg, const ngm_params* params, int32_t F, int64_t P, const float* points,
-                       const float* field_pos, const float* field_quat, const float* d_out, const ngm_grads* grads,
-                       void* workspace, int64_t workspace_bytes, void* stream) {
+// ---- point evaluation: forward, training forward and backward ------------------------------------------------------------------
+// The reference's unchanged _optimization_iteration reaches NeuralFieldSet.forward(use_vmap=True) under autograd.  With a stash
+// offered (ABI 11: ngm_field_eval_fwd_train / ngm_field_eval_bwd_stash) the forward writes what the fused step's forward writes
+// (ActStash, 256 B per sample and hidden layer) and k_field_bwd_b3 reads it in point mode; without one the backward recomputes.
+static BwdPlan plan_points(const ngm_field_cfg* fc, int32_t F, int64_t P, bool stash_offered) { return plan_mlp_bwd(fc, BwdAsk{nullptr, F, P, false, stash_offered}); }
+static int64_t field_eval_stash_stride(int32_t F, int64_t P) { return align_up((int64_t)F * P, 32) * 64 + 2048; }   // floats per layer
+int64_t ngm_field_eval_stash_bytes(const ngm_field_cfg* fcfg, int32_t F, int64_t P) {
+  if (check_field_cfg(fcfg) || F < 1 || P < 0) return NGM_E_INVALID;
+  if (P == 0 || !plan_points(fcfg, F, P, true).stash_kind) return 0;
+  return align_up(fcfg->num_layers * field_eval_stash_stride(F, P) * 4 + 64, 256) + 256;
+}
+// stash_offered: ngm_field_eval_fwd_train, which writes the stash or refuses
+static int field_eval_fwd(const ngm_field_cfg* fcfg, const ngm_params* params, int32_t F, int64_t P,
+                          const float* points, const float* field_pos, const float* field_quat, float* out, bool stash_offered,
+                          void* stash, int64_t stash_bytes, void* stream) {
   int rc = check_field_cfg(fcfg);
   if (rc) return rc;
-  rc = check_bwd_cfg(fcfg);
+  rc = check_params(fcfg, params);
+  if (rc) return rc;
+  if (!points || !out || F < 1 || P < 0) return fail(NGM_E_INVALID, "ngm_field_eval_fwd: bad argument");
+  if ((field_pos == nullptr) != (field_quat == nullptr)) return fail(NGM_E_INVALID, "pos/quat must both be given");
+  if (P == 0) return NGM_OK;
+  PointsFwdArgs a;
+  memset(&a, 0, sizeof(a));
+  a.fc = *fcfg; a.pr = *params; a.F = F; a.P = P; a.points = points; a.pos = field_pos; a.quat = field_quat; a.out = out;
+  if (stash_offered) {
+    const int64_t need = ngm_field_eval_stash_bytes(fcfg, F, P);
+    if (need <= 0) return fail(NGM_E_UNSUPPORTED, "ngm_field_eval_fwd_train: no stash-reading backward for this configuration (ngm_field_eval_stash_bytes == 0): use ngm_field_eval_fwd / ngm_field_eval_bwd");
+    if (!stash || stash_bytes < need) return fail(NGM_E_WORKSPACE, "ngm_field_eval_fwd_train: stash too small (ngm_field_eval_stash_bytes)");
+    a.act = reinterpret_cast<float*>(align_up((int64_t)stash, 256)); a.act_layer_stride = field_eval_stash_stride(F, P);
+  }
+  const int ncu = num_cus();
+  int64_t bpf = (ncu + F - 1) / F;                         // workgroups per field
+  int64_t per = align_up((P + bpf - 1) / bpf, NGM_BLOCK);
+  bpf = (P + per - 1) / per;
+  a.per_block = per;
+  rc = ngm_launch_points_fwd(a, (int)(bpf * F), (hipStream_t)stream);
+  if (rc) return fail(rc, "ngm_field_eval_fwd: no kernel for this (D,H,L)");
+  return check_launch("ngm_field_eval_fwd");
+}
+int ngm_field_eval_fwd(const ngm_field_cfg* fcfg, const ngm_params* params, int32_t F, int64_t P, const float* points,
+                       const float* field_pos, const float* field_quat, float* out, void* stream) {
+  return field_eval_fwd(fcfg, params, F, P, points, field_pos, field_quat, out, false, nullptr, 0, stream);
+}
+int ngm_field_eval_fwd_train(const ngm_field_cfg* fcfg, const ngm_params* params, int32_t F, int64_t P, const float* points,
+                             const float* field_pos, const float* field_quat, float* out, void* stash, int64_t stash_bytes,
+                             void* stream) {
+  return field_eval_fwd(fcfg, params, F, P, points, field_pos, field_quat, out, true, stash, stash_bytes, stream);
+}
+
+// stash_offered: ngm_field_eval_bwd_stash, which reads the stash or refuses
+static int field_eval_bwd(const ngm_field_cfg* fcfg, const ngm_params* params, int32_t F, int64_t P,
+                          const float* points, const float* field_pos, const float* field_quat, const float* d_out,
+                          const ngm_grads* grads, bool stash_offered, const void* stash, int64_t stash_bytes, void* workspace,
+                          int64_t workspace_bytes, void* stream) {
+  int rc = check_field_cfg(fcfg);
   if (rc) return rc;
   rc = check_params(fcfg, params);
   if (rc) return rc;
   if (!points || !d_out || !grads || F < 1 || P < 1) return fail(NGM_E_INVALID, "ngm_field_eval_bwd: bad argument");
-  if (workspace_bytes < ngm_field_eval_bwd_workspace(fcfg, F, P) || !workspace) return fail(NGM_E_WORKSPACE, "workspace too small");
+  if ((field_pos == nullptr) != (field_quat == nullptr)) return fail(NGM_E_INVALID, "pos/quat must both be given");
+  const BwdPlan plan = plan_points(fcfg, F, P, stash_offered);
+  if (plan.status) return fail(plan.status, plan.why);
   FieldBwdArgs a;
   memset(&a, 0, sizeof(a));
+  if (stash_offered) {
+    if (!plan.stash_kind) return fail(NGM_E_UNSUPPORTED, "ngm_field_eval_bwd_stash: no stash-reading backward for this configuration");
+    if (!stash || stash_bytes < ngm_field_eval_stash_bytes(fcfg, F, P)) return fail(NGM_E_WORKSPACE, "ngm_field_eval_bwd_stash: stash too small");
+    a.act = reinterpret_cast<const float*>(align_up((int64_t)stash, 256)); a.act_layer_stride = field_eval_stash_stride(F, P);
+  }
+  if (workspace_bytes < ngm_field_eval_bwd_workspace(fcfg, F, P) || !workspace) return fail(NGM_E_WORKSPACE, "workspace too small");
+  hipStream_t st = (hipStream_t)stream;
   a.fc = *fcfg; a.pr = *params; a.F = F; a.P = P; a.points = points; a.pos = field_pos; a.quat = field_quat;
   a.d_out = reinterpret_cast<const float4*>(d_out);
-  plan_bwd(F, P, &a.per_block, &a.blocks_per_field);
+  a.per_block = plan.per_block; a.blocks_per_field = plan.blocks_per_field;
   a.p_pad = param_pad(fcfg);
   a.partials = reinterpret_cast<float*>(align_up((int64_t)workspace, 256));
   carve_hash_scratch(fcfg, F, P, reinterpret_cast<char*>(a.partials) + align_up((int64_t)F * a.blocks_per_field * a.p_pad * 4 + 256, 256), a);
-  rc = prep_lattice_grad(fcfg, grads, F, a, (hipStream_t)stream);
+  rc = check_enc_grads(fcfg, grads, a);
   if (rc) return rc;
-  rc = launch_bwd_any(a, a.blocks_per_field * F, (hipStream_t)stream);
-  if (rc) return fail(rc, "ngm_field_eval_bwd: no kernel for this (D,H,L)");
-  rc = check_launch("ngm_field_eval_bwd");
+  if (a.tri_acc) (void)hipMemsetAsync(a.tri_acc, 0, (size_t)F * a.tri_numel * 8, st);
+  rc = launch_mlp_bwd(plan, a, st);
   if (rc) return rc;
-  if (fcfg->encoding == NGM_ENC_TRIPLANE) { ngm_launch_tri_finish(a, (hipStream_t)stream); rc = check_launch("ngm_tri_finish"); if (rc) return rc; }
+  if (fcfg->encoding == NGM_ENC_TRIPLANE) { ngm_launch_tri_finish(a, st); rc = check_launch("ngm_tri_finish"); if (rc) return rc; }
   if (fcfg->encoding == NGM_ENC_PERMUTO) {
-    rc = ngm_launch_hash_grad(a, (hipStream_t)stream);
+    rc = ngm_launch_hash_grad(a, st);
     if (rc) return fail(rc, "permutohedral backward: hash table too large for the LDS-staged scatter");
     rc = check_launch("ngm_hash_grad");
     if (rc) return rc;
@@ -603,88 +698,18 @@ int ngm_field_eval_bwd(const ngm_field_cfg* fcfg, const ngm_params* params, int3
   GradReduceArgs g;
   memset(&g.adam, 0, sizeof(g.adam));
   g.fc = *fcfg; g.gr = *grads; g.F = F; g.blocks_per_field = a.blocks_per_field; g.partials = a.partials; g.p_pad = a.p_pad;
-  ngm_launch_grad_reduce(g, (hipStream_t)stream);
+  ngm_launch_grad_reduce(g, st);
   return check_launch("ngm_grad_reduce");
 }
-
-// ---- training forward / backward of the point evaluation with an activation stash (ABI 11) ---------------------------------
-// The reference's unchanged _optimization_iteration reaches NeuralFieldSet.forward(use_vmap=True) under autograd; its backward
-// used to be k_field_bwd16 alone (fp32 MFMA, every hidden layer recomputed: 0.45 of the fp32 MFMA peak).  With the stash the
-// forward writes what the fused training step's forward writes (ngm_field.h ActStash, 256 B per sample and hidden layer) and
-// the backward is the fused step's kernel, k_field_bwd_b3, in point mode.
-static int act_stash_kind(const ngm_field_cfg* fc);
-static bool field_eval_stash_applies(const ngm_field_cfg* fc, int32_t F, int64_t P) {
-  if (act_stash_kind(fc) != 1) return false;
-  FieldBwdArgs probe;
-  memset(&probe, 0, sizeof(probe));
-  probe.fc = *fc; probe.F = F; probe.P = P;
-  probe.act = reinterpret_cast<const float*>(1); probe.points = reinterpret_cast<const float*>(1);
-  return ngm_field_bwd_b3_applies(probe);
-}
-static int64_t field_eval_stash_stride(int32_t F, int64_t P) { return align_up((int64_t)F * P, 32) * 64 + 2048; }   // floats per layer
-int64_t ngm_field_eval_stash_bytes(const ngm_field_cfg* fcfg, int32_t F, int64_t P) {
-  if (check_field_cfg(fcfg) || F < 1 || P < 0) return NGM_E_INVALID;
-  if (P == 0 || !field_eval_stash_applies(fcfg, F, P)) return 0;
-  return align_up(fcfg->num_layers * field_eval_stash_stride(F, P) * 4 + 64, 256) + 256;
-}
-int ngm_field_eval_fwd_train(const ngm_field_cfg* fcfg, const ngm_params* params, int32_t F, int64_t P, const float* points,
-                             const float* field_pos, const float* field_quat, float* out, void* stash, int64_t stash_bytes,
-                             void* stream) {
-  int rc = check_field_cfg(fcfg);
-  if (rc) return rc;
-  rc = check_params(fcfg, params);
-  if (rc) return rc;
-  if (!points || !out || F < 1 || P < 0) return fail(NGM_E_INVALID, "ngm_field_eval_fwd_train: bad argument");
-  if ((field_pos == nullptr) != (field_quat == nullptr)) return fail(NGM_E_INVALID, "pos/quat must both be given");
-  if (P == 0) return NGM_OK;
-  const int64_t need = ngm_field_eval_stash_bytes(fcfg, F, P);
-  if (need <= 0) return fail(NGM_E_UNSUPPORTED, "ngm_field_eval_fwd_train: no stash-reading backward for this configuration (ngm_field_eval_stash_bytes == 0): use ngm_field_eval_fwd / ngm_field_eval_bwd");
-  if (!stash || stash_bytes < need) return fail(NGM_E_WORKSPACE, "ngm_field_eval_fwd_train: stash too small (ngm_field_eval_stash_bytes)");
-  PointsFwdArgs a;
-  memset(&a, 0, sizeof(a));
-  a.fc = *fcfg; a.pr = *params; a.F = F; a.P = P; a.points = points; a.pos = field_pos; a.quat = field_quat; a.out = out;
-  a.act = reinterpret_cast<float*>(align_up((int64_t)stash, 256)); a.act_layer_stride = field_eval_stash_stride(F, P);
-  const int ncu = num_cus();
-  int64_t bpf = (ncu + F - 1) / F;
-  int64_t per = align_up((P + bpf - 1) / bpf, NGM_BLOCK);
-  bpf = (P + per - 1) / per;
-  a.per_block = per;
-  rc = ngm_launch_points_fwd(a, (int)(bpf * F), (hipStream_t)stream);
-  if (rc) return fail(rc, "ngm_field_eval_fwd_train: no kernel for this (D,H,L)");
-  return check_launch("ngm_field_eval_fwd_train");
+int ngm_field_eval_bwd(const ngm_field_cfg* fcfg, const ngm_params* params, int32_t F, int64_t P, const float* points,
+                       const float* field_pos, const float* field_quat, const float* d_out, const ngm_grads* grads,
+                       void* workspace, int64_t workspace_bytes, void* stream) {
+  return field_eval_bwd(fcfg, params, F, P, points, field_pos, field_quat, d_out, grads, false, nullptr, 0, workspace, workspace_bytes, stream);
 }
 int ngm_field_eval_bwd_stash(const ngm_field_cfg* fcfg, const ngm_params* params, int32_t F, int64_t P, const float* points,
                              const float* field_pos, const float* field_quat, const float* d_out, const ngm_grads* grads,
                              const void* stash, int64_t stash_bytes, void* workspace, int64_t workspace_bytes, void* stream) {
-  int rc = check_field_cfg(fcfg);
-  if (rc) return rc;
-  rc = check_params(fcfg, params);
-  if (rc) return rc;
-  if (!points || !d_out || !grads || F < 1 || P < 1) return fail(NGM_E_INVALID, "ngm_field_eval_bwd_stash: bad argument");
-  if ((field_pos == nullptr) != (field_quat == nullptr)) return fail(NGM_E_INVALID, "pos/quat must both be given");
-  const int64_t need = ngm_field_eval_stash_bytes(fcfg, F, P);
-  if (need <= 0) return fail(NGM_E_UNSUPPORTED, "ngm_field_eval_bwd_stash: no stash-reading backward for this configuration");
-  if (!stash || stash_bytes < need) return fail(NGM_E_WORKSPACE, "ngm_field_eval_bwd_stash: stash too small");
-  if (workspace_bytes < ngm_field_eval_bwd_workspace(fcfg, F, P) || !workspace) return fail(NGM_E_WORKSPACE, "workspace too small");
-  FieldBwdArgs a;
-  memset(&a, 0, sizeof(a));
-  a.fc = *fcfg; a.pr = *params; a.F = F; a.P = P; a.points = points; a.pos = field_pos; a.quat = field_quat;
-  a.d_out = reinterpret_cast<const float4*>(d_out);
-  plan_bwd(F, P, &a.per_block, &a.blocks_per_field);
-  a.p_pad = param_pad(fcfg);
-  a.partials = reinterpret_cast<float*>(align_up((int64_t)workspace, 256));
-  a.act = reinterpret_cast<const float*>(align_up((int64_t)stash, 256)); a.act_layer_stride = field_eval_stash_stride(F, P);
-  a.debug_cycles = nullptr;
-  rc = ngm_launch_field_bwd_b3(a, a.blocks_per_field * F, (hipStream_t)stream);
-  g_last_bwd_variant = 3; g_last_stash_mode = 0; g_last_comp_fused = 0;
-  if (rc) return fail(rc, "ngm_field_eval_bwd_stash: k_field_bwd_b3 does not take this problem");
-  rc = check_launch("ngm_field_eval_bwd_stash");
-  if (rc) return rc;
-  GradReduceArgs g;
-  memset(&g.adam, 0, sizeof(g.adam));
-  g.fc = *fcfg; g.gr = *grads; g.F = F; g.blocks_per_field = a.blocks_per_field; g.partials = a.partials; g.p_pad = a.p_pad;
-  ngm_launch_grad_reduce(g, (hipStream_t)stream);
-  return check_launch("ngm_grad_reduce");
+  return field_eval_bwd(fcfg, params, F, P, points, field_pos, field_quat, d_out, grads, true, stash, stash_bytes, workspace, workspace_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -734,48 +759,15 @@ int ngm_composite_bwd(const ngm_render_cfg* cfg, int64_t N, int32_t S, const flo
 // ------------------------------------------------------------------------------------------------
 struct RenderPlan {
   int S, rays_per_block, blocks_fwd, waves_fwd, maxs, b3;
-  int64_t per_block_bwd; int blocks_per_field_bwd;
+  BwdPlan bwd;                     // train: the MLP backward this workspace is carved for, and the stash the forward writes for it
   int64_t p_pad;
   int64_t off_rayseed;             // (F*R, 8) per-ray loss derivatives without the normalisers (fused compositing backward)
   int64_t off_raytab, off_stashA, off_stashB, off_losspart, off_gradpart, off_hash, off_act, act_layer_stride, total;
-  int stash_mode;                  // 0: every hidden layer's output; 1: layer 0's only (half stash, k_field_bwd_b3<HS>)
   int64_t off_dout, off_disd;      // neus: separate per-sample gradient buffer, per-ray d loss / d isd
 };
-// The training forward stashes the hidden activations (64 floats per sample and layer) when the backward
-// has a kernel that consumes them: 49..64-wide hidden layers, 1-2 layers, non-hash encoding.  The
-// backward then skips its forward recompute.  NGM_NO_ACT_STASH=1 turns it off (recompute; saves
-// 256 B * L per sample of workspace).
-// 0: none; 1: post-ReLU hidden activations of 64-wide layers (k_field_bwd16s); 2: the hash encoding itself
-// (<= 32 features; k_field_bwd16 then skips the simplex search and the table gathers, the hidden layers are recomputed)
-static int act_stash_kind(const ngm_field_cfg* fc) {
-  static const bool off = getenv("NGM_NO_ACT_STASH") != nullptr;
-  if (off) return 0;
-  const int th = (fc->dim_hidden + 15) / 16, ti = (fc->dim_enc + 15) / 16;
-  if (fc->encoding == NGM_ENC_PERMUTO) return (ti == 2 && fc->dim_hidden <= 32 && fc->skip_mode == NGM_SKIP_NO) ? 2 : 0;   // the stash's consumers (k_hash_mlp_bwd, k_field_bwd16) are skip-less
-  if (fc->encoding == NGM_ENC_TRIPLANE) return 0;      // 32-sample-tile backward (recompute: it needs the taps anyway)
-  // with a skip connection the stashed activation no longer tells the ReLU mask
-  return (fc->skip_mode == NGM_SKIP_NO && th == 4 && ti == 4 && fc->num_layers >= 1 && fc->num_layers <= 2) ? 1 : 0;
-}
-
-// Half stash (round 5): with two hidden layers on the split path the forward stashes layer 0's output only and
-// k_field_bwd_b3<.., HS> recomputes the output layer's input from it on the matrix pipe: 256 instead of 512 bytes of stash per
-// sample each way.  Decided from the field configuration and the samples per field alone, so that ngm_render_fwd and
-// ngm_render_bwd* (which see the same fcfg and rays) agree; the forward's choice is also recorded per workspace.
-// ABI 10: the mode is ngm_field_cfg.activation_stash; the override below is a developer A/B switch only (tools/)
-static int g_stash_override = -1;      // ngm_debug_stash_mode
-static int stash_pref(const ngm_field_cfg* fc) {
-  if (g_stash_override >= 0) return g_stash_override;
-  return fc->activation_stash == NGM_STASH_HALF ? 1 : 0;
-}
-static bool half_stash_applies(const ngm_field_cfg* fc, int64_t P) {
-  if (stash_pref(fc) == 0 || fc->num_layers != 2 || act_stash_kind(fc) != 1) return false;
-  FieldBwdArgs probe;
-  memset(&probe, 0, sizeof(probe));
-  probe.fc = *fc; probe.P = P; probe.act = reinterpret_cast<const float*>(1);
-  return ngm_field_bwd_b3_applies(probe);
-}
-
-static RenderPlan plan_render(const ngm_field_cfg* fc, const ngm_render_cfg* rc, int F, int R, bool guided, bool train) {
+// ask: the backward's seed mode and the forward's per-workspace records (ngm_render_bwd*); the forward and the sizing leave it empty
+static RenderPlan plan_render(const ngm_field_cfg* fc, const ngm_render_cfg* rc, int F, int R, bool guided, bool train,
+                              BwdAsk ask = BwdAsk()) {
   RenderPlan p;
   memset(&p, 0, sizeof(p));
   p.S = rc->num_samples_coarse + (guided ? rc->num_samples_guided : 0);
@@ -846,18 +838,13 @@ static RenderPlan plan_render(const ngm_field_cfg* fc, const ngm_render_cfg* rc,
       p.off_dout = o; o = align_up(o + NS * 16, 256);
       p.off_disd = o; o = align_up(o + NR * 4, 256);
     }
-    plan_bwd(F, (int64_t)R * p.S, &p.per_block_bwd, &p.blocks_per_field_bwd, fc->encoding == NGM_ENC_PERMUTO ? 256 : 128);
-    p.off_gradpart = o; o = align_up(o + (int64_t)F * p.blocks_per_field_bwd * p.p_pad * 4, 256);
+    ask.rc = rc; ask.F = F; ask.P = (int64_t)R * p.S;
+    p.bwd = plan_mlp_bwd(fc, ask);
+    p.off_gradpart = o; o = align_up(o + (int64_t)F * p.bwd.blocks_per_field * p.p_pad * 4, 256);
     p.off_hash = o; o = align_up(o + hash_scratch_bytes(fc, F, (int64_t)R * p.S), 256);
-    const int kind = act_stash_kind(fc);
-    if (kind == 1) {
-      p.act_layer_stride = align_up(NS, 32) * 64 + 2048;      // floats: whole 32-sample tiles (+1: a field may start mid-tile)
-      const bool half = half_stash_applies(fc, (int64_t)R * p.S);                              // half stash: layer 0's output only
-      p.stash_mode = half ? 1 : 0;
-      p.off_act = o; o = align_up(o + (half ? 1 : fc->num_layers) * p.act_layer_stride * 4 + 64, 256);
-    } else if (kind == 2) {
-      p.act_layer_stride = align_up(NS, 32) * 32 + 1024;      // one "layer": the 32-feature encoding
-      p.off_act = o; o = align_up(o + p.act_layer_stride * 4 + 64, 256);
+    if (p.bwd.stash_kind) {     // floats per layer: whole 32-sample tiles (+1: a field may start mid-tile) of 64 activations / 32 features
+      p.act_layer_stride = p.bwd.stash_kind == 1 ? align_up(NS, 32) * 64 + 2048 : align_up(NS, 32) * 32 + 1024;
+      p.off_act = o; o = align_up(o + p.bwd.stash_layers * p.act_layer_stride * 4 + 64, 256);
     }
   }
   p.total = o + 256;
@@ -872,22 +859,19 @@ int64_t ngm_render_workspace(const ngm_field_cfg* fcfg, const ngm_render_cfg* rc
   return plan_render(fcfg, rcfg, F, R, true, train != 0).total;
 }
 
-// permutohedral: validate the gradient table (it is fully overwritten by k_hash_reduce)
-static int prep_lattice_grad(const ngm_field_cfg* fc, const ngm_grads* grads, int F, FieldBwdArgs& a, hipStream_t st) {
-  a.lattice_grad = nullptr; a.lattice_grad_stride = 0;
-  a.planes_grad = nullptr; a.planes_grad_stride = 0;
+// The encoding's gradient tensors, validated before anything launches.  permutohedral: the table is fully overwritten by
+// k_hash_reduce (no zero-fill); triplane: the caller zeroes a.tri_acc on the stream before the MLP backward.
+static int check_enc_grads(const ngm_field_cfg* fc, const ngm_grads* grads, FieldBwdArgs& a) {
   if (fc->encoding == NGM_ENC_TRIPLANE) {
     if (!grads->planes || grads->planes_stride < tri_numel(fc)) return fail(NGM_E_INVALID, "triplane: grads.planes missing / stride too small");
     if (!a.tri_acc) return fail(NGM_E_WORKSPACE, "triplane: no accumulator scratch");
     a.planes_grad = grads->planes; a.planes_grad_stride = grads->planes_stride;
-    (void)hipMemsetAsync(a.tri_acc, 0, (size_t)F * tri_numel(fc) * 8, st);
     return NGM_OK;
   }
   if (fc->encoding != NGM_ENC_PERMUTO) return NGM_OK;
   if (!grads->lattice) return fail(NGM_E_INVALID, "permutohedral: grads.lattice is NULL");
   const int64_t per = (int64_t)fc->nr_levels * ((int64_t)1 << fc->log2_hashmap_size) * 2;
   if (grads->lattice_stride < per) return fail(NGM_E_INVALID, "permutohedral: grads.lattice_stride too small");
-  (void)st;   // k_hash_reduce overwrites every table entry: no zero-fill
   a.lattice_grad = grads->lattice; a.lattice_grad_stride = grads->lattice_stride;
   return NGM_OK;
 }
@@ -963,8 +947,7 @@ static int render_fwd_impl(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg
     a.stashB = reinterpret_cast<float2*>(ws + p.off_stashB);
     a.loss_partials = reinterpret_cast<float*>(ws + p.off_losspart);
     if (p.act_layer_stride) { a.act = reinterpret_cast<float*>(ws + p.off_act); a.act_layer_stride = p.act_layer_stride; }
-    a.act_layers = (a.act && p.stash_mode) ? 1 : 0;
-    note_forward_stash(workspace, p.stash_mode);
+    a.act_layers = p.bwd.half;
     static const bool timing = getenv("NGM_PHASE_TIMING") != nullptr;
     if (timing) {
       if (!g_debug_cycles_fwd) { (void)hipMalloc(&g_debug_cycles_fwd, NGM_FWD_DEBUG_WORDS * 8); (void)hipMemset(g_debug_cycles_fwd, 0, NGM_FWD_DEBUG_WORDS * 8); }
@@ -973,7 +956,10 @@ static int render_fwd_impl(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg
   }
   e = ngm_launch_render_fwd(a, p.blocks_fwd, (hipStream_t)stream);
   if (e) return fail(e, "render_fwd: no kernel for this (D,H,L)");
-  if (save) note_forward_seeds(workspace, a.rayseed ? targets->rgbds : nullptr);
+  if (save) {
+    note_forward_stash(workspace, p.bwd.half);
+    note_forward_seeds(workspace, a.rayseed ? targets->rgbds : nullptr);
+  }
   e = check_launch("ngm_render_fwd");
   if (e) return e;
   if (has_tg && loss_sums) {      // loss_sums == NULL: deferred -- ngm_render_bwd* (loss_sums == NULL) reduces the partials itself
@@ -1002,9 +988,23 @@ static int render_bwd_common(const ngm_field_cfg* fcfg, const ngm_render_cfg* rc
                              int64_t workspace_bytes, hipStream_t st, const GradAdam* adam = nullptr,
                              const GradAdam* lattice_adam = nullptr, bool* lattice_adam_applied = nullptr,
                              const int32_t* num_active = nullptr) {
-  const RenderPlan p = plan_render(fcfg, rcfg, rays->F, rays->R, rays->gt != nullptr, true);
+  // the plan and every argument check first: a refusal launches nothing
+  BwdAsk ask;      // with what the forward on THIS workspace wrote
+  ask.seeded = sb.seed_mode != 0; ask.rec_layers = forward_stash_layers(workspace); ask.seeds_written = forward_wrote_seeds_for(workspace, sb.tg.rgbds);
+  const RenderPlan p = plan_render(fcfg, rcfg, rays->F, rays->R, rays->gt != nullptr, true, ask);
+  if (p.bwd.status) return fail(p.bwd.status, p.bwd.why);
   if (!workspace || workspace_bytes < p.total) return fail(NGM_E_WORKSPACE, "render_bwd: workspace too small");
+  const bool nll_loss = rcfg->photometric_mode == NGM_PHOTO_GAUSSIAN_NLL || rcfg->depth_mode != NGM_DEPTH_HUBER;
+  if (nll_loss && sb.seed_mode == 0 && (!sb.pred.color_vars || !sb.pred.depth_vars))
+    return fail(NGM_E_INVALID, "render_bwd: the *_nll loss modes need pred.color_vars and pred.depth_vars");
   char* ws = reinterpret_cast<char*>(align_up((int64_t)workspace, 256));
+  FieldBwdArgs a;
+  memset(&a, 0, sizeof(a));
+  a.fc = *fcfg; a.pr = *params; a.F = rays->F; a.P = (int64_t)rays->R * p.S; a.S = p.S;
+  a.num_active = num_active;
+  carve_hash_scratch(fcfg, rays->F, a.P, ws + p.off_hash, a);
+  int e = check_enc_grads(fcfg, grads, a);
+  if (e) return e;
   sb.rc = *rcfg; sb.F = rays->F; sb.R = rays->R; sb.S = p.S;
   sb.num_active = num_active;
   if (!rays->gt) sb.rc.w_freespace = sb.rc.w_tsdf = 0.f;       // no gt: the reference forms no free-space / TSDF terms (rm.py:624, 632)
@@ -1023,39 +1023,18 @@ static int render_bwd_common(const ngm_field_cfg* fcfg, const ngm_render_cfg* rc
     sb.counter = (rays->philox_offset_autoinc && rays->philox_offset_dev)
                      ? reinterpret_cast<unsigned long long*>(const_cast<uint64_t*>(rays->philox_offset_dev)) : nullptr;
   }
-  FieldBwdArgs a;
-  memset(&a, 0, sizeof(a));
-  a.fc = *fcfg; a.pr = *params; a.F = rays->F; a.P = (int64_t)rays->R * p.S; a.S = p.S;
-  a.num_active = num_active;
-  carve_hash_scratch(fcfg, rays->F, a.P, ws + p.off_hash, a);
-  a.per_block = p.per_block_bwd; a.blocks_per_field = p.blocks_per_field_bwd;
+  a.per_block = p.bwd.per_block; a.blocks_per_field = p.bwd.blocks_per_field;
   a.raytab = sb.raytab; a.stashB = sb.stashB; a.d_out = neus ? sb.d_out : sb.stashA;
   a.partials = reinterpret_cast<float*>(ws + p.off_gradpart); a.p_pad = p.p_pad;
-  if (p.act_layer_stride) { a.act = reinterpret_cast<const float*>(ws + p.off_act); a.act_layer_stride = p.act_layer_stride; }
-  {
-    const int rec = forward_stash_layers(workspace);       // what the forward on THIS workspace wrote (-1: no record: the plan's mode)
-    a.act_half = a.act ? (rec < 0 ? p.stash_mode : rec) : 0;
-  }
-  // Compositing backward inside the MLP backward (k_field_bwd_b3<FC>, k_hash_mlp_bwd<FC>): loss seeds, pointwise geometry
-  // modes, and a kernel that takes the problem with the fused fields set (launch_bwd_any tries the same two first).  Otherwise
-  // k_stash_bwd runs first and leaves dL/d(raw outputs) in place of the forward's stash.  ngm_debug_disable_fused_comp: never.
-  const bool pointwise = rcfg->geometry_mode != NGM_GEO_NEUS && rcfg->geometry_mode != NGM_GEO_DENSITY;
-  // the variance-weighted loss modes (gradients through the rendered variances) are k_stash_bwd's
-  const bool nll_loss = rcfg->photometric_mode == NGM_PHOTO_GAUSSIAN_NLL || rcfg->depth_mode != NGM_DEPTH_HUBER;
-  if (nll_loss && sb.seed_mode == 0 && (!sb.pred.color_vars || !sb.pred.depth_vars))
-    return fail(NGM_E_INVALID, "render_bwd: the *_nll loss modes need pred.color_vars and pred.depth_vars");
-  FieldBwdArgs af = a;
-  af.fused_comp = 1; af.rc = sb.rc;
-  af.rayseed = reinterpret_cast<const float*>(ws + p.off_rayseed);
-  af.loss_sums = sb.loss_sums; af.loss_partials = sb.loss_partials; af.n_partials = sb.n_partials;
-  af.sums_out = sb.sums_out; af.loss_out = sb.loss_out; af.counter = sb.counter;
-  // (hash encoding: k_hash_mlp_bwd writes the positions k_hash_grad needs into a.hash_xyz itself)
-  const bool fuse = !g_no_fused_comp && !nll_loss && sb.seed_mode == 0 && pointwise && a.P < (1 << 24) &&
-                    forward_wrote_seeds_for(workspace, sb.tg.rgbds) && (ngm_field_bwd_b3_applies(af) || ngm_hash_mlp_bwd_applies(af));
-  int e = 0;
-  if (fuse) {
-    a = af;
+  if (p.bwd.stash_kind) { a.act = reinterpret_cast<const float*>(ws + p.off_act); a.act_layer_stride = p.act_layer_stride; a.act_half = p.bwd.half; }
+  if (p.bwd.fused_comp) {
+    // d_out holds the forward's stash untouched (hash encoding: k_hash_mlp_bwd writes the positions k_hash_grad needs itself)
+    a.fused_comp = 1; a.rc = sb.rc;
+    a.rayseed = reinterpret_cast<const float*>(ws + p.off_rayseed);
+    a.loss_sums = sb.loss_sums; a.loss_partials = sb.loss_partials; a.n_partials = sb.n_partials;
+    a.sums_out = sb.sums_out; a.loss_out = sb.loss_out; a.counter = sb.counter;
   } else {
+    // k_stash_bwd runs first and leaves dL/d(raw outputs) in place of the forward's stash
     sb.xyz_out = a.hash_xyz;                 // positions for the table-gradient kernel (hash encoding)
     a.hash_xyz_ready = a.hash_xyz != nullptr;
     e = ngm_launch_stash_bwd(sb, st);
@@ -1066,11 +1045,8 @@ static int render_bwd_common(const ngm_field_cfg* fcfg, const ngm_render_cfg* rc
   if (neus && grads->neus_sd)
     ngm_launch_neus_sd_grad(sb.d_isd_rays, rays->F, rays->R, params->neus_sd, params->neus_sd_stride, params->field_index,
                             grads->neus_sd, st);
-  e = prep_lattice_grad(fcfg, grads, rays->F, a, st);
-  if (e) return e;
-  e = launch_bwd_any(a, a.blocks_per_field * a.F, st);
-  if (e) return fail(e, "render_bwd: no kernel for this (D,H,L)");
-  e = check_launch("ngm_field_bwd");
+  if (a.tri_acc) (void)hipMemsetAsync(a.tri_acc, 0, (size_t)a.F * a.tri_numel * 8, st);
+  e = launch_mlp_bwd(p.bwd, a, st);
   if (e) return e;
   if (fcfg->encoding == NGM_ENC_TRIPLANE) { ngm_launch_tri_finish(a, st); e = check_launch("ngm_tri_finish"); if (e) return e; }
   GradReduceArgs g;
@@ -1097,8 +1073,6 @@ static int render_bwd_impl(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg
                            const ngm_targets* targets, const ngm_prediction* pred, const float* loss_sums, const ngm_grads* grads,
                            float* loss_out, void* workspace, int64_t workspace_bytes, void* stream, const int32_t* num_active) {
   int e = check_render(fcfg, rcfg, params, rays);
-  if (e) return e;
-  e = check_bwd_cfg(fcfg);
   if (e) return e;
   if (!targets || !targets->rgbds || !targets->depth_mask || !pred || !pred->rgbds || !pred->term_probs || !grads)
     return fail(NGM_E_INVALID, "render_bwd: NULL argument");
@@ -1131,8 +1105,6 @@ static int render_bwd_adam_impl(const ngm_field_cfg* fcfg, const ngm_render_cfg*
                                 float eps, float weight_decay, float* loss_out, void* workspace, int64_t workspace_bytes,
                                 void* stream, const int32_t* num_active) {
   int e = check_render(fcfg, rcfg, params, rays);
-  if (e) return e;
-  e = check_bwd_cfg(fcfg);
   if (e) return e;
   if (!targets || !targets->rgbds || !targets->depth_mask || !pred || !pred->rgbds || !pred->term_probs || !grads ||
       !mlp_tensors || num_mlp_tensors < 1 || (step < 1 && !step_dev))
@@ -1182,29 +1154,13 @@ int ngm_render_bwd_adam_counted(const ngm_field_cfg* fcfg, const ngm_render_cfg*
                               stream, num_active);
 }
 
-int ngm_render_bwd_seeded(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg, const ngm_params* params,
-                          const ngm_rays* rays, const float* d_rgbds, const float* d_term, const float* d_geom_samples,
-                          const ngm_grads* grads, void* workspace, int64_t workspace_bytes, void* stream) {
-  int e = check_render(fcfg, rcfg, params, rays);
-  if (e) return e;
-  e = check_bwd_cfg(fcfg);
-  if (e) return e;
-  if (!d_rgbds || !grads) return fail(NGM_E_INVALID, "render_bwd_seeded: NULL argument");
-  StashBwdArgs sb;
-  memset(&sb, 0, sizeof(sb));
-  sb.seed_mode = 1; sb.d_rgbds = d_rgbds; sb.d_term = d_term; sb.d_geom_samples = d_geom_samples;
-  return render_bwd_common(fcfg, rcfg, params, rays, sb, grads, workspace, workspace_bytes, (hipStream_t)stream);
-}
-
 int ngm_render_bwd_seeded_vars(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg, const ngm_params* params,
                                const ngm_rays* rays, const ngm_prediction* pred, const float* d_rgbds, const float* d_color_vars,
                                const float* d_depth_vars, const float* d_term, const float* d_geom_samples,
                                const ngm_grads* grads, void* workspace, int64_t workspace_bytes, void* stream) {
   int e = check_render(fcfg, rcfg, params, rays);
   if (e) return e;
-  e = check_bwd_cfg(fcfg);
-  if (e) return e;
-  if (!d_rgbds || !grads) return fail(NGM_E_INVALID, "render_bwd_seeded_vars: NULL argument");
+  if (!d_rgbds || !grads) return fail(NGM_E_INVALID, "render_bwd_seeded: NULL argument");
   if ((d_color_vars || d_depth_vars) && (!pred || !pred->rgbds || !pred->term_probs))
     return fail(NGM_E_INVALID, "render_bwd_seeded_vars: seeds on the variances need the forward's pred.rgbds and pred.term_probs");
   StashBwdArgs sb;
@@ -1213,6 +1169,13 @@ int ngm_render_bwd_seeded_vars(const ngm_field_cfg* fcfg, const ngm_render_cfg* 
   sb.d_cvars = d_color_vars; sb.d_dvars = d_depth_vars;
   if (pred) sb.pred = *pred;
   return render_bwd_common(fcfg, rcfg, params, rays, sb, grads, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int ngm_render_bwd_seeded(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg, const ngm_params* params,
+                          const ngm_rays* rays, const float* d_rgbds, const float* d_term, const float* d_geom_samples,
+                          const ngm_grads* grads, void* workspace, int64_t workspace_bytes, void* stream) {
+  return ngm_render_bwd_seeded_vars(fcfg, rcfg, params, rays, nullptr, d_rgbds, nullptr, nullptr, d_term, d_geom_samples, grads,
+                                    workspace, workspace_bytes, stream);
 }
 
 int ngm_render_read_samples(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg, int32_t F, int32_t R, int32_t S,
@@ -1379,12 +1342,32 @@ int ngm_ipc_close(void* ptr) {
   const hipError_t e = hipIpcCloseMemHandle(ptr);
   return e == hipSuccess ? NGM_OK : hip_fail(e, "hipIpcCloseMemHandle");
 }
-int ngm_debug_last_stash_mode(void) { return g_last_stash_mode; }
+int ngm_debug_last_stash_mode(void) { return g_last_bwd.stash_kind ? g_last_bwd.half : -1; }
 int ngm_debug_stash_mode(int mode) {
   const int prev = g_stash_override;
   if (mode >= 0 && mode <= 1) g_stash_override = mode;
   else if (mode == -2) g_stash_override = -1;
   return prev;
+}
+
+int ngm_debug_plan_bwd(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg, int32_t F, int64_t n, int32_t guided,
+                       int32_t stash_offered, int32_t seeds_written, int32_t* out5) {
+  const int e = check_field_cfg(fcfg);
+  if (e) return e;
+  if (!out5 || F < 1 || n < 1 || (rcfg && n > INT32_MAX)) return fail(NGM_E_INVALID, "ngm_debug_plan_bwd: bad argument");
+  BwdPlan bp;
+  int fwd_matmul = -1;
+  if (rcfg) {
+    BwdAsk ask;
+    ask.seeds_written = seeds_written != 0;
+    const RenderPlan p = plan_render(fcfg, rcfg, F, (int)n, guided != 0, true, ask);
+    bp = p.bwd;
+    fwd_matmul = (p.b3 && rcfg->geometry_mode != NGM_GEO_NEUS) ? NGM_MATMUL_BF16X3 : NGM_MATMUL_F32;   // as render_fwd_impl resolves it
+  } else {
+    bp = plan_points(fcfg, F, n, stash_offered != 0);
+  }
+  out5[0] = bp.variant; out5[1] = bp.fused_comp; out5[2] = bp.stash_kind; out5[3] = bp.stash_layers; out5[4] = fwd_matmul;
+  return bp.status ? fail(bp.status, bp.why) : NGM_OK;
 }
 
 double ngm_peer_set_timeout(double seconds) { return ngm_peer_set_timeout_impl(seconds); }

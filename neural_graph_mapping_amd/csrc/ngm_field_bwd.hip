@@ -745,7 +745,7 @@ static int launch_bwd(const FieldBwdArgs& a, int blocks, hipStream_t st) {
 #define NGM_LB(NC, EG, HS, CT)                                                                                          \
   do {                                                                                                                  \
     const size_t lds = BwdLds<MI, MH, L, CT>::TOTAL * sizeof(float);                                                    \
-    if (lds > 160 * 1024) return NGM_E_UNSUPPORTED;                                                                      \
+    static_assert(BwdLds<MI, MH, L, CT>::TOTAL * sizeof(float) <= 160 * 1024, "k_field_bwd: LDS over 160 KiB");          \
     (void)hipFuncSetAttribute((const void*)k_field_bwd<MI, MH, L, NC, EG, HS, CT>, hipFuncAttributeMaxDynamicSharedMemorySize, \
                               (int)lds);                                                                                \
     hipLaunchKernelGGL((k_field_bwd<MI, MH, L, NC, EG, HS, CT>), dim3(blocks), dim3(NGM_BLOCK), lds, st, a);            \
@@ -753,9 +753,9 @@ static int launch_bwd(const FieldBwdArgs& a, int blocks, hipStream_t st) {
   const bool cat = a.fc.skip_mode == NGM_SKIP_CONCAT;      // every encoding (models.py:159-161 is encoding-agnostic)
   if (a.fc.encoding == NGM_ENC_PERMUTO) {
     if constexpr (MI == 1) { if (cat) NGM_LB(false, false, 1, true); else NGM_LB(false, false, 1, false); }
-    else return NGM_E_UNSUPPORTED;
+    else return NGM_E_INVALID;
   } else if (a.fc.encoding == NGM_ENC_TRIPLANE) {
-    if (!a.tri_acc) return NGM_E_UNSUPPORTED;
+    if (!a.tri_acc) return NGM_E_INVALID;
     if (cat) NGM_LB(false, false, 2, true); else NGM_LB(false, false, 2, false);
   } else if (a.fc.encoding == NGM_ENC_FOURIER) { if (cat) NGM_LB(false, true, 0, true); else NGM_LB(false, true, 0, false); }
   else if (a.fc.encoding == NGM_ENC_NERF) { if (cat) NGM_LB(true, false, 0, true); else NGM_LB(true, false, 0, false); }
@@ -777,16 +777,28 @@ int ngm_launch_tri_finish(const FieldBwdArgs& a, hipStream_t st) {
   return 0;
 }
 
+// the compiled (MI,MH,L) instances
+#ifdef NGM_FAST_BUILD
+#define NGM_BWD_INSTANCES(X) X(2, 2, 2)
+#else
+#define NGM_BWD_INSTANCES(X) X(2, 2, 2) X(2, 2, 1) X(1, 1, 1) X(1, 1, 2)
+#endif
+bool ngm_field_bwd_takes(const ngm_field_cfg& fc, const BwdProblem& q) {
+  const FieldShape s = field_shape(&fc);
+  if (q.half || q.fused_comp || (fc.encoding == NGM_ENC_PERMUTO && s.MI != 1)) return false;
+#define NGM_X(mi, mh, l) if (s.MI == mi && s.MH == mh && s.L == l) return true;
+  NGM_BWD_INSTANCES(NGM_X)
+#undef NGM_X
+  return false;
+}
 int ngm_launch_field_bwd(const FieldBwdArgs& a, int blocks, hipStream_t st) {
+  if (!ngm_field_bwd_takes(a.fc, bwd_problem(a))) return NGM_E_INVALID;
   NgmProfScope prof_(NGM_K_FIELD_BWD, st);
   const FieldShape s = field_shape(&a.fc);
-  if (s.MI == 2 && s.MH == 2 && s.L == 2) return launch_bwd<2, 2, 2>(a, blocks, st);
-#ifndef NGM_FAST_BUILD
-  if (s.MI == 2 && s.MH == 2 && s.L == 1) return launch_bwd<2, 2, 1>(a, blocks, st);
-  if (s.MI == 1 && s.MH == 1 && s.L == 1) return launch_bwd<1, 1, 1>(a, blocks, st);
-  if (s.MI == 1 && s.MH == 1 && s.L == 2) return launch_bwd<1, 1, 2>(a, blocks, st);
-#endif
-  return NGM_E_UNSUPPORTED;
+#define NGM_X(mi, mh, l) if (s.MI == mi && s.MH == mh && s.L == l) return launch_bwd<mi, mh, l>(a, blocks, st);
+  NGM_BWD_INSTANCES(NGM_X)
+#undef NGM_X
+  return NGM_E_INVALID;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -297,8 +297,8 @@ template <int TI, int TH, int L>
 static int launch_bwd16(const FieldBwdArgs& a, int blocks, hipStream_t st) {
   using LYH = Lds16<TI, TH, L>;
   constexpr int epi = LYH::WTOTAL + B16_WAVES * 4 * 4 * 64;    // epilogue staging (EPI_W per wave)
-  const size_t lds = (size_t)(LYH::TOTAL > epi ? LYH::TOTAL : epi) * sizeof(float);
-  if (lds > 160 * 1024) return NGM_E_UNSUPPORTED;
+  constexpr size_t lds = (size_t)(LYH::TOTAL > epi ? LYH::TOTAL : epi) * sizeof(float);
+  static_assert(lds <= 160 * 1024, "k_field_bwd16: LDS over 160 KiB");
 #define NGM_LB16(NC, EG, HS)                                                                                                \
   do {                                                                                                                      \
     (void)hipFuncSetAttribute((const void*)k_field_bwd16<TI, TH, L, NC, EG, HS>, hipFuncAttributeMaxDynamicSharedMemorySize, \
@@ -307,7 +307,7 @@ static int launch_bwd16(const FieldBwdArgs& a, int blocks, hipStream_t st) {
   } while (0)
   if (a.fc.encoding == NGM_ENC_PERMUTO) {
     if constexpr (TI <= 2) NGM_LB16(false, false, true);
-    else return NGM_E_UNSUPPORTED;
+    else return NGM_E_INVALID;
   } else if (a.fc.encoding == NGM_ENC_FOURIER) NGM_LB16(false, true, false);
   else if (a.fc.encoding == NGM_ENC_NERF) NGM_LB16(true, false, false);
   else NGM_LB16(false, false, false);
@@ -315,24 +315,28 @@ static int launch_bwd16(const FieldBwdArgs& a, int blocks, hipStream_t st) {
   return 0;
 }
 
-// returns NGM_E_UNSUPPORTED when no 16-wide instantiation exists (caller falls back to k_field_bwd)
+// the compiled (TI,TH,L) instances
+#ifdef NGM_FAST_BUILD
+#define NGM_BWD16_INSTANCES(X) X(4, 4, 2)
+#else
+#define NGM_BWD16_INSTANCES(X) X(4, 4, 2) X(4, 4, 1) X(2, 2, 1) X(2, 2, 2) X(3, 3, 1)
+#endif
+bool ngm_field_bwd16_takes(const ngm_field_cfg& fc, const BwdProblem& q) {
+  const int TI = (fc.dim_enc + 15) / 16, TH = (fc.dim_hidden + 15) / 16, L = fc.num_layers;
+  // skip connections and the triplane taps: 32-sample-tile kernel
+  if (q.half || q.fused_comp || fc.skip_mode != NGM_SKIP_NO || fc.encoding == NGM_ENC_TRIPLANE || (fc.encoding == NGM_ENC_PERMUTO && TI > 2))
+    return false;
+#define NGM_X(ti, th, l) if (TI == ti && TH == th && L == l) return true;
+  NGM_BWD16_INSTANCES(NGM_X)
+#undef NGM_X
+  return false;
+}
 int ngm_launch_field_bwd16(const FieldBwdArgs& a, int blocks, hipStream_t st) {
   const int TI = (a.fc.dim_enc + 15) / 16, TH = (a.fc.dim_hidden + 15) / 16, L = a.fc.num_layers;
-  const bool hash_ok = a.fc.encoding != NGM_ENC_PERMUTO || TI <= 2;
-#ifdef NGM_FAST_BUILD
-  const bool have = (TI == 4 && TH == 4 && L == 2);
-#else
-  const bool have = (TI == 4 && TH == 4 && (L == 1 || L == 2)) || (TI == 2 && TH == 2 && (L == 1 || L == 2)) ||
-                    (TI == 3 && TH == 3 && L == 1);
-#endif
-  if (!have || !hash_ok || a.fc.skip_mode != NGM_SKIP_NO || a.fc.encoding == NGM_ENC_TRIPLANE) return NGM_E_UNSUPPORTED;   // skip connections: 32-sample-tile kernel
+  if (!ngm_field_bwd16_takes(a.fc, bwd_problem(a))) return NGM_E_INVALID;
   NgmProfScope prof_(NGM_K_FIELD_BWD, st);
-  if (TI == 4 && TH == 4 && L == 2) return launch_bwd16<4, 4, 2>(a, blocks, st);
-#ifndef NGM_FAST_BUILD
-  if (TI == 4 && TH == 4 && L == 1) return launch_bwd16<4, 4, 1>(a, blocks, st);
-  if (TI == 2 && TH == 2 && L == 1) return launch_bwd16<2, 2, 1>(a, blocks, st);
-  if (TI == 2 && TH == 2 && L == 2) return launch_bwd16<2, 2, 2>(a, blocks, st);
-  if (TI == 3 && TH == 3 && L == 1) return launch_bwd16<3, 3, 1>(a, blocks, st);
-#endif
-  return NGM_E_UNSUPPORTED;
+#define NGM_X(ti, th, l) if (TI == ti && TH == th && L == l) return launch_bwd16<ti, th, l>(a, blocks, st);
+  NGM_BWD16_INSTANCES(NGM_X)
+#undef NGM_X
+  return NGM_E_INVALID;
 }

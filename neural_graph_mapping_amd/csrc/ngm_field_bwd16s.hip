@@ -419,7 +419,7 @@ __global__ __launch_bounds__(B16_THREADS) void k_field_bwd16s(FieldBwdArgs a) {
 template <int L>
 static int launch_bwd16s(const FieldBwdArgs& a, int blocks, hipStream_t st) {
   const size_t lds = (size_t)Lds16s<L>::TOTAL * sizeof(float);
-  if (lds > 160 * 1024) return NGM_E_UNSUPPORTED;
+  static_assert(Lds16s<L>::TOTAL * sizeof(float) <= 160 * 1024, "k_field_bwd16s: LDS over 160 KiB");
 #define NGM_LB16S(NC, EG)                                                                                             \
   do {                                                                                                                \
     (void)hipFuncSetAttribute((const void*)k_field_bwd16s<L, NC, EG>, hipFuncAttributeMaxDynamicSharedMemorySize,     \
@@ -433,15 +433,21 @@ static int launch_bwd16s(const FieldBwdArgs& a, int blocks, hipStream_t st) {
   return 0;
 }
 
-// returns NGM_E_UNSUPPORTED when the stash variant does not apply (caller falls back to the recompute kernels)
-int ngm_launch_field_bwd16s(const FieldBwdArgs& a, int blocks, hipStream_t st) {
-  const int TI = (a.fc.dim_enc + 15) / 16, TH = (a.fc.dim_hidden + 15) / 16, L = a.fc.num_layers;
-  if (!a.act || a.points || a.fc.skip_mode != NGM_SKIP_NO || a.fc.encoding == NGM_ENC_PERMUTO || a.fc.encoding == NGM_ENC_TRIPLANE || TI != 4 || TH != 4 || L < 1 || L > 2) return NGM_E_UNSUPPORTED;
-  if ((a.P + 64) * 256 >= ((int64_t)1 << 32)) return NGM_E_UNSUPPORTED;   // 32-bit byte offsets inside a field
-  NgmProfScope prof_(NGM_K_FIELD_BWD, st);
-  if (L == 2) return launch_bwd16s<2>(a, blocks, st);
-#ifndef NGM_FAST_BUILD
-  if (L == 1) return launch_bwd16s<1>(a, blocks, st);
+bool ngm_field_bwd16s_takes(const ngm_field_cfg& fc, const BwdProblem& q) {
+  const int TI = (fc.dim_enc + 15) / 16, TH = (fc.dim_hidden + 15) / 16, L = fc.num_layers;
+  if (q.stash_kind != 1 || q.half || q.fused_comp || q.points || fc.skip_mode != NGM_SKIP_NO || fc.encoding == NGM_ENC_PERMUTO || fc.encoding == NGM_ENC_TRIPLANE || TI != 4 || TH != 4) return false;
+  if ((q.P + 64) * 256 >= ((int64_t)1 << 32)) return false;   // 32-bit byte offsets inside a field
+#ifdef NGM_FAST_BUILD
+  if (L != 2) return false;
 #endif
-  return NGM_E_UNSUPPORTED;
+  return L >= 1 && L <= 2;
+}
+int ngm_launch_field_bwd16s(const FieldBwdArgs& a, int blocks, hipStream_t st) {
+  if (!ngm_field_bwd16s_takes(a.fc, bwd_problem(a))) return NGM_E_INVALID;
+  NgmProfScope prof_(NGM_K_FIELD_BWD, st);
+  if (a.fc.num_layers == 2) return launch_bwd16s<2>(a, blocks, st);
+#ifndef NGM_FAST_BUILD
+  if (a.fc.num_layers == 1) return launch_bwd16s<1>(a, blocks, st);
+#endif
+  return NGM_E_INVALID;
 }

@@ -904,27 +904,25 @@ static int launch_bwd_b3(const FieldBwdArgs& a, int blocks, hipStream_t st) {
   return 0;
 }
 
-bool ngm_field_bwd_b3_applies(const FieldBwdArgs& a) {
-  const int MI = (a.fc.dim_enc + 31) / 32, MH = (a.fc.dim_hidden + 31) / 32, L = a.fc.num_layers;
-  if (!a.act || (a.points && (a.fused_comp || a.act_half)) || a.fc.skip_mode != NGM_SKIP_NO || a.fc.matmul_mode == NGM_MATMUL_F32 || MI != 2 || MH != 2 || L < 1 || L > 2)
+bool ngm_field_bwd_b3_takes(const ngm_field_cfg& fc, const BwdProblem& q) {
+  const int MI = (fc.dim_enc + 31) / 32, MH = (fc.dim_hidden + 31) / 32, L = fc.num_layers;
+  if (q.stash_kind != 1 || (q.points && (q.fused_comp || q.half)) || fc.skip_mode != NGM_SKIP_NO || fc.matmul_mode == NGM_MATMUL_F32 || MI != 2 || MH != 2 || L < 1 || L > 2)
     return false;
-  if (a.fc.encoding != NGM_ENC_FOURIER && a.fc.encoding != NGM_ENC_NERF && a.fc.encoding != NGM_ENC_NONE) return false;
-  if ((a.P + 64) * 256 >= ((int64_t)1 << 32)) return false;   // 32-bit byte offsets inside a field
+  if (fc.encoding != NGM_ENC_FOURIER && fc.encoding != NGM_ENC_NERF && fc.encoding != NGM_ENC_NONE) return false;
+  if ((q.P + 64) * 256 >= ((int64_t)1 << 32)) return false;   // 32-bit byte offsets inside a field
+  if (q.half && L != 2) return false;                         // the half stash is layer 0 of two
+  if (q.fused_comp && q.per_block % (B3B_WAVES * 32)) return false;   // whole 32-sample tiles per wave
 #ifdef NGM_FAST_BUILD
   if (L != 2) return false;
 #endif
   return true;
 }
-// returns NGM_E_UNSUPPORTED when this variant does not apply (caller falls back to the fp32-MFMA kernels)
 int ngm_launch_field_bwd_b3(const FieldBwdArgs& a, int blocks, hipStream_t st) {
-  const int L = a.fc.num_layers;
-  if (!ngm_field_bwd_b3_applies(a)) return NGM_E_UNSUPPORTED;
-  if (a.fused_comp && (a.per_block % (B3B_WAVES * 32) || !a.rayseed)) return NGM_E_INVALID;
+  if (!ngm_field_bwd_b3_takes(a.fc, bwd_problem(a)) || (a.fused_comp && !a.rayseed)) return NGM_E_INVALID;
   NgmProfScope prof_(NGM_K_FIELD_BWD, st);
-  if (a.act_half && L != 2) return NGM_E_INVALID;
-  if (L == 2) return a.act_half ? launch_bwd_b3<2, true>(a, blocks, st) : launch_bwd_b3<2, false>(a, blocks, st);
+  if (a.fc.num_layers == 2) return a.act_half ? launch_bwd_b3<2, true>(a, blocks, st) : launch_bwd_b3<2, false>(a, blocks, st);
 #ifndef NGM_FAST_BUILD
-  if (L == 1) return launch_bwd_b3<1, false>(a, blocks, st);
+  if (a.fc.num_layers == 1) return launch_bwd_b3<1, false>(a, blocks, st);
 #endif
-  return NGM_E_UNSUPPORTED;
+  return NGM_E_INVALID;
 }

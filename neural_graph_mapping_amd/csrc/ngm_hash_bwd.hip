@@ -476,18 +476,18 @@ __global__ __launch_bounds__(HB_THREADS) void k_hash_mlp_bwd(FieldBwdArgs a) {
   }
 }
 
-bool ngm_hash_mlp_bwd_applies(const FieldBwdArgs& a) {
-  if (a.fc.encoding != NGM_ENC_PERMUTO || !a.act || a.points || !a.raytab || !a.stashB || a.fc.skip_mode != NGM_SKIP_NO ||
-      a.fc.matmul_mode == NGM_MATMUL_F32 || a.fc.num_layers != 1 || a.fc.dim_enc > 32 || a.fc.dim_hidden > 32 || a.fc.dim_enc <= 16 ||
-      a.fc.dim_out != 4 || !a.hash_dE)
+bool ngm_hash_mlp_bwd_takes(const ngm_field_cfg& fc, const BwdProblem& q) {
+  if (fc.encoding != NGM_ENC_PERMUTO || q.stash_kind != 2 || q.points || fc.skip_mode != NGM_SKIP_NO ||
+      fc.matmul_mode == NGM_MATMUL_F32 || fc.num_layers != 1 || fc.dim_enc > 32 || fc.dim_hidden > 32 || fc.dim_enc <= 16 ||
+      fc.dim_out != 4)
     return false;
-  // fused compositing: the loss seeds, and whole 32-sample tiles per wave; else the positions from k_stash_bwd
-  if (a.fused_comp ? (!a.rayseed || !a.hash_xyz || a.per_block % (HB_WAVES * 32)) : !a.hash_xyz_ready) return false;
-  return (a.P + 64) * 128 < ((int64_t)1 << 32);     // 32-bit byte offsets inside a field
+  if (q.fused_comp && q.per_block % (HB_WAVES * 32)) return false;   // fused compositing: whole 32-sample tiles per wave
+  return (q.P + 64) * 128 < ((int64_t)1 << 32);     // 32-bit byte offsets inside a field
 }
-// returns NGM_E_UNSUPPORTED when this kernel does not apply (caller falls back to k_field_bwd16)
 int ngm_launch_hash_mlp_bwd(const FieldBwdArgs& a, int blocks, hipStream_t st) {
-  if (!ngm_hash_mlp_bwd_applies(a)) return NGM_E_UNSUPPORTED;
+  if (!ngm_hash_mlp_bwd_takes(a.fc, bwd_problem(a)) || !a.raytab || !a.stashB || !a.hash_dE) return NGM_E_INVALID;
+  // fused compositing: the loss seeds and room for the positions; else the positions from k_stash_bwd
+  if (a.fused_comp ? (!a.rayseed || !a.hash_xyz) : !a.hash_xyz_ready) return NGM_E_INVALID;
   NgmProfScope prof_(NGM_K_FIELD_BWD, st);
   const size_t lds = (size_t)LdsHB::TOTAL * sizeof(float);
   if (a.fused_comp) {

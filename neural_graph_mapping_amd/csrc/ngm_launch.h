@@ -115,8 +115,24 @@ struct FieldBwdArgs {
   float* sums_out; float* loss_out; unsigned long long* counter;   // as StashBwdArgs
   const int32_t* num_active;          // counted step: device count of active rows (NULL: all F)
 };
-bool ngm_field_bwd_b3_applies(const FieldBwdArgs& a);   // would ngm_launch_field_bwd_b3 take this problem
-bool ngm_hash_mlp_bwd_applies(const FieldBwdArgs& a);   // would ngm_launch_hash_mlp_bwd take this problem
+// The MLP backward problem as plain values: what plan_mlp_bwd (ngm_api.hip) knows before anything is carved or launched
+struct BwdProblem {
+  bool points;                   // point mode (explicit points), else ray mode
+  int64_t P, per_block;          // samples per field / per workgroup
+  int stash_kind;                // what the forward left: 0 nothing, 1 hidden activations, 2 the hash encoding
+  bool half, fused_comp;         // kind 1: layer 0 of two only; the compositing backward rides inside the kernel
+};
+static inline BwdProblem bwd_problem(const FieldBwdArgs& a) {
+  return {a.points != nullptr, a.P, a.per_block, a.act ? (a.fc.encoding == NGM_ENC_PERMUTO ? 2 : 1) : 0, a.act_half != 0, a.fused_comp != 0};
+}
+// One predicate per backward kernel, beside its launcher: a compiled instance takes this configuration and problem (NGM_FAST_BUILD
+// included; that every instance fits the 160 KiB of LDS is a static_assert beside its launch).  plan_mlp_bwd walks them; a launcher
+// handed a problem its predicate rejects returns NGM_E_INVALID.
+bool ngm_field_bwd_b3_takes(const ngm_field_cfg& fc, const BwdProblem& q);   // variant 3
+bool ngm_hash_mlp_bwd_takes(const ngm_field_cfg& fc, const BwdProblem& q);   // variant 5
+bool ngm_field_bwd16s_takes(const ngm_field_cfg& fc, const BwdProblem& q);   // variant 2
+bool ngm_field_bwd16_takes(const ngm_field_cfg& fc, const BwdProblem& q);    // variant 1
+bool ngm_field_bwd_takes(const ngm_field_cfg& fc, const BwdProblem& q);      // variant 0
 struct GradReduceArgs;
 // mlp_reduce (optional): the MLP's gradient reduction (+ Adam) to run as extra workgroups of the same launch; *mlp_reduced tells
 // the caller that it did (no ngm_launch_grad_reduce needed then)
@@ -207,7 +223,7 @@ int ngm_launch_tri_finish(const FieldBwdArgs& a, hipStream_t st);
 int ngm_launch_field_bwd_b3(const FieldBwdArgs& a, int blocks, hipStream_t st);   // 32-sample tiles on the bf16 matrix pipe (three-way split), activation stash
 int ngm_launch_hash_mlp_bwd(const FieldBwdArgs& a, int blocks, hipStream_t st);          // hash encoding + 1 x 32 MLP (the reference's default network), bf16 split, encoding stash
 int ngm_launch_field_bwd16s(const FieldBwdArgs& a, int blocks, hipStream_t st);  // 16-sample tiles, activations from the forward's stash
-int ngm_launch_field_bwd16(const FieldBwdArgs& a, int blocks, hipStream_t st);   // 16-sample tiles, 8 waves; NGM_E_UNSUPPORTED -> fall back
+int ngm_launch_field_bwd16(const FieldBwdArgs& a, int blocks, hipStream_t st);   // 16-sample tiles, 8 waves, forward recompute
 int ngm_launch_grad_reduce(const GradReduceArgs& a, hipStream_t st);
 int ngm_launch_composite_fwd(const CompositeArgs& a, hipStream_t st);
 int ngm_launch_composite_bwd(const CompositeArgs& a, hipStream_t st);

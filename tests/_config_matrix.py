@@ -16,7 +16,8 @@ Outcomes, per mode ("f32", "auto"; "bf16x3" where the entry is about the explici
                     ops.FIELD_EVAL_STASH_MAX_BYTES = 0
   step(mm, v, fc)   fused step: arithmetic of the forward, backward variant, ngm_debug_last_comp_fused
 
-The kernels named here were read off the dispatchers, with TI / TH = ceil(dim / 16) and MI / MH = ceil(dim / 32):
+The forward kernels named here were read off the shape dispatch, the backward ones off plan_mlp_bwd (csrc/ngm_api.hip; the
+library answers for it without a GPU: ngm_debug_plan_bwd), with TI / TH = ceil(dim / 16) and MI / MH = ceil(dim / 32):
   forward shape <MI,MH,L>     NGM_SHAPE_DISPATCH (ngm_field_fwd.hip), launch_eval's caller (ngm_knn.hip): <2,2,2> <2,2,1> <1,1,1>
                               <1,1,2> <2,2,3>; bf16x3 only at <2,2,L<=2>, Fourier / none, skip no (points / knn: a preference;
                               fused forward: `auto` resolves to it, explicit `bf16x3` elsewhere is refused)

@@ -104,3 +104,46 @@ def test_validator_refuses_exactly_what_no_kernel_takes(lib, name):
         assert "num_layers" in msg and "kernel" in msg
     else:
         assert ws > 0
+
+
+def _plan(lib, fc, rc, F, n, stash_offered=0):
+    """ngm_debug_plan_bwd: (status, variant, comp_fused, stash kind, stash layers, forward arithmetic); guided rays, seeds written
+    for the backward's targets -- what the fused step of the matrix does"""
+    out = (C.c_int32 * 5)()
+    status = lib.ngm_debug_plan_bwd(C.byref(fc), None if rc is None else C.byref(rc), F, n, 1, stash_offered, 1, out)
+    return (status,) + tuple(out)
+
+
+def test_plan_query_reproduces_the_step_and_autograd_columns(lib):
+    """The backward plan (plan_mlp_bwd behind ngm_debug_plan_bwd: no launch, no GPU) against every (entry, mode) cell of the
+    `step` and `autograd` columns: forward arithmetic, backward variant and fusion flag at both STEP_SHAPES; the point
+    evaluation's variant at P = 257 with a stash offered and without; three-layer entries refused with NGM_E_UNSUPPORTED.
+    Left out: the cells whose refusal is the forward launcher's (explicit bf16x3 outside its shape), not the plan's."""
+    arithmetic = {K.MATMUL["f32"]: "f32", K.MATMUL["bf16x3"]: "bf16x3"}
+    skipped = set()
+    for e in CM.ENTRIES:
+        if e["shape"] is None:
+            continue
+        for mode, o in e["step"].items():
+            fc = K.field_cfg(**e["fkw"], matmul_mode=mode)
+            for F, R, n_c, n_g in CM.STEP_SHAPES:
+                rc = K.render_cfg(geometry_mode=e["geometry"], num_samples_coarse=n_c, num_samples_guided=n_g)
+                status, variant, fused, kind, layers, mm = _plan(lib, fc, rc, F, R)
+                if o == CM.REFUSE and fc.num_layers <= 2:
+                    skipped.add((e["name"], mode))
+                elif o == CM.REFUSE:
+                    assert status == K.NGM_E_UNSUPPORTED and "forward only" in lib.ngm_last_error().decode(), (e["name"], mode)
+                else:
+                    assert status == K.NGM_OK and (arithmetic[mm], variant, fused) == o[1:], (e["name"], mode, (F, R))
+                    assert (variant not in (2, 3, 5) or kind == (2 if variant == 5 else 1)) and (layers > 0) == (kind != 0)
+        for mode, o in e["autograd"].items():
+            fc = K.field_cfg(**e["fkw"], matmul_mode=mode)
+            got = [_plan(lib, fc, None, 3, 257, stash_offered=s) for s in (1, 0)]
+            if o == CM.REFUSE:
+                assert fc.num_layers == 3 and [g[0] for g in got] == [K.NGM_E_UNSUPPORTED] * 2, (e["name"], mode)
+            else:
+                assert [g[:2] for g in got] == [(K.NGM_OK, o[1]), (K.NGM_OK, o[2])], (e["name"], mode)
+                assert [g[3] for g in got] == [int(o[1] == 3), 0] and all(g[2] == 0 for g in got)    # only k_field_bwd_b3 reads a stash
+    forward_refusals = {(e["name"], mode) for e in CM.ENTRIES if e["shape"] is not None for mode, o in e["render"].items()
+                        if o == CM.REFUSE and e["fkw"]["num_layers"] <= 2}
+    assert skipped == forward_refusals and len(skipped) <= 2

@@ -453,6 +453,50 @@ def test_stash_modes_bitwise_deterministic_and_close_to_full():
             assert torch.equal(g0[k], full[k]), k
 
 
+def test_backward_the_plan_refuses_launches_nothing():
+    """A forward that wrote a half stash, then a backward whose configuration says f32: no kernel reads a half stash in fp32
+    MFMA, so the backward plan refuses (NGM_E_INVALID) -- before k_stash_bwd, which would have overwritten the forward's stash
+    and advanced the device counter.  Workspace, counters, parameters, moments and the gradient arena keep their bits, and
+    the renderer's next iteration is that of a renderer which never saw the refusal.  (2, 33, 1, 1): one ragged tile per field."""
+    F, R = 2, 33
+    pos, quat, t = synth_target(F, R, seed=5)
+    ckw = dict(num_samples_coarse=1, num_samples_depth_guided=1, termination_weight=0.3, activation_stash="half", mlp_matmul="auto")
+    r, ref = make_renderer(FOURIER, ckw, F), make_renderer(FOURIER, ckw, F)
+    _perturb(r)
+    for k, v in r._model.all_fields_params.items():
+        ref._model.all_fields_params[k].copy_(v)
+    tgt = make_target(t, torch.arange(F))
+    for x in (r, ref):
+        x.set_field_poses(pos.to(DEV), quat.to(DEV))
+        x.optimization_iteration(tgt, seed=9, update=False)              # workspace, gradient arena and moments exist from here on
+    assert K.lib().ngm_debug_last_bwd_variant() == 3 and K.lib().ngm_debug_last_stash_mode() == 1
+    ctx = r._iteration_forward(tgt, seed=9)
+    w = ctx["w"]
+
+    def state():
+        torch.cuda.synchronize()
+        s = dict(ws=w["ws"], step_dev=r._step_dev, gflat=w["gflat"], **{"p." + k: v for k, v in r._model.all_fields_params.items()})
+        for k, st in r._optim_state.items():
+            s["m." + k], s["v." + k] = st["exp_avg"], st["exp_avg_sq"]
+        return {k: v.clone() for k, v in s.items()}, r._step
+
+    before, step = state()
+    fc32 = K.FieldCfg.from_buffer_copy(ctx["fc"])
+    fc32.matmul_mode = K.MATMUL["f32"]
+    with pytest.raises(K.NgmError) as ex:
+        r._iteration_backward(dict(ctx, fc=fc32), update=True)
+    assert ex.value.code == K.NGM_E_INVALID
+    after, step_after = state()
+    assert step_after == step
+    for k in before:
+        assert torch.equal(after[k], before[k]), k
+    got = r.optimization_iteration(tgt, seed=9, update=False)["grads"]
+    want = ref.optimization_iteration(tgt, seed=9, update=False)["grads"]
+    assert set(got) == set(want)
+    for k in want:
+        assert torch.equal(got[k], want[k]), k
+
+
 @pytest.mark.parametrize("num_knn,S", [(6, 64), (8, 640), (5, 40), (10, 64), (16, 40)])
 def test_image_path_with_more_than_four_neighbours(num_knn, S):
     """K = 5..8: assignment, evaluation and -- since the end of round 5 -- the blend inside the one-call image path's quadrature
