@@ -679,6 +679,15 @@ int ngm_debug_last_stash_mode(void);   /* the stash the last MLP backward actual
  * message in ngm_last_error) where the backward would refuse. */
 int ngm_debug_plan_bwd(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg, int32_t F, int64_t n, int32_t guided,
                        int32_t stash_offered, int32_t seeds_written, int32_t* out5);
+/* Debug: the forward plan of a call with these arguments, without launching anything (no GPU needed; 256 compute units are
+ * assumed without one).  surface 0: the fused render forward on F fields x n rays (rcfg required; guided: the rays carry gt
+ * distances), 1: the point evaluation on F x n points, 2: the kNN evaluation (rcfg NULL for both).  out12 = compiled shape MI, MH, L,
+ * arithmetic (NGM_MATMUL_F32 / NGM_MATMUL_BF16X3), one-tile wave step, waves per workgroup, dynamic LDS bytes, the neus instance,
+ * threads per workgroup, rays per workgroup, samples buffered per wave, workgroups.  Returns the plan's refusal (NGM_E_UNSUPPORTED,
+ * message in ngm_last_error) where the forward would refuse: no compiled instance, or an explicit NGM_MATMUL_BF16X3 outside the
+ * split path's shape in the fused render forward. */
+int ngm_debug_plan_fwd(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg, int32_t surface, int32_t F, int64_t n, int32_t guided,
+                       int32_t* out12);
 
 /* ---- one-shot exchange of the loss sums between the ranks of one node ---------------
  * Replaces torch.distributed.all_reduce (RCCL) on the 16 floats between ngm_render_fwd and ngm_render_bwd* by ONE small

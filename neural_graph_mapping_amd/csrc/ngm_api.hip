@@ -30,13 +30,13 @@ int ngm_launch_mc_emit(const float* vol, int nx, int ny, int nz, float iso, floa
 int ngm_mc_copy_tables(int8_t* tri_table, int32_t* tri_count);
 int ngm_launch_knn(const ngm_field_cfg* fc, const ngm_params* pr, int num_fields, int64_t P, const float* points,
                    const float* pos, const float* quat, int K, float distance_factor, float outside_value, float mask_radius,
-                   float* out, void* workspace, int64_t workspace_bytes, hipStream_t st);
+                   float* out, void* workspace, int64_t workspace_bytes, const FwdPlan& plan, hipStream_t st);
 int64_t ngm_knn_workspace_bytes(int num_fields, int64_t P, int K);
 int64_t ngm_knn_render_workspace_bytes(int num_fields, int ray_block, int S, int K);
 int ngm_launch_render_eval_knn(const ngm_field_cfg* fc, const ngm_render_cfg* rc, const ngm_params* pr, int num_fields,
                                const float* pos, const float* quat, const ngm_rays* rays, int K, float distance_factor,
                                float outside_value, float mask_radius, int ray_block, const ngm_prediction* pred,
-                               void* workspace, int64_t workspace_bytes, hipStream_t st);
+                               void* workspace, int64_t workspace_bytes, const FwdPlan& plan, hipStream_t st);
 
 #include <mutex>
 #include <unordered_map>
@@ -96,8 +96,6 @@ static int fail(int code, const char* msg) {
 }
 #define NGM_FWD_DEBUG_WORDS (16 + 8 * 64)   // 16 summary slots + 8 waves x 64 timeline entries
 static unsigned long long* g_debug_cycles = nullptr;
-int g_ngm_last_matmul[3] = {-1, -1, -1};   // ngm_launch.h
-int g_ngm_last_fwd_one_tile = 0;
 static int g_no_fused_comp = 0;       // ngm_debug_disable_fused_comp
 static int g_stash_override = -1;     // ngm_debug_stash_mode
 // Which targets the LAST forward on a workspace wrote its per-ray loss seeds for (host-side bookkeeping by pointer identity:
@@ -154,13 +152,106 @@ static int num_cus() {
   return cached;
 }
 static inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
-// floats of LDS taken by one field's weights (mirrors FieldLds<MI,MH,L>::TOTAL in ngm_field.h)
-static int64_t field_lds_floats(const ngm_field_cfg* fc) {
-  const int64_t MI = (fc->dim_enc + 31) / 32, MH = (fc->dim_hidden + 31) / 32;
-  const int64_t MC = MH + (fc->skip_mode == NGM_SKIP_CONCAT ? MI : 0);      // input tiles of layers >= 1 and of the output layer
-  int64_t t = MI * 32 * 4;
-  for (int l = 0; l < fc->num_layers; ++l) t += MH * (l == 0 ? MI : MC) * 16 * 2 * 33 + MH * 32;
-  return t + MC * 32 * 4 + 8;
+// ---- the forward plan ----------------------------------------------------------------------------------------------------------
+// Which forward instance a call runs -- shape, arithmetic, wave step -- and how it is launched: plan_fwd fills one FwdPlan
+// (ngm_launch.h) from plain values, before anything is carved or launched; the launchers switch on it.
+struct FwdAsk {
+  int surface = NGM_FWD_RENDER;         // NGM_FWD_RENDER / NGM_FWD_POINTS / NGM_FWD_KNN
+  const ngm_render_cfg* rc = nullptr;   // fused render: geometry mode
+  int F = 1;
+  int64_t n = 0;                        // fused render: rays per field; point evaluation: points per field
+  int S = 0;                            // fused render: samples per ray
+  bool counted = false;                 // fused render: the call carries a device count of active rows
+};
+static const char* const no_instance = "forward: the launcher does not take the planned instance (internal error)";
+static FwdPlan g_last_fwd[3];           // per surface, the last plan that launched (ngm_debug_last_matmul / _fwd_one_tile)
+// The only reader of NGM_NO_HALF_STEP (developer A/B switch: never the one-tile wave step).  A refused fused-render plan still
+// carries the launch shape the workspace is sized by.
+static FwdPlan plan_fwd(const ngm_field_cfg* fc, const FwdAsk& q) {
+  static const bool no_half = getenv("NGM_NO_HALF_STEP") != nullptr;
+  static thread_local char why[256];
+  FwdPlan p;
+  p.surface = q.surface;
+  p.MI = (fc->dim_enc + 31) / 32; p.MH = (fc->dim_hidden + 31) / 32; p.L = fc->num_layers;
+  p.need_cos = fc->encoding == NGM_ENC_NERF;
+  p.hash = fc->encoding == NGM_ENC_PERMUTO ? 1 : fc->encoding == NGM_ENC_TRIPLANE ? 2 : 0;
+  p.skip = fc->skip_mode;
+  const int ncu = num_cus();
+  const bool neus = q.rc && q.rc->geometry_mode == NGM_GEO_NEUS;
+  p.counted = q.counted;
+  p.neus = neus;
+  const char* const no_kernel = "no forward kernel for this (D,H,L)";
+  auto finish = [&](bool b3, const char* refusal) {
+    p.matmul = b3 ? NGM_MATMUL_BF16X3 : NGM_MATMUL_F32;
+    p.threads = 64 * p.waves;
+    if (!refusal && p.lds_bytes > NGM_LDS_MAX) refusal = "the forward's weights and sample planes do not fit the LDS";
+    if (refusal) { p.status = NGM_E_UNSUPPORTED; p.why = refusal; }
+    return p;
+  };
+  if (q.surface != NGM_FWD_RENDER) {     // the evaluations: the mode is a preference (fp32 MFMA where the split is not compiled)
+    const bool points = q.surface == NGM_FWD_POINTS;
+    const bool b3 = fc->matmul_mode != NGM_MATMUL_F32 && (points ? ngm_points_fwd_takes(*fc, true) : ngm_knn_eval_takes(*fc, true));
+    p.waves = b3 ? 8 : NGM_WAVES_PER_BLOCK;
+    p.lds_bytes = ngm_fwd_lds_bytes(*fc, b3, 0, 0);
+    if (points) {
+      int64_t bpf = (ncu + q.F - 1) / q.F;                     // workgroups per field
+      p.per_block = align_up((q.n + bpf - 1) / bpf, NGM_BLOCK);
+      bpf = (q.n + p.per_block - 1) / p.per_block;
+      p.blocks = (int)(bpf * q.F);
+    } else {
+      p.blocks = (b3 ? 1 : 4) * ncu;
+    }
+    return finish(b3, (points ? ngm_points_fwd_takes(*fc, false) : ngm_knn_eval_takes(*fc, false)) ? nullptr : no_kernel);
+  }
+  // fused render: one workgroup per CU-slot; 8 waves (2 per SIMD: latency hiding) unless the per-wave LDS sample planes would
+  // not fit, then 4 waves
+  const int F = q.F, R = (int)q.n;
+  auto shape = [&](int waves, bool planes, int64_t maxs_cap = 1024) {
+    int ch = (ncu + F - 1) / F;
+    const int max_ch = (R + waves - 1) / waves;
+    if (ch > max_ch) ch = max_ch;
+    if (ch < 1) ch = 1;
+    int rpb = (R + ch - 1) / ch;
+    rpb = (int)align_up(rpb, waves);
+    const int rpw = rpb / waves;
+    int64_t maxs = align_up((int64_t)(rpw < 32 ? rpw : 32) * q.S, 64);
+    if (maxs > maxs_cap) maxs = maxs_cap;                // samples a wave buffers per ray batch (whole rays)
+    if (maxs < align_up(q.S, 64)) maxs = align_up(q.S, 64);
+    p.rays_per_block = rpb; p.waves = waves; p.maxs = (int)maxs;
+    p.blocks = F * ((R + rpb - 1) / rpb);
+    p.lds_bytes = ngm_fwd_lds_bytes(*fc, planes, waves, p.maxs);
+    return p.lds_bytes <= NGM_LDS_MAX;
+  };
+  if (!shape(8, false) || R < 8) shape(4, false);        // exact-fp32 plan first: 8 waves unless its LDS does not fit
+  // a grid of 8-wave workgroups that leaves CUs idle (a rank with one or two active fields, DESIGN 5): 4 waves per
+  // workgroup on twice as many CUs -- one wave per SIMD runs a step in about half the time (F = 1: 29 -> 25.5 us, split path)
+  const bool few = R >= 8 && (int64_t)F * ((R + 7) / 8) < ncu;
+  // The split path's weight planes (48 KB for two 64-wide layers) compete with the per-wave sample planes for LDS: a
+  // batch of many samples per ray (8192 x 256: 1024 samples buffered per wave) leaves no room at 8 waves.  Smaller ray
+  // batches per wave do (one 256-sample ray at a time: 8.7 KB per wave), at no measurable cost -- tried in that order.
+  auto fit_b3 = [&]() {
+    for (int64_t cap : {(int64_t)1024, (int64_t)512, (int64_t)256})
+      if (shape(8, true, cap) && R >= 8) return true;
+    return shape(4, true);
+  };
+  bool b3 = false;
+  if (fc->matmul_mode == NGM_MATMUL_BF16X3) {           // explicit: whatever shape makes it fit, refused where it is not compiled
+    b3 = !neus;
+    (void)fit_b3();
+    if (!ngm_render_fwd_takes(*fc, neus, true)) {
+      snprintf(why, sizeof(why), "render_fwd: matmul_mode bf16x3 has no fused-forward instance for shape <%d,%d,%d> with this encoding, "
+               "skip mode and geometry mode (neus runs fp32 MFMA): use NGM_MATMUL_AUTO or NGM_MATMUL_F32", p.MI, p.MH, p.L);
+      return finish(b3, why);
+    }
+  } else if (fc->matmul_mode == NGM_MATMUL_AUTO && ngm_render_fwd_takes(*fc, neus, true)) {
+    const FwdPlan keep = p;
+    b3 = (few && shape(4, true)) || (fit_b3() && p.waves == 8);      // auto: the planes next to an 8-wave plan, else exact-fp32 MFMA
+    if (!b3) p = keep;
+  }
+  // every wave's batches hold at most 32 samples (rays per wave x samples per ray): the one-tile instance of the split path and
+  // of the hash encoding without skip connection
+  p.one_tile = !neus && !no_half && (int64_t)(p.rays_per_block / p.waves) * q.S <= 32 && (b3 || (p.hash == 1 && p.skip == NGM_SKIP_NO));
+  return finish(b3, ngm_render_fwd_takes(*fc, neus, b3) ? nullptr : no_kernel);
 }
 
 // ---- the MLP backward plan -----------------------------------------------------------------------------------------------------
@@ -444,8 +535,8 @@ int ngm_target_sv_rays(int32_t F, int32_t R, const float* field_pos_cam, float r
 }
 
 int ngm_debug_last_bwd_variant(void) { return g_last_bwd.variant; }
-int ngm_debug_last_matmul(int which) { return (which >= 0 && which < 3) ? g_ngm_last_matmul[which] : -1; }
-int ngm_debug_last_fwd_one_tile(void) { return g_ngm_last_fwd_one_tile; }
+int ngm_debug_last_matmul(int which) { return (which >= 0 && which < 3) ? g_last_fwd[which].matmul : -1; }
+int ngm_debug_last_fwd_one_tile(void) { return g_last_fwd[NGM_FWD_RENDER].one_tile; }
 int ngm_debug_last_comp_fused(void) { return g_last_bwd.fused_comp; }
 int ngm_debug_disable_fused_comp(int on) { const int old = g_no_fused_comp; g_no_fused_comp = on ? 1 : 0; return old; }
 
@@ -627,6 +718,10 @@ static int field_eval_fwd(const ngm_field_cfg* fcfg, const ngm_params* params, i
   if (!points || !out || F < 1 || P < 0) return fail(NGM_E_INVALID, "ngm_field_eval_fwd: bad argument");
   if ((field_pos == nullptr) != (field_quat == nullptr)) return fail(NGM_E_INVALID, "pos/quat must both be given");
   if (P == 0) return NGM_OK;
+  FwdAsk ask;
+  ask.surface = NGM_FWD_POINTS; ask.F = F; ask.n = P;
+  const FwdPlan plan = plan_fwd(fcfg, ask);
+  if (plan.status) return fail(plan.status, plan.why);
   PointsFwdArgs a;
   memset(&a, 0, sizeof(a));
   a.fc = *fcfg; a.pr = *params; a.F = F; a.P = P; a.points = points; a.pos = field_pos; a.quat = field_quat; a.out = out;
@@ -636,13 +731,10 @@ static int field_eval_fwd(const ngm_field_cfg* fcfg, const ngm_params* params, i
     if (!stash || stash_bytes < need) return fail(NGM_E_WORKSPACE, "ngm_field_eval_fwd_train: stash too small (ngm_field_eval_stash_bytes)");
     a.act = reinterpret_cast<float*>(align_up((int64_t)stash, 256)); a.act_layer_stride = field_eval_stash_stride(F, P);
   }
-  const int ncu = num_cus();
-  int64_t bpf = (ncu + F - 1) / F;                         // workgroups per field
-  int64_t per = align_up((P + bpf - 1) / bpf, NGM_BLOCK);
-  bpf = (P + per - 1) / per;
-  a.per_block = per;
-  rc = ngm_launch_points_fwd(a, (int)(bpf * F), (hipStream_t)stream);
-  if (rc) return fail(rc, "ngm_field_eval_fwd: no kernel for this (D,H,L)");
+  a.per_block = plan.per_block;
+  rc = ngm_launch_points_fwd(a, plan, (hipStream_t)stream);
+  if (rc) return fail(rc, no_instance);
+  g_last_fwd[NGM_FWD_POINTS] = plan;
   return check_launch("ngm_field_eval_fwd");
 }
 int ngm_field_eval_fwd(const ngm_field_cfg* fcfg, const ngm_params* params, int32_t F, int64_t P, const float* points,
@@ -758,7 +850,8 @@ int ngm_composite_bwd(const ngm_render_cfg* cfg, int64_t N, int32_t S, const flo
 // fused render / train step
 // ------------------------------------------------------------------------------------------------
 struct RenderPlan {
-  int S, rays_per_block, blocks_fwd, waves_fwd, maxs, b3;
+  int S;
+  FwdPlan fwd;                     // the fused forward: instance, launch shape, LDS
   BwdPlan bwd;                     // train: the MLP backward this workspace is carved for, and the stash the forward writes for it
   int64_t p_pad;
   int64_t off_rayseed;             // (F*R, 8) per-ray loss derivatives without the normalisers (fused compositing backward)
@@ -767,64 +860,12 @@ struct RenderPlan {
 };
 // ask: the backward's seed mode and the forward's per-workspace records (ngm_render_bwd*); the forward and the sizing leave it empty
 static RenderPlan plan_render(const ngm_field_cfg* fc, const ngm_render_cfg* rc, int F, int R, bool guided, bool train,
-                              BwdAsk ask = BwdAsk()) {
-  RenderPlan p;
-  memset(&p, 0, sizeof(p));
+                              BwdAsk ask = BwdAsk(), bool counted = false) {
+  RenderPlan p = RenderPlan();
   p.S = rc->num_samples_coarse + (guided ? rc->num_samples_guided : 0);
-  const int ncu = num_cus();
-  // forward: one workgroup per CU-slot; 8 waves (2 per SIMD: latency hiding) unless the per-wave LDS
-  // sample planes would not fit in 160 KiB, then 4 waves
-  // the bf16 weight planes of the split path (ngm_matmul_mode): 3 planes x 2 bytes per hidden weight
-  const int64_t MIp = (fc->dim_enc + 31) / 32, MHp = (fc->dim_hidden + 31) / 32;
-  const int64_t b3_bytes = 3 * 2 * 1024 * MHp * (MIp + (fc->num_layers - 1) * MHp);
-  const bool b3_compiled = MIp == 2 && MHp == 2 && fc->num_layers <= 2 && fc->skip_mode == NGM_SKIP_NO &&
-                           (fc->encoding == NGM_ENC_FOURIER || fc->encoding == NGM_ENC_NONE);
-  auto shape = [&](int waves, int64_t extra, int64_t* lds_out, int64_t maxs_cap = 1024) {
-    int ch = (ncu + F - 1) / F;
-    const int max_ch = (R + waves - 1) / waves;
-    if (ch > max_ch) ch = max_ch;
-    if (ch < 1) ch = 1;
-    int rpb = (R + ch - 1) / ch;
-    rpb = (int)align_up(rpb, waves);
-    const int rpw = rpb / waves;
-    int64_t maxs = align_up((int64_t)(rpw < 32 ? rpw : 32) * p.S, 64);
-    if (maxs > maxs_cap) maxs = maxs_cap;                // samples a wave buffers per ray batch (whole rays)
-    if (maxs < align_up(p.S, 64)) maxs = align_up(p.S, 64);
-    *lds_out = 4 * (field_lds_floats(fc) + (int64_t)waves * (32 * 28 + 5 * maxs)) + extra;
-    p.rays_per_block = rpb; p.waves_fwd = waves; p.maxs = (int)maxs;
-    p.blocks_fwd = F * ((R + rpb - 1) / rpb);
-  };
-  const int64_t LDS_MAX = 160 * 1024;
-  int64_t lds = 0;
-  shape(8, 0, &lds);                                    // exact-fp32 plan first: 8 waves unless its LDS does not fit
-  if (lds > LDS_MAX || R < 8) shape(4, 0, &lds);
-  // a grid of 8-wave workgroups that leaves CUs idle (a rank with one or two active fields, DESIGN 5): 4 waves per
-  // workgroup on twice as many CUs -- one wave per SIMD runs a step in about half the time (F = 1: 29 -> 25.5 us, split path)
-  const bool few = R >= 8 && (int64_t)F * ((R + 7) / 8) < ncu;
-  p.b3 = 0;
-  // The split path's weight planes (48 KB for two 64-wide layers) compete with the per-wave sample planes for LDS: a
-  // batch of many samples per ray (8192 x 256: 1024 samples buffered per wave) leaves no room at 8 waves.  Smaller ray
-  // batches per wave do (one 256-sample ray at a time: 8.7 KB per wave), at no measurable cost -- tried in that order.
-  auto fit_b3 = [&]() {
-    for (int64_t cap : {(int64_t)1024, (int64_t)512, (int64_t)256}) {
-      shape(8, b3_bytes, &lds, cap);
-      if (lds <= LDS_MAX && R >= 8) return true;
-    }
-    shape(4, b3_bytes, &lds);
-    return lds <= LDS_MAX;
-  };
-  if (fc->matmul_mode == NGM_MATMUL_BF16X3) {           // explicit: whatever shape makes it fit, else the launcher fails loudly
-    p.b3 = 1;
-    (void)fit_b3();
-  } else if (fc->matmul_mode == NGM_MATMUL_AUTO && b3_compiled && rc->geometry_mode != NGM_GEO_NEUS) {
-    const int64_t lds_f32 = lds;
-    const RenderPlan keep = p;
-    bool ok = false;
-    if (few) { shape(4, b3_bytes, &lds); ok = lds <= LDS_MAX; }
-    if (!ok) ok = fit_b3() && p.waves_fwd == 8;                       // auto: the planes next to an 8-wave plan, else exact-fp32 MFMA
-    if (ok) p.b3 = 1;
-    else { p = keep; lds = lds_f32; }
-  }
+  FwdAsk fq;
+  fq.rc = rc; fq.F = F; fq.n = R; fq.S = p.S; fq.counted = counted;
+  p.fwd = plan_fwd(fc, fq);
   p.p_pad = param_pad(fc);
   int64_t o = 0;
   if (train) {
@@ -833,7 +874,7 @@ static RenderPlan plan_render(const ngm_field_cfg* fc, const ngm_render_cfg* rc,
     p.off_rayseed = o; o = align_up(o + NR * 8 * 4, 256);
     p.off_stashA = o; o = align_up(o + NS * 16, 256);
     p.off_stashB = o; o = align_up(o + NS * 8, 256);
-    p.off_losspart = o; o = align_up(o + (int64_t)p.blocks_fwd * NGM_NUM_LOSS_SUMS * 4, 256);
+    p.off_losspart = o; o = align_up(o + (int64_t)p.fwd.blocks * NGM_NUM_LOSS_SUMS * 4, 256);
     if (rc->geometry_mode == NGM_GEO_NEUS) {
       p.off_dout = o; o = align_up(o + NS * 16, 256);
       p.off_disd = o; o = align_up(o + NR * 4, 256);
@@ -924,22 +965,19 @@ static int render_fwd_impl(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg
   if (has_tg && targets->term_mask && !targets->term_probs) return fail(NGM_E_INVALID, "render_fwd: term_mask without term_probs");
   if (has_tg && !save) return fail(NGM_E_WORKSPACE, "render_fwd: targets need a workspace");
   if (save && (!pred->rgbds || !pred->term_probs)) return fail(NGM_E_INVALID, "render_fwd(save): pred.rgbds/term_probs required");
-  const RenderPlan p = plan_render(fcfg, rcfg, rays->F, rays->R, rays->gt != nullptr, save);
+  const RenderPlan p = plan_render(fcfg, rcfg, rays->F, rays->R, rays->gt != nullptr, save, BwdAsk(), num_active != nullptr);
+  if (p.fwd.status) return fail(p.fwd.status, p.fwd.why);
   if (save && workspace_bytes < p.total) return fail(NGM_E_WORKSPACE, "render_fwd: workspace too small");
   char* ws = reinterpret_cast<char*>(align_up((int64_t)workspace, 256));
   RenderFwdArgs a;
   memset(&a, 0, sizeof(a));
   a.fc = *fcfg; a.pr = *params; a.rc = *rcfg; a.rays = *rays; a.pred = *pred;
-  a.fc.matmul_mode = p.b3 ? NGM_MATMUL_BF16X3 : NGM_MATMUL_F32;       // AUTO resolved by the plan (LDS budget of this batch shape)
-  if (rcfg->geometry_mode == NGM_GEO_NEUS) {                          // compiled with exact-fp32 MFMA
-    if (fcfg->matmul_mode == NGM_MATMUL_BF16X3) return fail(NGM_E_UNSUPPORTED, "render_fwd: neus runs the fp32-MFMA kernel");
-    a.fc.matmul_mode = NGM_MATMUL_F32;
-    a.neus_sd = params->neus_sd; a.neus_sd_stride = params->neus_sd_stride;
-  }
+  a.fc.matmul_mode = p.fwd.matmul;                                    // AUTO resolved by the plan (LDS budget of this batch shape)
+  if (p.fwd.neus) { a.neus_sd = params->neus_sd; a.neus_sd_stride = params->neus_sd_stride; }
   a.has_targets = has_tg ? 1 : 0;
   a.num_active = num_active;
   if (has_tg) a.tg = *targets;
-  a.S = p.S; a.rays_per_block = p.rays_per_block; a.waves_per_block = p.waves_fwd; a.maxs = p.maxs;
+  a.S = p.S; a.rays_per_block = p.fwd.rays_per_block; a.waves_per_block = p.fwd.waves; a.maxs = p.fwd.maxs;
   if (save) {
     a.raytab = reinterpret_cast<float*>(ws + p.off_raytab);
     if (has_tg) a.rayseed = reinterpret_cast<float*>(ws + p.off_rayseed);
@@ -954,8 +992,9 @@ static int render_fwd_impl(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg
       a.debug_cycles = g_debug_cycles_fwd;
     }
   }
-  e = ngm_launch_render_fwd(a, p.blocks_fwd, (hipStream_t)stream);
-  if (e) return fail(e, "render_fwd: no kernel for this (D,H,L)");
+  e = ngm_launch_render_fwd(a, p.fwd, (hipStream_t)stream);
+  if (e) return fail(e, no_instance);
+  g_last_fwd[NGM_FWD_RENDER] = p.fwd;
   if (save) {
     note_forward_stash(workspace, p.bwd.half);
     note_forward_seeds(workspace, a.rayseed ? targets->rgbds : nullptr);
@@ -963,7 +1002,7 @@ static int render_fwd_impl(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg
   e = check_launch("ngm_render_fwd");
   if (e) return e;
   if (has_tg && loss_sums) {      // loss_sums == NULL: deferred -- ngm_render_bwd* (loss_sums == NULL) reduces the partials itself
-    ngm_launch_loss_reduce(a.loss_partials, p.blocks_fwd, loss_sums,
+    ngm_launch_loss_reduce(a.loss_partials, p.fwd.blocks, loss_sums,
                            (rays->philox_offset_autoinc && rays->philox_offset_dev) ? const_cast<uint64_t*>(rays->philox_offset_dev) : nullptr,
                            (hipStream_t)stream);
     e = check_launch("ngm_loss_reduce");
@@ -1019,7 +1058,7 @@ static int render_bwd_common(const ngm_field_cfg* fcfg, const ngm_render_cfg* rc
   }
   if (sb.seed_mode == 0 && !sb.loss_sums) {      // deferred loss reduction: the forward left its partials in the workspace
     sb.loss_partials = reinterpret_cast<const float*>(ws + p.off_losspart);
-    sb.n_partials = p.blocks_fwd;
+    sb.n_partials = p.fwd.blocks;
     sb.counter = (rays->philox_offset_autoinc && rays->philox_offset_dev)
                      ? reinterpret_cast<unsigned long long*>(const_cast<uint64_t*>(rays->philox_offset_dev)) : nullptr;
   }
@@ -1221,6 +1260,11 @@ int ngm_step_advance(int64_t* step_dev, uint64_t* philox_offset_dev, void* strea
   return check_launch("ngm_step_advance");
 }
 
+static FwdPlan plan_knn(const ngm_field_cfg* fc) {
+  FwdAsk ask;
+  ask.surface = NGM_FWD_KNN;
+  return plan_fwd(fc, ask);
+}
 int64_t ngm_field_eval_knn_workspace(int32_t num_fields, int64_t P, int32_t num_knn) {
   const int K = num_knn < num_fields ? num_knn : num_fields;
   if (num_fields < 1 || P < 0 || K < 1) return NGM_E_INVALID;
@@ -1239,10 +1283,13 @@ int ngm_field_eval_knn(const ngm_field_cfg* fcfg, const ngm_params* params, int3
   if (P == 0) return NGM_OK;
   const int K = num_knn < num_fields ? num_knn : num_fields;
   if (K < 1 || K > 16) return fail(NGM_E_UNSUPPORTED, "ngm_field_eval_knn: K must be in [1,16]");
+  const FwdPlan plan = plan_knn(fcfg);         // the evaluation is planned before the grid build and the assignment launch
+  if (plan.status) return fail(plan.status, plan.why);
   e = ngm_launch_knn(fcfg, params, num_fields, P, points, field_pos, field_quat, K, distance_factor, outside_value,
-                     mask_radius > 0.f ? mask_radius : fcfg->field_radius, out, workspace, workspace_bytes, (hipStream_t)stream);
+                     mask_radius > 0.f ? mask_radius : fcfg->field_radius, out, workspace, workspace_bytes, plan, (hipStream_t)stream);
   if (e == NGM_E_WORKSPACE) return fail(e, "ngm_field_eval_knn: workspace too small");
   if (e) return fail(e, "ngm_field_eval_knn: not available for this configuration");
+  g_last_fwd[NGM_FWD_KNN] = plan;
   return check_launch("ngm_field_eval_knn");
 }
 
@@ -1266,11 +1313,14 @@ int ngm_render_eval_knn(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg, c
   if ((int64_t)rays->F * rays->R == 0) return NGM_OK;
   const int K = num_knn < num_fields ? num_knn : num_fields;
   if (K < 1 || K > 8) return fail(NGM_E_UNSUPPORTED, "ngm_render_eval_knn: K must be in [1,8] (the blend inside the quadrature is compiled for up to 8 neighbours; K = 9..16: the staged entry points, ngm_sample_rays_world -> ngm_field_eval_knn -> ngm_composite_fwd_packed)");
+  const FwdPlan plan = plan_knn(fcfg);
+  if (plan.status) return fail(plan.status, plan.why);
   e = ngm_launch_render_eval_knn(fcfg, rcfg, params, num_fields, field_pos, field_quat, rays, K, distance_factor, outside_value,
                                  mask_radius > 0.f ? mask_radius : fcfg->field_radius, ray_block, pred, workspace,
-                                 workspace_bytes, (hipStream_t)stream);
+                                 workspace_bytes, plan, (hipStream_t)stream);
   if (e == NGM_E_WORKSPACE) return fail(e, "ngm_render_eval_knn: workspace too small");
   if (e) return fail(e, "ngm_render_eval_knn: not available for this configuration (samples per ray <= 1024, ray_block * samples * K < 2^31)");
+  g_last_fwd[NGM_FWD_KNN] = plan;
   return check_launch("ngm_render_eval_knn");
 }
 
@@ -1362,12 +1412,27 @@ int ngm_debug_plan_bwd(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg, in
     ask.seeds_written = seeds_written != 0;
     const RenderPlan p = plan_render(fcfg, rcfg, F, (int)n, guided != 0, true, ask);
     bp = p.bwd;
-    fwd_matmul = (p.b3 && rcfg->geometry_mode != NGM_GEO_NEUS) ? NGM_MATMUL_BF16X3 : NGM_MATMUL_F32;   // as render_fwd_impl resolves it
+    fwd_matmul = p.fwd.matmul;
   } else {
     bp = plan_points(fcfg, F, n, stash_offered != 0);
   }
   out5[0] = bp.variant; out5[1] = bp.fused_comp; out5[2] = bp.stash_kind; out5[3] = bp.stash_layers; out5[4] = fwd_matmul;
   return bp.status ? fail(bp.status, bp.why) : NGM_OK;
+}
+
+int ngm_debug_plan_fwd(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg, int32_t surface, int32_t F, int64_t n, int32_t guided,
+                       int32_t* out12) {
+  const int e = check_field_cfg(fcfg);
+  if (e) return e;
+  if (!out12 || surface < NGM_FWD_RENDER || surface > NGM_FWD_KNN || (surface == NGM_FWD_RENDER) != (rcfg != nullptr) || F < 1 || n < 1 ||
+      (rcfg && n > INT32_MAX))
+    return fail(NGM_E_INVALID, "ngm_debug_plan_fwd: bad argument");
+  FwdAsk ask;
+  ask.surface = surface; ask.F = F; ask.n = n;
+  const FwdPlan p = rcfg ? plan_render(fcfg, rcfg, F, (int)n, guided != 0, false).fwd : plan_fwd(fcfg, ask);
+  const int32_t out[12] = {p.MI, p.MH, p.L, p.matmul, p.one_tile, p.waves, (int32_t)p.lds_bytes, p.neus, p.threads, p.rays_per_block, p.maxs, p.blocks};
+  memcpy(out12, out, sizeof(out));
+  return p.status ? fail(p.status, p.why) : NGM_OK;
 }
 
 double ngm_peer_set_timeout(double seconds) { return ngm_peer_set_timeout_impl(seconds); }

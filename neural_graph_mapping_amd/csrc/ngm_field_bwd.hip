@@ -745,7 +745,7 @@ static int launch_bwd(const FieldBwdArgs& a, int blocks, hipStream_t st) {
 #define NGM_LB(NC, EG, HS, CT)                                                                                          \
   do {                                                                                                                  \
     const size_t lds = BwdLds<MI, MH, L, CT>::TOTAL * sizeof(float);                                                    \
-    static_assert(BwdLds<MI, MH, L, CT>::TOTAL * sizeof(float) <= 160 * 1024, "k_field_bwd: LDS over 160 KiB");          \
+    static_assert(BwdLds<MI, MH, L, CT>::TOTAL * sizeof(float) <= NGM_LDS_MAX, "k_field_bwd: LDS over 160 KiB");          \
     (void)hipFuncSetAttribute((const void*)k_field_bwd<MI, MH, L, NC, EG, HS, CT>, hipFuncAttributeMaxDynamicSharedMemorySize, \
                               (int)lds);                                                                                \
     hipLaunchKernelGGL((k_field_bwd<MI, MH, L, NC, EG, HS, CT>), dim3(blocks), dim3(NGM_BLOCK), lds, st, a);            \

@@ -298,7 +298,7 @@ static int launch_bwd16(const FieldBwdArgs& a, int blocks, hipStream_t st) {
   using LYH = Lds16<TI, TH, L>;
   constexpr int epi = LYH::WTOTAL + B16_WAVES * 4 * 4 * 64;    // epilogue staging (EPI_W per wave)
   constexpr size_t lds = (size_t)(LYH::TOTAL > epi ? LYH::TOTAL : epi) * sizeof(float);
-  static_assert(lds <= 160 * 1024, "k_field_bwd16: LDS over 160 KiB");
+  static_assert(lds <= NGM_LDS_MAX, "k_field_bwd16: LDS over 160 KiB");
 #define NGM_LB16(NC, EG, HS)                                                                                                \
   do {                                                                                                                      \
     (void)hipFuncSetAttribute((const void*)k_field_bwd16<TI, TH, L, NC, EG, HS>, hipFuncAttributeMaxDynamicSharedMemorySize, \

@@ -419,7 +419,7 @@ __global__ __launch_bounds__(B16_THREADS) void k_field_bwd16s(FieldBwdArgs a) {
 template <int L>
 static int launch_bwd16s(const FieldBwdArgs& a, int blocks, hipStream_t st) {
   const size_t lds = (size_t)Lds16s<L>::TOTAL * sizeof(float);
-  static_assert(Lds16s<L>::TOTAL * sizeof(float) <= 160 * 1024, "k_field_bwd16s: LDS over 160 KiB");
+  static_assert(Lds16s<L>::TOTAL * sizeof(float) <= NGM_LDS_MAX, "k_field_bwd16s: LDS over 160 KiB");
 #define NGM_LB16S(NC, EG)                                                                                             \
   do {                                                                                                                \
     (void)hipFuncSetAttribute((const void*)k_field_bwd16s<L, NC, EG>, hipFuncAttributeMaxDynamicSharedMemorySize,     \

@@ -880,7 +880,7 @@ template <int L, bool HS>
 static int launch_bwd_b3(const FieldBwdArgs& a, int blocks, hipStream_t st) {
 #define NGM_LBB3(NC, EG)                                                                                              \
   do {                                                                                                                \
-    static_assert(LdsB3b<L, EG, HS>::TOTAL * sizeof(float) <= 160 * 1024, "k_field_bwd_b3: LDS over 160 KiB");       \
+    static_assert(LdsB3b<L, EG, HS>::TOTAL * sizeof(float) <= NGM_LDS_MAX, "k_field_bwd_b3: LDS over 160 KiB");       \
     const size_t lds = (size_t)LdsB3b<L, EG, HS>::TOTAL * sizeof(float);                                              \
     if (a.fused_comp) NGM_LBB3_ONE(NC, EG, true); else NGM_LBB3_ONE(NC, EG, false);                                    \
   } while (0)

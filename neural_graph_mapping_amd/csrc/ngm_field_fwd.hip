@@ -735,156 +735,115 @@ __global__ __launch_bounds__(512) void k_render_fwd(RenderFwdArgs a) {
 // ------------------------------------------------------------------------------------------------
 // host launchers
 // ------------------------------------------------------------------------------------------------
-// every encoding x skip_mode {no, add, concat} (models.py:159-169 is encoding-agnostic)
-#define NGM_LAUNCH_ONE(KERNEL, NC, HS, SK, GRID, BLK, LDSW, LDSX)                                                       \
-  do {                                                                                                                 \
-    const size_t lds_ = (FieldLds<MI, MH, L, (SK) == 2>::TOTAL + (LDSX)) * sizeof(float);                              \
-    (void)(LDSW);                                                                                                      \
-    (void)hipFuncSetAttribute((const void*)KERNEL<MI, MH, L, NC, HS, SK>, hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                              (int)lds_);                                                                              \
-    hipLaunchKernelGGL((KERNEL<MI, MH, L, NC, HS, SK>), dim3(GRID), BLK, lds_, st, a);                                 \
-  } while (0)
-#define NGM_LAUNCH_VARIANT(KERNEL, NC, HS, GRID, BLK, LDSW, LDSX)                               \
-  do {                                                                                          \
-    if (a.fc.skip_mode == NGM_SKIP_ADD) NGM_LAUNCH_ONE(KERNEL, NC, HS, 1, GRID, BLK, LDSW, LDSX);   \
-    else if (a.fc.skip_mode == NGM_SKIP_CONCAT) NGM_LAUNCH_ONE(KERNEL, NC, HS, 2, GRID, BLK, LDSW, LDSX); \
-    else NGM_LAUNCH_ONE(KERNEL, NC, HS, 0, GRID, BLK, LDSW, LDSX);                              \
-  } while (0)
-
-// the bf16 split path (ngm_matmul_mode) is compiled for 49..64-wide layers, <= 2 hidden layers, Fourier / no encoding, skip no
-template <int MI, int MH, int L>
-static constexpr bool b3_shape() { return MI == 2 && MH == 2 && L <= 2; }
-static bool b3_wanted(const ngm_field_cfg& fc) {
-  return (fc.matmul_mode == NGM_MATMUL_BF16X3 || fc.matmul_mode == NGM_MATMUL_AUTO) && fc.skip_mode == NGM_SKIP_NO &&
-         (fc.encoding == NGM_ENC_FOURIER || fc.encoding == NGM_ENC_NONE);
+// The shape table (NGM_FWD_SHAPES, ngm_launch.h) as a run-time test, and the LDS of an instance from the kernels' own carves
+static bool fwd_shape_compiled(const ngm_field_cfg& fc) { return ngm_fwd_lds_bytes(fc, false, 0, 0) >= 0; }
+int64_t ngm_fwd_lds_bytes(const ngm_field_cfg& fc, bool b3, int waves, int maxs) {
+  const FieldShape s = field_shape(&fc);
+  const bool cat = fc.skip_mode == NGM_SKIP_CONCAT;
+  const int64_t wave_floats = (int64_t)waves * RenderWaveLds::floats(maxs);
+#define NGM_FWD_LDS(MI_, MH_, L_)                                                                                              \
+  if (s.MI == MI_ && s.MH == MH_ && s.L == L_)                                                                                 \
+    return ((cat ? FieldLds<MI_, MH_, L_, true>::TOTAL : FieldLds<MI_, MH_, L_>::TOTAL) + wave_floats) * (int64_t)sizeof(float) + \
+           (b3 ? (int64_t)B3Lds<MI_, MH_, L_>::TOTAL * 16 : 0);
+  NGM_FWD_SHAPES(NGM_FWD_LDS)
+#undef NGM_FWD_LDS
+  return -1;
+}
+// every encoding x skip_mode {no, add, concat} (models.py:159-169 is encoding-agnostic); the hash encoding at <= 32 features
+bool ngm_points_fwd_takes(const ngm_field_cfg& fc, bool b3) {
+  if (!fwd_shape_compiled(fc) || (fc.encoding == NGM_ENC_PERMUTO && fc.dim_enc > 32)) return false;
+  return !b3 || ngm_fwd_split_takes(fc);
+}
+// neus in the fused kernel (two-pass compositing over the wave's LDS planes): Fourier / no encoding, skip no, fp32 MFMA
+bool ngm_render_fwd_takes(const ngm_field_cfg& fc, bool neus, bool b3) {
+  if (!ngm_points_fwd_takes(fc, b3)) return false;
+  return !neus || (!b3 && fc.skip_mode == NGM_SKIP_NO && (fc.encoding == NGM_ENC_FOURIER || fc.encoding == NGM_ENC_NONE));
 }
 
-template <int MI, int MH, int L>
-static int launch_points(const PointsFwdArgs& a, int blocks, hipStream_t st) {
-  const dim3 blk(NGM_BLOCK);
-  if constexpr (b3_shape<MI, MH, L>()) {
-    if (b3_wanted(a.fc)) {       // standalone evaluation: the mode is a preference here (fp32 MFMA where not compiled)
-      g_ngm_last_matmul[1] = NGM_MATMUL_BF16X3;
-      const size_t lds = FieldLds<MI, MH, L>::TOTAL * sizeof(float) + (size_t)B3Lds<MI, MH, L>::TOTAL * 16;
-      (void)hipFuncSetAttribute((const void*)k_field_points_fwd<MI, MH, L, false, 0, 0, true, 512>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((k_field_points_fwd<MI, MH, L, false, 0, 0, true, 512>), dim3(blocks), dim3(512), lds, st, a);
-      return 0;
-    }
-  }
-  g_ngm_last_matmul[1] = NGM_MATMUL_F32;
-  if (a.fc.encoding == NGM_ENC_PERMUTO) {
-    if constexpr (MI == 1) NGM_LAUNCH_VARIANT(k_field_points_fwd, false, 1, blocks, blk, 0, 0);
-    else return NGM_E_UNSUPPORTED;
-  } else if (a.fc.encoding == NGM_ENC_TRIPLANE) NGM_LAUNCH_VARIANT(k_field_points_fwd, false, 2, blocks, blk, 0, 0); else if (a.fc.encoding == NGM_ENC_NERF) NGM_LAUNCH_VARIANT(k_field_points_fwd, true, 0, blocks, blk, 0, 0);
-  else NGM_LAUNCH_VARIANT(k_field_points_fwd, false, 0, blocks, blk, 0, 0);
+template <typename Args>
+static int launch_inst(void (*kernel)(Args), const Args& a, const FwdPlan& p, hipStream_t st) {
+  (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
+  hipLaunchKernelGGL(kernel, dim3(p.blocks), dim3(p.threads), (size_t)p.lds_bytes, st, a);
   return 0;
+}
+template <int MI, int MH, int L, bool NC, int HS>
+static int launch_points_skips(const PointsFwdArgs& a, const FwdPlan& p, hipStream_t st) {
+  return p.skip == 1   ? launch_inst(k_field_points_fwd<MI, MH, L, NC, HS, 1>, a, p, st)
+         : p.skip == 2 ? launch_inst(k_field_points_fwd<MI, MH, L, NC, HS, 2>, a, p, st)
+                       : launch_inst(k_field_points_fwd<MI, MH, L, NC, HS, 0>, a, p, st);
+}
+template <int MI, int MH, int L>
+static int launch_points(const PointsFwdArgs& a, const FwdPlan& p, hipStream_t st) {
+  if (p.matmul == NGM_MATMUL_BF16X3) {           // 83 KB of weights, one workgroup per CU: eight waves
+    if constexpr (ngm_fwd_split_shape(MI, MH, L)) {
+      if (p.need_cos || p.hash || p.skip || p.threads != 512) return NGM_E_INVALID;
+      return launch_inst(k_field_points_fwd<MI, MH, L, false, 0, 0, true, 512>, a, p, st);
+    }
+    return NGM_E_INVALID;
+  }
+  if (p.threads != NGM_BLOCK) return NGM_E_INVALID;
+  if (p.hash == 1) {
+    if constexpr (MI == 1) return launch_points_skips<MI, MH, L, false, 1>(a, p, st);
+    return NGM_E_INVALID;
+  }
+  if (p.hash == 2) return launch_points_skips<MI, MH, L, false, 2>(a, p, st);
+  return p.need_cos ? launch_points_skips<MI, MH, L, true, 0>(a, p, st) : launch_points_skips<MI, MH, L, false, 0>(a, p, st);
 }
 // one instance of k_render_fwd: the COUNTED twin when the call carries a device count (never for the triplane encoding)
 template <int MI, int MH, int L, bool NC, int HS, int SK, bool B3, bool HALF>
-static void launch_render_inst(const RenderFwdArgs& a, int blocks, dim3 blk, size_t lds, hipStream_t st) {
-  if constexpr (HS != 2) {
-    if (a.num_active) {
-      (void)hipFuncSetAttribute((const void*)k_render_fwd<MI, MH, L, NC, HS, SK, B3, false, HALF, true>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((k_render_fwd<MI, MH, L, NC, HS, SK, B3, false, HALF, true>), dim3(blocks), blk, lds, st, a);
-      return;
-    }
+static int launch_render_inst(const RenderFwdArgs& a, const FwdPlan& p, hipStream_t st) {
+  if (p.counted) {
+    if constexpr (HS != 2) return launch_inst(k_render_fwd<MI, MH, L, NC, HS, SK, B3, false, HALF, true>, a, p, st);
+    return NGM_E_INVALID;
   }
-  (void)hipFuncSetAttribute((const void*)k_render_fwd<MI, MH, L, NC, HS, SK, B3, false, HALF>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((k_render_fwd<MI, MH, L, NC, HS, SK, B3, false, HALF>), dim3(blocks), blk, lds, st, a);
+  return launch_inst(k_render_fwd<MI, MH, L, NC, HS, SK, B3, false, HALF>, a, p, st);
 }
-#define NGM_RENDER_VARIANT(NC, HS)                                                                                        \
-  do {                                                                                                                   \
-    if (a.fc.skip_mode == NGM_SKIP_ADD)                                                                                  \
-      launch_render_inst<MI, MH, L, NC, HS, 1, false, false>(a, blocks, blk, (FieldLds<MI, MH, L, false>::TOTAL + wave_lds) * sizeof(float), st); \
-    else if (a.fc.skip_mode == NGM_SKIP_CONCAT)                                                                          \
-      launch_render_inst<MI, MH, L, NC, HS, 2, false, false>(a, blocks, blk, (FieldLds<MI, MH, L, true>::TOTAL + wave_lds) * sizeof(float), st);  \
-    else                                                                                                                 \
-      launch_render_inst<MI, MH, L, NC, HS, 0, false, false>(a, blocks, blk, (FieldLds<MI, MH, L, false>::TOTAL + wave_lds) * sizeof(float), st); \
-  } while (0)
+template <int MI, int MH, int L, bool NC, int HS>
+static int launch_render_skips(const RenderFwdArgs& a, const FwdPlan& p, hipStream_t st) {
+  return p.skip == 1   ? launch_render_inst<MI, MH, L, NC, HS, 1, false, false>(a, p, st)
+         : p.skip == 2 ? launch_render_inst<MI, MH, L, NC, HS, 2, false, false>(a, p, st)
+                       : launch_render_inst<MI, MH, L, NC, HS, 0, false, false>(a, p, st);
+}
 template <int MI, int MH, int L>
-static int launch_render(const RenderFwdArgs& a, int blocks, hipStream_t st) {
-  const size_t wave_lds = (size_t)a.waves_per_block * RenderWaveLds::floats(a.maxs);
-  const dim3 blk(64 * a.waves_per_block);
-  g_ngm_last_matmul[0] = NGM_MATMUL_F32;
-  g_ngm_last_fwd_one_tile = 0;
-  if (a.rc.geometry_mode == NGM_GEO_NEUS) {
-    // neus in the fused kernel (two-pass compositing over the wave's LDS planes): Fourier / no encoding, skip no, fp32 MFMA
-    if (a.fc.skip_mode != NGM_SKIP_NO || (a.fc.encoding != NGM_ENC_FOURIER && a.fc.encoding != NGM_ENC_NONE) || !a.neus_sd)
-      return NGM_E_UNSUPPORTED;
-    const size_t lds = (FieldLds<MI, MH, L>::TOTAL + wave_lds) * sizeof(float);
-    (void)hipFuncSetAttribute((const void*)k_render_fwd<MI, MH, L, false, 0, 0, false, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((k_render_fwd<MI, MH, L, false, 0, 0, false, true>), dim3(blocks), blk, lds, st, a);
-    return 0;
+static int launch_render(const RenderFwdArgs& a, const FwdPlan& p, hipStream_t st) {
+  const bool plain = !p.need_cos && !p.hash && !p.skip;       // Fourier / no encoding, skip no
+  if (p.neus) {
+    if (!plain || p.matmul != NGM_MATMUL_F32 || p.one_tile || p.counted) return NGM_E_INVALID;
+    return launch_inst(k_render_fwd<MI, MH, L, false, 0, 0, false, true>, a, p, st);
   }
-  if (a.fc.matmul_mode == NGM_MATMUL_BF16X3) {
-    // opt-in: hidden layers as a three-way bf16 split on v_mfma_f32_32x32x16_bf16 (ngm_field.h, layer_fwd_b3)
-    if constexpr (MI == 2 && MH == 2 && L <= 2) {
-      if (a.fc.skip_mode == NGM_SKIP_NO && (a.fc.encoding == NGM_ENC_FOURIER || a.fc.encoding == NGM_ENC_NONE)) {
-        const size_t lds = (FieldLds<MI, MH, L>::TOTAL + wave_lds) * sizeof(float) + (size_t)B3Lds<MI, MH, L>::TOTAL * 16;
-        if (lds > 160 * 1024) return NGM_E_UNSUPPORTED;
-        g_ngm_last_matmul[0] = NGM_MATMUL_BF16X3;
-        // every wave's batches hold at most 32 samples (rays per wave x samples per ray): the one-tile instance
-        const int per_wave = (a.rays_per_block + a.waves_per_block - 1) / a.waves_per_block;
-        static const bool no_half = getenv("NGM_NO_HALF_STEP") != nullptr;          // developer A/B switch
-        g_ngm_last_fwd_one_tile = (per_wave * a.S <= 32 && !no_half) ? 1 : 0;
-        if (per_wave * a.S <= 32 && !no_half) {
-          launch_render_inst<MI, MH, L, false, 0, 0, true, true>(a, blocks, blk, lds, st);
-          return 0;
-        }
-        launch_render_inst<MI, MH, L, false, 0, 0, true, false>(a, blocks, blk, lds, st);
-        return 0;
-      }
+  if (p.matmul == NGM_MATMUL_BF16X3) {
+    if constexpr (ngm_fwd_split_shape(MI, MH, L)) {
+      if (!plain) return NGM_E_INVALID;
+      return p.one_tile ? launch_render_inst<MI, MH, L, false, 0, 0, true, true>(a, p, st)
+                        : launch_render_inst<MI, MH, L, false, 0, 0, true, false>(a, p, st);
     }
-    return NGM_E_UNSUPPORTED;
+    return NGM_E_INVALID;
   }
-  if (a.fc.encoding == NGM_ENC_PERMUTO) {
+  if (p.hash == 1) {
     if constexpr (MI == 1) {
-      // the reference's default network on small per-rank batches: the one-tile instance (see the split path above)
-      const int per_wave = (a.rays_per_block + a.waves_per_block - 1) / a.waves_per_block;
-      static const bool no_half = getenv("NGM_NO_HALF_STEP") != nullptr;
-      if (per_wave * a.S <= 32 && !no_half && a.fc.skip_mode == NGM_SKIP_NO) {
-        const size_t lds_ = (FieldLds<MI, MH, L>::TOTAL + wave_lds) * sizeof(float);
-        launch_render_inst<MI, MH, L, false, 1, 0, false, true>(a, blocks, blk, lds_, st);
-        g_ngm_last_fwd_one_tile = 1;
-        return 0;
-      }
-      NGM_RENDER_VARIANT(false, 1);
+      // the reference's default network on small per-rank batches: the one-tile instance (skip no)
+      if (p.one_tile) return p.skip ? NGM_E_INVALID : launch_render_inst<MI, MH, L, false, 1, 0, false, true>(a, p, st);
+      return launch_render_skips<MI, MH, L, false, 1>(a, p, st);
     }
-    else return NGM_E_UNSUPPORTED;
-  } else if (a.fc.encoding == NGM_ENC_TRIPLANE) NGM_RENDER_VARIANT(false, 2); else if (a.fc.encoding == NGM_ENC_NERF) NGM_RENDER_VARIANT(true, 0);
-  else NGM_RENDER_VARIANT(false, 0);
-  return 0;
+    return NGM_E_INVALID;
+  }
+  if (p.one_tile) return NGM_E_INVALID;
+  if (p.hash == 2) return launch_render_skips<MI, MH, L, false, 2>(a, p, st);
+  return p.need_cos ? launch_render_skips<MI, MH, L, true, 0>(a, p, st) : launch_render_skips<MI, MH, L, false, 0>(a, p, st);
 }
 
-#ifdef NGM_FAST_BUILD
-#define NGM_SHAPE_DISPATCH(FN, ...)                                             \
-  do {                                                                          \
-    const FieldShape s_ = field_shape(&a.fc);                                   \
-    if (s_.MI == 2 && s_.MH == 2 && s_.L == 2) return FN<2, 2, 2>(__VA_ARGS__); \
-    return NGM_E_UNSUPPORTED;                                                   \
-  } while (0)
-#else
-#define NGM_SHAPE_DISPATCH(FN, ...)                                             \
-  do {                                                                          \
-    const FieldShape s_ = field_shape(&a.fc);                                   \
-    if (s_.MI == 2 && s_.MH == 2 && s_.L == 2) return FN<2, 2, 2>(__VA_ARGS__); \
-    if (s_.MI == 2 && s_.MH == 2 && s_.L == 1) return FN<2, 2, 1>(__VA_ARGS__); \
-    if (s_.MI == 1 && s_.MH == 1 && s_.L == 1) return FN<1, 1, 1>(__VA_ARGS__); \
-    if (s_.MI == 1 && s_.MH == 1 && s_.L == 2) return FN<1, 1, 2>(__VA_ARGS__); \
-    if (s_.MI == 2 && s_.MH == 2 && s_.L == 3) return FN<2, 2, 3>(__VA_ARGS__); \
-    return NGM_E_UNSUPPORTED;                                                   \
-  } while (0)
-#endif
-
-int ngm_launch_points_fwd(const PointsFwdArgs& a, int blocks, hipStream_t st) {
+#define NGM_FWD_DISPATCH(MI_, MH_, L_) if (p.MI == MI_ && p.MH == MH_ && p.L == L_) return NGM_FWD_LAUNCH<MI_, MH_, L_>(a, p, st);
+int ngm_launch_points_fwd(const PointsFwdArgs& a, const FwdPlan& p, hipStream_t st) {
   NgmProfScope prof_(NGM_K_POINTS_FWD, st);
-  NGM_SHAPE_DISPATCH(launch_points, a, blocks, st);
+#define NGM_FWD_LAUNCH launch_points
+  NGM_FWD_SHAPES(NGM_FWD_DISPATCH)
+#undef NGM_FWD_LAUNCH
+  return NGM_E_INVALID;
 }
-int ngm_launch_render_fwd(const RenderFwdArgs& a, int blocks, hipStream_t st) {
+int ngm_launch_render_fwd(const RenderFwdArgs& a, const FwdPlan& p, hipStream_t st) {
   NgmProfScope prof_(NGM_K_RENDER_FWD, st);
-  NGM_SHAPE_DISPATCH(launch_render, a, blocks, st);
+#define NGM_FWD_LAUNCH launch_render
+  NGM_FWD_SHAPES(NGM_FWD_DISPATCH)
+#undef NGM_FWD_LAUNCH
+  return NGM_E_INVALID;
 }

@@ -642,55 +642,38 @@ int64_t ngm_knn_render_workspace_bytes(int num_fields, int ray_block, int S, int
   return ngm_knn_workspace_bytes(num_fields, P, K) + 4 * (P + 64) + 28 * ((int64_t)ray_block + 64) + 1024;
 }
 
-// compute units of the device: the persistent evaluation kernel runs one workgroup per CU in its 83 KB bf16-split variant
-// (eight waves), four per CU in the fp32 variants (<= 35 KB, four waves each)
-static int knn_num_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-            ? prop.multiProcessorCount : 256;
-    (void)hipGetLastError();
-  }
-  return n;
-}
-
-template <int MI, int MH, int L>
-static int launch_eval(const KnnArgs& a, int max_tiles, hipStream_t st) {
-  const int grid = std::max(1, std::min(max_tiles, 4 * knn_num_cus())), grid_b3 = std::max(1, std::min(max_tiles, knn_num_cus()));
-#define NGM_KE(NC, HS, SK)                                                                                             \
-  do {                                                                                                                 \
-    const size_t lds = FieldLds<MI, MH, L, (SK) == 2>::TOTAL * sizeof(float);                                          \
-    (void)hipFuncSetAttribute((const void*)k_knn_eval<MI, MH, L, NC, HS, SK>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                              (int)lds);                                                                               \
-    hipLaunchKernelGGL((k_knn_eval<MI, MH, L, NC, HS, SK>), dim3(grid), dim3(NGM_BLOCK), lds, st, a);                  \
-  } while (0)
-  const int sk = a.fc.skip_mode;
-  g_ngm_last_matmul[2] = NGM_MATMUL_F32;
-  if constexpr (MI == 2 && MH == 2 && L <= 2) {
-    if ((a.fc.matmul_mode == NGM_MATMUL_BF16X3 || a.fc.matmul_mode == NGM_MATMUL_AUTO) && sk == NGM_SKIP_NO &&
-        (a.fc.encoding == NGM_ENC_FOURIER || a.fc.encoding == NGM_ENC_NONE)) {
-      g_ngm_last_matmul[2] = NGM_MATMUL_BF16X3;
-      const size_t lds = FieldLds<MI, MH, L>::TOTAL * sizeof(float) + (size_t)B3Lds<MI, MH, L>::TOTAL * 16;
-      (void)hipFuncSetAttribute((const void*)k_knn_eval<MI, MH, L, false, 0, 0, true, KNN_EVAL_B3_THREADS>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((k_knn_eval<MI, MH, L, false, 0, 0, true, KNN_EVAL_B3_THREADS>), dim3(grid_b3), dim3(KNN_EVAL_B3_THREADS), lds, st, a);
-      return 0;
-    }
-  }
-  if (a.fc.encoding == NGM_ENC_PERMUTO) {
-    if constexpr (MI == 1) { if (sk == NGM_SKIP_ADD) NGM_KE(false, 1, 1); else if (sk == NGM_SKIP_CONCAT) NGM_KE(false, 1, 2); else NGM_KE(false, 1, 0); }
-    else return NGM_E_UNSUPPORTED;
-  } else if (a.fc.encoding == NGM_ENC_TRIPLANE) {
-    if (sk == NGM_SKIP_ADD) NGM_KE(false, 2, 1); else if (sk == NGM_SKIP_CONCAT) NGM_KE(false, 2, 2); else NGM_KE(false, 2, 0);
-  } else if (a.fc.encoding == NGM_ENC_NERF) {
-    if (sk == NGM_SKIP_ADD) NGM_KE(true, 0, 1); else if (sk == NGM_SKIP_CONCAT) NGM_KE(true, 0, 2); else NGM_KE(true, 0, 0);
-  } else {
-    if (sk == NGM_SKIP_ADD) NGM_KE(false, 0, 1); else if (sk == NGM_SKIP_CONCAT) NGM_KE(false, 0, 2); else NGM_KE(false, 0, 0);
-  }
-#undef NGM_KE
+// The persistent evaluation kernel: the instances of the point evaluation (every compiled shape x encoding x skip class; the
+// bf16 split at its shape).  plan_fwd sizes the grid: one workgroup per CU in the 83 KB split variant (eight waves), four per CU
+// in the fp32 variants (<= 35 KB, four waves each); never more than there are tiles.
+bool ngm_knn_eval_takes(const ngm_field_cfg& fc, bool b3) { return ngm_points_fwd_takes(fc, b3); }
+template <typename Kernel>
+static int launch_eval_inst(Kernel kernel, const KnnArgs& a, const FwdPlan& p, int max_tiles, hipStream_t st) {
+  (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
+  hipLaunchKernelGGL(kernel, dim3(std::max(1, std::min(max_tiles, p.blocks))), dim3(p.threads), (size_t)p.lds_bytes, st, a);
   return 0;
+}
+template <int MI, int MH, int L, bool NC, int HS>
+static int launch_eval_skips(const KnnArgs& a, const FwdPlan& p, int max_tiles, hipStream_t st) {
+  return p.skip == 1   ? launch_eval_inst(k_knn_eval<MI, MH, L, NC, HS, 1>, a, p, max_tiles, st)
+         : p.skip == 2 ? launch_eval_inst(k_knn_eval<MI, MH, L, NC, HS, 2>, a, p, max_tiles, st)
+                       : launch_eval_inst(k_knn_eval<MI, MH, L, NC, HS, 0>, a, p, max_tiles, st);
+}
+template <int MI, int MH, int L>
+static int launch_eval(const KnnArgs& a, const FwdPlan& p, int max_tiles, hipStream_t st) {
+  if (p.matmul == NGM_MATMUL_BF16X3) {
+    if constexpr (ngm_fwd_split_shape(MI, MH, L)) {
+      if (p.need_cos || p.hash || p.skip || p.threads != KNN_EVAL_B3_THREADS) return NGM_E_INVALID;
+      return launch_eval_inst(k_knn_eval<MI, MH, L, false, 0, 0, true, KNN_EVAL_B3_THREADS>, a, p, max_tiles, st);
+    }
+    return NGM_E_INVALID;
+  }
+  if (p.threads != NGM_BLOCK) return NGM_E_INVALID;
+  if (p.hash == 1) {
+    if constexpr (MI == 1) return launch_eval_skips<MI, MH, L, false, 1>(a, p, max_tiles, st);
+    return NGM_E_INVALID;
+  }
+  if (p.hash == 2) return launch_eval_skips<MI, MH, L, false, 2>(a, p, max_tiles, st);
+  return p.need_cos ? launch_eval_skips<MI, MH, L, true, 0>(a, p, max_tiles, st) : launch_eval_skips<MI, MH, L, false, 0>(a, p, max_tiles, st);
 }
 
 // workspace carving shared by the two entry points; `a.NF`, `a.K`, `a.P` (the largest P of the call) are set
@@ -717,7 +700,7 @@ static void knn_carve(KnnArgs& a, void* workspace, char** end) {
 }
 
 // grid build (optional) -> assignment -> offsets -> scatter -> per-field evaluation of the pairs; the blend is the caller's
-static int knn_stages(KnnArgs& a, bool build_grid, hipStream_t st) {
+static int knn_stages(KnnArgs& a, const FwdPlan& p, bool build_grid, hipStream_t st) {
   const int64_t n = a.P * a.K;
   // (the pair counts are zero here: k_knn_grid zeroes them, k_knn_offsets re-zeroes them after use)
   const int pb = (int)std::min<int64_t>((a.P + 255) / 256, KNN_ASSIGN_MAX_WG);
@@ -769,19 +752,11 @@ static int knn_stages(KnnArgs& a, bool build_grid, hipStream_t st) {
   const int nb = (int)((n + SC_ITEMS * 256 - 1) / (SC_ITEMS * 256));
   hipLaunchKernelGGL(k_knn_scatter, dim3(std::max(nb, 1)), dim3(256), a.hist_in_lds ? lds_h : 0, st, a);
   const int max_tiles = (int)std::min<int64_t>((n + KNN_TILE - 1) / KNN_TILE + a.NF, 0x7fffffff);
-  const FieldShape s = field_shape(&a.fc);
-  int le = NGM_E_UNSUPPORTED;
-  {
-    NgmProfScope prof_eval_(NGM_K_KNN_EVAL, st);
-    if (s.MI == 2 && s.MH == 2 && s.L == 2) le = launch_eval<2, 2, 2>(a, max_tiles, st);
-#ifndef NGM_FAST_BUILD
-    else if (s.MI == 2 && s.MH == 2 && s.L == 1) le = launch_eval<2, 2, 1>(a, max_tiles, st);
-    else if (s.MI == 1 && s.MH == 1 && s.L == 1) le = launch_eval<1, 1, 1>(a, max_tiles, st);
-    else if (s.MI == 1 && s.MH == 1 && s.L == 2) le = launch_eval<1, 1, 2>(a, max_tiles, st);
-    else if (s.MI == 2 && s.MH == 2 && s.L == 3) le = launch_eval<2, 2, 3>(a, max_tiles, st);
-#endif
-  }
-  return le;
+  NgmProfScope prof_eval_(NGM_K_KNN_EVAL, st);
+#define NGM_KNN_DISPATCH(MI_, MH_, L_) if (p.MI == MI_ && p.MH == MH_ && p.L == L_) return launch_eval<MI_, MH_, L_>(a, p, max_tiles, st);
+  NGM_FWD_SHAPES(NGM_KNN_DISPATCH)
+#undef NGM_KNN_DISPATCH
+  return NGM_E_INVALID;
 }
 
 static void knn_common(KnnArgs& a, const ngm_field_cfg* fc, const ngm_params* pr, int num_fields, const float* pos,
@@ -796,7 +771,7 @@ static void knn_common(KnnArgs& a, const ngm_field_cfg* fc, const ngm_params* pr
 
 int ngm_launch_knn(const ngm_field_cfg* fc, const ngm_params* pr, int num_fields, int64_t P, const float* points,
                    const float* pos, const float* quat, int K, float distance_factor, float outside_value, float mask_radius,
-                   float* out, void* workspace, int64_t workspace_bytes, hipStream_t st) {
+                   float* out, void* workspace, int64_t workspace_bytes, const FwdPlan& plan, hipStream_t st) {
   if (workspace_bytes < ngm_knn_workspace_bytes(num_fields, P, K) || !workspace) return NGM_E_WORKSPACE;
   if (num_fields < 1 || P * K > 0x7fffffff) return NGM_E_UNSUPPORTED;
   KnnArgs a;
@@ -804,7 +779,7 @@ int ngm_launch_knn(const ngm_field_cfg* fc, const ngm_params* pr, int num_fields
   a.P = P; a.points = points; a.out = out;
   char* end;
   knn_carve(a, workspace, &end);
-  const int le = knn_stages(a, true, st);
+  const int le = knn_stages(a, plan, true, st);
   if (le) return le;
   const int pb = (int)std::min<int64_t>((P + 255) / 256, 4096);
   hipLaunchKernelGGL(k_knn_blend, dim3(std::max(pb, 1)), dim3(256), 0, st, a);
@@ -819,7 +794,7 @@ int ngm_launch_knn(const ngm_field_cfg* fc, const ngm_params* pr, int num_fields
 int ngm_launch_render_eval_knn(const ngm_field_cfg* fc, const ngm_render_cfg* rc, const ngm_params* pr, int num_fields,
                                const float* pos, const float* quat, const ngm_rays* rays, int K, float distance_factor,
                                float outside_value, float mask_radius, int ray_block, const ngm_prediction* pred,
-                               void* workspace, int64_t workspace_bytes, hipStream_t st) {
+                               void* workspace, int64_t workspace_bytes, const FwdPlan& plan, hipStream_t st) {
   const int S = rc->num_samples_coarse;
   const int64_t total = (int64_t)rays->F * rays->R;
   if (ray_block < 1 || S < 1 || S > CQ_MAXS_EVAL || (int64_t)ray_block * S * K > 0x7fffffff || num_fields < 1) return NGM_E_UNSUPPORTED;
@@ -846,7 +821,7 @@ int ngm_launch_render_eval_knn(const ngm_field_cfg* fc, const ngm_render_cfg* rc
     a.rays = rb;
     a.P = (int64_t)nr * S;
     hipLaunchKernelGGL(k_knn_raytab, dim3((nr + 255) / 256), dim3(256), 0, st, a);
-    const int le = knn_stages(a, r0 == 0, st);
+    const int le = knn_stages(a, plan, r0 == 0, st);
     if (le) return le;
     CompositeArgs c;
     memset(&c, 0, sizeof(c));

@@ -203,11 +203,49 @@ struct StashBwdArgs {
   const int32_t* num_active;  // counted step: only the rays of rows f < *num_active are walked (NULL: all F)
 };
 
-// which arithmetic the last launch of each forward-type kernel resolved to (ngm_debug_last_matmul): 0 = the fused render
-// forward, 1 = the point evaluation, 2 = the kNN evaluation; values NGM_MATMUL_F32 / NGM_MATMUL_BF16X3, -1 = none yet
-extern int g_ngm_last_matmul[3];
-extern int g_ngm_last_fwd_one_tile;      // the last fused render forward ran the one-tile wave step instance (k_render_fwd<.., HALF>)
-int ngm_launch_points_fwd(const PointsFwdArgs& a, int blocks, hipStream_t st);
+// ---- the forward plan ----------------------------------------------------------------------------------------------------------
+// The compiled forward shapes <MI,MH,L> (MI / MH = ceil(dim / 32)), listed once: the fused render forward, the point evaluation
+// and the kNN evaluation instantiate exactly these.
+#ifdef NGM_FAST_BUILD
+#define NGM_FWD_SHAPES(X) X(2, 2, 2)
+#else
+#define NGM_FWD_SHAPES(X) X(2, 2, 2) X(2, 2, 1) X(1, 1, 1) X(1, 1, 2) X(2, 2, 3)
+#endif
+#define NGM_LDS_MAX (160 * 1024)      // bytes of LDS a workgroup may ask for (gfx950)
+// The bf16 split path (ngm_matmul_mode): hidden layers as a three-way bf16 split on v_mfma_f32_32x32x16_bf16, compiled for 33..64-wide
+// layers, at most two hidden layers, Fourier / no encoding, no skip connection
+constexpr bool ngm_fwd_split_shape(int MI, int MH, int L) { return MI == 2 && MH == 2 && L <= 2; }
+static inline bool ngm_fwd_split_takes(const ngm_field_cfg& fc) {
+  return ngm_fwd_split_shape((fc.dim_enc + 31) / 32, (fc.dim_hidden + 31) / 32, fc.num_layers) && fc.skip_mode == NGM_SKIP_NO &&
+         (fc.encoding == NGM_ENC_FOURIER || fc.encoding == NGM_ENC_NONE);
+}
+enum { NGM_FWD_RENDER = 0, NGM_FWD_POINTS = 1, NGM_FWD_KNN = 2 };     // the forward surfaces (the index of ngm_debug_last_matmul)
+// Which forward instance runs and how it is launched: ONE decision, taken by plan_fwd (ngm_api.hip) from plain values before
+// anything is launched.  The three launchers switch on it and answer NGM_E_INVALID to a plan they have no instance for.
+struct FwdPlan {
+  int status = NGM_OK; const char* why = nullptr;   // NGM_OK, or the refusal (NGM_E_UNSUPPORTED) and its message
+  int surface = NGM_FWD_RENDER;
+  int MI = 0, MH = 0, L = 0;            // the compiled shape
+  int matmul = -1;                      // the arithmetic of the hidden layers: NGM_MATMUL_F32 / NGM_MATMUL_BF16X3
+  bool need_cos = false;                // instance parameters: NeRF octaves; encoding class 0 Fourier / none / NeRF, 1 hash,
+  int hash = 0, skip = 0;               // 2 triplane; skip class 0 no, 1 add, 2 concat
+  bool neus = false, one_tile = false, counted = false;   // fused render: the neus instance, the one-tile wave step, the counted twin
+  int waves = 0, threads = 0;           // per workgroup
+  int rays_per_block = 0, maxs = 0;     // fused render: rays of a workgroup, samples a wave buffers per ray batch
+  int64_t per_block = 0;                // point evaluation: samples per workgroup
+  int blocks = 0;                       // workgroups (kNN evaluation: at most; the launcher knows the tile count)
+  int64_t lds_bytes = 0;                // dynamic LDS
+};
+// One predicate per forward kernel, beside its launcher: a compiled instance (NGM_FAST_BUILD included) takes this configuration
+// with the split arithmetic (b3) or with exact-fp32 MFMA.
+bool ngm_render_fwd_takes(const ngm_field_cfg& fc, bool neus, bool b3);
+bool ngm_points_fwd_takes(const ngm_field_cfg& fc, bool b3);
+bool ngm_knn_eval_takes(const ngm_field_cfg& fc, bool b3);
+// Dynamic LDS of a forward instance, from FieldLds / B3Lds / RenderWaveLds: one field's weights, the split path's bf16 planes
+// (b3) and, in the fused render forward, `waves` per-wave carves of `maxs` samples (waves = 0: point and kNN evaluation).
+// -1: the shape is not compiled.
+int64_t ngm_fwd_lds_bytes(const ngm_field_cfg& fc, bool b3, int waves, int maxs);
+int ngm_launch_points_fwd(const PointsFwdArgs& a, const FwdPlan& p, hipStream_t st);
 int64_t ngm_encode_bwd_fourier_scratch(int F, int64_t P);
 int ngm_launch_encode_bwd_fourier(const ngm_field_cfg& fc, const ngm_params& pr, int F, int64_t P, const float* points,
                                   const float* pos, const float* quat, const float* d_enc, float* grad, int64_t grad_stride,
@@ -217,7 +255,7 @@ int ngm_launch_encode_bwd_prep_hash(const ngm_field_cfg& fc, const ngm_params& p
                                     hipStream_t st);
 int ngm_launch_encode_points(const ngm_field_cfg& fc, const ngm_params& pr, int F, int64_t P, const float* points, const float* pos,
                              const float* quat, float* out, hipStream_t st);   // the positional encoding alone -> (F, P, dim_enc)
-int ngm_launch_render_fwd(const RenderFwdArgs& a, int blocks, hipStream_t st);
+int ngm_launch_render_fwd(const RenderFwdArgs& a, const FwdPlan& p, hipStream_t st);
 int ngm_launch_field_bwd(const FieldBwdArgs& a, int blocks, hipStream_t st);
 int ngm_launch_tri_finish(const FieldBwdArgs& a, hipStream_t st);
 int ngm_launch_field_bwd_b3(const FieldBwdArgs& a, int blocks, hipStream_t st);   // 32-sample tiles on the bf16 matrix pipe (three-way split), activation stash

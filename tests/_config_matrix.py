@@ -16,11 +16,13 @@ Outcomes, per mode ("f32", "auto"; "bf16x3" where the entry is about the explici
                     ops.FIELD_EVAL_STASH_MAX_BYTES = 0
   step(mm, v, fc)   fused step: arithmetic of the forward, backward variant, ngm_debug_last_comp_fused
 
-The forward kernels named here were read off the shape dispatch, the backward ones off plan_mlp_bwd (csrc/ngm_api.hip; the
-library answers for it without a GPU: ngm_debug_plan_bwd), with TI / TH = ceil(dim / 16) and MI / MH = ceil(dim / 32):
-  forward shape <MI,MH,L>     NGM_SHAPE_DISPATCH (ngm_field_fwd.hip), launch_eval's caller (ngm_knn.hip): <2,2,2> <2,2,1> <1,1,1>
-                              <1,1,2> <2,2,3>; bf16x3 only at <2,2,L<=2>, Fourier / none, skip no (points / knn: a preference;
-                              fused forward: `auto` resolves to it, explicit `bf16x3` elsewhere is refused)
+Both halves are checked against the library without a GPU (tests/test_config_matrix_cpu.py): the forward columns -- shape,
+arithmetic, refusal -- against plan_fwd through ngm_debug_plan_fwd, the backward ones against plan_mlp_bwd through
+ngm_debug_plan_bwd (both csrc/ngm_api.hip), with TI / TH = ceil(dim / 16) and MI / MH = ceil(dim / 32):
+  forward shape <MI,MH,L>     NGM_FWD_SHAPES (csrc/ngm_launch.h), shared by the three forward launchers: <2,2,2> <2,2,1> <1,1,1>
+                              <1,1,2> <2,2,3>; bf16x3 only where ngm_fwd_split_takes: <2,2,L<=2>, Fourier / none, skip no (points /
+                              knn: a preference; fused forward: `auto` resolves to it, explicit `bf16x3` elsewhere is refused by
+                              the plan)
   variant 3  k_field_bwd_b3   stash kind 1 (TI = TH = 4, skip no, Fourier / NeRF / none, L <= 2) and mode != f32
   variant 5  k_hash_mlp_bwd   hash, L = 1, 17..32 features, <= 32 hidden units, mode != f32, fused step only
   variant 2  k_field_bwd16s   stash kind 1 and mode f32, fused step only

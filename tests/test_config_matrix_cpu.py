@@ -1,6 +1,7 @@
 """CPU companion of tests/test_gpu_config_matrix.py: the table of tests/_config_matrix.py builds and evaluates in the oracle,
 its fused-step problems can be made kink-free inside the usual cap, it is internally consistent, and the library's validator
-draws the line where the table says it does (argument validation needs no GPU)."""
+draws the line where the table says it does (argument validation needs no GPU), and the library's two host-side plans
+(ngm_debug_plan_fwd, ngm_debug_plan_bwd) reproduce the table's forward and backward columns."""
 import ctypes as C
 
 import pytest
@@ -114,13 +115,23 @@ def _plan(lib, fc, rc, F, n, stash_offered=0):
     return (status,) + tuple(out)
 
 
+ARITHMETIC = {K.MATMUL["f32"]: "f32", K.MATMUL["bf16x3"]: "bf16x3"}
+SURFACE = {"render": 0, "points": 1, "knn": 2}          # ngm_debug_plan_fwd (= the index of ngm_debug_last_matmul)
+
+
+def _plan_fwd(lib, fc, rc, surface, F, n, guided=1):
+    """ngm_debug_plan_fwd: (status, {shape, arithmetic, one-tile, waves, LDS bytes, neus instance})"""
+    out = (C.c_int32 * 12)()
+    status = lib.ngm_debug_plan_fwd(C.byref(fc), None if rc is None else C.byref(rc), SURFACE[surface], F, n, guided, out)
+    return status, dict(shape=f"<{out[0]},{out[1]},{out[2]}>", mm=ARITHMETIC.get(out[3]), one_tile=out[4], waves=out[5], lds=out[6],
+                        neus=out[7])
+
+
 def test_plan_query_reproduces_the_step_and_autograd_columns(lib):
     """The backward plan (plan_mlp_bwd behind ngm_debug_plan_bwd: no launch, no GPU) against every (entry, mode) cell of the
-    `step` and `autograd` columns: forward arithmetic, backward variant and fusion flag at both STEP_SHAPES; the point
-    evaluation's variant at P = 257 with a stash offered and without; three-layer entries refused with NGM_E_UNSUPPORTED.
-    Left out: the cells whose refusal is the forward launcher's (explicit bf16x3 outside its shape), not the plan's."""
-    arithmetic = {K.MATMUL["f32"]: "f32", K.MATMUL["bf16x3"]: "bf16x3"}
-    skipped = set()
+    `step` and `autograd` columns: backward variant and fusion flag at both STEP_SHAPES, the forward arithmetic from the forward
+    plan (ngm_debug_plan_fwd); the point evaluation's variant at P = 257 with a stash offered and without; three-layer entries
+    refused with NGM_E_UNSUPPORTED; an explicit bf16x3 outside its shape refused by the forward plan, by name."""
     for e in CM.ENTRIES:
         if e["shape"] is None:
             continue
@@ -130,11 +141,14 @@ def test_plan_query_reproduces_the_step_and_autograd_columns(lib):
                 rc = K.render_cfg(geometry_mode=e["geometry"], num_samples_coarse=n_c, num_samples_guided=n_g)
                 status, variant, fused, kind, layers, mm = _plan(lib, fc, rc, F, R)
                 if o == CM.REFUSE and fc.num_layers <= 2:
-                    skipped.add((e["name"], mode))
+                    fstatus, _ = _plan_fwd(lib, fc, rc, "render", F, R)
+                    assert fstatus == K.NGM_E_UNSUPPORTED and "bf16x3" in lib.ngm_last_error().decode(), (e["name"], mode)
                 elif o == CM.REFUSE:
                     assert status == K.NGM_E_UNSUPPORTED and "forward only" in lib.ngm_last_error().decode(), (e["name"], mode)
                 else:
-                    assert status == K.NGM_OK and (arithmetic[mm], variant, fused) == o[1:], (e["name"], mode, (F, R))
+                    fstatus, f = _plan_fwd(lib, fc, rc, "render", F, R)
+                    assert status == fstatus == K.NGM_OK and (f["mm"], variant, fused) == o[1:], (e["name"], mode, (F, R))
+                    assert ARITHMETIC[mm] == f["mm"] and f["shape"] == e["shape"]
                     assert (variant not in (2, 3, 5) or kind == (2 if variant == 5 else 1)) and (layers > 0) == (kind != 0)
         for mode, o in e["autograd"].items():
             fc = K.field_cfg(**e["fkw"], matmul_mode=mode)
@@ -144,6 +158,94 @@ def test_plan_query_reproduces_the_step_and_autograd_columns(lib):
             else:
                 assert [g[:2] for g in got] == [(K.NGM_OK, o[1]), (K.NGM_OK, o[2])], (e["name"], mode)
                 assert [g[3] for g in got] == [int(o[1] == 3), 0] and all(g[2] == 0 for g in got)    # only k_field_bwd_b3 reads a stash
-    forward_refusals = {(e["name"], mode) for e in CM.ENTRIES if e["shape"] is not None for mode, o in e["render"].items()
-                        if o == CM.REFUSE and e["fkw"]["num_layers"] <= 2}
-    assert skipped == forward_refusals and len(skipped) <= 2
+
+
+def test_forward_plan_reproduces_the_forward_columns(lib):
+    """The forward plan (plan_fwd behind ngm_debug_plan_fwd: no launch, no GPU) against every (entry, mode) cell of the `points`,
+    `render` and `knn` columns: compiled shape and arithmetic -- 257 points per field, the 7-field kNN case, the fused forward at
+    both STEP_SHAPES.  A refused cell is NGM_E_UNSUPPORTED: the validator's for the entries without a shape, the plan's -- naming
+    the mode -- for an explicit bf16x3 outside its shape."""
+    for e in CM.ENTRIES:
+        for surface in ("points", "render", "knn"):
+            for mode, o in e[surface].items():
+                fc = K.field_cfg(**e["fkw"], matmul_mode=mode)
+                if surface == "render":
+                    calls = [(K.render_cfg(geometry_mode=e["geometry"], num_samples_coarse=n_c, num_samples_guided=n_g), F, R)
+                             for F, R, n_c, n_g in CM.STEP_SHAPES]
+                else:
+                    calls = [(None, 3, 257)] if surface == "points" else [(None, 7, 500)]
+                for rc, F, n in calls:
+                    status, f = _plan_fwd(lib, fc, rc, surface, F, n)
+                    msg = lib.ngm_last_error().decode()
+                    if o == CM.REFUSE:
+                        assert status == K.NGM_E_UNSUPPORTED, (e["name"], surface, mode)
+                        assert ("num_layers" in msg) if e["shape"] is None else (mode == "bf16x3" and "bf16x3" in msg and e["shape"] in msg)
+                    else:
+                        assert status == K.NGM_OK and (f["shape"], f["mm"]) == (e["shape"], o[1]), (e["name"], surface, mode, f)
+                        assert f["waves"] in (4, 8) and 0 < f["lds"] <= 160 * 1024 and f["neus"] == int(surface == "render" and e["geometry"] == "neus")
+
+
+def test_validator_and_shape_table_agree(lib):
+    """check_field_cfg's width and depth rules against the one list of compiled shapes (NGM_FWD_SHAPES): over every Fourier
+    (dim_enc, dim_hidden, num_layers) the validator either refuses, or the forward plan of each surface finds a compiled shape
+    -- the plan's own "no forward kernel" refusal is unreachable in the full build -- and every compiled shape is reached."""
+    fc, rc = K.field_cfg(), K.render_cfg(num_samples_coarse=5, num_samples_guided=2)
+    reached = set()
+    for L_ in range(1, K.NGM_MAX_LAYERS + 1):
+        for D in range(3, 65):
+            for H in range(1, 65):
+                fc.dim_enc, fc.dim_hidden, fc.num_layers = D, H, L_
+                got = [_plan_fwd(lib, fc, rc if s == "render" else None, s, 3, 37) for s in ("render", "points", "knn")]
+                assert len({g[0] for g in got}) == 1 and got[0][0] in (K.NGM_OK, K.NGM_E_UNSUPPORTED), (D, H, L_, got)
+                if got[0][0] == K.NGM_OK:
+                    assert len({g[1]["shape"] for g in got}) == 1 and got[0][1]["shape"] in CM.FORWARD_SHAPES, (D, H, L_, got)
+                    reached.add(got[0][1]["shape"])
+                else:
+                    assert "no forward kernel" not in lib.ngm_last_error().decode(), (D, H, L_)
+    assert reached == set(CM.FORWARD_SHAPES)
+
+
+def test_neus_fused_rule_is_the_plans(lib):
+    """NeuralGraphRenderer._neus_fused (which neus configurations take the fused step rather than the staged one) says what the
+    forward plan says about the fused forward with geometry neus, for every entry that has a forward at all."""
+    import types
+    from neural_graph_mapping_amd.renderer import NeuralGraphRenderer
+    rc = K.render_cfg(geometry_mode="neus", num_samples_coarse=5, num_samples_guided=2)
+    seen = set()
+    for e in CM.ENTRIES:
+        if e["shape"] is None:
+            continue
+        for mode in ("f32", "auto"):
+            fc = K.field_cfg(**e["fkw"], matmul_mode=mode)
+            status, f = _plan_fwd(lib, fc, rc, "render", 3, 37)
+            rule = NeuralGraphRenderer._neus_fused(types.SimpleNamespace(_fc=fc))
+            assert rule == (status == K.NGM_OK), (e["name"], mode)
+            assert status in (K.NGM_OK, K.NGM_E_UNSUPPORTED) and (status != K.NGM_OK or (f["neus"] == 1 and f["mm"] == "f32"))
+            seen.add(rule)
+    assert seen == {True, False}
+
+
+ONE_TILE_NETS = ("fourier64_L2", "hash16_L1")
+
+
+def _one_tile(lib, name, F):
+    """512 rays x (8 + 16) samples per field, mode auto: rays per wave x samples per ray <= 32 at F = 4 (256 CUs: 64 workgroups of
+    8 rays per field, one ray per wave), not at F = 8 (16 rays per workgroup, two per wave)"""
+    fc = K.field_cfg(**CM.BY_NAME[name]["fkw"], matmul_mode="auto")
+    status, f = _plan_fwd(lib, fc, K.render_cfg(num_samples_coarse=8, num_samples_guided=16), "render", F, 512)
+    assert status == K.NGM_OK
+    return f["one_tile"]
+
+
+def test_one_tile_wave_step_is_planned_for_small_batches_only(lib):
+    """The one-tile rule without a GPU (the library assumes the MI355X's 256 CUs there), and its switch: with NGM_NO_HALF_STEP=1
+    (read once per process: a child process) no plan is one-tile."""
+    import os
+    import subprocess
+    import sys
+    for name in ONE_TILE_NETS:
+        assert (_one_tile(lib, name, 4), _one_tile(lib, name, 8)) == (1, 0), name
+    code = ("import sys; sys.path[:0] = %r; import test_config_matrix_cpu as T; from neural_graph_mapping_amd import _capi as K; "
+            "print([T._one_tile(K.lib(), n, F) for n in T.ONE_TILE_NETS for F in (4, 8)])" % (sys.path,))
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, NGM_NO_HALF_STEP="1"), capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.strip().splitlines()[-1] == "[0, 0, 0, 0]", (r.stdout, r.stderr[-2000:])
