@@ -1,13 +1,15 @@
 """End-to-end smoke of the drop-in path on one MI355X: keyframe store -> training-target sampler -> fused
 training step (forward, losses, backward, sparse Adam) -> kNN-blended render -> PSNR.
 
-    python examples/fit_synthetic.py [--iters 300] [--device-iteration]
+    python examples/fit_synthetic.py [--iters 300] [--device-iteration | --live]
 
 A synthetic RGB-D "scan" of a textured wall with a sphere in front of it is observed from a few keyframes; fields
 on a grid in front of the cameras are trained exactly as NeuralGraphMap._optimization_iteration would
 (rm.py:1123-1221), with every tensor operation of the hot path running in the HIP kernels.
 --device-iteration trains through NeuralGraphRenderer.capture_training instead: targets drawn on the device and consumed at
 their fixed capacity, sampler + training step replayed as one captured graph per iteration (no host synchronisation).
+--live runs the mapping loop's shape instead of a frozen scene: a new current frame every five iterations, keyframes added
+to a KeyframeStore while training, the observed fields recomputed per frame on the device -- and still ONE capture.
 """
 import argparse
 import math
@@ -61,8 +63,10 @@ def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0):
     "device" -- capture_training: one graph replay per iteration;
     "materialize" -- the same device-drawn targets and jitter stream as "device" (sampler seed 0, iteration i; jitter
     seed `jitter_seed`), but sliced to their count on the host every iteration (DeviceTarget.materialize: one
-    synchronisation, a data-dependent batch shape)."""
-    if loop not in ("torch", "device", "materialize"):
+    synchronisation, a data-dependent batch shape);
+    "live" -- capture_training once over fixed-capacity buffers (KeyframeStore, observed_fields_device(out=...)): the
+    current frame changes every 5 iterations, each camera's first visit adds a keyframe, the graph is never re-captured."""
+    if loop not in ("torch", "device", "materialize", "live"):
         raise ValueError(loop)
     torch.manual_seed(0)
     dev = torch.device(device)
@@ -97,8 +101,30 @@ def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0):
 
     losses = []
     step = r.capture_training(cur, c2ws, store, cid, 32, 256, seed=jitter_seed, camera=cam) if loop == "device" else None
+    if loop == "live":
+        from neural_graph_mapping_amd.keyframes import KeyframeStore
+        ks = KeyframeStore(len(eyes) + 1, H, W, device=dev)
+        ids_buf = torch.full((NF,), -1, dtype=torch.int64, device=dev)
+        cnt_buf = torch.zeros(1, dtype=torch.int32, device=dev)
+        r.track_training_iterations = True
+
+        def next_frame(f):
+            k = f % len(eyes)
+            ks.set_current(store[k], c2ws[k], frame_id=f)
+            if f < len(eyes):
+                ks.add_keyframe(store[k], f)                        # a camera's first visit becomes a keyframe
+            r.observed_fields_device(ks.nc_rgbd[0], ks.c_c2w[0], seed=0, frame=f, out=(ids_buf, cnt_buf), camera=cam)
     for it in range(iters):
-        if loop == "device":
+        if loop == "live":
+            if it % 5 == 0:                                         # num_iterations_per_frame: 5
+                next_frame(it // 5)
+            if step is None:
+                step = r.capture_training(ids_buf, ks.c_c2w, ks.nc_rgbd, ks.frame_cid_to_ncid, 32, 256, seed=jitter_seed,
+                                          camera=cam, current_count=cnt_buf, num_frames=ks.num_frames)
+                graph = step.graph
+            out = step()
+            assert step.graph is graph                              # one capture serves every frame and keyframe
+        elif loop == "device":
             out = step()
         elif loop == "materialize":
             tgt = r.sample_target_mv_device(cur, c2ws, store, cid, 32, 256, camera=cam, seed=0, iteration=it).materialize()
@@ -122,6 +148,9 @@ def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0):
     if not quiet:
         print(f"keyframe 0 re-rendered: PSNR {psnr:.2f} dB, median |depth error| {derr:.3f} m over "
               f"{100 * float(valid.float().mean()):.0f} % of the pixels ({NF} fields)")
+        if loop == "live":
+            print(f"{ks.num_keyframes} keyframes, {int(cnt_buf)} fields observed by the last frame, "
+                  f"{int(r.get_field_ids(50).numel())} fields trained in at least 50 iterations")
     return losses, psnr, derr
 
 
@@ -130,5 +159,7 @@ if __name__ == "__main__":
     ap.add_argument("--iters", type=int, default=300)
     ap.add_argument("--device-iteration", action="store_true",
                     help="train through capture_training: device-drawn targets, one captured graph per iteration")
+    ap.add_argument("--live", action="store_true",
+                    help="one captured graph across changing frames and keyframes (KeyframeStore + observed_fields_device)")
     a = ap.parse_args()
-    main(a.iters, loop="device" if a.device_iteration else "torch")
+    main(a.iters, loop="live" if a.live else "device" if a.device_iteration else "torch")

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define NGM_ABI_VERSION 11 /* 11 (+ addition, number unchanged: ngm_render_fwd_counted / ngm_render_bwd_counted / ngm_render_bwd_adam_counted, the training step launched at a capacity with the number of active rows in device memory; nothing existing changed); 11 (+ addition, number unchanged: ngm_target_sample_mv_workspace / ngm_target_sample_mv and struct ngm_target_sample, the device-side training-target sampler; nothing existing changed); 11: ngm_field_eval_stash_bytes / ngm_field_eval_fwd_train / ngm_field_eval_bwd_stash (training forward of the point evaluation writes the activation stash, its backward is the fused step's kernel); 10: ngm_field_cfg.activation_stash / .hash_grad_atomics (per configuration, no process-wide switch), empty loss selections report NaN like the reference; 9: ngm_sample_rays_weighted; 8: ngm_peer_set_timeout (a time-out now also poisons the sums with NaN); 7: ngm_encode_bwd; 6: ngm_render_eval_knn; 5: ngm_encode_fwd, ngm_render_bwd_seeded_vars, *_nll loss modes (+ loss-sum slot 10), peer status bits */
+#define NGM_ABI_VERSION 11 /* 11 (+ addition, number unchanged: ngm_target_sample_mv_live(_workspace) / struct ngm_target_live, ngm_target_observed_fields(_workspace) / struct ngm_observed_fields, ngm_field_counts_add: the sampler with its counts in device memory, the observed-field test and the per-field iteration counts on the device; nothing existing changed); 11 (+ addition, number unchanged: ngm_render_fwd_counted / ngm_render_bwd_counted / ngm_render_bwd_adam_counted, the training step launched at a capacity with the number of active rows in device memory; nothing existing changed); 11 (+ addition, number unchanged: ngm_target_sample_mv_workspace / ngm_target_sample_mv and struct ngm_target_sample, the device-side training-target sampler; nothing existing changed); 11: ngm_field_eval_stash_bytes / ngm_field_eval_fwd_train / ngm_field_eval_bwd_stash (training forward of the point evaluation writes the activation stash, its backward is the fused step's kernel); 10: ngm_field_cfg.activation_stash / .hash_grad_atomics (per configuration, no process-wide switch), empty loss selections report NaN like the reference; 9: ngm_sample_rays_weighted; 8: ngm_peer_set_timeout (a time-out now also poisons the sums with NaN); 7: ngm_encode_bwd; 6: ngm_render_eval_knn; 5: ngm_encode_fwd, ngm_render_bwd_seeded_vars, *_nll loss modes (+ loss-sum slot 10), peer status bits */
 /* Array bound of the per-layer pointers below (hidden layers; +1 output layer).  NOT the depth every entry point takes -- the
  * kernels are compiled per depth L = num_layers and padded width class (dim_enc and dim_hidden both <= 32, or both 33..64):
  *   L = 1, 2   every entry point, both width classes (forward, backward, fused step, kNN evaluation)
@@ -577,6 +577,68 @@ typedef struct ngm_target_sample {
 int64_t ngm_target_sample_mv_workspace(int32_t num_frames, int32_t num_current, int32_t num_fields, int32_t capacity);
 int ngm_target_sample_mv(const ngm_keyframes* kf, const ngm_target_sample* s, const ngm_target_out* out, void* workspace,
                          int64_t workspace_bytes, void* stream);
+
+/* ---- the same sampler with its counts in device memory (opt-in; additive to ABI 11) ---------------------------------
+ * ngm_target_sample_mv whose num_current and num_frames are read from DEVICE int32s at run time, so that one captured graph
+ * serves every frame (a new observed set) and every keyframe (a longer pose list) -- same three kernels, same keying, and
+ * bit for bit the result of ngm_target_sample_mv called with those counts.  The host gives the maxima only:
+ *   kf->num_frames = max_frames (row stride of the workspace, grids, the LDS / workspace decision for the keyframe lists),
+ *   s->num_current = max_current, s->num_observed = min(T / 2, max_current), s->num_random = min(T, num_fields)  (the
+ *   sizes of subset_observed / subset_random), s->capacity = min(min(T, num_fields), fields of this rank)
+ * with T = live->num_train_fields.  On the device: nc = clamp(*num_current, 0, max_current), nf = clamp(*num_frames, 0,
+ * max_frames), n_obs = min(T / 2, nc), n_rand = max(min(T - n_obs, num_fields - n_obs), 0) -- their sum is min(T, num_fields)
+ * whatever nc is, hence the host-known capacity.  *num_observed / *num_random receive n_obs / n_rand; subset_observed /
+ * subset_random hold -1 past them.  Nothing past nc in current_field_ids, or past nf in kf->c2ws / kf->frame_to_store, is
+ * read.  nf == 0 is legal: no field is seen, *count = 0. */
+typedef struct ngm_target_live {
+  const int32_t* num_current;   /* device (1)                                                          */
+  const int32_t* num_frames;    /* device (1)                                                          */
+  int32_t* num_observed;        /* device out (1)                                                      */
+  int32_t* num_random;          /* device out (1)                                                      */
+  int32_t num_train_fields;     /* T                                                                   */
+  int32_t reserved0;
+} ngm_target_live;
+int64_t ngm_target_sample_mv_live_workspace(int32_t max_frames, int32_t max_current, int32_t num_fields, int32_t capacity);
+int ngm_target_sample_mv_live(const ngm_keyframes* kf, const ngm_target_sample* s, const ngm_target_live* live,
+                              const ngm_target_out* out, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- observed fields of one RGB-D frame, on the device (NeuralGraphMap._get_observed_fields, rm.py:1642-1670) ---------
+ * Which fields does the frame see?  num_points pixels are drawn uniformly without replacement among those with depth != 0
+ * (camera.py:374 + rm.py:1651), back-projected (OpenGL camera frame), and a field is observed when its sphere's AABB meets
+ * the points' AABB (geometry.py:26-42) and some segment camera origin -> point passes through the sphere (geometry.py:67-105).
+ * No host synchronisation, fixed output shapes: 11 launches (3 with subset_in).
+ * Draw: key_p = (word 0 of Philox block ctr = linear pixel index p, stream 0x54470005, offset = frame) << 32 | p over the
+ * pixels with depth; the num_points smallest keys (radix select across workgroups, integer atomics: the chosen SET is
+ * deterministic, the order of `pixels` is not).  Fewer valid pixels than num_points: all of them; none: *current_count = 0.
+ * frame >= 0: this frame; < 0: *frame_dev is read and advanced by one.  subset_in (num_points linear pixel indices, entries
+ * outside [0, H*W) unused) replaces the draw.  1 <= num_points <= NGM_OBSERVED_MAX_POINTS, H*W < 2^31. */
+#define NGM_OBSERVED_MAX_POINTS 2048
+typedef struct ngm_observed_fields {
+  const float* rgbd;              /* (H,W,4) the frame [r,g,b,depth]                                    */
+  const float* c2w;               /* DEVICE (4,4) row-major camera pose, read at run time               */
+  const float* field_positions;   /* (>= num_fields, 3)                                                 */
+  int32_t height, width;
+  int32_t num_fields, num_points;
+  float fx, fy, cx, cy;           /* intrinsics at pixel centre 0                                       */
+  float radius;                   /* _field_radius                                                      */
+  int32_t reserved0;
+  uint64_t seed;
+  int64_t frame;
+  int64_t* frame_dev;
+  const int64_t* subset_in;       /* (num_points) or NULL                                               */
+  int64_t* current_field_ids;     /* out (num_fields): observed ids ascending, -1 past *current_count   */
+  int32_t* current_count;         /* out (1)                                                            */
+  int64_t* pixels;                /* out (num_points): chosen linear pixel indices, -1 past *num_used   */
+  int32_t* num_used;              /* out (1): min(num_points, valid pixels)                             */
+} ngm_observed_fields;
+int64_t ngm_target_observed_fields_workspace(int32_t height, int32_t width);
+int ngm_target_observed_fields(const ngm_observed_fields* a, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* training_iterations[field_ids[i]] += 1 for i < min(rows, *count) (count == NULL: rows), skipping -1 (padding rows) and
+ * ids outside [0, num_fields): the reference's `training_iterations[field_ids] += 1` (rm.py:1188) as one launch that a
+ * captured iteration can hold.  field_ids duplicate-free, as the sampler's are. */
+int ngm_field_counts_add(const int64_t* field_ids, const int32_t* count, int32_t rows, int64_t* training_iterations,
+                         int32_t num_fields, void* stream);
 
 /* Device part of NeuralGraphMap._sample_target_sv (rm.py:1461-1583), the single-view variant (`update_mode: single_view`):
  * hit (F,N) u8 = the segment camera origin -> point n of the (subsampled) back-projected depth image passes through the

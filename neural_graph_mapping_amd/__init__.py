@@ -4,4 +4,4 @@ Only the per-field NeRF path is here (ray sampler, encodings, per-field MLP fwd/
 losses, sparse Adam); the SLAM / mapping loop of the reference stays in the caller.  All compute
 goes through hand-written HIP kernels behind the C ABI in include/ngm_hip.h.
 """
-__all__ = ["models", "renderer", "ops", "distributed", "build"]
+__all__ = ["models", "renderer", "ops", "distributed", "keyframes", "build"]

@@ -144,6 +144,39 @@ def target_sample_mv_plan(num_current, num_fields, num_train_fields, num_rays, w
     return n_obs, n_rand, min(n_obs + n_rand, owned)
 
 
+NGM_OBSERVED_MAX_POINTS = 2048                 # include/ngm_hip.h: points one ngm_target_observed_fields call may draw
+
+
+class TargetLive(C.Structure):
+    _fields_ = [("num_current", C.c_void_p), ("num_frames", C.c_void_p), ("num_observed", C.c_void_p),
+                ("num_random", C.c_void_p), ("num_train_fields", C.c_int32), ("reserved0", C.c_int32)]
+
+
+class ObservedFields(C.Structure):
+    _fields_ = [("rgbd", f32p), ("c2w", f32p), ("field_positions", f32p), ("height", C.c_int32), ("width", C.c_int32),
+                ("num_fields", C.c_int32), ("num_points", C.c_int32), ("fx", C.c_float), ("fy", C.c_float),
+                ("cx", C.c_float), ("cy", C.c_float), ("radius", C.c_float), ("reserved0", C.c_int32),
+                ("seed", C.c_uint64), ("frame", C.c_int64), ("frame_dev", C.c_void_p), ("subset_in", C.c_void_p),
+                ("current_field_ids", C.c_void_p), ("current_count", C.c_void_p), ("pixels", C.c_void_p),
+                ("num_used", C.c_void_p)]
+
+
+def target_sample_mv_live_plan(max_current, num_fields, num_train_fields, num_rays, world_size=1, rank=0):
+    """Host-side sizes of ngm_target_sample_mv_live: (max_observed, max_random, capacity) = (min(T // 2, max_current),
+    min(T, num_fields), min(min(T, num_fields), fields of this rank)): what target_sample_mv_plan gives for every count
+    of current fields, since n_obs + n_rand = min(T, num_fields) whatever it is.  Raises on bad input."""
+    target_sample_mv_plan(0, num_fields, num_train_fields, num_rays, world_size, rank)
+    if isinstance(max_current, bool) or not isinstance(max_current, int):
+        raise TypeError(f"target_sample_mv_live: max_current must be an int, got {type(max_current).__name__}")
+    if max_current < 1:
+        raise ValueError(f"target_sample_mv_live: max_current must be >= 1, got {max_current}")
+    if max_current > num_fields:
+        raise ValueError(f"target_sample_mv_live: max_current {max_current} but only {num_fields} fields in the map")
+    n_all = min(num_train_fields, num_fields)
+    owned = (num_fields - rank + world_size - 1) // world_size if num_fields > rank else 0
+    return min(num_train_fields // 2, max_current), n_all, min(n_all, owned)
+
+
 _lib = None
 
 
@@ -244,6 +277,16 @@ def lib():
     L.ngm_target_sample_mv_workspace.restype = i64
     L.ngm_target_sample_mv.argtypes = [P(Keyframes), P(TargetSample), P(TargetOut), vp, i64, vp]
     L.ngm_target_sample_mv.restype = C.c_int
+    L.ngm_target_sample_mv_live_workspace.argtypes = [i32, i32, i32, i32]
+    L.ngm_target_sample_mv_live_workspace.restype = i64
+    L.ngm_target_sample_mv_live.argtypes = [P(Keyframes), P(TargetSample), P(TargetLive), P(TargetOut), vp, i64, vp]
+    L.ngm_target_sample_mv_live.restype = C.c_int
+    L.ngm_target_observed_fields_workspace.argtypes = [i32, i32]
+    L.ngm_target_observed_fields_workspace.restype = i64
+    L.ngm_target_observed_fields.argtypes = [P(ObservedFields), vp, i64, vp]
+    L.ngm_target_observed_fields.restype = C.c_int
+    L.ngm_field_counts_add.argtypes = [vp, vp, i32, vp, i32, vp]
+    L.ngm_field_counts_add.restype = C.c_int
     L.ngm_marching_cubes_workspace.argtypes = [i32, i32, i32]
     L.ngm_marching_cubes_workspace.restype = i64
     L.ngm_marching_cubes_count.argtypes = [vp, i32, i32, i32, f32, vp, vp, i64, vp]
@@ -276,6 +319,8 @@ EXPORTED = ["ngm_abi_version", "ngm_last_error", "ngm_device_info", "ngm_permuto
             "ngm_field_eval_knn", "ngm_field_eval_knn_workspace", "ngm_render_eval_knn", "ngm_render_eval_knn_workspace", "ngm_adam_sparse_multi", "ngm_step_advance", "ngm_profile_enable", "ngm_profile_reset", "ngm_profile_read",
             "ngm_debug_phase_cycles", "ngm_debug_fwd_phase_cycles", "ngm_debug_last_bwd_variant", "ngm_debug_last_matmul", "ngm_debug_last_fwd_one_tile", "ngm_debug_last_comp_fused", "ngm_debug_disable_fused_comp", "ngm_debug_stash_mode", "ngm_debug_last_stash_mode", "ngm_debug_plan_bwd", "ngm_debug_plan_fwd", "ngm_target_visibility", "ngm_target_rays", "ngm_target_sv_intersect", "ngm_target_sv_rays",
             "ngm_target_sample_mv_workspace", "ngm_target_sample_mv",
+            "ngm_target_sample_mv_live_workspace", "ngm_target_sample_mv_live", "ngm_target_observed_fields_workspace",
+            "ngm_target_observed_fields", "ngm_field_counts_add",
             "ngm_render_fwd_counted", "ngm_render_bwd_counted", "ngm_render_bwd_adam_counted",
             "ngm_peer_mailbox_bytes", "ngm_peer_alloc", "ngm_peer_free", "ngm_ipc_export", "ngm_ipc_open", "ngm_ipc_close", "ngm_loss_exchange", "ngm_peer_set_timeout",
             "ngm_marching_cubes_workspace", "ngm_marching_cubes_count", "ngm_marching_cubes_emit", "ngm_marching_cubes_tables"]

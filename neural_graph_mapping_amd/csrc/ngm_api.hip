@@ -514,6 +514,71 @@ int ngm_target_sample_mv(const ngm_keyframes* kf, const ngm_target_sample* s, co
   return check_launch("ngm_target_sample_mv");
 }
 
+int64_t ngm_target_sample_mv_live_workspace(int32_t max_frames, int32_t max_current, int32_t num_fields, int32_t capacity) {
+  if (max_frames < 1 || max_current < 1 || num_fields < 0 || capacity < 0 || capacity > NGM_TARGET_MAX_DRAW) return -1;
+  return ngm_target_sample_mv_bytes(max_frames, max_current, num_fields, capacity);
+}
+int ngm_target_sample_mv_live(const ngm_keyframes* kf, const ngm_target_sample* s, const ngm_target_live* live,
+                              const ngm_target_out* out, void* workspace, int64_t workspace_bytes, void* stream) {
+  int e = check_keyframes(kf);
+  if (e) return e;
+  if (!s || !out || !live) return fail(NGM_E_INVALID, "ngm_target_sample_mv_live: NULL argument");
+  if (s->num_current < 1 || s->num_fields < 0 || s->num_rays < 1 || s->world_size < 1 || s->rank < 0 || s->rank >= s->world_size ||
+      live->num_train_fields < 0)
+    return fail(NGM_E_INVALID, "ngm_target_sample_mv_live: bad sizes (max_current >= 1, num_rays >= 1, 0 <= rank < world_size)");
+  if (s->num_current > s->num_fields) return fail(NGM_E_INVALID, "ngm_target_sample_mv_live: max_current > num_fields");
+  const int32_t T = live->num_train_fields;
+  const int32_t max_obs = T / 2 < s->num_current ? T / 2 : s->num_current, n_all = T < s->num_fields ? T : s->num_fields;
+  if (s->num_observed != max_obs || s->num_random != n_all)
+    return fail(NGM_E_INVALID, "ngm_target_sample_mv_live: num_observed / num_random must be their maxima min(T / 2, max_current) / min(T, num_fields)");
+  if (n_all > NGM_TARGET_MAX_DRAW) return fail(NGM_E_UNSUPPORTED, "ngm_target_sample_mv_live: more than NGM_TARGET_MAX_DRAW fields drawn");
+  const int64_t owned = s->num_fields > s->rank ? ((int64_t)s->num_fields - s->rank + s->world_size - 1) / s->world_size : 0;
+  if (s->capacity != (n_all < owned ? n_all : owned))
+    return fail(NGM_E_INVALID, "ngm_target_sample_mv_live: capacity must be min(min(T, num_fields), fields of this rank)");
+  if (!live->num_current || !live->num_frames || !live->num_observed || !live->num_random)
+    return fail(NGM_E_INVALID, "ngm_target_sample_mv_live: NULL device count");
+  if (!s->current_field_ids || (s->num_fields > 0 && !s->field_positions) || !s->count || !s->field_ids ||
+      (s->num_observed > 0 && !s->subset_observed) || (s->num_random > 0 && !s->subset_random) || !s->offsets || !s->frame_cids ||
+      !s->u_xy || (s->iteration < 0 && !s->iteration_dev))
+    return fail(NGM_E_INVALID, "ngm_target_sample_mv_live: NULL array (iteration < 0 needs iteration_dev)");
+  if (!out->ijs || !out->near || !out->far || !out->gt || !out->rgbds || !out->rgb_mask || !out->depth_mask || !out->term_probs ||
+      !out->term_mask)
+    return fail(NGM_E_INVALID, "ngm_target_sample_mv_live: NULL output array");
+  if ((int64_t)s->capacity * s->num_rays > INT32_MAX) return fail(NGM_E_UNSUPPORTED, "ngm_target_sample_mv_live: capacity x num_rays >= 2^31");
+  const int64_t need = ngm_target_sample_mv_bytes(kf->num_frames, s->num_current, s->num_fields, s->capacity);
+  if (!workspace || workspace_bytes < need) return fail(NGM_E_WORKSPACE, "ngm_target_sample_mv_live: workspace too small");
+  ngm_launch_target_sample_mv_live(*kf, *s, *live, *out, workspace, (hipStream_t)stream);
+  return check_launch("ngm_target_sample_mv_live");
+}
+
+int64_t ngm_target_observed_fields_workspace(int32_t height, int32_t width) {
+  if (height < 1 || width < 1 || (int64_t)height * width > INT32_MAX) return -1;
+  return ngm_target_observed_fields_bytes(height, width);
+}
+int ngm_target_observed_fields(const ngm_observed_fields* a, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!a) return fail(NGM_E_INVALID, "ngm_target_observed_fields: NULL argument");
+  if (a->height < 1 || a->width < 1 || (int64_t)a->height * a->width > INT32_MAX || a->num_fields < 0 || !(a->radius >= 0.f))
+    return fail(NGM_E_INVALID, "ngm_target_observed_fields: bad sizes (H, W >= 1, H x W < 2^31, num_fields >= 0, radius >= 0)");
+  if (a->num_points < 1 || a->num_points > NGM_OBSERVED_MAX_POINTS)
+    return fail(NGM_E_UNSUPPORTED, "ngm_target_observed_fields: 1 <= num_points <= NGM_OBSERVED_MAX_POINTS");
+  if (!a->rgbd || !a->c2w || (a->num_fields > 0 && (!a->field_positions || !a->current_field_ids)) || !a->current_count || !a->pixels ||
+      !a->num_used || (a->frame < 0 && !a->frame_dev))
+    return fail(NGM_E_INVALID, "ngm_target_observed_fields: NULL array (frame < 0 needs frame_dev)");
+  const int64_t need = ngm_target_observed_fields_bytes(a->height, a->width);
+  if (!workspace || workspace_bytes < need) return fail(NGM_E_WORKSPACE, "ngm_target_observed_fields: workspace too small");
+  ngm_launch_target_observed_fields(*a, workspace, (hipStream_t)stream);
+  return check_launch("ngm_target_observed_fields");
+}
+
+int ngm_field_counts_add(const int64_t* field_ids, const int32_t* count, int32_t rows, int64_t* training_iterations, int32_t num_fields,
+                         void* stream) {
+  if (rows < 0 || num_fields < 0 || (rows > 0 && (!field_ids || !training_iterations)))
+    return fail(NGM_E_INVALID, "ngm_field_counts_add: bad argument");
+  if (rows == 0 || num_fields == 0) return NGM_OK;
+  ngm_launch_field_counts_add(field_ids, count, rows, num_fields, training_iterations, (hipStream_t)stream);
+  return check_launch("ngm_field_counts_add");
+}
+
 int ngm_target_sv_intersect(int32_t F, int64_t N, const float* field_pos_cam, const float* points_cam, float radius, uint8_t* hit,
                             void* stream) {
   if (F < 0 || N < 0 || radius < 0.f || (F > 0 && N > 0 && (!field_pos_cam || !points_cam || !hit)))

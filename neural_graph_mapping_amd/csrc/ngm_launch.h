@@ -281,6 +281,12 @@ int ngm_launch_target_rays(const ngm_keyframes& kf, int F, int R, const float* f
 int64_t ngm_target_sample_mv_bytes(int num_frames, int num_current, int num_fields, int capacity);
 int ngm_launch_target_sample_mv(const ngm_keyframes& kf, const ngm_target_sample& s, const ngm_target_out& o, void* workspace,
                                 hipStream_t st);
+int ngm_launch_target_sample_mv_live(const ngm_keyframes& kf, const ngm_target_sample& s, const ngm_target_live& live,
+                                     const ngm_target_out& o, void* workspace, hipStream_t st);
+int64_t ngm_target_observed_fields_bytes(int height, int width);
+int ngm_launch_target_observed_fields(const ngm_observed_fields& a, void* workspace, hipStream_t st);
+int ngm_launch_field_counts_add(const int64_t* field_ids, const int32_t* count, int rows, int num_fields, int64_t* training_iterations,
+                                hipStream_t st);
 
 // flat parameter vector layout of one field: [enc_w][w0][b0]...[wL][bL]
 __host__ __device__ static inline int64_t ngm_param_offsets(const ngm_field_cfg* fc, int64_t* enc_off, int64_t* w_off, int64_t* b_off) {

@@ -312,7 +312,24 @@ __device__ void tsmv_k_smallest(const uint64_t* keys, int n, int k, uint64_t* ou
   __syncthreads();
 }
 
-__global__ __launch_bounds__(TSMV_DRAW_THREADS) void k_tsmv_draw(ngm_target_sample s, tsmv_ws w) {
+// The live variant (ngm_target_sample_mv_live): s.num_current / s.num_observed / s.num_random / kf.num_frames are the host's
+// MAXIMA (strides, grids, workspace), the counts in force are read from device memory by every kernel.  LIVE = false is the
+// code of ngm_target_sample_mv as it was: `lv` is not touched there.
+struct tsmv_live {
+  const int32_t* num_current;   // device: 0 <= * <= s.num_current (clamped)
+  const int32_t* num_frames;    // device: 0 <= * <= kf.num_frames (clamped)
+  int32_t* num_observed_out;    // device out (1)
+  int32_t* num_random_out;      // device out (1)
+  int num_train_fields;         // T
+};
+template <bool LIVE>
+__device__ __forceinline__ int tsmv_num_frames(const ngm_keyframes& kf, const tsmv_live& lv) {
+  if (!LIVE) return kf.num_frames;
+  return min(max(*lv.num_frames, 0), kf.num_frames);
+}
+
+template <bool LIVE>
+__global__ __launch_bounds__(TSMV_DRAW_THREADS) void k_tsmv_draw(ngm_target_sample s, tsmv_ws w, tsmv_live lv) {
   __shared__ uint64_t sel[NGM_TARGET_MAX_DRAW], scratch[NGM_TARGET_MAX_DRAW];
   __shared__ int64_t drawn[NGM_TARGET_MAX_DRAW];
   __shared__ int hist[256], st[4];
@@ -328,19 +345,28 @@ __global__ __launch_bounds__(TSMV_DRAW_THREADS) void k_tsmv_draw(ngm_target_samp
   __syncthreads();
   const uint64_t it = (uint64_t)s_iter;
   if (tid == 0 && s.iteration < 0) *s.iteration_dev = (int64_t)it + 1;          // after the barrier: every read is done
-  const int n_obs = s.num_observed, n_rand = s.num_random, n_all = n_obs + n_rand;
+  int num_current = s.num_current, n_obs = s.num_observed, n_rand = s.num_random;
+  if (LIVE) {                                            // block-uniform: every thread reads the same word
+    num_current = min(max(*lv.num_current, 0), s.num_current);
+    n_obs = min(lv.num_train_fields / 2, num_current);
+    n_rand = max(min(lv.num_train_fields - n_obs, s.num_fields - n_obs), 0);
+    if (tid == 0) { *lv.num_observed_out = n_obs; *lv.num_random_out = n_rand; }
+    for (int i = n_obs + tid; i < s.num_observed; i += nt) s.subset_observed[i] = -1;
+    for (int i = n_rand + tid; i < s.num_random; i += nt) s.subset_random[i] = -1;
+  }
+  const int n_all = n_obs + n_rand;
   // 1. observed fields: the n_obs smallest of (philox(id) << 32 | position), in key order = random order
-  for (int j = tid; j < s.num_current; j += nt) {
+  for (int j = tid; j < num_current; j += nt) {
     uint32_t q[4];
     philox_block(s.seed, it, (uint64_t)s.current_field_ids[j], TSMV_STREAM_OBS, q);
     w.keys[j] = ((uint64_t)q[0] << 32) | (uint32_t)j;
   }
   __syncthreads();
-  tsmv_k_smallest(w.keys, s.num_current, n_obs, sel, scratch, hist, st);
+  tsmv_k_smallest(w.keys, num_current, n_obs, sel, scratch, hist, st);
   for (int i = tid; i < n_obs; i += nt) {
     const int64_t j = (int64_t)(sel[i] & 0xFFFFFFFFull);       // < num_current: the select returns exactly n_obs keys
     s.subset_observed[i] = j;
-    drawn[i] = j < s.num_current ? s.current_field_ids[j] : -1;
+    drawn[i] = j < num_current ? s.current_field_ids[j] : -1;
   }
   __syncthreads();
   // 2. random fields: the n_rand smallest of (philox(f) << 32 | f) over the fields not drawn in 1.
@@ -423,11 +449,13 @@ __global__ __launch_bounds__(TSMV_DRAW_THREADS) void k_tsmv_draw(ngm_target_samp
   }
 }
 
-__global__ void k_tsmv_visibility(ngm_keyframes kf, int capacity, float radius, tsmv_ws w) {
+template <bool LIVE>
+__global__ void k_tsmv_visibility(ngm_keyframes kf, int capacity, float radius, tsmv_ws w, tsmv_live lv) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (int64_t)capacity * kf.num_frames) return;
   const int slot = (int)(idx / kf.num_frames), c = (int)(idx - (int64_t)slot * kf.num_frames);
   if (slot >= (int)w.hdr[1]) return;
+  if (LIVE && c >= tsmv_num_frames<true>(kf, lv)) return;          // kf.num_frames is the row stride there
   float4 box;
   const bool seen = target_visibility_one(kf, c, w.slot_pos[3 * slot], w.slot_pos[3 * slot + 1], w.slot_pos[3 * slot + 2],
                                           TSMV_NUM_OFFSETS, w.offsets, radius, &box);
@@ -436,7 +464,9 @@ __global__ void k_tsmv_visibility(ngm_keyframes kf, int capacity, float radius, 
   if (seen) w.flags[slot] = 1;                       // every writer stores the same 1 (flags zeroed by k_tsmv_draw)
 }
 
-__global__ __launch_bounds__(TSMV_RAY_THREADS) void k_tsmv_rays(ngm_keyframes kf, ngm_target_sample s, ngm_target_out o, tsmv_ws w) {
+template <bool LIVE>
+__global__ __launch_bounds__(TSMV_RAY_THREADS) void k_tsmv_rays(ngm_keyframes kf, ngm_target_sample s, ngm_target_out o, tsmv_ws w,
+                                                                tsmv_live lv) {
   __shared__ int list[TSMV_LDS_FRAMES];
   __shared__ int red[2], wave_cnt[TSMV_RAY_THREADS / 64];
   const int slot = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -478,9 +508,9 @@ __global__ __launch_bounds__(TSMV_RAY_THREADS) void k_tsmv_rays(ngm_keyframes kf
     return;
   }
   // the field's visible keyframes in ascending frame id (every block of the slot writes the same global list when it is used)
-  const int Nc = kf.num_frames;
-  int* lst = Nc <= TSMV_LDS_FRAMES ? list : w.list + (int64_t)slot * Nc;
-  const uint8_t* m = w.kf_mask + (int64_t)slot * Nc;
+  const int stride = kf.num_frames, Nc = tsmv_num_frames<LIVE>(kf, lv);       // stride == Nc unless LIVE
+  int* lst = stride <= TSMV_LDS_FRAMES ? list : w.list + (int64_t)slot * stride;
+  const uint8_t* m = w.kf_mask + (int64_t)slot * stride;
   int base = 0;
   for (int c0 = 0; c0 < Nc; c0 += TSMV_RAY_THREADS) {
     const int c = c0 + tid;
@@ -507,7 +537,7 @@ __global__ __launch_bounds__(TSMV_RAY_THREADS) void k_tsmv_rays(ngm_keyframes kf
   s.frame_cids[idx] = c;
   s.u_xy[2 * idx] = ux; s.u_xy[2 * idx + 1] = uy;
   target_ray_one(kf, w.slot_pos[3 * slot], w.slot_pos[3 * slot + 1], w.slot_pos[3 * slot + 2], s.radius,
-                 w.bbox[(int64_t)slot * Nc + c], (int64_t)c, ux, uy, o, idx);
+                 w.bbox[(int64_t)slot * stride + c], (int64_t)c, ux, uy, o, idx);
 }
 
 int64_t ngm_target_sample_mv_bytes(int num_frames, int num_current, int num_fields, int capacity) {
@@ -517,11 +547,286 @@ int ngm_launch_target_sample_mv(const ngm_keyframes& kf, const ngm_target_sample
                                 hipStream_t st) {
   tsmv_ws w;
   tsmv_layout(kf.num_frames, s.num_current, s.num_fields, s.capacity, (char*)workspace, &w);
-  hipLaunchKernelGGL(k_tsmv_draw, dim3(1), dim3(TSMV_DRAW_THREADS), 0, st, s, w);
+  const tsmv_live lv = {nullptr, nullptr, nullptr, nullptr, 0};
+  hipLaunchKernelGGL(k_tsmv_draw<false>, dim3(1), dim3(TSMV_DRAW_THREADS), 0, st, s, w, lv);
   if (s.capacity == 0) return 0;
   const int64_t pairs = (int64_t)s.capacity * kf.num_frames;
-  hipLaunchKernelGGL(k_tsmv_visibility, dim3((unsigned)((pairs + 127) / 128)), dim3(128), 0, st, kf, s.capacity, s.radius, w);
-  hipLaunchKernelGGL(k_tsmv_rays, dim3((unsigned)((s.num_rays + TSMV_RAY_THREADS - 1) / TSMV_RAY_THREADS), (unsigned)s.capacity),
-                     dim3(TSMV_RAY_THREADS), 0, st, kf, s, o, w);
+  hipLaunchKernelGGL(k_tsmv_visibility<false>, dim3((unsigned)((pairs + 127) / 128)), dim3(128), 0, st, kf, s.capacity, s.radius, w, lv);
+  hipLaunchKernelGGL(k_tsmv_rays<false>, dim3((unsigned)((s.num_rays + TSMV_RAY_THREADS - 1) / TSMV_RAY_THREADS), (unsigned)s.capacity),
+                     dim3(TSMV_RAY_THREADS), 0, st, kf, s, o, w, lv);
+  return 0;
+}
+// kf.num_frames = max_frames, s.num_current = max_current, s.num_observed / s.num_random = their maxima (include/ngm_hip.h)
+int ngm_launch_target_sample_mv_live(const ngm_keyframes& kf, const ngm_target_sample& s, const ngm_target_live& live,
+                                     const ngm_target_out& o, void* workspace, hipStream_t st) {
+  tsmv_ws w;
+  tsmv_layout(kf.num_frames, s.num_current, s.num_fields, s.capacity, (char*)workspace, &w);
+  const tsmv_live lv = {live.num_current, live.num_frames, live.num_observed, live.num_random, live.num_train_fields};
+  hipLaunchKernelGGL(k_tsmv_draw<true>, dim3(1), dim3(TSMV_DRAW_THREADS), 0, st, s, w, lv);
+  if (s.capacity == 0) return 0;
+  const int64_t pairs = (int64_t)s.capacity * kf.num_frames;
+  hipLaunchKernelGGL(k_tsmv_visibility<true>, dim3((unsigned)((pairs + 127) / 128)), dim3(128), 0, st, kf, s.capacity, s.radius, w, lv);
+  hipLaunchKernelGGL(k_tsmv_rays<true>, dim3((unsigned)((s.num_rays + TSMV_RAY_THREADS - 1) / TSMV_RAY_THREADS), (unsigned)s.capacity),
+                     dim3(TSMV_RAY_THREADS), 0, st, kf, s, o, w, lv);
+  return 0;
+}
+
+// ---- per-field training-iteration counts (rm.py:1188) -------------------------------------------------------------------
+// training_iterations[field_ids[i]] += 1 for i < min(rows, *count); -1 (padding) and ids outside [0, num_fields) skipped.
+__global__ void k_field_counts_add(const int64_t* __restrict__ field_ids, const int32_t* __restrict__ count, int rows, int num_fields,
+                                   int64_t* __restrict__ training_iterations) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int n = count ? min(max(*count, 0), rows) : rows;
+  if (i >= n) return;
+  const int64_t id = field_ids[i];
+  if (id < 0 || id >= num_fields) return;
+  atomicAdd(reinterpret_cast<unsigned long long*>(training_iterations + id), 1ull);   // integer: order does not matter
+}
+int ngm_launch_field_counts_add(const int64_t* field_ids, const int32_t* count, int rows, int num_fields, int64_t* training_iterations,
+                                hipStream_t st) {
+  hipLaunchKernelGGL(k_field_counts_add, dim3((rows + 255) / 256), dim3(256), 0, st, field_ids, count, rows, num_fields,
+                     training_iterations);
+  return 0;
+}
+
+// ---- observed fields of one RGB-D frame (NeuralGraphMap._get_observed_fields, rm.py:1642-1670) ---------------------------
+//   k_obs_keys     one thread per pixel (grid stride): key = (Philox word 0 of block ctr = pixel, stream ..05, offset = frame)
+//                  << 32 | pixel for pixels with depth != 0, TSMV_EXCLUDED for the others; zeroes the histograms and counters
+//   k_obs_hist x 8 MSB-first radix select of the num_points smallest keys over all workgroups: pass p histograms digit p of the
+//                  keys that match the prefix so far (LDS histogram per workgroup, integer atomics into the global one).  Every
+//                  workgroup derives the prefix from the finished histograms of the earlier passes itself, so there is no
+//                  launch and no host read between passes; passes after the select is decided return at once
+//   k_obs_collect  every key at or below the decided prefix takes a slot of `pixels` (integer atomic: the SET is
+//                  deterministic, the order is not) -- or copies subset_in
+//   k_obs_fields   one workgroup: back-projects the chosen pixels (LDS), their AABB, per field the AABB test and the
+//                  origin -> point segment test against the field sphere (k_target_sv_intersect's arithmetic), then the
+//                  observed ids ascending (ballot + prefix), -1 past the count; advances the frame counter
+constexpr uint32_t TSMV_STREAM_PIXELS = 0x54470005u;
+constexpr int OBS_THREADS = 256, OBS_MAX_BLOCKS = 1024, OBS_FIELD_THREADS = 1024, OBS_PASSES = 8;
+
+struct obs_ws {
+  uint64_t* keys;     // H x W
+  int* hist;          // OBS_PASSES x 256
+  int* counters;      // [0] slots handed out by k_obs_collect
+};
+static int64_t obs_layout(int64_t pixels, char* base, obs_ws* w) {
+  int64_t off = 0;
+  auto take = [&](int64_t bytes) { char* p = base ? base + off : nullptr; off += (bytes + 255) / 256 * 256; return p; };
+  obs_ws t;
+  t.keys = (uint64_t*)take(pixels * (int64_t)sizeof(uint64_t));
+  t.hist = (int*)take(OBS_PASSES * 256 * sizeof(int));
+  t.counters = (int*)take(4 * sizeof(int));
+  if (w) *w = t;
+  return off;
+}
+
+__global__ __launch_bounds__(OBS_THREADS) void k_obs_keys(ngm_observed_fields a, obs_ws w) {
+  const int64_t n = (int64_t)a.height * a.width;
+  const int64_t gid = (int64_t)blockIdx.x * OBS_THREADS + threadIdx.x, gsz = (int64_t)gridDim.x * OBS_THREADS;
+  if (gid < OBS_PASSES * 256) w.hist[gid] = 0;            // the grid has at least OBS_PASSES workgroups (see the launch)
+  if (gid < 4) w.counters[gid] = 0;
+  const uint64_t frame = (uint64_t)(a.frame >= 0 ? a.frame : *a.frame_dev);     // advanced by k_obs_fields, after every read
+  for (int64_t i = gid; i < n; i += gsz) {
+    uint64_t key = TSMV_EXCLUDED;
+    if (a.rgbd[4 * i + 3] != 0.0f) {
+      uint32_t q[4];
+      philox_block(a.seed, frame, (uint64_t)i, TSMV_STREAM_PIXELS, q);
+      key = ((uint64_t)q[0] << 32) | (uint32_t)i;
+    }
+    w.keys[i] = key;
+  }
+}
+
+// The state of the select after `passes` finished passes, from their histograms (called by thread 0; sh = the histograms in
+// LDS).  take_all: no more valid keys than wanted.  done: the keys whose leading digits are <= prefix (at `shift`) are exactly
+// the k smallest.
+struct obs_state { uint64_t prefix; int shift, rem, done, take_all; };
+__device__ obs_state obs_select_state(const int* sh, int passes, int k) {
+  obs_state s = {0ull, 64, k, 0, 0};
+  if (passes == 0) return s;
+  int total = 0;
+  for (int b = 0; b < 256; ++b) total += sh[b];           // pass 0 counts every valid key
+  if (total <= k) { s.take_all = 1; s.done = 1; return s; }
+  for (int p = 0; p < passes; ++p) {
+    const int* h = sh + 256 * p;
+    int cum = 0, b = 0;
+    for (; b < 255; ++b) {
+      if (cum + h[b] >= s.rem) break;
+      cum += h[b];
+    }
+    s.shift -= 8;
+    s.prefix = (s.prefix << 8) | (uint64_t)b;
+    s.rem -= cum;
+    if (h[b] == s.rem || s.shift == 0) { s.done = 1; break; }
+  }
+  return s;
+}
+__device__ __forceinline__ obs_state obs_state_block(const obs_ws& w, int passes, int k, int* sh, obs_state* sst) {
+  for (int i = threadIdx.x; i < 256 * passes; i += OBS_THREADS) sh[i] = w.hist[i];
+  __syncthreads();
+  if (threadIdx.x == 0) *sst = obs_select_state(sh, passes, k);
+  __syncthreads();
+  return *sst;
+}
+
+__global__ __launch_bounds__(OBS_THREADS) void k_obs_hist(ngm_observed_fields a, obs_ws w, int pass) {
+  __shared__ int sh[OBS_PASSES * 256];
+  __shared__ int local[256];
+  __shared__ obs_state sst;
+  const obs_state s = obs_state_block(w, pass, a.num_points, sh, &sst);
+  if (s.done) return;                                     // block-uniform
+  const int shift = s.shift - 8;                          // this pass' digit
+  local[threadIdx.x] = 0;                                 // OBS_THREADS == 256
+  __syncthreads();
+  const int64_t n = (int64_t)a.height * a.width, gsz = (int64_t)gridDim.x * OBS_THREADS;
+  for (int64_t i = (int64_t)blockIdx.x * OBS_THREADS + threadIdx.x; i < n; i += gsz) {
+    const uint64_t key = w.keys[i];
+    if (key == TSMV_EXCLUDED || (pass > 0 && (key >> (shift + 8)) != s.prefix)) continue;
+    atomicAdd(&local[(key >> shift) & 255u], 1);
+  }
+  __syncthreads();
+  const int v = local[threadIdx.x];
+  if (v) atomicAdd(&w.hist[256 * pass + threadIdx.x], v);
+}
+
+__global__ __launch_bounds__(OBS_THREADS) void k_obs_collect(ngm_observed_fields a, obs_ws w) {
+  __shared__ int sh[OBS_PASSES * 256];
+  __shared__ obs_state sst;
+  const int64_t gid = (int64_t)blockIdx.x * OBS_THREADS + threadIdx.x, gsz = (int64_t)gridDim.x * OBS_THREADS;
+  const int64_t n = (int64_t)a.height * a.width;
+  if (a.subset_in) {                                      // recorded draws: out-of-range entries become -1 (unused)
+    for (int64_t i = gid; i < a.num_points; i += gsz) {
+      const int64_t p = a.subset_in[i];
+      a.pixels[i] = (p >= 0 && p < n) ? p : -1;
+    }
+    return;
+  }
+  const obs_state s = obs_state_block(w, OBS_PASSES, a.num_points, sh, &sst);
+  for (int64_t i = gid; i < n; i += gsz) {
+    const uint64_t key = w.keys[i];
+    if (key == TSMV_EXCLUDED) continue;
+    if (!s.take_all && (key >> s.shift) > s.prefix) continue;
+    const int p = atomicAdd(&w.counters[0], 1);
+    if (p < a.num_points) a.pixels[p] = i;
+  }
+}
+
+__global__ __launch_bounds__(OBS_FIELD_THREADS) void k_obs_fields(ngm_observed_fields a, obs_ws w) {
+  __shared__ float pts[3 * NGM_OBSERVED_MAX_POINTS];
+  __shared__ float wmin[3 * (OBS_FIELD_THREADS / 64)], wmax[3 * (OBS_FIELD_THREADS / 64)];
+  __shared__ float box[6];
+  __shared__ int wave_cnt[OBS_FIELD_THREADS / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  constexpr int NW = OBS_FIELD_THREADS / 64;
+  const int64_t n = (int64_t)a.height * a.width;
+  // 1. how many pixels were chosen; slots past them are -1
+  int used = 0;
+  if (a.subset_in) {
+    used = a.num_points;                                  // entries of -1 are skipped below, one by one
+  } else {
+    used = min(w.counters[0], a.num_points);
+    for (int i = used + tid; i < a.num_points; i += OBS_FIELD_THREADS) a.pixels[i] = -1;
+  }
+  // 2. back-projection (camera.py:374-390, OpenGL) and the AABB of the points
+  float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+  int mine = 0;
+  for (int i = tid; i < a.num_points; i += OBS_FIELD_THREADS) {
+    const int64_t p = i < used ? a.pixels[i] : -1;
+    const bool ok = p >= 0 && p < n;
+    float x = 0.f, y = 0.f, z = 0.f;
+    if (ok) {
+      const int r = (int)(p / a.width), c = (int)(p - (int64_t)r * a.width);
+      const float d = a.rgbd[4 * p + 3];
+      x = (((float)c - a.cx) * d) / a.fx;
+      y = ((-((float)r - a.cy)) * d) / a.fy;
+      z = -d;
+      mn[0] = fminf(mn[0], x); mn[1] = fminf(mn[1], y); mn[2] = fminf(mn[2], z);
+      mx[0] = fmaxf(mx[0], x); mx[1] = fmaxf(mx[1], y); mx[2] = fmaxf(mx[2], z);
+      ++mine;
+    }
+    pts[3 * i] = x; pts[3 * i + 1] = y; pts[3 * i + 2] = ok ? z : NAN;      // NaN z marks an unused slot
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    for (int o = 32; o > 0; o >>= 1) {
+      mn[k] = fminf(mn[k], __shfl_xor(mn[k], o));
+      mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], o));
+    }
+    if (lane == 0) { wmin[3 * wv + k] = mn[k]; wmax[3 * wv + k] = mx[k]; }
+  }
+  const uint64_t any_b = __ballot(mine > 0);
+  if (lane == 0) wave_cnt[wv] = __popcll(any_b);
+  __syncthreads();
+  if (tid < 3) {
+    float lo = INFINITY, hi = -INFINITY;
+    for (int q = 0; q < NW; ++q) { lo = fminf(lo, wmin[3 * q + tid]); hi = fmaxf(hi, wmax[3 * q + tid]); }
+    box[tid] = lo; box[3 + tid] = hi;
+  }
+  int have = 0;
+  for (int q = 0; q < NW; ++q) have += wave_cnt[q];
+  __syncthreads();                                        // box ready, wave_cnt free again
+  if (tid == 0) {
+    int cnt = 0;                                          // valid chosen pixels (subset_in may hold unused entries)
+    if (a.subset_in) { for (int i = 0; i < a.num_points; ++i) cnt += pts[3 * i + 2] == pts[3 * i + 2] ? 1 : 0; }
+    else cnt = used;
+    *a.num_used = cnt;
+  }
+  // 3. per field: sphere AABB vs. point AABB (geometry.py:26-42), then the segment test over the points (geometry.py:67-105)
+  const float* T = a.c2w;
+  const float r = a.radius, r2 = r * r;
+  int base = 0;
+  for (int f0 = 0; f0 < a.num_fields; f0 += OBS_FIELD_THREADS) {
+    const int f = f0 + tid;
+    bool seen = false;
+    if (f < a.num_fields && have > 0) {
+      const Cam3 c = world_to_cam(T, a.field_positions[3 * f], a.field_positions[3 * f + 1], a.field_positions[3 * f + 2]);
+      const bool in_box = c.x - r <= box[3] && c.y - r <= box[4] && c.z - r <= box[5] && c.x + r >= box[0] && c.y + r >= box[1] &&
+                          c.z + r >= box[2];
+      if (in_box) {
+        for (int i = 0; i < a.num_points && !seen; ++i) {
+          const float px = pts[3 * i], py = pts[3 * i + 1], pz = pts[3 * i + 2];
+          if (pz != pz) continue;
+          float sq = (px * px + py * py) + pz * pz;
+          if (sq == 0.0f) sq = 1.0f;
+          const float t = fminf(fmaxf(((c.x * px + c.y * py) + c.z * pz) / sq, 0.0f), 1.0f);
+          const float ex = c.x - px * t, ey = c.y - py * t, ez = c.z - pz * t;
+          seen = (ex * ex + ey * ey) + ez * ez <= r2;
+        }
+      }
+    }
+    // ascending compaction of this chunk
+    const uint64_t bal = __ballot(seen);
+    if (lane == 0) wave_cnt[wv] = __popcll(bal);
+    __syncthreads();
+    int off = base, tot = 0;
+    for (int q = 0; q < NW; ++q) {
+      off += q < wv ? wave_cnt[q] : 0;
+      tot += wave_cnt[q];
+    }
+    if (seen) a.current_field_ids[off + __popcll(bal & ((1ull << lane) - 1ull))] = f;
+    base += tot;
+    __syncthreads();
+  }
+  for (int i = base + tid; i < a.num_fields; i += OBS_FIELD_THREADS) a.current_field_ids[i] = -1;
+  if (tid == 0) {
+    *a.current_count = base;
+    if (a.frame < 0) *a.frame_dev = *a.frame_dev + 1;     // every read of the counter was in k_obs_keys, an earlier launch
+  }
+}
+
+int64_t ngm_target_observed_fields_bytes(int height, int width) { return obs_layout((int64_t)height * width, nullptr, nullptr); }
+int ngm_launch_target_observed_fields(const ngm_observed_fields& a, void* workspace, hipStream_t st) {
+  obs_ws w;
+  obs_layout((int64_t)a.height * a.width, (char*)workspace, &w);
+  const int64_t n = (int64_t)a.height * a.width;
+  int blocks = (int)((n + OBS_THREADS - 1) / OBS_THREADS);
+  blocks = blocks < OBS_PASSES ? OBS_PASSES : blocks > OBS_MAX_BLOCKS ? OBS_MAX_BLOCKS : blocks;
+  if (!a.subset_in) {
+    hipLaunchKernelGGL(k_obs_keys, dim3(blocks), dim3(OBS_THREADS), 0, st, a, w);
+    for (int p = 0; p < OBS_PASSES; ++p) hipLaunchKernelGGL(k_obs_hist, dim3(blocks), dim3(OBS_THREADS), 0, st, a, w, p);
+  }
+  hipLaunchKernelGGL(k_obs_collect, dim3(a.subset_in ? (a.num_points + OBS_THREADS - 1) / OBS_THREADS : blocks), dim3(OBS_THREADS), 0, st,
+                     a, w);
+  hipLaunchKernelGGL(k_obs_fields, dim3(1), dim3(OBS_FIELD_THREADS), 0, st, a, w);
   return 0;
 }

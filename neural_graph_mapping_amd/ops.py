@@ -1100,3 +1100,190 @@ def target_sample_mv(current_field_ids, c2ws, rgbd_store, frame_to_store, field_
                                              int(num_train_fields), int(num_rays_per_field), int(seed),
                                              -1 if iteration is None else int(iteration), int(world_size), int(rank))
     return dict(zip(TARGET_SAMPLE_MV_OUT, outs))
+
+
+# ------------------------------------------------------------------------------------------------
+# the same sampler with its counts in device memory (include/ngm_hip.h ngm_target_sample_mv_live)
+# ------------------------------------------------------------------------------------------------
+TARGET_SAMPLE_MV_LIVE_OUT = TARGET_SAMPLE_MV_OUT + ("num_observed", "num_random")
+
+
+def _target_sample_mv_live_shapes(max_obs, max_rand, cap, R):
+    return _target_sample_mv_shapes(max_obs, max_rand, cap, R) + [((1,), torch.int32), ((1,), torch.int32)]
+
+
+@_op("target_sample_mv_live", mutates_args=("iteration_dev",))
+def _target_sample_mv_live_op(current_field_ids: torch.Tensor, current_count: torch.Tensor, c2ws: torch.Tensor,
+                              num_frames: torch.Tensor, rgbd_store: torch.Tensor, frame_to_store: torch.Tensor,
+                              field_positions: torch.Tensor, iteration_dev: Optional[torch.Tensor], intrinsics: List[float],
+                              radius: float, num_fields: int, num_train_fields: int, num_rays: int, seed: int, iteration: int,
+                              world_size: int, rank: int) -> List[torch.Tensor]:
+    """TARGET_SAMPLE_MV_LIVE_OUT; current_field_ids / c2ws / frame_to_store are sized for their maxima, the counts in force
+    are current_count / num_frames (device int32)"""
+    max_current = current_field_ids.shape[0]
+    max_obs, max_rand, cap = K.target_sample_mv_live_plan(max_current, num_fields, num_train_fields, num_rays, world_size, rank)
+    dev = field_positions.device
+    outs = [torch.empty(shape, dtype=dt, device=dev) for shape, dt in _target_sample_mv_live_shapes(max_obs, max_rand, cap, num_rays)]
+    o = dict(zip(TARGET_SAMPLE_MV_LIVE_OUT, outs))
+    kf = keyframes_struct(c2ws, rgbd_store, frame_to_store, *intrinsics)
+    ws_bytes = K.lib().ngm_target_sample_mv_live_workspace(kf.num_frames, max_current, num_fields, cap)
+    if ws_bytes < 0:
+        raise K.NgmError("ngm_target_sample_mv_live_workspace: bad sizes")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    s = K.TargetSample(_ptr(current_field_ids), _ptr(field_positions), max_current, num_fields, max_obs, max_rand,
+                       num_rays, cap, world_size, rank, float(radius), 0, int(seed), int(iteration), _ptr(iteration_dev))
+    for k in ("field_ids", "count", "subset_observed", "subset_random", "offsets", "frame_cids", "u_xy"):
+        setattr(s, k, o[k].data_ptr())
+    live = K.TargetLive(_ptr(current_count), _ptr(num_frames), o["num_observed"].data_ptr(), o["num_random"].data_ptr(),
+                        num_train_fields, 0)
+    out = K.TargetOut()
+    for k in ("ijs", "c2ws", "near", "far", "gt", "rgbds", "rgb_mask", "depth_mask", "term_probs", "term_mask"):
+        setattr(out, k, o[k].data_ptr())
+    K.check(K.lib().ngm_target_sample_mv_live(C.byref(kf), C.byref(s), C.byref(live), C.byref(out), _ptr(ws), ws_bytes, _stream()),
+            "ngm_target_sample_mv_live")
+    return outs
+
+
+@_target_sample_mv_live_op.register_fake
+def _(current_field_ids, current_count, c2ws, num_frames, rgbd_store, frame_to_store, field_positions, iteration_dev, intrinsics,
+      radius, num_fields, num_train_fields, num_rays, seed, iteration, world_size, rank):
+    max_obs, max_rand, cap = K.target_sample_mv_live_plan(current_field_ids.shape[0], num_fields, num_train_fields, num_rays,
+                                                          world_size, rank)
+    return [torch.empty(shape, dtype=dt, device=field_positions.device)
+            for shape, dt in _target_sample_mv_live_shapes(max_obs, max_rand, cap, num_rays)]
+
+
+def _check_device_count(fn, name, t):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.numel() != 1:
+        raise TypeError(f"{fn}: {name} must be a one-element int32 tensor")
+
+
+def target_sample_mv_live(current_field_ids, current_count, c2ws, num_frames, rgbd_store, frame_to_store, field_positions, fx, fy,
+                          cx, cy, radius, num_fields, num_train_fields, num_rays_per_field, seed=0, iteration=None,
+                          iteration_dev=None, world_size=1, rank=0):
+    """target_sample_mv with the number of current fields and of keyframes read from device memory
+    (torch.ops.ngm355.target_sample_mv_live): current_field_ids (max_current,), c2ws (max_frames, 4, 4) and frame_to_store
+    (max_frames,) are fixed-capacity buffers, current_count / num_frames one-element int32 device tensors.  Bit for bit
+    target_sample_mv(current_field_ids[:n], c2ws[:m], ...) for the counts n, m in force; nothing past them is read.
+    Returns a dict keyed by TARGET_SAMPLE_MV_LIVE_OUT: subset_observed / subset_random at their maxima with -1 past
+    num_observed / num_random (int32, device)."""
+    _check_target_sample_mv(current_field_ids, c2ws, rgbd_store, frame_to_store, field_positions, iteration_dev, int(num_fields))
+    _check_device_count("target_sample_mv_live", "current_count", current_count)
+    _check_device_count("target_sample_mv_live", "num_frames", num_frames)
+    K.target_sample_mv_live_plan(current_field_ids.shape[0], int(num_fields), int(num_train_fields), int(num_rays_per_field),
+                                 int(world_size), int(rank))
+    if iteration is None and iteration_dev is None:
+        raise ValueError("target_sample_mv_live: iteration=None needs iteration_dev (the device counter)")
+    if iteration is not None and int(iteration) < 0:
+        raise ValueError(f"target_sample_mv_live: iteration must be >= 0, got {iteration}")
+    if not 0 <= int(seed) < 2 ** 63:
+        raise ValueError(f"target_sample_mv_live: seed must be in [0, 2^63), got {seed}")
+    _require_gpu(current_field_ids, current_count, c2ws, num_frames, rgbd_store, frame_to_store, field_positions, iteration_dev)
+    outs = torch.ops.ngm355.target_sample_mv_live(current_field_ids, current_count, c2ws, num_frames, rgbd_store, frame_to_store,
+                                                  field_positions, iteration_dev, [float(fx), float(fy), float(cx), float(cy)],
+                                                  float(radius), int(num_fields), int(num_train_fields), int(num_rays_per_field),
+                                                  int(seed), -1 if iteration is None else int(iteration), int(world_size),
+                                                  int(rank))
+    return dict(zip(TARGET_SAMPLE_MV_LIVE_OUT, outs))
+
+
+# ------------------------------------------------------------------------------------------------
+# observed fields of one frame, on the device (include/ngm_hip.h ngm_target_observed_fields)
+# ------------------------------------------------------------------------------------------------
+TARGET_OBSERVED_FIELDS_OUT = ("current_field_ids", "current_count", "pixels", "num_used")
+
+
+@_op("target_observed_fields", mutates_args=("frame_dev", "ids_out", "count_out"))
+def _target_observed_fields_op(rgbd: torch.Tensor, c2w: torch.Tensor, field_positions: torch.Tensor, frame_dev: Optional[torch.Tensor],
+                               subset_in: Optional[torch.Tensor], ids_out: torch.Tensor, count_out: torch.Tensor,
+                               intrinsics: List[float], radius: float, num_fields: int, num_points: int, seed: int,
+                               frame: int) -> List[torch.Tensor]:
+    """(pixels (num_points,) int64, num_used (1,) int32); the observed ids and their count go to ids_out / count_out"""
+    dev = rgbd.device
+    H, W = rgbd.shape[0], rgbd.shape[1]
+    pixels = torch.empty(num_points, dtype=torch.int64, device=dev)
+    used = torch.empty(1, dtype=torch.int32, device=dev)
+    ws_bytes = K.lib().ngm_target_observed_fields_workspace(H, W)
+    if ws_bytes < 0:
+        raise K.NgmError("ngm_target_observed_fields_workspace: bad sizes")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    a = K.ObservedFields()
+    a.rgbd, a.c2w = C.cast(rgbd.data_ptr(), K.f32p), C.cast(c2w.data_ptr(), K.f32p)
+    a.field_positions = C.cast(field_positions.data_ptr(), K.f32p)
+    a.height, a.width, a.num_fields, a.num_points = H, W, num_fields, num_points
+    a.fx, a.fy, a.cx, a.cy = intrinsics
+    a.radius, a.seed, a.frame = float(radius), int(seed), int(frame)
+    a.frame_dev, a.subset_in = _ptr(frame_dev), _ptr(subset_in)
+    a.current_field_ids, a.current_count = ids_out.data_ptr(), count_out.data_ptr()
+    a.pixels, a.num_used = pixels.data_ptr(), used.data_ptr()
+    K.check(K.lib().ngm_target_observed_fields(C.byref(a), _ptr(ws), ws_bytes, _stream()), "ngm_target_observed_fields")
+    return [pixels, used]
+
+
+@_target_observed_fields_op.register_fake
+def _(rgbd, c2w, field_positions, frame_dev, subset_in, ids_out, count_out, intrinsics, radius, num_fields, num_points, seed, frame):
+    return [torch.empty(num_points, dtype=torch.int64, device=rgbd.device), torch.empty(1, dtype=torch.int32, device=rgbd.device)]
+
+
+def target_observed_fields(rgbd, c2w, field_positions, fx, fy, cx, cy, radius, num_fields, num_points=500, seed=0, frame=None,
+                           frame_dev=None, subset_in=None, ids_out=None, count_out=None):
+    """NeuralGraphMap._get_observed_fields (rm.py:1642-1670) on the device (torch.ops.ngm355.target_observed_fields): no host
+    synchronisation, fixed shapes.  rgbd (H, W, 4) and c2w (4, 4) are device tensors read when the kernels run.  frame=None:
+    frame_dev (one-element int64 device tensor) is read and advanced.  subset_in: num_points linear pixel indices that
+    replace the draw.  ids_out (>= num_fields,) int64 / count_out (1,) int32 are written in place when given.  Returns a
+    dict keyed by TARGET_OBSERVED_FIELDS_OUT: the observed ids ascending with -1 past current_count, the chosen pixels (order
+    unspecified) with -1 past num_used."""
+    def need(cond, msg, exc=ValueError):
+        if not cond:
+            raise exc("target_observed_fields: " + msg)
+    num_fields, num_points = int(num_fields), int(num_points)
+    for name, t in (("rgbd", rgbd), ("c2w", c2w), ("field_positions", field_positions)):
+        need(isinstance(t, torch.Tensor), f"{name} must be a tensor", TypeError)
+        need(t.dtype == torch.float32, f"{name} must be float32, got {t.dtype}", TypeError)
+        need(t.is_contiguous(), f"{name} must be contiguous")
+    need(rgbd.dim() == 3 and rgbd.shape[2] == 4 and rgbd.shape[0] >= 1 and rgbd.shape[1] >= 1,
+         f"rgbd must be (H, W, 4), got {tuple(rgbd.shape)}")
+    need(tuple(c2w.shape) == (4, 4), f"c2w must be (4, 4), got {tuple(c2w.shape)}")
+    need(num_fields >= 0 and field_positions.dim() == 2 and field_positions.shape[1] == 3 and field_positions.shape[0] >= num_fields,
+         f"field_positions must be (>= num_fields = {num_fields}, 3), got {tuple(field_positions.shape)}")
+    need(1 <= num_points <= K.NGM_OBSERVED_MAX_POINTS, f"num_points must be in [1, {K.NGM_OBSERVED_MAX_POINTS}], got {num_points}")
+    need(frame is not None or frame_dev is not None, "frame=None needs frame_dev (the device counter)")
+    need(frame is None or int(frame) >= 0, f"frame must be >= 0, got {frame}")
+    need(0 <= int(seed) < 2 ** 63, f"seed must be in [0, 2^63), got {seed}")
+    if frame_dev is not None:
+        need(isinstance(frame_dev, torch.Tensor) and frame_dev.dtype == torch.int64 and frame_dev.numel() == 1,
+             "frame_dev must be a one-element int64 tensor", TypeError)
+    if subset_in is not None:
+        need(isinstance(subset_in, torch.Tensor) and subset_in.dtype == torch.int64, "subset_in must be an int64 tensor", TypeError)
+        need(tuple(subset_in.shape) == (num_points,) and subset_in.is_contiguous(),
+             f"subset_in must be a contiguous ({num_points},) tensor, got {tuple(subset_in.shape)}")
+    if ids_out is not None:
+        need(isinstance(ids_out, torch.Tensor) and ids_out.dtype == torch.int64, "ids_out must be an int64 tensor", TypeError)
+        need(ids_out.dim() == 1 and ids_out.shape[0] >= num_fields and ids_out.is_contiguous(),
+             f"ids_out must be a contiguous (>= {num_fields},) tensor, got {tuple(ids_out.shape)}")
+    if count_out is not None:
+        _check_device_count("target_observed_fields", "count_out", count_out)
+    _require_gpu(rgbd, c2w, field_positions, frame_dev, subset_in, ids_out, count_out)
+    dev = rgbd.device
+    if ids_out is None:
+        ids_out = torch.empty(num_fields, dtype=torch.int64, device=dev)
+    if count_out is None:
+        count_out = torch.empty(1, dtype=torch.int32, device=dev)
+    pixels, used = torch.ops.ngm355.target_observed_fields(rgbd, c2w, field_positions, frame_dev, subset_in, ids_out, count_out,
+                                                           [float(fx), float(fy), float(cx), float(cy)], float(radius), num_fields,
+                                                           num_points, int(seed), -1 if frame is None else int(frame))
+    return dict(current_field_ids=ids_out, current_count=count_out, pixels=pixels, num_used=used)
+
+
+def field_counts_add(field_ids, count, training_iterations, num_fields):
+    """training_iterations[field_ids[i]] += 1 for i < count (device int32, or None: every row), skipping -1: one launch
+    (ngm_field_counts_add), no synchronisation."""
+    if field_ids.dtype != torch.int64 or training_iterations.dtype != torch.int64:
+        raise TypeError("field_counts_add: field_ids and training_iterations must be int64")
+    if count is not None:
+        _check_device_count("field_counts_add", "count", count)
+    if training_iterations.shape[0] < int(num_fields) or not training_iterations.is_contiguous() or not field_ids.is_contiguous():
+        raise ValueError("field_counts_add: training_iterations must be a contiguous (>= num_fields,) tensor, field_ids contiguous")
+    _require_gpu(field_ids, count, training_iterations)
+    K.check(K.lib().ngm_field_counts_add(_ptr(field_ids), _ptr(count), int(field_ids.shape[0]), _ptr(training_iterations),
+                                         int(num_fields), _stream()), "ngm_field_counts_add")

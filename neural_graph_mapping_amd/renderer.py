@@ -48,6 +48,23 @@ class DeviceTarget(namedtuple("DeviceTarget", Target._fields + ("count", "subset
                     frame_cids=self.frame_cids[:n], u_xy=self.u_xy[:n])
 
 
+class LiveDeviceTarget(DeviceTarget):
+    """The DeviceTarget of sample_target_mv_device(current_count=..., num_frames=...): subset_observed / subset_random are
+    sized for their maxima with -1 past `num_observed` / `num_random` (device int32 tensors (1,)), since the number of
+    current fields is read on the device.  materialize() / draws() slice by the device counts (they synchronise anyway)."""
+
+    def __new__(cls, *args, num_observed, num_random, **kw):
+        self = super().__new__(cls, *args, **kw)
+        self.num_observed, self.num_random = num_observed, num_random
+        return self
+
+    def draws(self) -> dict:
+        d = super().draws()
+        d["subset_observed"] = self.subset_observed[:int(self.num_observed.item())]
+        d["subset_random"] = self.subset_random[:int(self.num_random.item())]
+        return d
+
+
 class Camera:
     """Pinhole intrinsics with the reference's pixel-centre convention (camera.py:15-116)."""
 
@@ -173,6 +190,11 @@ class NeuralGraphRenderer:
         self.field_draw_generator = None   # torch.Generator of sample_target_mv(field_draw="balanced_by_owner"), see there
         self._target_iter_dev = None       # sample_target_mv_device's iteration counter (device int64, advanced by each call)
         self._warned_counted_fallback = False
+        # opt-in: every update=True iteration adds one launch, training_iterations[field_ids] += 1 (rm.py:1188), so that
+        # get_field_ids(min_iterations) keeps working when the iteration (and who trained in it) lives on the device
+        self.track_training_iterations = False
+        self._observe_frame_dev = None     # observed_fields_device's frame counter (device int64, advanced by each call)
+        self.last_observed = None          # the chosen pixels / their number of the last observed_fields_device call
 
     def last_matmul(self, kernel: str = "forward") -> Optional[str]:
         """The arithmetic the library resolved `mlp_matmul` to in the LAST launch of the fused forward ("forward"), the
@@ -184,7 +206,38 @@ class NeuralGraphRenderer:
 
     # -- map bookkeeping supplied by the caller ------------------------------------------------
     def set_field_poses(self, positions: torch.Tensor, orientations: torch.Tensor):
+        old = self._global_map_dict
         self._global_map_dict = {"positions": positions, "orientations": orientations, "num": positions.shape[0]}
+        if old is not None and "training_iterations" in old:            # the counts belong to the fields, not to their poses
+            self._global_map_dict["training_iterations"] = old["training_iterations"]
+
+    def _training_iterations(self) -> torch.Tensor:
+        """_global_map_dict["training_iterations"] (int64, one per field; rm.py:1188), created on first use and extended
+        with zeros when fields were added, as add_fields extends the parameters"""
+        md = self._global_map_dict
+        ti, num = md.get("training_iterations"), md["num"]
+        if ti is None or ti.shape[0] < num:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("training_iterations must exist before a graph capture (capture_iteration / "
+                                   "capture_training create it when track_training_iterations is set)")
+            new = torch.zeros(num, dtype=torch.int64, device=self._device)
+            if ti is not None:
+                new[:ti.shape[0]] = ti
+            md["training_iterations"] = ti = new
+        return ti
+
+    def _count_training_iteration(self, field_ids: torch.Tensor, count: Optional[torch.Tensor]) -> None:
+        if self.track_training_iterations and field_ids.shape[0] > 0:
+            fids = field_ids if field_ids.dtype == torch.int64 else field_ids.long()
+            ops.field_counts_add(fids.contiguous(), count, self._training_iterations(), self._global_map_dict["num"])
+
+    def get_field_ids(self, min_iterations: Optional[int] = None) -> torch.Tensor:
+        """NeuralGraphMap.get_field_ids (rm.py:2175-2181): the fields trained in at least min_iterations iterations (all
+        fields for None).  The counts are kept only while track_training_iterations is set."""
+        num = self._global_map_dict["num"]
+        if min_iterations is None:
+            return torch.arange(0, num, device=self._device)
+        return torch.where(self._training_iterations()[:num] >= min_iterations)[0]
 
     def add_fields(self, num_new: int):
         """NeuralGraphMap._add_fields (rm.py:364-389): grow params + zero moments, keep the shared step."""
@@ -507,6 +560,7 @@ class NeuralGraphRenderer:
         if self._step_dev is not None:
             self._step_dev.fill_(self._step)
         self._model.refresh_lp()           # this path updates the fp32 masters tensor by tensor
+        self._count_training_iteration(fids, None)
         return out
 
     def compute_losses(self, target: Target, prediction: Prediction) -> dict:
@@ -614,7 +668,8 @@ class NeuralGraphRenderer:
     @torch.no_grad()
     def sample_target_mv_device(self, current_field_ids, c_c2w, nc_rgbd, frame_cid_to_ncid, num_train_fields, num_rays_per_field,
                                 num_fields=None, camera: Optional[Camera] = None, seed: int = 0, iteration: Optional[int] = None,
-                                world_size: int = 1, rank: int = 0) -> DeviceTarget:
+                                world_size: int = 1, rank: int = 0, *, current_count: Optional[torch.Tensor] = None,
+                                num_frames: Optional[torch.Tensor] = None) -> DeviceTarget:
         """sample_target_mv with every draw made on the device (ngm_target_sample_mv: three kernels, no host synchronisation,
         no data-dependent shapes), so it can be captured in a graph.  Same distribution as the reference's sampler, NOT the
         same random numbers: the draws come from Philox4x32-10 keyed by (seed, iteration) -- the field draw and offsets by
@@ -624,7 +679,14 @@ class NeuralGraphRenderer:
         world_size / rank: every rank draws the same fields; rows are made only for drawn fields with id % world_size == rank
         (distributed.field_owner), in draw order, bit for bit the single-process rows of those fields.
         Precondition (not checked: that would synchronise): current_field_ids is duplicate-free, ids in [0, num_fields), as
-        the reference's is.  Returns a DeviceTarget; .materialize() gives the Target for optimization_iteration."""
+        the reference's is.  Returns a DeviceTarget; .materialize() gives the Target for optimization_iteration.
+        current_count / num_frames (both or neither; one-element int32 device tensors): the live sampler
+        (ngm_target_sample_mv_live) -- current_field_ids, c_c2w and frame_cid_to_ncid are then fixed-capacity buffers
+        (observed_fields_device and KeyframeStore fill such), only their first current_count / num_frames entries are read,
+        and the result is bit for bit that of this call on the sliced tensors: the shapes no longer follow the frame, so a
+        captured graph outlives it.  Returns a LiveDeviceTarget."""
+        if (current_count is None) != (num_frames is None):
+            raise ValueError("sample_target_mv_device: current_count and num_frames go together (both device tensors, or neither)")
         cam = camera or self._camera
         dev = self._device
         num_fields = self._global_map_dict["num"] if num_fields is None else num_fields
@@ -640,6 +702,18 @@ class NeuralGraphRenderer:
                 self._target_iter_dev = torch.zeros(1, dtype=torch.int64, device=dev)
             counter = self._target_iter_dev
         fx, fy, cx, cy, _ = cam.get_pinhole_camera_parameters(0.0)
+        if current_count is not None:
+            o = ops.target_sample_mv_live(cur.contiguous(), current_count, c_c2w.contiguous(), num_frames, nc_rgbd.contiguous(),
+                                          frame_cid_to_ncid.contiguous(), self._global_map_dict["positions"].contiguous(), fx, fy,
+                                          cx, cy, self._field_radius + 0.0, int(num_fields), int(num_train_fields),
+                                          int(num_rays_per_field), seed=seed, iteration=iteration, iteration_dev=counter,
+                                          world_size=world_size, rank=rank)
+            return LiveDeviceTarget(ijs=o["ijs"], c2ws=o["c2ws"], near_distances=o["near"], far_distances=o["far"],
+                                    gt_distances=o["gt"], field_ids=o["field_ids"], rgbds=o["rgbds"], rgb_mask=o["rgb_mask"],
+                                    depth_mask=o["depth_mask"], term_probs=o["term_probs"], term_mask=o["term_mask"],
+                                    count=o["count"], subset_observed=o["subset_observed"], subset_random=o["subset_random"],
+                                    offsets=o["offsets"], frame_cids=o["frame_cids"], u_xy=o["u_xy"], world_size=int(world_size),
+                                    num_observed=o["num_observed"], num_random=o["num_random"])
         o = ops.target_sample_mv(cur.contiguous(), c_c2w.contiguous(), nc_rgbd.contiguous(), frame_cid_to_ncid.contiguous(),
                                  self._global_map_dict["positions"].contiguous(), fx, fy, cx, cy, self._field_radius + 0.0,
                                  int(num_fields), int(num_train_fields), int(num_rays_per_field), seed=seed, iteration=iteration,
@@ -649,6 +723,36 @@ class NeuralGraphRenderer:
                             term_probs=o["term_probs"], term_mask=o["term_mask"], count=o["count"],
                             subset_observed=o["subset_observed"], subset_random=o["subset_random"], offsets=o["offsets"],
                             frame_cids=o["frame_cids"], u_xy=o["u_xy"], world_size=int(world_size))
+
+    @torch.no_grad()
+    def observed_fields_device(self, rgbd_image, c2w, num_points: int = 500, seed: int = 0, frame: Optional[int] = None,
+                               out=None, draws: Optional[dict] = None, camera: Optional[Camera] = None):
+        """NeuralGraphMap._get_observed_fields (rm.py:1642-1670) on the device (ngm_target_observed_fields): which fields
+        does this RGB-D frame see?  No host synchronisation and fixed shapes -- returns (ids, count): ids (num_fields,)
+        int64, the observed field ids ascending with -1 past count, a one-element int32 device tensor; exactly what
+        sample_target_mv_device(current_count=...) and capture_training read.  out=(ids, count) writes into given tensors
+        (the buffers a captured graph keeps reading).  rgbd_image (H, W, 4) and c2w (4, 4) are device tensors.
+        Same distribution as the reference's multinomial draw of num_points valid pixels, NOT torch's random numbers:
+        Philox keyed by (seed, frame); frame=None reads and advances a device counter owned by this renderer.
+        draws=dict(pixels=...) replays num_points recorded linear pixel indices instead.  The chosen pixels and their
+        number are kept in `last_observed` (device tensors)."""
+        cam = camera or self._camera
+        dev = self._device
+        counter = None
+        if frame is None:
+            if self._observe_frame_dev is None:
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("observed_fields_device: call it once outside the graph capture first (or pass frame=...)")
+                self._observe_frame_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+            counter = self._observe_frame_dev
+        ids_out, count_out = out if out is not None else (None, None)
+        fx, fy, cx, cy, _ = cam.get_pinhole_camera_parameters(0.0)
+        o = ops.target_observed_fields(rgbd_image, c2w, self._global_map_dict["positions"].contiguous(), fx, fy, cx, cy,
+                                       self._field_radius + 0.0, int(self._global_map_dict["num"]), num_points=num_points,
+                                       seed=seed, frame=frame, frame_dev=counter,
+                                       subset_in=None if draws is None else draws["pixels"], ids_out=ids_out, count_out=count_out)
+        self.last_observed = dict(pixels=o["pixels"], num_used=o["num_used"])
+        return o["current_field_ids"], o["current_count"]
 
     def sample_target_sv(self, rgbd_image, c2w, active_field_ids, num_train_fields, num_rays_per_field,
                          camera: Optional[Camera] = None, draws: Optional[dict] = None, num_points: int = 50000) -> Target:
@@ -1018,6 +1122,8 @@ class NeuralGraphRenderer:
             K.check(L.ngm_render_bwd(C.byref(fc), C.byref(rc), C.byref(ps), C.byref(rays), C.byref(tg), C.byref(pred),
                                      sums_ptr, C.byref(gs), w["loss"].data_ptr(), w["ws"].data_ptr(), w["wsb"],
                                      st), "ngm_render_bwd")
+        if update:
+            self._count_training_iteration(fids, count)
         lv = w["loss"]
         loss = {"combined": lv[0], "termination": lv[1], "photometric_" + self._config["photometric_loss"]: lv[2],
                 "depth_" + self._config["depth_loss"]: lv[3],
@@ -1044,6 +1150,8 @@ class NeuralGraphRenderer:
                 raise RuntimeError(f"capture_iteration(DeviceTarget): {why} is outside the counted step; capture a "
                                    "materialised Target instead")
             count = target.count
+        if self.track_training_iterations:
+            self._training_iterations()                       # must exist before the capture
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -1099,7 +1207,8 @@ class NeuralGraphRenderer:
         return replay2
 
     def capture_training(self, current_field_ids, c_c2w, nc_rgbd, frame_cid_to_ncid, num_train_fields, num_rays_per_field,
-                         seed=0, camera: Optional[Camera] = None, world_size: int = 1, rank: int = 0):
+                         seed=0, camera: Optional[Camera] = None, world_size: int = 1, rank: int = 0, *,
+                         current_count: Optional[torch.Tensor] = None, num_frames: Optional[torch.Tensor] = None):
         """The whole training iteration as ONE captured graph: sample_target_mv_device(iteration=None) followed by the
         counted optimization_iteration on its DeviceTarget -- sampler, forward, losses, backward and sparse Adam, with no
         host synchronisation and no data-dependent shape.  Returns a callable; every call replays the graph, i.e. draws the
@@ -1115,6 +1224,11 @@ class NeuralGraphRenderer:
         contiguous device tensors (current_field_ids / frame_cid_to_ncid int64), since a copy made here would be the
         one the graph keeps reading.
 
+        current_count / num_frames (both or neither; one-element int32 device tensors): the live sampler, see
+        sample_target_mv_device.  current_field_ids, c_c2w and frame_cid_to_ncid are then fixed-capacity buffers whose
+        first current_count / num_frames entries are read at every replay, so ONE capture serves every frame (a new
+        observed set: observed_fields_device(out=...)) and every keyframe (KeyframeStore) until fields are added.
+
         Every rank must own at least one field of the map (a capacity of 0 rows raises ValueError: nothing to capture).
 
         Before the capture the sampler and the counted step run once with update=False (allocations, the device
@@ -1124,8 +1238,12 @@ class NeuralGraphRenderer:
         if why is not None:
             raise RuntimeError(f"capture_training: {why} is outside the counted step (optimization_iteration would fall "
                                "back to DeviceTarget.materialize(), which synchronises)")
+        if (current_count is None) != (num_frames is None):
+            raise ValueError("capture_training: current_count and num_frames go together (both device tensors, or neither)")
         dev = torch.device(self._device)
         named = dict(current_field_ids=current_field_ids, c_c2w=c_c2w, nc_rgbd=nc_rgbd, frame_cid_to_ncid=frame_cid_to_ncid)
+        if current_count is not None:
+            named.update(current_count=current_count, num_frames=num_frames)
         for n, t in named.items():
             if not t.is_cuda or not t.is_contiguous():
                 raise ValueError(f"capture_training: {n} must be a contiguous device tensor (it is read in place at every replay)")
@@ -1137,6 +1255,8 @@ class NeuralGraphRenderer:
         def watched():
             ts = dict(named, positions=self._global_map_dict["positions"], orientations=self._global_map_dict["orientations"])
             ts.update({"param " + n: v for n, v in self._model.all_fields_params.items()})
+            if self.track_training_iterations:
+                ts["training_iterations"] = self._training_iterations()
             return {n: (t.data_ptr(), tuple(t.shape)) for n, t in ts.items()}
         for n in ("positions", "orientations"):
             if not self._global_map_dict[n].is_contiguous():
@@ -1145,7 +1265,10 @@ class NeuralGraphRenderer:
         def sample():
             return self.sample_target_mv_device(current_field_ids, c_c2w, nc_rgbd, frame_cid_to_ncid, num_train_fields,
                                                 num_rays_per_field, num_fields=num_fields, camera=camera, seed=seed,
-                                                iteration=None, world_size=world_size, rank=rank)
+                                                iteration=None, world_size=world_size, rank=rank, current_count=current_count,
+                                                num_frames=num_frames)
+        if self.track_training_iterations:
+            self._training_iterations()                       # must exist before the capture
         # once outside the capture, on a side stream: creates the device counters, the workspace and the gradient buffers
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
