@@ -28,9 +28,18 @@ ngm_debug_plan_bwd (both csrc/ngm_api.hip), with TI / TH = ceil(dim / 16) and MI
   variant 2  k_field_bwd16s   stash kind 1 and mode f32, fused step only
   variant 1  k_field_bwd16    (TI,TH,L) in {(4,4,1) (4,4,2) (2,2,1) (2,2,2) (3,3,1)}, skip no, not triplane
   variant 0  k_field_bwd      everything else at L <= 2
-No backward kernel takes L = 3; nothing takes L = 4 or L = 3 at <= 32 units (refused by check_field_cfg itself)."""
+No backward kernel takes L = 3; nothing takes L = 4 or L = 3 at <= 32 units (refused by check_field_cfg itself).
+
+The storage axis (tests/test_gpu_storage_matrix.py): STORAGE = 16-bit `weight_dtype`s; `storage16(entry, surface, mode)` is the
+outcome with the weights stored in 16 bits.  Storage is no input of either plan (ngm_debug_plan_fwd / ngm_debug_plan_bwd take
+none), so it is the entry's own outcome -- same arithmetic, backward variant and comp_fused, same NGM_E_UNSUPPORTED where fp32
+refuses -- and what runs must equal the run on fp32 storage of the same (16-bit-representable) weights bit for bit.  One
+exception: the triplane planes exist in fp32 only -- REFUSE_STORAGE: NotImplementedError from NeuralFieldSet, NGM_E_INVALID
+("triplane encoding needs fp32 planes", check_params) at the ops level, on every surface, before any plan is made."""
 
 REFUSE = "refuse"
+REFUSE_STORAGE = "refuse-storage"       # 16-bit storage of an encoding that has fp32 tensors only: NGM_E_INVALID, nothing launched
+STORAGE = ("bfloat16", "float16")
 SURFACES = ("points", "autograd", "step", "render", "knn")
 STEP_SHAPES = ((3, 37, 5, 2), (2, 33, 1, 1))            # (F, R, n_c, n_g) of the fused surfaces
 FORWARD_SHAPES = ("<1,1,1>", "<1,1,2>", "<2,2,1>", "<2,2,2>", "<2,2,3>")
@@ -50,7 +59,7 @@ def step(mm, variant, comp_fused):
 
 
 def runs(outcome):
-    return outcome != REFUSE
+    return outcome not in (REFUSE, REFUSE_STORAGE)
 
 
 def _both(o):
@@ -186,6 +195,13 @@ NAMES = [e["name"] for e in ENTRIES]
 
 def modes(entry, surface):
     return list(entry[surface])
+
+
+def storage16(entry, surface, mode):
+    """outcome of (entry, surface, mode) with the weights stored as either of STORAGE: see the module docstring"""
+    if entry["fkw"]["encoding"] == "triplane":
+        return REFUSE_STORAGE
+    return entry[surface][mode]
 
 
 def is_hash(entry):

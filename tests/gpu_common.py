@@ -430,4 +430,28 @@ def matrix_knn_case(entry, NF=7, K_=3, P=500):
     return case
 
 
+def matrix_storage_twin(case, dt):
+    """The storage twin of a matrix case (points / step / knn): every trainable tensor rounded to the 16-bit type `dt`.
+    -> dict(f32 = the rounded values kept as fp32 (the fp32 twin), lp = the same tensors as `dt`); the constant hash shifts stay
+    fp32 in both.  Everything else -- points, rays, jitter, targets, d_out -- is the case's own: the comparison between the two
+    storages is bitwise, so a sample near a ReLU kink is on the same side in both.  Cached with the case."""
+    key = ("twin", id(case), dt)
+    if key not in _MATRIX_CACHE:
+        const = lambda k: k in K.NO_GRAD_PARAMS or k == "_neus_sd"
+        lp = {k: (v.clone() if const(k) else v.to(dt)) for k, v in case["params"].items()}
+        _MATRIX_CACHE[key] = dict(f32={k: v.float() for k, v in lp.items()}, lp=lp, case=case)     # (case: keeps id(case) alive)
+    return _MATRIX_CACHE[key]
+
+
+def matrix_twin_oracle(entry, dt, P=257):
+    """the oracle's point evaluation, fp64, at the ROUNDED parameters of matrix_points_case(entry, P) -> (F, P, 4) fp32.  Cached."""
+    key = ("twin-oracle", entry["name"], dt, P)
+    if key not in _MATRIX_CACHE:
+        c = matrix_points_case(entry, P)
+        p64 = {k: v.double() for k, v in matrix_storage_twin(c, dt)["f32"].items()}
+        with torch.no_grad():
+            _MATRIX_CACHE[key] = O.field_set_forward_vmap(c["q"].double(), c["pos"].double(), c["quat"].double(), p64, c["fs"]).float()
+    return _MATRIX_CACHE[key]
+
+
 from _philox_host import host_philox_draws, host_philox_uniform  # noqa: E402,F401  (numpy-only: also imported by the CPU tests)

@@ -1,14 +1,16 @@
 """CPU companion of tests/test_gpu_config_matrix.py: the table of tests/_config_matrix.py builds and evaluates in the oracle,
 its fused-step problems can be made kink-free inside the usual cap, it is internally consistent, and the library's validator
 draws the line where the table says it does (argument validation needs no GPU), and the library's two host-side plans
-(ngm_debug_plan_fwd, ngm_debug_plan_bwd) reproduce the table's forward and backward columns."""
+(ngm_debug_plan_fwd, ngm_debug_plan_bwd) reproduce the table's forward and backward columns.  For the storage axis
+(tests/test_gpu_storage_matrix.py): the rounded twin problems are inside the conditions under which a bitwise comparison of the
+two storages says something, before any kernel runs, and `storage16` follows from the fp32 columns."""
 import ctypes as C
 
 import pytest
 import torch
 
 import _config_matrix as CM
-from gpu_common import matrix_knn_case, matrix_points_case, matrix_step_case
+from gpu_common import matrix_knn_case, matrix_points_case, matrix_step_case, matrix_storage_twin, matrix_twin_oracle
 from neural_graph_mapping_amd import _capi as K
 from oracle import ngm_oracle as O
 
@@ -82,6 +84,62 @@ def test_forward_shape_follows_from_the_widths():
         assert mi == mh, e["name"]                        # what check_field_cfg demands of every entry
         if e["shape"] is not None:
             assert e["shape"] == f"<{mi},{mh},{fc.num_layers}>", e["name"]
+
+
+F16_MIN_NORMAL = 2.0 ** -14
+
+
+@pytest.mark.parametrize("wd", CM.STORAGE)
+@pytest.mark.parametrize("name", CM.NAMES)
+def test_rounded_twin_is_a_problem_worth_comparing(name, wd):
+    """The point-evaluation parameters of every entry (the refused ones are handed to the library too), rounded to either storage type: finite (max |w| = 8.565, far
+    from fp16's 65504), at least half of each tensor's elements changed by the rounding (the twin is another problem than the
+    case), under 1 % of a tensor's elements lost to zero, fp16 subnormals present in every entry (so their widening is
+    exercised), the 16-bit set exactly the fp32 twin, and the oracle's forward at the rounded parameters finite.  The step and
+    kNN parameters of the entry stay finite too."""
+    e = CM.BY_NAME[name]
+    dt = getattr(torch, wd)
+    c = matrix_points_case(e, 257)
+    tw = matrix_storage_twin(c, dt)
+    assert matrix_storage_twin(c, dt) is tw                              # cached
+    subnormal = 0
+    for k, v in c["params"].items():
+        r, lp = tw["f32"][k], tw["lp"][k]
+        assert r.dtype == torch.float32 and torch.isfinite(r).all(), k
+        if k in K.NO_GRAD_PARAMS:
+            assert lp.dtype == torch.float32 and torch.equal(r, v) and torch.equal(lp, v), k
+            continue
+        assert lp.dtype == dt and torch.equal(lp.float(), r) and torch.equal(r.to(dt), lp), k      # representable: the round trip is exact
+        assert float(v.abs().max()) < 2.0 ** 15, k                          # half of fp16's range (the largest weight is 8.565)
+        assert float((r != v).float().mean()) >= 0.5, (k, "rounding changes less than half of the elements")
+        assert float(((r == 0) & (v != 0)).float().mean()) < 0.01, (k, "rounding loses 1 % of the elements to zero")
+        h = v.to(torch.float16).float().abs()
+        subnormal += int(((h > 0) & (h < F16_MIN_NORMAL)).sum())
+    assert subnormal >= 1, "no fp16 subnormal in the entry: their widening would not be exercised"
+    out = matrix_twin_oracle(e, dt)
+    assert out.shape == (3, 257, 4) and torch.isfinite(out).all() and not torch.equal(out, c["out"])
+    for other in (matrix_knn_case(e),) + tuple(matrix_step_case(e, s) for s in CM.STEP_SHAPES):
+        for k, v in matrix_storage_twin(other, dt)["f32"].items():
+            assert torch.isfinite(v).all() and float(v.abs().max()) < 65504, k
+
+
+def test_storage_axis_follows_from_the_fp32_columns():
+    """storage16 is defined for every (entry, surface, mode): the entry's own outcome, REFUSE_STORAGE for the triplane planes and
+    for nothing else; what refuses in fp32 refuses (a 16-bit copy opens no kernel), what runs names the same kernels."""
+    assert CM.STORAGE == ("bfloat16", "float16")
+    tri = 0
+    for e in CM.ENTRIES:
+        for s in CM.SURFACES:
+            for mode in CM.modes(e, s):
+                o = CM.storage16(e, s, mode)
+                if e["fkw"]["encoding"] == "triplane":
+                    assert o == CM.REFUSE_STORAGE and not CM.runs(o)
+                    tri += 1
+                else:
+                    assert o == e[s][mode] and o != CM.REFUSE_STORAGE and CM.runs(o) == (e[s][mode] != CM.REFUSE)
+    assert tri > 0
+    with pytest.raises(KeyError):
+        CM.storage16(CM.ENTRIES[0], "points", "fp8")
 
 
 @pytest.fixture(scope="module")

@@ -89,12 +89,14 @@ def _renderer(e, c, mode, **extra):
     return r
 
 
-def _step_matches(e, c, mode, expect):
-    """one fused step with update=False against the oracle: prediction, every loss term, every gradient, the kernels that ran"""
+def _step_matches(e, c, mode, expect, r=None, ids=None):
+    """one fused step with update=False against the oracle: prediction, every loss term, every gradient, the kernels that ran
+    (r, ids: a renderer that holds the case's fields in the rows `ids` of a larger set, tests/test_gpu_storage_matrix.py)"""
     _, mm, variant, fused = expect
     KINK.extend(dict(k, test=_test_id()) for k in c["kink"])          # the margins report: rays taken out of this comparison
-    r = _renderer(e, c, mode)
-    res = r.optimization_iteration(make_target(c["t"], torch.arange(c["F"])), c["u_c"].to(DEV), c["u_g"].to(DEV), update=False)
+    r = _renderer(e, c, mode) if r is None else r
+    ids = torch.arange(c["F"]) if ids is None else ids
+    res = r.optimization_iteration(make_target(c["t"], ids), c["u_c"].to(DEV), c["u_g"].to(DEV), update=False)
     torch.cuda.synchronize()
     assert (_reported(0), L().ngm_debug_last_bwd_variant(), L().ngm_debug_last_comp_fused()) == (mm, variant, fused)
     _fwd_close(e, res["prediction"].rgbds, c["pred"]["rgbds"], "rgbds", mode)
