@@ -164,17 +164,16 @@ class ObservedFields(C.Structure):
 def target_sample_mv_live_plan(max_current, num_fields, num_train_fields, num_rays, world_size=1, rank=0):
     """Host-side sizes of ngm_target_sample_mv_live: (max_observed, max_random, capacity) = (min(T // 2, max_current),
     min(T, num_fields), min(min(T, num_fields), fields of this rank)): what target_sample_mv_plan gives for every count
-    of current fields, since n_obs + n_rand = min(T, num_fields) whatever it is.  Raises on bad input."""
-    target_sample_mv_plan(0, num_fields, num_train_fields, num_rays, world_size, rank)
+    of current fields, since n_obs + n_rand = min(T, num_fields) whatever it is (taken from it at no current field, where
+    n_obs = 0).  Raises on bad input."""
+    _, n_all, capacity = target_sample_mv_plan(0, num_fields, num_train_fields, num_rays, world_size, rank)
     if isinstance(max_current, bool) or not isinstance(max_current, int):
         raise TypeError(f"target_sample_mv_live: max_current must be an int, got {type(max_current).__name__}")
     if max_current < 1:
         raise ValueError(f"target_sample_mv_live: max_current must be >= 1, got {max_current}")
     if max_current > num_fields:
         raise ValueError(f"target_sample_mv_live: max_current {max_current} but only {num_fields} fields in the map")
-    n_all = min(num_train_fields, num_fields)
-    owned = (num_fields - rank + world_size - 1) // world_size if num_fields > rank else 0
-    return min(num_train_fields // 2, max_current), n_all, min(n_all, owned)
+    return min(num_train_fields // 2, max_current), n_all, capacity
 
 
 _lib = None

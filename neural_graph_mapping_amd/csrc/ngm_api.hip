@@ -482,73 +482,61 @@ int ngm_target_rays(const ngm_keyframes* kf, int32_t F, int32_t R, const float* 
   return check_launch("ngm_target_rays");
 }
 
+// ngm_target_sample_mv and ngm_target_sample_mv_live (is_live; its sizes are maxima, include/ngm_hip.h): one list of checks in
+// which five conditions differ, one launcher.  `fn` is the entry point that was called.
+static int target_sample_mv(const char* fn, bool is_live, const ngm_keyframes* kf, const ngm_target_sample* s, const ngm_target_live* live,
+                            const ngm_target_out* out, void* workspace, int64_t workspace_bytes, void* stream) {
+  char msg[256];
+  auto refuse = [&](int code, const char* what) { return snprintf(msg, sizeof(msg), "%s: %s", fn, what), fail(code, msg); };
+  int e = check_keyframes(kf);
+  if (e) return e;
+  if (!s || !out || (is_live && !live)) return refuse(NGM_E_INVALID, "NULL argument");
+  if (s->num_current < (is_live ? 1 : 0) || s->num_fields < 0 || s->num_rays < 1 || s->world_size < 1 || s->rank < 0 ||
+      s->rank >= s->world_size || (is_live && live->num_train_fields < 0))
+    return refuse(NGM_E_INVALID, is_live ? "bad sizes (max_current >= 1, num_rays >= 1, 0 <= rank < world_size)"
+                                         : "bad sizes (num_rays >= 1, 0 <= rank < world_size)");
+  if (is_live && s->num_current > s->num_fields) return refuse(NGM_E_INVALID, "max_current > num_fields");
+  const int32_t T = is_live ? live->num_train_fields : 0, max_obs = T / 2 < s->num_current ? T / 2 : s->num_current;
+  const int64_t n_all = is_live ? (T < s->num_fields ? T : s->num_fields) : (int64_t)s->num_observed + s->num_random;
+  if (is_live && (s->num_observed != max_obs || s->num_random != n_all))
+    return refuse(NGM_E_INVALID, "num_observed / num_random must be their maxima min(T / 2, max_current) / min(T, num_fields)");
+  if (!is_live && (s->num_observed < 0 || s->num_observed > s->num_current || s->num_random < 0 ||
+                   s->num_random > s->num_fields - s->num_observed))
+    return refuse(NGM_E_INVALID, "num_observed <= num_current and num_random <= num_fields - num_observed");
+  if (n_all > NGM_TARGET_MAX_DRAW) return refuse(NGM_E_UNSUPPORTED, "more than NGM_TARGET_MAX_DRAW fields drawn");
+  const int64_t owned = s->num_fields > s->rank ? ((int64_t)s->num_fields - s->rank + s->world_size - 1) / s->world_size : 0;
+  if (s->capacity != (n_all < owned ? n_all : owned))
+    return refuse(NGM_E_INVALID, is_live ? "capacity must be min(min(T, num_fields), fields of this rank)"
+                                         : "capacity must be min(num_observed + num_random, fields of this rank)");
+  if (is_live && (!live->num_current || !live->num_frames || !live->num_observed || !live->num_random))
+    return refuse(NGM_E_INVALID, "NULL device count");
+  if (((is_live || s->num_current > 0) && !s->current_field_ids) || (s->num_fields > 0 && !s->field_positions) || !s->count ||
+      !s->field_ids || (s->num_observed > 0 && !s->subset_observed) || (s->num_random > 0 && !s->subset_random) || !s->offsets ||
+      !s->frame_cids || !s->u_xy || (s->iteration < 0 && !s->iteration_dev))
+    return refuse(NGM_E_INVALID, "NULL array (iteration < 0 needs iteration_dev)");
+  if (!out->ijs || !out->near || !out->far || !out->gt || !out->rgbds || !out->rgb_mask || !out->depth_mask || !out->term_probs ||
+      !out->term_mask)
+    return refuse(NGM_E_INVALID, "NULL output array");
+  if ((int64_t)s->capacity * s->num_rays > INT32_MAX) return refuse(NGM_E_UNSUPPORTED, "capacity x num_rays >= 2^31");
+  const int64_t need = ngm_target_sample_mv_bytes(kf->num_frames, s->num_current, s->num_fields, s->capacity);
+  if (!workspace || workspace_bytes < need) return refuse(NGM_E_WORKSPACE, "workspace too small");
+  ngm_launch_target_sample_mv(*kf, *s, is_live ? live : nullptr, *out, workspace, (hipStream_t)stream);
+  return check_launch(fn);
+}
 int64_t ngm_target_sample_mv_workspace(int32_t num_frames, int32_t num_current, int32_t num_fields, int32_t capacity) {
   if (num_frames < 1 || num_current < 0 || num_fields < 0 || capacity < 0 || capacity > NGM_TARGET_MAX_DRAW) return -1;
   return ngm_target_sample_mv_bytes(num_frames, num_current, num_fields, capacity);
 }
+int64_t ngm_target_sample_mv_live_workspace(int32_t max_frames, int32_t max_current, int32_t num_fields, int32_t capacity) {
+  return max_current < 1 ? -1 : ngm_target_sample_mv_workspace(max_frames, max_current, num_fields, capacity);   // a maximum: >= 1
+}
 int ngm_target_sample_mv(const ngm_keyframes* kf, const ngm_target_sample* s, const ngm_target_out* out, void* workspace,
                          int64_t workspace_bytes, void* stream) {
-  int e = check_keyframes(kf);
-  if (e) return e;
-  if (!s || !out) return fail(NGM_E_INVALID, "ngm_target_sample_mv: NULL argument");
-  if (s->num_current < 0 || s->num_fields < 0 || s->num_rays < 1 || s->world_size < 1 || s->rank < 0 || s->rank >= s->world_size)
-    return fail(NGM_E_INVALID, "ngm_target_sample_mv: bad sizes (num_rays >= 1, 0 <= rank < world_size)");
-  if (s->num_observed < 0 || s->num_observed > s->num_current || s->num_random < 0 || s->num_random > s->num_fields - s->num_observed)
-    return fail(NGM_E_INVALID, "ngm_target_sample_mv: num_observed <= num_current and num_random <= num_fields - num_observed");
-  const int64_t n_all = (int64_t)s->num_observed + s->num_random;
-  if (n_all > NGM_TARGET_MAX_DRAW) return fail(NGM_E_UNSUPPORTED, "ngm_target_sample_mv: more than NGM_TARGET_MAX_DRAW fields drawn");
-  const int64_t owned = s->num_fields > s->rank ? ((int64_t)s->num_fields - s->rank + s->world_size - 1) / s->world_size : 0;
-  if (s->capacity != (n_all < owned ? n_all : owned))
-    return fail(NGM_E_INVALID, "ngm_target_sample_mv: capacity must be min(num_observed + num_random, fields of this rank)");
-  if ((s->num_current > 0 && !s->current_field_ids) || (s->num_fields > 0 && !s->field_positions) || !s->count || !s->field_ids ||
-      (s->num_observed > 0 && !s->subset_observed) || (s->num_random > 0 && !s->subset_random) || !s->offsets || !s->frame_cids ||
-      !s->u_xy || (s->iteration < 0 && !s->iteration_dev))
-    return fail(NGM_E_INVALID, "ngm_target_sample_mv: NULL array (iteration < 0 needs iteration_dev)");
-  if (!out->ijs || !out->near || !out->far || !out->gt || !out->rgbds || !out->rgb_mask || !out->depth_mask || !out->term_probs ||
-      !out->term_mask)
-    return fail(NGM_E_INVALID, "ngm_target_sample_mv: NULL output array");
-  if ((int64_t)s->capacity * s->num_rays > INT32_MAX) return fail(NGM_E_UNSUPPORTED, "ngm_target_sample_mv: capacity x num_rays >= 2^31");
-  const int64_t need = ngm_target_sample_mv_bytes(kf->num_frames, s->num_current, s->num_fields, s->capacity);
-  if (!workspace || workspace_bytes < need) return fail(NGM_E_WORKSPACE, "ngm_target_sample_mv: workspace too small");
-  ngm_launch_target_sample_mv(*kf, *s, *out, workspace, (hipStream_t)stream);
-  return check_launch("ngm_target_sample_mv");
-}
-
-int64_t ngm_target_sample_mv_live_workspace(int32_t max_frames, int32_t max_current, int32_t num_fields, int32_t capacity) {
-  if (max_frames < 1 || max_current < 1 || num_fields < 0 || capacity < 0 || capacity > NGM_TARGET_MAX_DRAW) return -1;
-  return ngm_target_sample_mv_bytes(max_frames, max_current, num_fields, capacity);
+  return target_sample_mv("ngm_target_sample_mv", false, kf, s, nullptr, out, workspace, workspace_bytes, stream);
 }
 int ngm_target_sample_mv_live(const ngm_keyframes* kf, const ngm_target_sample* s, const ngm_target_live* live,
                               const ngm_target_out* out, void* workspace, int64_t workspace_bytes, void* stream) {
-  int e = check_keyframes(kf);
-  if (e) return e;
-  if (!s || !out || !live) return fail(NGM_E_INVALID, "ngm_target_sample_mv_live: NULL argument");
-  if (s->num_current < 1 || s->num_fields < 0 || s->num_rays < 1 || s->world_size < 1 || s->rank < 0 || s->rank >= s->world_size ||
-      live->num_train_fields < 0)
-    return fail(NGM_E_INVALID, "ngm_target_sample_mv_live: bad sizes (max_current >= 1, num_rays >= 1, 0 <= rank < world_size)");
-  if (s->num_current > s->num_fields) return fail(NGM_E_INVALID, "ngm_target_sample_mv_live: max_current > num_fields");
-  const int32_t T = live->num_train_fields;
-  const int32_t max_obs = T / 2 < s->num_current ? T / 2 : s->num_current, n_all = T < s->num_fields ? T : s->num_fields;
-  if (s->num_observed != max_obs || s->num_random != n_all)
-    return fail(NGM_E_INVALID, "ngm_target_sample_mv_live: num_observed / num_random must be their maxima min(T / 2, max_current) / min(T, num_fields)");
-  if (n_all > NGM_TARGET_MAX_DRAW) return fail(NGM_E_UNSUPPORTED, "ngm_target_sample_mv_live: more than NGM_TARGET_MAX_DRAW fields drawn");
-  const int64_t owned = s->num_fields > s->rank ? ((int64_t)s->num_fields - s->rank + s->world_size - 1) / s->world_size : 0;
-  if (s->capacity != (n_all < owned ? n_all : owned))
-    return fail(NGM_E_INVALID, "ngm_target_sample_mv_live: capacity must be min(min(T, num_fields), fields of this rank)");
-  if (!live->num_current || !live->num_frames || !live->num_observed || !live->num_random)
-    return fail(NGM_E_INVALID, "ngm_target_sample_mv_live: NULL device count");
-  if (!s->current_field_ids || (s->num_fields > 0 && !s->field_positions) || !s->count || !s->field_ids ||
-      (s->num_observed > 0 && !s->subset_observed) || (s->num_random > 0 && !s->subset_random) || !s->offsets || !s->frame_cids ||
-      !s->u_xy || (s->iteration < 0 && !s->iteration_dev))
-    return fail(NGM_E_INVALID, "ngm_target_sample_mv_live: NULL array (iteration < 0 needs iteration_dev)");
-  if (!out->ijs || !out->near || !out->far || !out->gt || !out->rgbds || !out->rgb_mask || !out->depth_mask || !out->term_probs ||
-      !out->term_mask)
-    return fail(NGM_E_INVALID, "ngm_target_sample_mv_live: NULL output array");
-  if ((int64_t)s->capacity * s->num_rays > INT32_MAX) return fail(NGM_E_UNSUPPORTED, "ngm_target_sample_mv_live: capacity x num_rays >= 2^31");
-  const int64_t need = ngm_target_sample_mv_bytes(kf->num_frames, s->num_current, s->num_fields, s->capacity);
-  if (!workspace || workspace_bytes < need) return fail(NGM_E_WORKSPACE, "ngm_target_sample_mv_live: workspace too small");
-  ngm_launch_target_sample_mv_live(*kf, *s, *live, *out, workspace, (hipStream_t)stream);
-  return check_launch("ngm_target_sample_mv_live");
+  return target_sample_mv("ngm_target_sample_mv_live", true, kf, s, live, out, workspace, workspace_bytes, stream);
 }
 
 int64_t ngm_target_observed_fields_workspace(int32_t height, int32_t width) {

@@ -279,10 +279,8 @@ int ngm_launch_target_sv_rays(int F, int R, const float* pos_c, float radius, co
 int ngm_launch_target_rays(const ngm_keyframes& kf, int F, int R, const float* field_pos, float radius, const float* bbox,
                            const int64_t* frame_cids, const float* u_xy, const ngm_target_out& o, hipStream_t st);
 int64_t ngm_target_sample_mv_bytes(int num_frames, int num_current, int num_fields, int capacity);
-int ngm_launch_target_sample_mv(const ngm_keyframes& kf, const ngm_target_sample& s, const ngm_target_out& o, void* workspace,
-                                hipStream_t st);
-int ngm_launch_target_sample_mv_live(const ngm_keyframes& kf, const ngm_target_sample& s, const ngm_target_live& live,
-                                     const ngm_target_out& o, void* workspace, hipStream_t st);
+int ngm_launch_target_sample_mv(const ngm_keyframes& kf, const ngm_target_sample& s, const ngm_target_live* live /* or NULL */,
+                                const ngm_target_out& o, void* workspace, hipStream_t st);
 int64_t ngm_target_observed_fields_bytes(int height, int width);
 int ngm_launch_target_observed_fields(const ngm_observed_fields& a, void* workspace, hipStream_t st);
 int ngm_launch_field_counts_add(const int64_t* field_ids, const int32_t* count, int rows, int num_fields, int64_t* training_iterations,

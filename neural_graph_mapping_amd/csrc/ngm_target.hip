@@ -543,31 +543,27 @@ __global__ __launch_bounds__(TSMV_RAY_THREADS) void k_tsmv_rays(ngm_keyframes kf
 int64_t ngm_target_sample_mv_bytes(int num_frames, int num_current, int num_fields, int capacity) {
   return tsmv_layout(num_frames, num_current, num_fields, capacity, nullptr, nullptr);
 }
-int ngm_launch_target_sample_mv(const ngm_keyframes& kf, const ngm_target_sample& s, const ngm_target_out& o, void* workspace,
-                                hipStream_t st) {
-  tsmv_ws w;
-  tsmv_layout(kf.num_frames, s.num_current, s.num_fields, s.capacity, (char*)workspace, &w);
-  const tsmv_live lv = {nullptr, nullptr, nullptr, nullptr, 0};
-  hipLaunchKernelGGL(k_tsmv_draw<false>, dim3(1), dim3(TSMV_DRAW_THREADS), 0, st, s, w, lv);
-  if (s.capacity == 0) return 0;
+// live == nullptr: the sizes of kf / s are the counts in force.  Otherwise kf.num_frames = max_frames, s.num_current =
+// max_current, s.num_observed / s.num_random = their maxima (include/ngm_hip.h) and the kernels read the counts from `live`.
+template <bool LIVE>
+static void tsmv_launch(const ngm_keyframes& kf, const ngm_target_sample& s, const tsmv_live& lv, const ngm_target_out& o,
+                        const tsmv_ws& w, hipStream_t st) {
+  hipLaunchKernelGGL(k_tsmv_draw<LIVE>, dim3(1), dim3(TSMV_DRAW_THREADS), 0, st, s, w, lv);
+  if (s.capacity == 0) return;
   const int64_t pairs = (int64_t)s.capacity * kf.num_frames;
-  hipLaunchKernelGGL(k_tsmv_visibility<false>, dim3((unsigned)((pairs + 127) / 128)), dim3(128), 0, st, kf, s.capacity, s.radius, w, lv);
-  hipLaunchKernelGGL(k_tsmv_rays<false>, dim3((unsigned)((s.num_rays + TSMV_RAY_THREADS - 1) / TSMV_RAY_THREADS), (unsigned)s.capacity),
+  hipLaunchKernelGGL(k_tsmv_visibility<LIVE>, dim3((unsigned)((pairs + 127) / 128)), dim3(128), 0, st, kf, s.capacity, s.radius, w, lv);
+  hipLaunchKernelGGL(k_tsmv_rays<LIVE>, dim3((unsigned)((s.num_rays + TSMV_RAY_THREADS - 1) / TSMV_RAY_THREADS), (unsigned)s.capacity),
                      dim3(TSMV_RAY_THREADS), 0, st, kf, s, o, w, lv);
-  return 0;
 }
-// kf.num_frames = max_frames, s.num_current = max_current, s.num_observed / s.num_random = their maxima (include/ngm_hip.h)
-int ngm_launch_target_sample_mv_live(const ngm_keyframes& kf, const ngm_target_sample& s, const ngm_target_live& live,
-                                     const ngm_target_out& o, void* workspace, hipStream_t st) {
+int ngm_launch_target_sample_mv(const ngm_keyframes& kf, const ngm_target_sample& s, const ngm_target_live* live,
+                                const ngm_target_out& o, void* workspace, hipStream_t st) {
   tsmv_ws w;
   tsmv_layout(kf.num_frames, s.num_current, s.num_fields, s.capacity, (char*)workspace, &w);
-  const tsmv_live lv = {live.num_current, live.num_frames, live.num_observed, live.num_random, live.num_train_fields};
-  hipLaunchKernelGGL(k_tsmv_draw<true>, dim3(1), dim3(TSMV_DRAW_THREADS), 0, st, s, w, lv);
-  if (s.capacity == 0) return 0;
-  const int64_t pairs = (int64_t)s.capacity * kf.num_frames;
-  hipLaunchKernelGGL(k_tsmv_visibility<true>, dim3((unsigned)((pairs + 127) / 128)), dim3(128), 0, st, kf, s.capacity, s.radius, w, lv);
-  hipLaunchKernelGGL(k_tsmv_rays<true>, dim3((unsigned)((s.num_rays + TSMV_RAY_THREADS - 1) / TSMV_RAY_THREADS), (unsigned)s.capacity),
-                     dim3(TSMV_RAY_THREADS), 0, st, kf, s, o, w, lv);
+  if (!live)
+    tsmv_launch<false>(kf, s, tsmv_live{nullptr, nullptr, nullptr, nullptr, 0}, o, w, st);
+  else
+    tsmv_launch<true>(kf, s, tsmv_live{live->num_current, live->num_frames, live->num_observed, live->num_random,
+                                       live->num_train_fields}, o, w, st);
   return 0;
 }
 

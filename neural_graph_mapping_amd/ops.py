@@ -1013,6 +1013,7 @@ def target_sv_rays(pos_c, radius, pts_ijs, segments, image, fx, fy, cx, cy):
 # ------------------------------------------------------------------------------------------------
 TARGET_SAMPLE_MV_OUT = ("ijs", "c2ws", "near", "far", "gt", "field_ids", "rgbds", "rgb_mask", "depth_mask", "term_probs",
                         "term_mask", "count", "subset_observed", "subset_random", "offsets", "frame_cids", "u_xy")
+TARGET_SAMPLE_MV_LIVE_OUT = TARGET_SAMPLE_MV_OUT + ("num_observed", "num_random")
 
 
 def _target_sample_mv_shapes(n_obs, n_rand, cap, R):
@@ -1023,42 +1024,94 @@ def _target_sample_mv_shapes(n_obs, n_rand, cap, R):
             ((n_obs,), i64), ((n_rand,), i64), ((20, 3), f32), ((cap, R), i64), ((cap, R, 2), f32)]
 
 
-@_op("target_sample_mv", mutates_args=("iteration_dev",))
-def _target_sample_mv_op(current_field_ids: torch.Tensor, c2ws: torch.Tensor, rgbd_store: torch.Tensor,
-                         frame_to_store: torch.Tensor, field_positions: torch.Tensor, iteration_dev: Optional[torch.Tensor],
-                         intrinsics: List[float], radius: float, num_fields: int, num_train_fields: int, num_rays: int,
-                         seed: int, iteration: int, world_size: int, rank: int) -> List[torch.Tensor]:
-    """TARGET_SAMPLE_MV_OUT, every per-field array at the host-known capacity (rows past count: padding)"""
-    n_obs, n_rand, cap = K.target_sample_mv_plan(current_field_ids.shape[0], num_fields, num_train_fields, num_rays, world_size, rank)
-    dev = field_positions.device
-    outs = [torch.empty(shape, dtype=dt, device=dev) for shape, dt in _target_sample_mv_shapes(n_obs, n_rand, cap, num_rays)]
-    o = dict(zip(TARGET_SAMPLE_MV_OUT, outs))
+def _target_sample_mv_empty(live, num_current, device, num_fields, num_train_fields, num_rays, world_size, rank):
+    """(n_obs, n_rand, capacity, outputs): the host-side plan and the unwritten outputs of torch.ops.ngm355.target_sample_mv
+    (live: target_sample_mv_live, num_current its maximum) in TARGET_SAMPLE_MV_OUT (TARGET_SAMPLE_MV_LIVE_OUT) order --
+    all a fake implementation returns"""
+    plan = K.target_sample_mv_live_plan if live else K.target_sample_mv_plan
+    n_obs, n_rand, cap = plan(num_current, num_fields, num_train_fields, num_rays, world_size, rank)
+    shapes = _target_sample_mv_shapes(n_obs, n_rand, cap, num_rays) + ([((1,), torch.int32)] * 2 if live else [])
+    return n_obs, n_rand, cap, [torch.empty(shape, dtype=dt, device=device) for shape, dt in shapes]
+
+
+def _target_sample_mv_call(current_field_ids, counts, c2ws, rgbd_store, frame_to_store, field_positions, iteration_dev, intrinsics,
+                           radius, num_fields, num_train_fields, num_rays, seed, iteration, world_size, rank):
+    """Both ops: counts = None calls ngm_target_sample_mv, counts = (current_count, num_frames) ngm_target_sample_mv_live
+    (current_field_ids / c2ws / frame_to_store are then sized for their maxima)"""
+    live = counts is not None
+    fn = "ngm_target_sample_mv_live" if live else "ngm_target_sample_mv"
+    num_current, dev = current_field_ids.shape[0], field_positions.device
+    n_obs, n_rand, cap, outs = _target_sample_mv_empty(live, num_current, dev, num_fields, num_train_fields, num_rays, world_size, rank)
+    o = dict(zip(TARGET_SAMPLE_MV_LIVE_OUT, outs))
     kf = keyframes_struct(c2ws, rgbd_store, frame_to_store, *intrinsics)
-    ws_bytes = K.lib().ngm_target_sample_mv_workspace(kf.num_frames, current_field_ids.shape[0], num_fields, cap)
+    ws_bytes = getattr(K.lib(), fn + "_workspace")(kf.num_frames, num_current, num_fields, cap)
     if ws_bytes < 0:
-        raise K.NgmError("ngm_target_sample_mv_workspace: bad sizes")
+        raise K.NgmError(fn + "_workspace: bad sizes")
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    s = K.TargetSample(_ptr(current_field_ids), _ptr(field_positions), current_field_ids.shape[0], num_fields, n_obs, n_rand,
+    s = K.TargetSample(_ptr(current_field_ids), _ptr(field_positions), num_current, num_fields, n_obs, n_rand,
                        num_rays, cap, world_size, rank, float(radius), 0, int(seed), int(iteration), _ptr(iteration_dev))
     for k in ("field_ids", "count", "subset_observed", "subset_random", "offsets", "frame_cids", "u_xy"):
         setattr(s, k, o[k].data_ptr())
     out = K.TargetOut()
     for k in ("ijs", "c2ws", "near", "far", "gt", "rgbds", "rgb_mask", "depth_mask", "term_probs", "term_mask"):
         setattr(out, k, o[k].data_ptr())
-    K.check(K.lib().ngm_target_sample_mv(C.byref(kf), C.byref(s), C.byref(out), _ptr(ws), ws_bytes, _stream()),
-            "ngm_target_sample_mv")
+    args = [C.byref(kf), C.byref(s), C.byref(out), _ptr(ws), ws_bytes, _stream()]
+    if live:
+        lv = K.TargetLive(_ptr(counts[0]), _ptr(counts[1]), o["num_observed"].data_ptr(), o["num_random"].data_ptr(),
+                          num_train_fields, 0)
+        args.insert(2, C.byref(lv))
+    K.check(getattr(K.lib(), fn)(*args), fn)
     return outs
+
+
+@_op("target_sample_mv", mutates_args=("iteration_dev",))
+def _target_sample_mv_op(current_field_ids: torch.Tensor, c2ws: torch.Tensor, rgbd_store: torch.Tensor,
+                         frame_to_store: torch.Tensor, field_positions: torch.Tensor, iteration_dev: Optional[torch.Tensor],
+                         intrinsics: List[float], radius: float, num_fields: int, num_train_fields: int, num_rays: int,
+                         seed: int, iteration: int, world_size: int, rank: int) -> List[torch.Tensor]:
+    """TARGET_SAMPLE_MV_OUT, every per-field array at the host-known capacity (rows past count: padding)"""
+    return _target_sample_mv_call(current_field_ids, None, c2ws, rgbd_store, frame_to_store, field_positions, iteration_dev,
+                                  intrinsics, radius, num_fields, num_train_fields, num_rays, seed, iteration, world_size, rank)
 
 
 @_target_sample_mv_op.register_fake
 def _(current_field_ids, c2ws, rgbd_store, frame_to_store, field_positions, iteration_dev, intrinsics, radius, num_fields,
       num_train_fields, num_rays, seed, iteration, world_size, rank):
-    n_obs, n_rand, cap = K.target_sample_mv_plan(current_field_ids.shape[0], num_fields, num_train_fields, num_rays, world_size, rank)
-    return [torch.empty(shape, dtype=dt, device=field_positions.device)
-            for shape, dt in _target_sample_mv_shapes(n_obs, n_rand, cap, num_rays)]
+    return _target_sample_mv_empty(False, current_field_ids.shape[0], field_positions.device, num_fields, num_train_fields,
+                                   num_rays, world_size, rank)[3]
 
 
-def _check_target_sample_mv(current_field_ids, c2ws, rgbd_store, frame_to_store, field_positions, iteration_dev, num_fields):
+# the same sampler with its counts in device memory (include/ngm_hip.h ngm_target_sample_mv_live)
+@_op("target_sample_mv_live", mutates_args=("iteration_dev",))
+def _target_sample_mv_live_op(current_field_ids: torch.Tensor, current_count: torch.Tensor, c2ws: torch.Tensor,
+                              num_frames: torch.Tensor, rgbd_store: torch.Tensor, frame_to_store: torch.Tensor,
+                              field_positions: torch.Tensor, iteration_dev: Optional[torch.Tensor], intrinsics: List[float],
+                              radius: float, num_fields: int, num_train_fields: int, num_rays: int, seed: int, iteration: int,
+                              world_size: int, rank: int) -> List[torch.Tensor]:
+    """TARGET_SAMPLE_MV_LIVE_OUT; current_field_ids / c2ws / frame_to_store are sized for their maxima, the counts in force
+    are current_count / num_frames (device int32)"""
+    return _target_sample_mv_call(current_field_ids, (current_count, num_frames), c2ws, rgbd_store, frame_to_store, field_positions,
+                                  iteration_dev, intrinsics, radius, num_fields, num_train_fields, num_rays, seed, iteration,
+                                  world_size, rank)
+
+
+@_target_sample_mv_live_op.register_fake
+def _(current_field_ids, current_count, c2ws, num_frames, rgbd_store, frame_to_store, field_positions, iteration_dev, intrinsics,
+      radius, num_fields, num_train_fields, num_rays, seed, iteration, world_size, rank):
+    return _target_sample_mv_empty(True, current_field_ids.shape[0], field_positions.device, num_fields, num_train_fields,
+                                   num_rays, world_size, rank)[3]
+
+
+def _check_device_count(fn, name, t):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.numel() != 1:
+        raise TypeError(f"{fn}: {name} must be a one-element int32 tensor")
+
+
+def _target_sample_mv_checked(fn, current_field_ids, counts, c2ws, rgbd_store, frame_to_store, field_positions, intrinsics, radius,
+                              num_fields, num_train_fields, num_rays, seed, iteration, iteration_dev, world_size, rank):
+    """The public wrappers' checks under the caller's name `fn`, then its op; the outputs as a dict"""
+    live = counts is not None
+
     def need(cond, msg, exc=ValueError):
         if not cond:
             raise exc("target_sample_mv: " + msg)
@@ -1077,6 +1130,23 @@ def _check_target_sample_mv(current_field_ids, c2ws, rgbd_store, frame_to_store,
     if iteration_dev is not None:
         need(isinstance(iteration_dev, torch.Tensor) and iteration_dev.dtype == torch.int64 and iteration_dev.numel() == 1,
              "iteration_dev must be a one-element int64 tensor", TypeError)
+    for name, t in zip(("current_count", "num_frames"), counts or ()):
+        _check_device_count(fn, name, t)
+    (K.target_sample_mv_live_plan if live else K.target_sample_mv_plan)(current_field_ids.shape[0], num_fields, num_train_fields,
+                                                                        num_rays, world_size, rank)
+    if iteration is None and iteration_dev is None:
+        raise ValueError(f"{fn}: iteration=None needs iteration_dev (the device counter)")
+    if iteration is not None and int(iteration) < 0:
+        raise ValueError(f"{fn}: iteration must be >= 0, got {iteration}")
+    if not 0 <= int(seed) < 2 ** 63:
+        raise ValueError(f"{fn}: seed must be in [0, 2^63), got {seed}")
+    _require_gpu(current_field_ids, *(counts or ()), c2ws, rgbd_store, frame_to_store, field_positions, iteration_dev)
+    tail = (rgbd_store, frame_to_store, field_positions, iteration_dev, intrinsics, float(radius), num_fields, num_train_fields,
+            num_rays, int(seed), -1 if iteration is None else int(iteration), world_size, rank)
+    if live:
+        return dict(zip(TARGET_SAMPLE_MV_LIVE_OUT, torch.ops.ngm355.target_sample_mv_live(current_field_ids, counts[0], c2ws,
+                                                                                          counts[1], *tail)))
+    return dict(zip(TARGET_SAMPLE_MV_OUT, torch.ops.ngm355.target_sample_mv(current_field_ids, c2ws, *tail)))
 
 
 def target_sample_mv(current_field_ids, c2ws, rgbd_store, frame_to_store, field_positions, fx, fy, cx, cy, radius, num_fields,
@@ -1084,78 +1154,11 @@ def target_sample_mv(current_field_ids, c2ws, rgbd_store, frame_to_store, field_
     """_sample_target_mv (rm.py:1259-1459) with the draws on the device, three launches, no host synchronisation
     (torch.ops.ngm355.target_sample_mv).  iteration=None: iteration_dev (one-element int64 device tensor) is read and
     advanced by one inside the call; an int uses that iteration and leaves iteration_dev alone.  Returns a dict keyed by
-    TARGET_SAMPLE_MV_OUT; per-field arrays have K.target_sample_mv_plan(...)[2] rows, `count` (int32, device) of them valid."""
-    _check_target_sample_mv(current_field_ids, c2ws, rgbd_store, frame_to_store, field_positions, iteration_dev, int(num_fields))
-    K.target_sample_mv_plan(current_field_ids.shape[0], int(num_fields), int(num_train_fields), int(num_rays_per_field),
-                            int(world_size), int(rank))
-    if iteration is None and iteration_dev is None:
-        raise ValueError("target_sample_mv: iteration=None needs iteration_dev (the device counter)")
-    if iteration is not None and int(iteration) < 0:
-        raise ValueError(f"target_sample_mv: iteration must be >= 0, got {iteration}")
-    if not 0 <= int(seed) < 2 ** 63:
-        raise ValueError(f"target_sample_mv: seed must be in [0, 2^63), got {seed}")
-    _require_gpu(current_field_ids, c2ws, rgbd_store, frame_to_store, field_positions, iteration_dev)
-    outs = torch.ops.ngm355.target_sample_mv(current_field_ids, c2ws, rgbd_store, frame_to_store, field_positions, iteration_dev,
-                                             [float(fx), float(fy), float(cx), float(cy)], float(radius), int(num_fields),
-                                             int(num_train_fields), int(num_rays_per_field), int(seed),
-                                             -1 if iteration is None else int(iteration), int(world_size), int(rank))
-    return dict(zip(TARGET_SAMPLE_MV_OUT, outs))
-
-
-# ------------------------------------------------------------------------------------------------
-# the same sampler with its counts in device memory (include/ngm_hip.h ngm_target_sample_mv_live)
-# ------------------------------------------------------------------------------------------------
-TARGET_SAMPLE_MV_LIVE_OUT = TARGET_SAMPLE_MV_OUT + ("num_observed", "num_random")
-
-
-def _target_sample_mv_live_shapes(max_obs, max_rand, cap, R):
-    return _target_sample_mv_shapes(max_obs, max_rand, cap, R) + [((1,), torch.int32), ((1,), torch.int32)]
-
-
-@_op("target_sample_mv_live", mutates_args=("iteration_dev",))
-def _target_sample_mv_live_op(current_field_ids: torch.Tensor, current_count: torch.Tensor, c2ws: torch.Tensor,
-                              num_frames: torch.Tensor, rgbd_store: torch.Tensor, frame_to_store: torch.Tensor,
-                              field_positions: torch.Tensor, iteration_dev: Optional[torch.Tensor], intrinsics: List[float],
-                              radius: float, num_fields: int, num_train_fields: int, num_rays: int, seed: int, iteration: int,
-                              world_size: int, rank: int) -> List[torch.Tensor]:
-    """TARGET_SAMPLE_MV_LIVE_OUT; current_field_ids / c2ws / frame_to_store are sized for their maxima, the counts in force
-    are current_count / num_frames (device int32)"""
-    max_current = current_field_ids.shape[0]
-    max_obs, max_rand, cap = K.target_sample_mv_live_plan(max_current, num_fields, num_train_fields, num_rays, world_size, rank)
-    dev = field_positions.device
-    outs = [torch.empty(shape, dtype=dt, device=dev) for shape, dt in _target_sample_mv_live_shapes(max_obs, max_rand, cap, num_rays)]
-    o = dict(zip(TARGET_SAMPLE_MV_LIVE_OUT, outs))
-    kf = keyframes_struct(c2ws, rgbd_store, frame_to_store, *intrinsics)
-    ws_bytes = K.lib().ngm_target_sample_mv_live_workspace(kf.num_frames, max_current, num_fields, cap)
-    if ws_bytes < 0:
-        raise K.NgmError("ngm_target_sample_mv_live_workspace: bad sizes")
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    s = K.TargetSample(_ptr(current_field_ids), _ptr(field_positions), max_current, num_fields, max_obs, max_rand,
-                       num_rays, cap, world_size, rank, float(radius), 0, int(seed), int(iteration), _ptr(iteration_dev))
-    for k in ("field_ids", "count", "subset_observed", "subset_random", "offsets", "frame_cids", "u_xy"):
-        setattr(s, k, o[k].data_ptr())
-    live = K.TargetLive(_ptr(current_count), _ptr(num_frames), o["num_observed"].data_ptr(), o["num_random"].data_ptr(),
-                        num_train_fields, 0)
-    out = K.TargetOut()
-    for k in ("ijs", "c2ws", "near", "far", "gt", "rgbds", "rgb_mask", "depth_mask", "term_probs", "term_mask"):
-        setattr(out, k, o[k].data_ptr())
-    K.check(K.lib().ngm_target_sample_mv_live(C.byref(kf), C.byref(s), C.byref(live), C.byref(out), _ptr(ws), ws_bytes, _stream()),
-            "ngm_target_sample_mv_live")
-    return outs
-
-
-@_target_sample_mv_live_op.register_fake
-def _(current_field_ids, current_count, c2ws, num_frames, rgbd_store, frame_to_store, field_positions, iteration_dev, intrinsics,
-      radius, num_fields, num_train_fields, num_rays, seed, iteration, world_size, rank):
-    max_obs, max_rand, cap = K.target_sample_mv_live_plan(current_field_ids.shape[0], num_fields, num_train_fields, num_rays,
-                                                          world_size, rank)
-    return [torch.empty(shape, dtype=dt, device=field_positions.device)
-            for shape, dt in _target_sample_mv_live_shapes(max_obs, max_rand, cap, num_rays)]
-
-
-def _check_device_count(fn, name, t):
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.numel() != 1:
-        raise TypeError(f"{fn}: {name} must be a one-element int32 tensor")
+    TARGET_SAMPLE_MV_OUT; per-field arrays have K.target_sample_mv_plan(...)[2] rows, `count` (int32, device) of them valid.
+    This and target_sample_mv_live run one implementation."""
+    return _target_sample_mv_checked("target_sample_mv", current_field_ids, None, c2ws, rgbd_store, frame_to_store, field_positions,
+                                     [float(fx), float(fy), float(cx), float(cy)], radius, int(num_fields), int(num_train_fields),
+                                     int(num_rays_per_field), seed, iteration, iteration_dev, int(world_size), int(rank))
 
 
 def target_sample_mv_live(current_field_ids, current_count, c2ws, num_frames, rgbd_store, frame_to_store, field_positions, fx, fy,
@@ -1167,24 +1170,10 @@ def target_sample_mv_live(current_field_ids, current_count, c2ws, num_frames, rg
     target_sample_mv(current_field_ids[:n], c2ws[:m], ...) for the counts n, m in force; nothing past them is read.
     Returns a dict keyed by TARGET_SAMPLE_MV_LIVE_OUT: subset_observed / subset_random at their maxima with -1 past
     num_observed / num_random (int32, device)."""
-    _check_target_sample_mv(current_field_ids, c2ws, rgbd_store, frame_to_store, field_positions, iteration_dev, int(num_fields))
-    _check_device_count("target_sample_mv_live", "current_count", current_count)
-    _check_device_count("target_sample_mv_live", "num_frames", num_frames)
-    K.target_sample_mv_live_plan(current_field_ids.shape[0], int(num_fields), int(num_train_fields), int(num_rays_per_field),
-                                 int(world_size), int(rank))
-    if iteration is None and iteration_dev is None:
-        raise ValueError("target_sample_mv_live: iteration=None needs iteration_dev (the device counter)")
-    if iteration is not None and int(iteration) < 0:
-        raise ValueError(f"target_sample_mv_live: iteration must be >= 0, got {iteration}")
-    if not 0 <= int(seed) < 2 ** 63:
-        raise ValueError(f"target_sample_mv_live: seed must be in [0, 2^63), got {seed}")
-    _require_gpu(current_field_ids, current_count, c2ws, num_frames, rgbd_store, frame_to_store, field_positions, iteration_dev)
-    outs = torch.ops.ngm355.target_sample_mv_live(current_field_ids, current_count, c2ws, num_frames, rgbd_store, frame_to_store,
-                                                  field_positions, iteration_dev, [float(fx), float(fy), float(cx), float(cy)],
-                                                  float(radius), int(num_fields), int(num_train_fields), int(num_rays_per_field),
-                                                  int(seed), -1 if iteration is None else int(iteration), int(world_size),
-                                                  int(rank))
-    return dict(zip(TARGET_SAMPLE_MV_LIVE_OUT, outs))
+    return _target_sample_mv_checked("target_sample_mv_live", current_field_ids, (current_count, num_frames), c2ws, rgbd_store,
+                                     frame_to_store, field_positions, [float(fx), float(fy), float(cx), float(cy)], radius,
+                                     int(num_fields), int(num_train_fields), int(num_rays_per_field), seed, iteration, iteration_dev,
+                                     int(world_size), int(rank))
 
 
 # ------------------------------------------------------------------------------------------------

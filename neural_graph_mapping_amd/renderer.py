@@ -32,6 +32,16 @@ class DeviceTarget(namedtuple("DeviceTarget", Target._fields + ("count", "subset
     the kernels read `count` on the device); materialize() is only needed by consumers that want data-dependent shapes."""
     __slots__ = ()
 
+    @staticmethod
+    def from_sampler(o: dict, world_size: int) -> "DeviceTarget":
+        """From the outputs of ops.target_sample_mv, or of ops.target_sample_mv_live (a LiveDeviceTarget then)"""
+        rows = (o["ijs"], o["c2ws"], o["near"], o["far"], o["gt"], o["field_ids"], o["rgbds"], o["rgb_mask"], o["depth_mask"],
+                o["term_probs"], o["term_mask"], o["count"], o["subset_observed"], o["subset_random"], o["offsets"],
+                o["frame_cids"], o["u_xy"], int(world_size))                                       # in the order of _fields
+        if "num_observed" in o:
+            return LiveDeviceTarget(*rows, num_observed=o["num_observed"], num_random=o["num_random"])
+        return DeviceTarget(*rows)
+
     def materialize(self) -> Target:
         """The usual Target, sliced to `count`: reading `count` is the one host synchronisation."""
         n = int(self.count.item())
@@ -702,27 +712,14 @@ class NeuralGraphRenderer:
                 self._target_iter_dev = torch.zeros(1, dtype=torch.int64, device=dev)
             counter = self._target_iter_dev
         fx, fy, cx, cy, _ = cam.get_pinhole_camera_parameters(0.0)
+        views = [cur.contiguous(), c_c2w.contiguous()]
         if current_count is not None:
-            o = ops.target_sample_mv_live(cur.contiguous(), current_count, c_c2w.contiguous(), num_frames, nc_rgbd.contiguous(),
-                                          frame_cid_to_ncid.contiguous(), self._global_map_dict["positions"].contiguous(), fx, fy,
-                                          cx, cy, self._field_radius + 0.0, int(num_fields), int(num_train_fields),
-                                          int(num_rays_per_field), seed=seed, iteration=iteration, iteration_dev=counter,
-                                          world_size=world_size, rank=rank)
-            return LiveDeviceTarget(ijs=o["ijs"], c2ws=o["c2ws"], near_distances=o["near"], far_distances=o["far"],
-                                    gt_distances=o["gt"], field_ids=o["field_ids"], rgbds=o["rgbds"], rgb_mask=o["rgb_mask"],
-                                    depth_mask=o["depth_mask"], term_probs=o["term_probs"], term_mask=o["term_mask"],
-                                    count=o["count"], subset_observed=o["subset_observed"], subset_random=o["subset_random"],
-                                    offsets=o["offsets"], frame_cids=o["frame_cids"], u_xy=o["u_xy"], world_size=int(world_size),
-                                    num_observed=o["num_observed"], num_random=o["num_random"])
-        o = ops.target_sample_mv(cur.contiguous(), c_c2w.contiguous(), nc_rgbd.contiguous(), frame_cid_to_ncid.contiguous(),
-                                 self._global_map_dict["positions"].contiguous(), fx, fy, cx, cy, self._field_radius + 0.0,
-                                 int(num_fields), int(num_train_fields), int(num_rays_per_field), seed=seed, iteration=iteration,
-                                 iteration_dev=counter, world_size=world_size, rank=rank)
-        return DeviceTarget(ijs=o["ijs"], c2ws=o["c2ws"], near_distances=o["near"], far_distances=o["far"], gt_distances=o["gt"],
-                            field_ids=o["field_ids"], rgbds=o["rgbds"], rgb_mask=o["rgb_mask"], depth_mask=o["depth_mask"],
-                            term_probs=o["term_probs"], term_mask=o["term_mask"], count=o["count"],
-                            subset_observed=o["subset_observed"], subset_random=o["subset_random"], offsets=o["offsets"],
-                            frame_cids=o["frame_cids"], u_xy=o["u_xy"], world_size=int(world_size))
+            views = [views[0], current_count, views[1], num_frames]
+        sampler = ops.target_sample_mv if current_count is None else ops.target_sample_mv_live
+        o = sampler(*views, nc_rgbd.contiguous(), frame_cid_to_ncid.contiguous(), self._global_map_dict["positions"].contiguous(),
+                    fx, fy, cx, cy, self._field_radius + 0.0, int(num_fields), int(num_train_fields), int(num_rays_per_field),
+                    seed=seed, iteration=iteration, iteration_dev=counter, world_size=world_size, rank=rank)
+        return DeviceTarget.from_sampler(o, world_size)
 
     @torch.no_grad()
     def observed_fields_device(self, rgbd_image, c2w, num_points: int = 500, seed: int = 0, frame: Optional[int] = None,
@@ -922,11 +919,16 @@ class NeuralGraphRenderer:
             return self._counted_iteration(target, u_coarse, u_guided, seed, update)
         if self._rc_train.geometry_mode == K.GEO["neus"] and not self._neus_fused():
             return self.optimization_iteration_staged(target, u_coarse, u_guided, seed, update)
-        if target.ijs.shape[0] == 0:
+        return self._fused_iteration(target, u_coarse, u_guided, seed, update)
+
+    def _fused_iteration(self, target: Target, u_coarse, u_guided, seed, update, count=None) -> dict:
+        """The iteration on the fused kernels, plain (count None) or counted: forward, loss exchange, backward"""
+        if target.ijs.shape[0] == 0:                      # counted: capacity 0 is known on the host (a rank that owns no field at all)
             return self._idle_iteration(update)
-        ctx = self._iteration_forward(target, u_coarse, u_guided, seed, advance=update)
+        ctx = self._iteration_forward(target, u_coarse, u_guided, seed, advance=update, count=count)
         if self.process_group is not None:
-            # the only cross-GPU exchange of the path: global loss sums / counts (64 bytes)
+            # the only cross-GPU exchange of the path: global loss sums / counts (64 bytes); counted: entered by every rank,
+            # whatever its own count
             self._exchange(ctx["w"]["sums"])
         return self._iteration_backward(ctx, update)
 
@@ -957,12 +959,7 @@ class NeuralGraphRenderer:
                               "DeviceTarget.materialize(), which synchronises with the host every iteration",
                               RuntimeWarning, stacklevel=3)
             return self.optimization_iteration(target.materialize(), u_coarse, u_guided, seed, update)
-        if target.ijs.shape[0] == 0:                      # capacity 0 is known on the host (a rank that owns no field at all)
-            return self._idle_iteration(update)
-        ctx = self._iteration_forward(target, u_coarse, u_guided, seed, advance=update, count=target.count)
-        if self.process_group is not None:
-            self._exchange(ctx["w"]["sums"])                # entered by every rank, whatever its own count
-        return self._iteration_backward(ctx, update)
+        return self._fused_iteration(target, u_coarse, u_guided, seed, update, count=target.count)
 
     def check_exchange(self):
         """Raise if the in-graph loss exchange ever timed out or lost step (its sums were partial then, i.e. the update of
@@ -1052,15 +1049,14 @@ class NeuralGraphRenderer:
         # single GPU: nothing happens between forward and backward, so the loss partials are reduced by the backward
         # itself (deferred reduction, one launch less); with a process group the sums are needed here for the all-reduce
         defer = self.process_group is None
+        fn, args = "ngm_render_fwd", [C.byref(fc), C.byref(rc), C.byref(ps), C.byref(rays), C.byref(tg), C.byref(pred),
+                                      None if defer else w["sums"].data_ptr(), w["ws"].data_ptr(), w["wsb"], st]
         if count is not None:
             if count.dtype != torch.int32 or count.numel() != 1 or not count.is_cuda:
                 raise TypeError("count must be a device int32 tensor of one element")
-            K.check(L.ngm_render_fwd_counted(C.byref(fc), C.byref(rc), C.byref(ps), C.byref(rays), C.byref(tg), C.byref(pred),
-                                             None if defer else w["sums"].data_ptr(), w["ws"].data_ptr(), w["wsb"], st,
-                                             count.data_ptr()), "ngm_render_fwd_counted")
-        else:
-            K.check(L.ngm_render_fwd(C.byref(fc), C.byref(rc), C.byref(ps), C.byref(rays), C.byref(tg), C.byref(pred),
-                                     None if defer else w["sums"].data_ptr(), w["ws"].data_ptr(), w["wsb"], st), "ngm_render_fwd")
+            fn += "_counted"
+            args.append(count.data_ptr())
+        K.check(getattr(L, fn)(*args), fn)
         return dict(fc=fc, rc=rc, ps=ps, rays=rays, tg=tg, pred=pred, w=w, F=F, fids=fids, allp=allp, lp=lp, defer=defer,
                     neus=neus, count=count, keep=(keep, dm, tm, rgbds_t, target))
 
@@ -1076,52 +1072,31 @@ class NeuralGraphRenderer:
         if ctx.get("neus") and "_neus_sd" not in grads:
             grads["_neus_sd"] = torch.zeros(F, device=self._device)
             gs.neus_sd = grads["_neus_sd"].data_ptr()
-        sums_ptr = None if ctx.get("defer") else w["sums"].data_ptr()
         count = ctx.get("count")
-        if count is not None:
-            # the counted step (neus / triplane never get here: their extra launches below run over all F rows)
-            if update:
-                arr, n_mlp, lat = ops.adam_tensor_arrays(fc, allp, self._optim_state, grads, ctx.get("lp"))
-                K.check(L.ngm_render_bwd_adam_counted(
-                    C.byref(fc), C.byref(rc), C.byref(ps), C.byref(rays), C.byref(tg), C.byref(pred), sums_ptr, C.byref(gs), arr,
-                    n_mlp, lat, ops._ptr(fids), int(self._step) + 1, ops._ptr(self._step_dev), self._learning_rate, 0.9, 0.999,
-                    self._adam_eps, self._adam_weight_decay, w["loss"].data_ptr(), w["ws"].data_ptr(), w["wsb"], st,
-                    count.data_ptr()), "ngm_render_bwd_adam_counted")
-                self._step += 1                                  # after the call: a refused step is no step
-            else:
-                K.check(L.ngm_render_bwd_counted(C.byref(fc), C.byref(rc), C.byref(ps), C.byref(rays), C.byref(tg), C.byref(pred),
-                                                 sums_ptr, C.byref(gs), w["loss"].data_ptr(), w["ws"].data_ptr(), w["wsb"],
-                                                 st, count.data_ptr()), "ngm_render_bwd_counted")
-        elif update:
-            # backward + sparse Adam in one call: the gradient-reduction kernel applies the update of the MLP tensors
-            # itself (rm.py:1183-1221); the device counter already holds the new step (the loss reduction advanced it)
+        # backward (+ sparse Adam in the same call: the gradient-reduction kernel applies the update of the MLP tensors itself,
+        # rm.py:1183-1221; the device counter already holds the new step, the loss reduction advanced it); with a count the
+        # *_counted entry point takes its pointer as one more argument
+        fn, args = "ngm_render_bwd", [C.byref(fc), C.byref(rc), C.byref(ps), C.byref(rays), C.byref(tg), C.byref(pred),
+                                      None if ctx.get("defer") else w["sums"].data_ptr(), C.byref(gs)]
+        if update:
             arr, n_mlp, lat = ops.adam_tensor_arrays(fc, allp, self._optim_state, grads, ctx.get("lp"))
-            K.check(L.ngm_render_bwd_adam(C.byref(fc), C.byref(rc), C.byref(ps), C.byref(rays), C.byref(tg), C.byref(pred),
-                                          sums_ptr, C.byref(gs), arr, n_mlp, lat, ops._ptr(fids), int(self._step) + 1,
-                                          ops._ptr(self._step_dev), self._learning_rate, 0.9, 0.999, self._adam_eps,
-                                          self._adam_weight_decay, w["loss"].data_ptr(), w["ws"].data_ptr(), w["wsb"], st),
-                    "ngm_render_bwd_adam")
-            self._step += 1                                  # one counter for all fields (rm.py:380-385); a refused step is no step
+            fn += "_adam"
+            args += [arr, n_mlp, lat, ops._ptr(fids), int(self._step) + 1, ops._ptr(self._step_dev), self._learning_rate, 0.9, 0.999,
+                     self._adam_eps, self._adam_weight_decay]
+        args += [w["loss"].data_ptr(), w["ws"].data_ptr(), w["wsb"], st]
+        if count is not None:
+            fn += "_counted"
+            args.append(count.data_ptr())
+        K.check(getattr(L, fn)(*args), fn)
+        if update:
+            self._step += 1                # one counter for all fields (rm.py:380-385); after the call: a refused step is no step
+        if update and count is None:       # the counted step has neither: these launches run over all F rows
             if fc.encoding == K.ENC["triplane"]:      # the feature planes: gradient from the fixed-point scatter, same sparse Adam
-                n = "_encoding.plane_coef"
-                pl, stt, gp = allp[n], self._optim_state[n], grads[n]
-                one = (K.AdamTensor * 1)(K.AdamTensor(pl.data_ptr(), stt["exp_avg"].data_ptr(), stt["exp_avg_sq"].data_ptr(),
-                                                      gp.data_ptr(), pl.stride(0), gp.stride(0), gp[0].numel()))
-                K.check(L.ngm_adam_sparse_multi(one, 1, ops._ptr(fids), F, int(self._step), ops._ptr(self._step_dev),
-                                                self._learning_rate, 0.9, 0.999, self._adam_eps, self._adam_weight_decay, 0,
-                                                None, st), "ngm_adam_sparse_multi")
+                gp = grads["_encoding.plane_coef"]
+                self._adam_one_tensor("_encoding.plane_coef", gp, allp["_encoding.plane_coef"].stride(0), gp.stride(0),
+                                      gp[0].numel(), fids, F, st)
             if ctx.get("neus"):      # the per-field standard deviation is a parameter of its own (rm.py:641-644): same Adam
-                n = "_neus_sd"
-                sd, stt = self._model.all_fields_params[n], self._optim_state[n]
-                one = (K.AdamTensor * 1)(K.AdamTensor(sd.data_ptr(), stt["exp_avg"].data_ptr(), stt["exp_avg_sq"].data_ptr(),
-                                                      grads[n].data_ptr(), 1, 1, 1))
-                K.check(L.ngm_adam_sparse_multi(one, 1, ops._ptr(fids), F, int(self._step), ops._ptr(self._step_dev),
-                                                self._learning_rate, 0.9, 0.999, self._adam_eps, self._adam_weight_decay, 0,
-                                                None, st), "ngm_adam_sparse_multi")
-        else:
-            K.check(L.ngm_render_bwd(C.byref(fc), C.byref(rc), C.byref(ps), C.byref(rays), C.byref(tg), C.byref(pred),
-                                     sums_ptr, C.byref(gs), w["loss"].data_ptr(), w["ws"].data_ptr(), w["wsb"],
-                                     st), "ngm_render_bwd")
+                self._adam_one_tensor("_neus_sd", grads["_neus_sd"], 1, 1, 1, fids, F, st)
         if update:
             self._count_training_iteration(fids, count)
         lv = w["loss"]
@@ -1132,6 +1107,15 @@ class NeuralGraphRenderer:
             loss["grads"] = grads
         loss["prediction"] = Prediction(w["rgbds"], w["color_vars"], w["depth_vars"], w["term_probs"], None, None)
         return loss
+
+    def _adam_one_tensor(self, name, grad, stride, grad_stride, numel, fids, F, st) -> None:
+        """sparse Adam on rows `fids` of one stacked parameter tensor, at the step this iteration has just counted"""
+        p, stt = self._model.all_fields_params[name], self._optim_state[name]
+        one = (K.AdamTensor * 1)(K.AdamTensor(p.data_ptr(), stt["exp_avg"].data_ptr(), stt["exp_avg_sq"].data_ptr(),
+                                              grad.data_ptr(), stride, grad_stride, numel))
+        K.check(K.lib().ngm_adam_sparse_multi(one, 1, ops._ptr(fids), F, int(self._step), ops._ptr(self._step_dev),
+                                              self._learning_rate, 0.9, 0.999, self._adam_eps, self._adam_weight_decay, 0,
+                                              None, st), "ngm_adam_sparse_multi")
 
     def capture_iteration(self, target: Target, seed=0, u_coarse=None, u_guided=None):
         """Capture optimization_iteration(target) into hipGraphs (torch.cuda.CUDAGraph); the returned callable
@@ -1156,14 +1140,28 @@ class NeuralGraphRenderer:
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             for _ in range(2):                                # warm-up on a side stream (allocations, lazy init)
-                out = self.optimization_iteration(target, u_coarse, u_guided, seed=seed)
+                self.optimization_iteration(target, u_coarse, u_guided, seed=seed)
         torch.cuda.current_stream().wait_stream(s)
+
+        def whole():
+            return self.optimization_iteration(target, u_coarse, u_guided, seed=seed)
+        return self._capture("capture_iteration", whole,
+                             lambda: self._iteration_forward(target, u_coarse, u_guided, seed, advance=True, count=count))
+
+    def _capture(self, caller: str, whole, forward):
+        """The capture both capture_iteration and capture_training end in, after their own warm-up.  `whole()` is one
+        iteration; `forward()` its part before the loss all-reduce, returning the context _iteration_backward(ctx, True)
+        finishes.  Single GPU, or the loss exchange is a kernel of the iteration (distributed.PeerExchange): `whole` as one
+        graph.  A process group without peer exchange: two graphs on one pool around the collective, captured in
+        thread-local mode (the process group's watchdog thread may touch the HIP runtime meanwhile); if that capture is
+        refused, `whole` itself is returned (`.graph` None, `.capture_error` the message) after a RuntimeWarning.  The
+        capture pass records, it does not execute: `_step` is put back, and every replay counts one step."""
+        step0 = self._step
         if self.process_group is None or self.peer_exchange is not None:
-            # one graph: single GPU, or the loss exchange is a kernel of the iteration (distributed.PeerExchange)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                out = self.optimization_iteration(target, u_coarse, u_guided, seed=seed)
-            self._step -= 1                                   # the capture pass records, it does not execute
+                out = whole()
+            self._step = step0
 
             def replay():
                 graph.replay()
@@ -1173,28 +1171,21 @@ class NeuralGraphRenderer:
                 return out
             replay.graph = graph
             return replay
-        # thread-local capture mode: the process group's watchdog thread may touch the HIP runtime meanwhile
-        step0 = self._step
         try:
             g1, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
             with torch.cuda.graph(g1, capture_error_mode="thread_local"):
-                ctx = self._iteration_forward(target, u_coarse, u_guided, seed, advance=True, count=count)
+                ctx = forward()
             with torch.cuda.graph(g2, pool=g1.pool(), capture_error_mode="thread_local"):
                 out = self._iteration_backward(ctx, True)
         except RuntimeError as err:
             # capture refused (runtime / collective library combination): plain launches still work, but the caller
-            # is told -- an iteration of ~10 launches is launch-bound without the graph (`replay.graph is None`)
+            # is told -- an iteration of ~10 launches is launch-bound without the graph (`.graph is None`)
             self._step = step0
             torch.cuda.synchronize()
-            warnings.warn(f"capture_iteration: graph capture refused ({err}); falling back to plain launches",
-                          RuntimeWarning, stacklevel=2)
-
-            def eager():
-                return self.optimization_iteration(target, u_coarse, u_guided, seed=seed)
-            eager.graph = None
-            eager.capture_error = str(err)
-            return eager
-        self._step -= 1
+            warnings.warn(f"{caller}: graph capture refused ({err}); falling back to plain launches", RuntimeWarning, stacklevel=3)
+            whole.graph, whole.capture_error = None, str(err)
+            return whole
+        self._step = step0
         sums, group = ctx["w"]["sums"], self.process_group
 
         def replay2():
@@ -1285,37 +1276,18 @@ class NeuralGraphRenderer:
             else:
                 self._target_iter_dev.copy_(it0)
         torch.cuda.current_stream().wait_stream(s)
-        step0 = self._step
-        two = self.process_group is not None and self.peer_exchange is None
-        if not two:
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                target = sample()
-                out = self.optimization_iteration(target, seed=seed)
-            self._step = step0                                # the capture pass records, it does not execute
-            graphs = graph
-        else:
-            try:
-                g1, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g1, capture_error_mode="thread_local"):
-                    target = sample()
-                    ctx = self._iteration_forward(target, None, None, seed, advance=True, count=target.count)
-                with torch.cuda.graph(g2, pool=g1.pool(), capture_error_mode="thread_local"):
-                    out = self._iteration_backward(ctx, True)
-            except RuntimeError as err:
-                self._step = step0
-                torch.cuda.synchronize()
-                warnings.warn(f"capture_training: graph capture refused ({err}); falling back to plain launches",
-                              RuntimeWarning, stacklevel=2)
 
-                def eager():
-                    eager.target = sample()
-                    return self.optimization_iteration(eager.target, seed=seed)
-                eager.graph, eager.target, eager.capture_error = None, None, str(err)
-                return eager
-            self._step = step0
-            graphs = (g1, g2)
-            sums, group = ctx["w"]["sums"], self.process_group
+        def step():                                           # the refused capture's fallback too: a fresh target per call
+            step.target = sample()
+            return self.optimization_iteration(step.target, seed=seed)
+
+        def forward():
+            step.target = sample()
+            return self._iteration_forward(step.target, None, None, seed, advance=True, count=step.target.count)
+        run = self._capture("capture_training", step, forward)
+        if run.graph is None:
+            run.target = None
+            return run
         seen = watched()
 
         def replay():
@@ -1324,15 +1296,6 @@ class NeuralGraphRenderer:
                 changed = sorted(n for n in now if now[n] != seen.get(n)) or ["number of fields"]
                 raise RuntimeError(f"capture_training: {changed} changed shape or storage since the capture; the graph "
                                    "reads the captured addresses -- capture again")
-            if two:
-                g1.replay()
-                torch.distributed.all_reduce(sums, group=group)
-                g2.replay()
-            else:
-                graph.replay()
-                if self.peer_exchange is not None:
-                    self._count_exchange()
-            self._step += 1
-            return out
-        replay.graph, replay.target = graphs, target
+            return run()
+        replay.graph, replay.target = run.graph, step.target
         return replay

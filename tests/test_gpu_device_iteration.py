@@ -735,3 +735,112 @@ def test_unsupported_configurations_fall_back_or_raise(cfg):
         y.add_(1.0)
         with pytest.raises(RuntimeError, match="cannot be captured"):
             ra.optimization_iteration(ta, seed=2)
+
+
+# ------------------------------------------------------------------------------------------------ 12. capture_iteration(DeviceTarget)
+def _small_scene():
+    """TWO's sizes, the smallest of this module: 24 fields (the even ids hidden), T = 6 -> a capacity of 6 rows of 16 rays;
+    every third field is current, so hidden fields are among the observed draws and padded rows exist"""
+    return PartScene(24, 12, hidden=list(range(0, 24, 2)), seed=1), torch.arange(0, 24, 3, device=DEV)
+
+
+@pytest.mark.parametrize("net", ["m1", "hash"])
+def test_capture_iteration_on_a_device_target(net):
+    """A DeviceTarget is captured as the counted step: 4 replays after the warm-up's two real updates are, bit for bit, six
+    eager counted iterations on the same target."""
+    T, R, SEED = TWO["T"], TWO["R"], 3
+    sc, cur = _small_scene()
+    ra, rb = sc.renderer(NETS[net]), sc.renderer(NETS[net])
+    ta = ra.sample_target_mv_device(*sc.args(cur, T, R), camera=sc.cam, seed=SEED, iteration=0)
+    tb = rb.sample_target_mv_device(*sc.args(cur, T, R), camera=sc.cam, seed=SEED, iteration=0)
+    assert ta.ijs.shape[0] == 6 and 0 < int(ta.count) < 6, int(ta.count)
+    replay = ra.capture_iteration(ta, seed=SEED)
+    assert isinstance(replay.graph, torch.cuda.CUDAGraph)
+    assert ra._step == 2
+    la = lb = None
+    for _ in range(4):
+        la = replay()
+    for _ in range(2 + 4):
+        lb = rb.optimization_iteration(tb, seed=SEED)
+    torch.cuda.synchronize()
+    assert_losses_equal(losses_of(la), losses_of(lb))
+    assert_state_equal(state(ra), state(rb), what="2 warm-up updates + 4 replays vs 6 eager counted iterations")
+    assert ra._step == int(ra._step_dev) == 6 and rb._step == int(rb._step_dev) == 6
+
+
+# ------------------------------------------------------------------------------------------------ 13. a refused capture
+class _RefusedGraph:
+    def __init__(self, *a, **kw):
+        raise RuntimeError("refused for the test")
+
+
+def _refused_worker(rank, store, out, net):
+    """One rank with a gloo group (so that both functions take their two-graph form) whose graph objects cannot be
+    constructed: a Python exception inside the functions' `try`, before any stream begins to capture."""
+    torch.cuda.set_device(0)
+    dist.init_process_group("gloo", store=dist.FileStore(store, 1), rank=0, world_size=1)
+    T, R, SEED = TWO["T"], TWO["R"], 3
+    sc, cur = _small_scene()
+
+    def renderer():
+        r = sc.renderer(NETS[net])
+        r.process_group = dist.group.WORLD
+        return r
+    real = torch.cuda.CUDAGraph
+    torch.cuda.CUDAGraph = _RefusedGraph
+    try:
+        # capture_iteration(Target): the warm-up's two real updates stay, then plain launches
+        ra, rb = renderer(), renderer()
+        t = ra.sample_target_mv_device(*sc.args(cur, T, R), camera=sc.cam, seed=SEED, iteration=0).materialize()
+        assert t.ijs.shape[0] > 0
+        with pytest.warns(RuntimeWarning, match="graph capture refused"):
+            step = ra.capture_iteration(t, seed=SEED)
+        assert step.graph is None and "refused for the test" in step.capture_error
+        assert ra._step == 2 == int(ra._step_dev)
+        la = lb = None
+        for _ in range(3):
+            la = step()
+        for _ in range(2 + 3):
+            lb = rb.optimization_iteration(t, seed=SEED)
+        torch.cuda.synchronize()
+        assert_losses_equal(losses_of(la), losses_of(lb))
+        assert_state_equal(state(ra), state(rb), what="capture_iteration, refused: 2 + 3 plain iterations")
+        assert ra._step == 5 == int(ra._step_dev)
+        # capture_training: nothing trained by the warm-up, the iteration counter put back, then sampler + step per call
+        ra, rb = renderer(), renderer()
+        start = state(ra)
+        with pytest.warns(RuntimeWarning, match="graph capture refused"):
+            step = ra.capture_training(*sc.args(cur, T, R), seed=SEED, camera=sc.cam)
+        assert step.graph is None and "refused for the test" in step.capture_error
+        assert step.target is None
+        assert ra._step == 0 and int(ra._target_iter_dev) == 0
+        assert_state_equal(start, state(ra), what="capture_training, refused, trains nothing by itself")
+        for i in range(3):
+            la = step()
+            assert isinstance(step.target, Rr.DeviceTarget)
+            lb = rb.optimization_iteration(rb.sample_target_mv_device(*sc.args(cur, T, R), camera=sc.cam, seed=SEED, iteration=i),
+                                           seed=SEED)
+        torch.cuda.synchronize()
+        assert_losses_equal(losses_of(la), losses_of(lb))
+        assert_state_equal(state(ra), state(rb), what="capture_training, refused: 3 plain sampler + step calls")
+        assert ra._step == 3 == int(ra._step_dev) and int(ra._target_iter_dev) == 3
+    finally:
+        torch.cuda.CUDAGraph = real
+    with open(os.path.join(out, f"refused_{net}.ok"), "w") as fh:
+        fh.write("ok")
+    dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("net", ["m1", "hash"])
+def test_refused_capture_falls_back_to_plain_launches(tmp_path, net):
+    """capture_iteration and capture_training when the runtime refuses the two-graph capture: a RuntimeWarning, `.graph is
+    None`, the message in `.capture_error`, `_step` as the warm-up left it, and calls that are plain iterations bit for bit
+    (the assertions are the child's: _refused_worker)."""
+    ctxm = mp.spawn(_refused_worker, args=(str(tmp_path / "store"), str(tmp_path), net), nprocs=1, join=False)
+    deadline = time.monotonic() + 120.0
+    while not ctxm.join(timeout=5):
+        if time.monotonic() > deadline:
+            for p in ctxm.processes:
+                p.kill()
+            raise AssertionError("the child did not finish within its time limit")
+    assert os.path.exists(os.path.join(tmp_path, f"refused_{net}.ok"))
