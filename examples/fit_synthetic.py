@@ -1,7 +1,7 @@
 """End-to-end smoke of the drop-in path on one MI355X: keyframe store -> training-target sampler -> fused
 training step (forward, losses, backward, sparse Adam) -> kNN-blended render -> PSNR.
 
-    python examples/fit_synthetic.py [--iters 300] [--device-iteration | --live]
+    python examples/fit_synthetic.py [--iters 300] [--device-iteration | --live [--grow]]
 
 A synthetic RGB-D "scan" of a textured wall with a sphere in front of it is observed from a few keyframes; fields
 on a grid in front of the cameras are trained exactly as NeuralGraphMap._optimization_iteration would
@@ -10,6 +10,9 @@ on a grid in front of the cameras are trained exactly as NeuralGraphMap._optimiz
 their fixed capacity, sampler + training step replayed as one captured graph per iteration (no host synchronisation).
 --live runs the mapping loop's shape instead of a frozen scene: a new current frame every five iterations, keyframes added
 to a KeyframeStore while training, the observed fields recomputed per frame on the device -- and still ONE capture.
+--live --grow also GROWS the map while that one graph keeps replaying: the renderer reserves rows for the whole map
+(reserve_fields), starts with half of it and appends the rest across the keyframes (add_fields(n, positions=, orientations=):
+one launch each, the number of fields read on the device).
 """
 import argparse
 import math
@@ -58,16 +61,20 @@ def synth_keyframe(c2w):
     return torch.cat([rgb, depth[..., None]], -1)
 
 
-def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0):
+def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0, grow=False):
     """loop: "torch" -- sample_target_mv (torch draws) -> optimization_iteration, the reference's loop;
     "device" -- capture_training: one graph replay per iteration;
     "materialize" -- the same device-drawn targets and jitter stream as "device" (sampler seed 0, iteration i; jitter
     seed `jitter_seed`), but sliced to their count on the host every iteration (DeviceTarget.materialize: one
     synchronisation, a data-dependent batch shape);
     "live" -- capture_training once over fixed-capacity buffers (KeyframeStore, observed_fields_device(out=...)): the
-    current frame changes every 5 iterations, each camera's first visit adds a keyframe, the graph is never re-captured."""
+    current frame changes every 5 iterations, each camera's first visit adds a keyframe, the graph is never re-captured.
+    grow (with "live"): rows are reserved for the whole map, half of it is there at the capture, every keyframe appends a
+    share of the rest in place."""
     if loop not in ("torch", "device", "materialize", "live"):
         raise ValueError(loop)
+    if grow and loop != "live":
+        raise ValueError("grow goes with the live loop")
     torch.manual_seed(0)
     dev = torch.device(device)
     cam = Rr.Camera(W, H, FOC, FOC, (W - 1) / 2, (H - 1) / 2, pixel_center=0.0)
@@ -90,8 +97,11 @@ def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0):
                learning_rate=2e-3, adam_eps=1e-15, adam_weight_decay=1e-5, num_samples_coarse=8, num_samples_depth_guided=16,
                near_distance=0.0, far_distance=5.0, eval_near_distance=0.5, eval_far_distance=4.5, eval_num_samples=160)
     r = Rr.NeuralGraphRenderer(model, cam, cfg, device=dev)
-    r.add_fields(NF)
-    r.set_field_poses(pos.to(dev), quat.to(dev))
+    n0 = NF // 2 if grow else NF
+    r.add_fields(n0)
+    r.set_field_poses(pos[:n0].to(dev), quat[:n0].to(dev))
+    if grow:
+        r.reserve_fields(NF)                                        # once; from here on nothing of the map is reallocated
     eyes = torch.tensor([[0.0, 0.0, 0.0], [0.7, 0.2, 0.1], [-0.7, -0.1, 0.2], [0.2, 0.5, 0.3]])
     c2ws = torch.stack([look_at(e, torch.tensor([0.0, 0.0, -2.6])) for e in eyes])
     store = torch.stack([synth_keyframe(T) for T in c2ws]).contiguous().to(dev)
@@ -113,6 +123,9 @@ def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0):
             ks.set_current(store[k], c2ws[k], frame_id=f)
             if f < len(eyes):
                 ks.add_keyframe(store[k], f)                        # a camera's first visit becomes a keyframe
+                if grow:                                            # ... and brings its share of the fields still missing
+                    new = torch.tensor_split(torch.arange(n0, NF), len(eyes))[k]
+                    r.add_fields(len(new), positions=pos[new].to(dev), orientations=quat[new].to(dev))
             r.observed_fields_device(ks.nc_rgbd[0], ks.c_c2w[0], seed=0, frame=f, out=(ids_buf, cnt_buf), camera=cam)
     for it in range(iters):
         if loop == "live":
@@ -151,6 +164,8 @@ def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0):
         if loop == "live":
             print(f"{ks.num_keyframes} keyframes, {int(cnt_buf)} fields observed by the last frame, "
                   f"{int(r.get_field_ids(50).numel())} fields trained in at least 50 iterations")
+            if grow:
+                print(f"the map grew from {n0} to {r._global_map_dict['num']} fields under that one graph")
     return losses, psnr, derr
 
 
@@ -161,5 +176,7 @@ if __name__ == "__main__":
                     help="train through capture_training: device-drawn targets, one captured graph per iteration")
     ap.add_argument("--live", action="store_true",
                     help="one captured graph across changing frames and keyframes (KeyframeStore + observed_fields_device)")
+    ap.add_argument("--grow", action="store_true",
+                    help="with --live: reserve rows for the whole map, start with half of it, append the rest across keyframes")
     a = ap.parse_args()
-    main(a.iters, loop="live" if a.live else "device" if a.device_iteration else "torch")
+    main(a.iters, loop="live" if a.live else "device" if a.device_iteration else "torch", grow=a.grow)

@@ -640,6 +640,63 @@ int ngm_target_observed_fields(const ngm_observed_fields* a, void* workspace, in
 int ngm_field_counts_add(const int64_t* field_ids, const int32_t* count, int32_t rows, int64_t* training_iterations,
                          int32_t num_fields, void* stream);
 
+/* ---- a map that grows under a live graph: reserved field rows (opt-in; additive to ABI 11) ------------------------------
+ * Every per-field array (stacked parameters, their 16-bit copies, both Adam moments, positions, orientations,
+ * training_iterations) is allocated once for max_fields rows, and the number of fields in force lives in device memory
+ * (num_fields_dev, one int32).  Adding fields is then one launch that fills the next rows and raises that count
+ * (ngm_fields_append); the sampler and the observed-field search read the count on the device (the *_grow entry points
+ * below), so a graph captured over them keeps replaying while the map grows up to max_fields.
+ *
+ * ngm_fields_append: for rows [first, first + num_new) of every tensor of the table: param = prototype, the 16-bit copy =
+ * the prototype rounded as ngm_adam_sparse_multi rounds an updated weight (round to nearest even; bit for bit what the
+ * refresh from the fp32 masters gives), exp_avg = exp_avg_sq = 0 (either may be NULL); training_iterations (optional) = 0;
+ * positions / orientations rows = new_positions / new_orientations; then *num_fields_dev = first + num_new.  One kernel on
+ * `stream`, no host synchronisation: whatever runs next on that stream sees complete fields.  first + num_new <= max_fields
+ * is checked on the host; rows outside [first, first + num_new) are not touched. */
+#define NGM_APPEND_MAX_TENSORS 16
+typedef struct ngm_append_tensor {
+  float* param;                    /* (max_fields, numel) rows with `stride` elements between fields             */
+  float* exp_avg;                  /* same layout, or NULL                                                       */
+  float* exp_avg_sq;               /* same layout, or NULL                                                       */
+  const float* prototype;          /* DEVICE (numel): the row every new field starts from                        */
+  int64_t stride, numel;
+  void* param_lp;                  /* optional 16-bit copy of `param` (same row layout), as in ngm_adam_tensor   */
+  int32_t lp_dtype;                /* ngm_param_dtype of the copy                                                */
+  int32_t reserved_;
+} ngm_append_tensor;
+typedef struct ngm_fields_append_args {
+  const ngm_append_tensor* tensors; /* HOST array of num_tensors descriptors                                     */
+  int32_t num_tensors;              /* 0 .. NGM_APPEND_MAX_TENSORS                                               */
+  int32_t first, num_new;           /* rows [first, first + num_new)                                             */
+  int32_t max_fields;               /* rows every array below and every tensor above is allocated for            */
+  const float* new_positions;       /* DEVICE (num_new, 3)                                                       */
+  const float* new_orientations;    /* DEVICE (num_new, 4)                                                       */
+  float* positions;                 /* (max_fields, 3)                                                           */
+  float* orientations;              /* (max_fields, 4)                                                           */
+  int64_t* training_iterations;     /* (max_fields) or NULL                                                      */
+  int32_t* num_fields_dev;          /* device (1): receives first + num_new                                      */
+} ngm_fields_append_args;
+int ngm_fields_append(const ngm_fields_append_args* a, void* stream);
+
+/* ngm_target_sample_mv_live with the number of fields read from device memory as well: s->num_fields is the CAPACITY
+ * max_fields (stride, grid, workspace, the maxima of num_random and capacity exactly as the live entry point derives them
+ * from num_fields), the count in force is nf = clamp(*num_fields_dev, 0, max_fields), read block-uniformly by the draw
+ * kernel.  On the device nc = clamp(*num_current, 0, min(max_current, nf)), n_obs = min(T / 2, nc), n_rand = max(min(T - n_obs,
+ * nf - n_obs), 0): n_obs + n_rand = min(T, nf) <= the host-known row capacity min(min(T, max_fields), fields of this rank
+ * among max_fields).  Every key is a function of the field id alone, so the result is bit for bit that of
+ * ngm_target_sample_mv_live on a map of exactly nf fields (rows below *count; the arrays here may have more padding rows).
+ * No id >= nf is ever emitted, which is why ngm_field_counts_add needs no twin: give it max_fields.
+ * Precondition, as before: current_field_ids duplicate-free with ids in [0, nf). */
+int64_t ngm_target_sample_mv_grow_workspace(int32_t max_frames, int32_t max_current, int32_t max_fields, int32_t capacity);
+int ngm_target_sample_mv_grow(const ngm_keyframes* kf, const ngm_target_sample* s, const ngm_target_live* live,
+                              const int32_t* num_fields_dev, const ngm_target_out* out, void* workspace, int64_t workspace_bytes,
+                              void* stream);
+/* ngm_target_observed_fields with a->num_fields = max_fields (the length of current_field_ids, -1 past *current_count up to
+ * there) and the fields tested bounded by clamp(*num_fields_dev, 0, max_fields). */
+int64_t ngm_target_observed_fields_grow_workspace(int32_t height, int32_t width);
+int ngm_target_observed_fields_grow(const ngm_observed_fields* a, const int32_t* num_fields_dev, void* workspace,
+                                    int64_t workspace_bytes, void* stream);
+
 /* Device part of NeuralGraphMap._sample_target_sv (rm.py:1461-1583), the single-view variant (`update_mode: single_view`):
  * hit (F,N) u8 = the segment camera origin -> point n of the (subsampled) back-projected depth image passes through the
  * sphere of field f (geometry.py:67-105); field centres and points in the camera frame. */

@@ -176,6 +176,36 @@ def target_sample_mv_live_plan(max_current, num_fields, num_train_fields, num_ra
     return min(num_train_fields // 2, max_current), n_all, capacity
 
 
+NGM_APPEND_MAX_TENSORS = 16                    # include/ngm_hip.h: tensors one ngm_fields_append call may fill
+
+
+class AppendTensor(C.Structure):
+    _fields_ = [("param", f32p), ("exp_avg", f32p), ("exp_avg_sq", f32p), ("prototype", f32p), ("stride", C.c_int64),
+                ("numel", C.c_int64), ("param_lp", C.c_void_p), ("lp_dtype", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class FieldsAppendArgs(C.Structure):
+    _fields_ = [("tensors", C.POINTER(AppendTensor)), ("num_tensors", C.c_int32), ("first", C.c_int32), ("num_new", C.c_int32),
+                ("max_fields", C.c_int32), ("new_positions", f32p), ("new_orientations", f32p), ("positions", f32p),
+                ("orientations", f32p), ("training_iterations", C.c_void_p), ("num_fields_dev", C.c_void_p)]
+
+
+def target_sample_mv_grow_plan(max_current, max_fields, num_train_fields, num_rays, world_size=1, rank=0):
+    """Host-side sizes of ngm_target_sample_mv_grow: target_sample_mv_live_plan at the capacity max_fields -- (max_observed,
+    max_random, capacity) = (min(T // 2, max_current), min(T, max_fields), min(min(T, max_fields), fields of this rank among
+    max_fields)).  For every count nf <= max_fields in force the device draws n_obs + n_rand = min(T, nf) fields, of which
+    this rank owns at most min(min(T, nf), its fields among nf) <= capacity (grow_counts restates it)."""
+    return target_sample_mv_live_plan(max_current, max_fields, num_train_fields, num_rays, world_size, rank)
+
+
+def grow_counts(num_current, num_fields, max_current, max_fields, num_train_fields):
+    """What k_tsmv_draw computes in the grow variant from the device counts: (nf, nc, n_obs, n_rand)"""
+    nf = min(max(num_fields, 0), max_fields)
+    nc = min(max(num_current, 0), min(max_current, nf))
+    n_obs = min(num_train_fields // 2, nc)
+    return nf, nc, n_obs, max(min(num_train_fields - n_obs, nf - n_obs), 0)
+
+
 _lib = None
 
 
@@ -286,6 +316,16 @@ def lib():
     L.ngm_target_observed_fields.restype = C.c_int
     L.ngm_field_counts_add.argtypes = [vp, vp, i32, vp, i32, vp]
     L.ngm_field_counts_add.restype = C.c_int
+    L.ngm_fields_append.argtypes = [P(FieldsAppendArgs), vp]
+    L.ngm_fields_append.restype = C.c_int
+    L.ngm_target_sample_mv_grow_workspace.argtypes = [i32, i32, i32, i32]
+    L.ngm_target_sample_mv_grow_workspace.restype = i64
+    L.ngm_target_sample_mv_grow.argtypes = [P(Keyframes), P(TargetSample), P(TargetLive), vp, P(TargetOut), vp, i64, vp]
+    L.ngm_target_sample_mv_grow.restype = C.c_int
+    L.ngm_target_observed_fields_grow_workspace.argtypes = [i32, i32]
+    L.ngm_target_observed_fields_grow_workspace.restype = i64
+    L.ngm_target_observed_fields_grow.argtypes = [P(ObservedFields), vp, vp, i64, vp]
+    L.ngm_target_observed_fields_grow.restype = C.c_int
     L.ngm_marching_cubes_workspace.argtypes = [i32, i32, i32]
     L.ngm_marching_cubes_workspace.restype = i64
     L.ngm_marching_cubes_count.argtypes = [vp, i32, i32, i32, f32, vp, vp, i64, vp]
@@ -320,6 +360,8 @@ EXPORTED = ["ngm_abi_version", "ngm_last_error", "ngm_device_info", "ngm_permuto
             "ngm_target_sample_mv_workspace", "ngm_target_sample_mv",
             "ngm_target_sample_mv_live_workspace", "ngm_target_sample_mv_live", "ngm_target_observed_fields_workspace",
             "ngm_target_observed_fields", "ngm_field_counts_add",
+            "ngm_fields_append", "ngm_target_sample_mv_grow_workspace", "ngm_target_sample_mv_grow",
+            "ngm_target_observed_fields_grow_workspace", "ngm_target_observed_fields_grow",
             "ngm_render_fwd_counted", "ngm_render_bwd_counted", "ngm_render_bwd_adam_counted",
             "ngm_peer_mailbox_bytes", "ngm_peer_alloc", "ngm_peer_free", "ngm_ipc_export", "ngm_ipc_open", "ngm_ipc_close", "ngm_loss_exchange", "ngm_peer_set_timeout",
             "ngm_marching_cubes_workspace", "ngm_marching_cubes_count", "ngm_marching_cubes_emit", "ngm_marching_cubes_tables"]

@@ -485,7 +485,8 @@ int ngm_target_rays(const ngm_keyframes* kf, int32_t F, int32_t R, const float* 
 // ngm_target_sample_mv and ngm_target_sample_mv_live (is_live; its sizes are maxima, include/ngm_hip.h): one list of checks in
 // which five conditions differ, one launcher.  `fn` is the entry point that was called.
 static int target_sample_mv(const char* fn, bool is_live, const ngm_keyframes* kf, const ngm_target_sample* s, const ngm_target_live* live,
-                            const ngm_target_out* out, void* workspace, int64_t workspace_bytes, void* stream) {
+                            const ngm_target_out* out, void* workspace, int64_t workspace_bytes, void* stream,
+                            const int32_t* num_fields_dev = nullptr) {
   char msg[256];
   auto refuse = [&](int code, const char* what) { return snprintf(msg, sizeof(msg), "%s: %s", fn, what), fail(code, msg); };
   int e = check_keyframes(kf);
@@ -520,7 +521,7 @@ static int target_sample_mv(const char* fn, bool is_live, const ngm_keyframes* k
   if ((int64_t)s->capacity * s->num_rays > INT32_MAX) return refuse(NGM_E_UNSUPPORTED, "capacity x num_rays >= 2^31");
   const int64_t need = ngm_target_sample_mv_bytes(kf->num_frames, s->num_current, s->num_fields, s->capacity);
   if (!workspace || workspace_bytes < need) return refuse(NGM_E_WORKSPACE, "workspace too small");
-  ngm_launch_target_sample_mv(*kf, *s, is_live ? live : nullptr, *out, workspace, (hipStream_t)stream);
+  ngm_launch_target_sample_mv(*kf, *s, is_live ? live : nullptr, *out, workspace, (hipStream_t)stream, num_fields_dev);
   return check_launch(fn);
 }
 int64_t ngm_target_sample_mv_workspace(int32_t num_frames, int32_t num_current, int32_t num_fields, int32_t capacity) {
@@ -538,12 +539,37 @@ int ngm_target_sample_mv_live(const ngm_keyframes* kf, const ngm_target_sample* 
                               const ngm_target_out* out, void* workspace, int64_t workspace_bytes, void* stream) {
   return target_sample_mv("ngm_target_sample_mv_live", true, kf, s, live, out, workspace, workspace_bytes, stream);
 }
+// the grow variant: the live entry point's checks with s->num_fields = max_fields (every maximum follows from it), + the count
+int64_t ngm_target_sample_mv_grow_workspace(int32_t max_frames, int32_t max_current, int32_t max_fields, int32_t capacity) {
+  return max_fields < 1 ? -1 : ngm_target_sample_mv_live_workspace(max_frames, max_current, max_fields, capacity);
+}
+int ngm_target_sample_mv_grow(const ngm_keyframes* kf, const ngm_target_sample* s, const ngm_target_live* live,
+                              const int32_t* num_fields_dev, const ngm_target_out* out, void* workspace, int64_t workspace_bytes,
+                              void* stream) {
+  if (!num_fields_dev) return fail(NGM_E_INVALID, "ngm_target_sample_mv_grow: NULL num_fields_dev");
+  return target_sample_mv("ngm_target_sample_mv_grow", true, kf, s, live, out, workspace, workspace_bytes, stream, num_fields_dev);
+}
 
 int64_t ngm_target_observed_fields_workspace(int32_t height, int32_t width) {
   if (height < 1 || width < 1 || (int64_t)height * width > INT32_MAX) return -1;
   return ngm_target_observed_fields_bytes(height, width);
 }
+static int observed_fields(const ngm_observed_fields* a, const int32_t* num_fields_dev, void* workspace, int64_t workspace_bytes,
+                           void* stream);
 int ngm_target_observed_fields(const ngm_observed_fields* a, void* workspace, int64_t workspace_bytes, void* stream) {
+  return observed_fields(a, nullptr, workspace, workspace_bytes, stream);
+}
+int64_t ngm_target_observed_fields_grow_workspace(int32_t height, int32_t width) {
+  return ngm_target_observed_fields_workspace(height, width);
+}
+int ngm_target_observed_fields_grow(const ngm_observed_fields* a, const int32_t* num_fields_dev, void* workspace,
+                                    int64_t workspace_bytes, void* stream) {
+  if (!num_fields_dev) return fail(NGM_E_INVALID, "ngm_target_observed_fields_grow: NULL num_fields_dev");
+  return observed_fields(a, num_fields_dev, workspace, workspace_bytes, stream);
+}
+// both entry points (the messages keep the first one's name: the checks are its checks)
+static int observed_fields(const ngm_observed_fields* a, const int32_t* num_fields_dev, void* workspace, int64_t workspace_bytes,
+                           void* stream) {
   if (!a) return fail(NGM_E_INVALID, "ngm_target_observed_fields: NULL argument");
   if (a->height < 1 || a->width < 1 || (int64_t)a->height * a->width > INT32_MAX || a->num_fields < 0 || !(a->radius >= 0.f))
     return fail(NGM_E_INVALID, "ngm_target_observed_fields: bad sizes (H, W >= 1, H x W < 2^31, num_fields >= 0, radius >= 0)");
@@ -554,8 +580,28 @@ int ngm_target_observed_fields(const ngm_observed_fields* a, void* workspace, in
     return fail(NGM_E_INVALID, "ngm_target_observed_fields: NULL array (frame < 0 needs frame_dev)");
   const int64_t need = ngm_target_observed_fields_bytes(a->height, a->width);
   if (!workspace || workspace_bytes < need) return fail(NGM_E_WORKSPACE, "ngm_target_observed_fields: workspace too small");
-  ngm_launch_target_observed_fields(*a, workspace, (hipStream_t)stream);
+  ngm_launch_target_observed_fields(*a, workspace, (hipStream_t)stream, num_fields_dev);
   return check_launch("ngm_target_observed_fields");
+}
+
+int ngm_fields_append(const ngm_fields_append_args* a, void* stream) {
+  if (!a) return fail(NGM_E_INVALID, "ngm_fields_append: NULL argument");
+  if (a->num_tensors < 0 || a->num_tensors > NGM_APPEND_MAX_TENSORS || (a->num_tensors > 0 && !a->tensors))
+    return fail(NGM_E_INVALID, "ngm_fields_append: 0 <= num_tensors <= NGM_APPEND_MAX_TENSORS");
+  if (a->max_fields < 1 || a->first < 0 || a->num_new < 0 || (int64_t)a->first + a->num_new > a->max_fields)
+    return fail(NGM_E_INVALID, "ngm_fields_append: rows [first, first + num_new) must lie inside [0, max_fields)");
+  if (!a->positions || !a->orientations || !a->num_fields_dev || (a->num_new > 0 && (!a->new_positions || !a->new_orientations)))
+    return fail(NGM_E_INVALID, "ngm_fields_append: NULL array");
+  for (int i = 0; i < a->num_tensors; ++i) {
+    const ngm_append_tensor& t = a->tensors[i];
+    if (!t.param || !t.prototype || t.numel < 1 || t.stride < t.numel)
+      return fail(NGM_E_INVALID, "ngm_fields_append: tensor without param / prototype, or stride < numel");
+    if (t.param_lp && t.lp_dtype != NGM_DT_BF16 && t.lp_dtype != NGM_DT_F16)
+      return fail(NGM_E_INVALID, "ngm_fields_append: a 16-bit copy is bfloat16 or float16");
+  }
+  if (a->num_new == 0) return NGM_OK;                    // nothing to add: the count already holds `first`
+  ngm_launch_fields_append(*a, (hipStream_t)stream);
+  return check_launch("ngm_fields_append");
 }
 
 int ngm_field_counts_add(const int64_t* field_ids, const int32_t* count, int32_t rows, int64_t* training_iterations, int32_t num_fields,

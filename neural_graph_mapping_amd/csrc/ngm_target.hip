@@ -321,6 +321,7 @@ struct tsmv_live {
   int32_t* num_observed_out;    // device out (1)
   int32_t* num_random_out;      // device out (1)
   int num_train_fields;         // T
+  const int32_t* num_fields;    // device, or NULL: the grow variant (ngm_target_sample_mv_grow), s.num_fields is the capacity then
 };
 template <bool LIVE>
 __device__ __forceinline__ int tsmv_num_frames(const ngm_keyframes& kf, const tsmv_live& lv) {
@@ -346,10 +347,12 @@ __global__ __launch_bounds__(TSMV_DRAW_THREADS) void k_tsmv_draw(ngm_target_samp
   const uint64_t it = (uint64_t)s_iter;
   if (tid == 0 && s.iteration < 0) *s.iteration_dev = (int64_t)it + 1;          // after the barrier: every read is done
   int num_current = s.num_current, n_obs = s.num_observed, n_rand = s.num_random;
+  int num_fields = s.num_fields;                         // the fields in force; s.num_fields stays the stride of every array
   if (LIVE) {                                            // block-uniform: every thread reads the same word
-    num_current = min(max(*lv.num_current, 0), s.num_current);
+    if (lv.num_fields) num_fields = min(max(*lv.num_fields, 0), s.num_fields);
+    num_current = min(max(*lv.num_current, 0), min(s.num_current, num_fields));
     n_obs = min(lv.num_train_fields / 2, num_current);
-    n_rand = max(min(lv.num_train_fields - n_obs, s.num_fields - n_obs), 0);
+    n_rand = max(min(lv.num_train_fields - n_obs, num_fields - n_obs), 0);
     if (tid == 0) { *lv.num_observed_out = n_obs; *lv.num_random_out = n_rand; }
     for (int i = n_obs + tid; i < s.num_observed; i += nt) s.subset_observed[i] = -1;
     for (int i = n_rand + tid; i < s.num_random; i += nt) s.subset_random[i] = -1;
@@ -371,7 +374,7 @@ __global__ __launch_bounds__(TSMV_DRAW_THREADS) void k_tsmv_draw(ngm_target_samp
   __syncthreads();
   // 2. random fields: the n_rand smallest of (philox(f) << 32 | f) over the fields not drawn in 1.
   if (n_rand > 0) {
-    for (int f = tid; f < s.num_fields; f += nt) {
+    for (int f = tid; f < num_fields; f += nt) {
       uint32_t q[4];
       philox_block(s.seed, it, (uint64_t)f, TSMV_STREAM_RAND, q);
       w.keys[f] = ((uint64_t)q[0] << 32) | (uint32_t)f;
@@ -379,10 +382,10 @@ __global__ __launch_bounds__(TSMV_DRAW_THREADS) void k_tsmv_draw(ngm_target_samp
     __syncthreads();
     for (int i = tid; i < n_obs; i += nt) {
       const int64_t id = drawn[i];
-      if (id >= 0 && id < s.num_fields) w.keys[id] = TSMV_EXCLUDED;
+      if (id >= 0 && id < num_fields) w.keys[id] = TSMV_EXCLUDED;
     }
     __syncthreads();
-    tsmv_k_smallest(w.keys, s.num_fields, n_rand, sel, scratch, hist, st);
+    tsmv_k_smallest(w.keys, num_fields, n_rand, sel, scratch, hist, st);
     for (int i = tid; i < n_rand; i += nt) {
       const int64_t id = (int64_t)(sel[i] & 0xFFFFFFFFull);
       s.subset_random[i] = id;
@@ -408,7 +411,7 @@ __global__ __launch_bounds__(TSMV_DRAW_THREADS) void k_tsmv_draw(ngm_target_samp
     int n = 0;
     for (int i = 0; i < n_all; ++i) {
       const int64_t id = drawn[i];
-      if (id >= 0 && id < s.num_fields && id % s.world_size == s.rank && n < s.capacity) scratch[n++] = (uint64_t)id;
+      if (id >= 0 && id < num_fields && id % s.world_size == s.rank && n < s.capacity) scratch[n++] = (uint64_t)id;
     }
     s_own = n;
     w.hdr[1] = n;
@@ -556,14 +559,14 @@ static void tsmv_launch(const ngm_keyframes& kf, const ngm_target_sample& s, con
                      dim3(TSMV_RAY_THREADS), 0, st, kf, s, o, w, lv);
 }
 int ngm_launch_target_sample_mv(const ngm_keyframes& kf, const ngm_target_sample& s, const ngm_target_live* live,
-                                const ngm_target_out& o, void* workspace, hipStream_t st) {
+                                const ngm_target_out& o, void* workspace, hipStream_t st, const int32_t* num_fields_dev) {
   tsmv_ws w;
   tsmv_layout(kf.num_frames, s.num_current, s.num_fields, s.capacity, (char*)workspace, &w);
   if (!live)
-    tsmv_launch<false>(kf, s, tsmv_live{nullptr, nullptr, nullptr, nullptr, 0}, o, w, st);
+    tsmv_launch<false>(kf, s, tsmv_live{nullptr, nullptr, nullptr, nullptr, 0, nullptr}, o, w, st);
   else
     tsmv_launch<true>(kf, s, tsmv_live{live->num_current, live->num_frames, live->num_observed, live->num_random,
-                                       live->num_train_fields}, o, w, st);
+                                       live->num_train_fields, num_fields_dev}, o, w, st);
   return 0;
 }
 
@@ -707,7 +710,8 @@ __global__ __launch_bounds__(OBS_THREADS) void k_obs_collect(ngm_observed_fields
   }
 }
 
-__global__ __launch_bounds__(OBS_FIELD_THREADS) void k_obs_fields(ngm_observed_fields a, obs_ws w) {
+// num_fields_dev (NULL: a.num_fields): the grow variant, a.num_fields is the length of current_field_ids then
+__global__ __launch_bounds__(OBS_FIELD_THREADS) void k_obs_fields(ngm_observed_fields a, obs_ws w, const int32_t* num_fields_dev) {
   __shared__ float pts[3 * NGM_OBSERVED_MAX_POINTS];
   __shared__ float wmin[3 * (OBS_FIELD_THREADS / 64)], wmax[3 * (OBS_FIELD_THREADS / 64)];
   __shared__ float box[6];
@@ -771,10 +775,11 @@ __global__ __launch_bounds__(OBS_FIELD_THREADS) void k_obs_fields(ngm_observed_f
   const float* T = a.c2w;
   const float r = a.radius, r2 = r * r;
   int base = 0;
-  for (int f0 = 0; f0 < a.num_fields; f0 += OBS_FIELD_THREADS) {
+  const int num_fields = num_fields_dev ? min(max(*num_fields_dev, 0), a.num_fields) : a.num_fields;      // block-uniform
+  for (int f0 = 0; f0 < num_fields; f0 += OBS_FIELD_THREADS) {
     const int f = f0 + tid;
     bool seen = false;
-    if (f < a.num_fields && have > 0) {
+    if (f < num_fields && have > 0) {
       const Cam3 c = world_to_cam(T, a.field_positions[3 * f], a.field_positions[3 * f + 1], a.field_positions[3 * f + 2]);
       const bool in_box = c.x - r <= box[3] && c.y - r <= box[4] && c.z - r <= box[5] && c.x + r >= box[0] && c.y + r >= box[1] &&
                           c.z + r >= box[2];
@@ -811,7 +816,7 @@ __global__ __launch_bounds__(OBS_FIELD_THREADS) void k_obs_fields(ngm_observed_f
 }
 
 int64_t ngm_target_observed_fields_bytes(int height, int width) { return obs_layout((int64_t)height * width, nullptr, nullptr); }
-int ngm_launch_target_observed_fields(const ngm_observed_fields& a, void* workspace, hipStream_t st) {
+int ngm_launch_target_observed_fields(const ngm_observed_fields& a, void* workspace, hipStream_t st, const int32_t* num_fields_dev) {
   obs_ws w;
   obs_layout((int64_t)a.height * a.width, (char*)workspace, &w);
   const int64_t n = (int64_t)a.height * a.width;
@@ -823,6 +828,75 @@ int ngm_launch_target_observed_fields(const ngm_observed_fields& a, void* worksp
   }
   hipLaunchKernelGGL(k_obs_collect, dim3(a.subset_in ? (a.num_points + OBS_THREADS - 1) / OBS_THREADS : blocks), dim3(OBS_THREADS), 0, st,
                      a, w);
-  hipLaunchKernelGGL(k_obs_fields, dim3(1), dim3(OBS_FIELD_THREADS), 0, st, a, w);
+  hipLaunchKernelGGL(k_obs_fields, dim3(1), dim3(OBS_FIELD_THREADS), 0, st, a, w, num_fields_dev);
+  return 0;
+}
+
+// ---- reserved field rows: a keyframe's growth as one launch (ngm_fields_append, include/ngm_hip.h) ------------------------
+// blockIdx.z = tensor, blockIdx.y = new row, blockIdx.x strides over the row (k_adam_multi's shape).  Block (0, 0, 0) also
+// writes the poses, the iteration counts and the new field count: nothing in this launch reads them, and the next launch on
+// the stream starts after every store of this one.
+struct FieldsAppendK {
+  ngm_append_tensor t[NGM_APPEND_MAX_TENSORS];
+  int n, first, num_new;
+  const float* new_pos; const float* new_quat;
+  float* pos; float* quat;
+  int64_t* training_iterations;
+  int32_t* num_fields_dev;
+};
+__global__ __launch_bounds__(256) void k_fields_append(FieldsAppendK a) {
+  const int tid = threadIdx.x;
+  if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) {
+    for (int i = tid; i < 3 * a.num_new; i += blockDim.x) a.pos[3 * (int64_t)a.first + i] = a.new_pos[i];
+    for (int i = tid; i < 4 * a.num_new; i += blockDim.x) a.quat[4 * (int64_t)a.first + i] = a.new_quat[i];
+    if (a.training_iterations)
+      for (int i = tid; i < a.num_new; i += blockDim.x) a.training_iterations[a.first + i] = 0;
+    if (tid == 0) *a.num_fields_dev = a.first + a.num_new;
+  }
+  if ((int)blockIdx.z >= a.n) return;                     // a launch without tensors still has one z slice
+  const ngm_append_tensor& t = a.t[blockIdx.z];
+  const int64_t row = (int64_t)a.first + blockIdx.y;
+  const int64_t base = row * t.stride;
+  const bool vec = ((t.numel | t.stride) & 3) == 0 &&
+                   ((reinterpret_cast<uintptr_t>(t.param) | reinterpret_cast<uintptr_t>(t.prototype) |
+                     reinterpret_cast<uintptr_t>(t.exp_avg) | reinterpret_cast<uintptr_t>(t.exp_avg_sq)) & 15) == 0;
+  const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + tid, step = (int64_t)gridDim.x * blockDim.x;
+  if (vec) {
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4* S4 = reinterpret_cast<const float4*>(t.prototype);
+    float4* P4 = reinterpret_cast<float4*>(t.param + base);
+    float4* M4 = t.exp_avg ? reinterpret_cast<float4*>(t.exp_avg + base) : nullptr;
+    float4* V4 = t.exp_avg_sq ? reinterpret_cast<float4*>(t.exp_avg_sq + base) : nullptr;
+    for (int64_t i = i0; i < (t.numel >> 2); i += step) {
+      const float4 p = S4[i];
+      P4[i] = p;
+      if (M4) M4[i] = zero;
+      if (V4) V4[i] = zero;
+      if (t.param_lp) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) ngm_stp(t.param_lp, base + 4 * i + c, (&p.x)[c], t.lp_dtype);
+      }
+    }
+    return;
+  }
+  for (int64_t i = i0; i < t.numel; i += step) {
+    const float p = t.prototype[i];
+    t.param[base + i] = p;
+    if (t.exp_avg) t.exp_avg[base + i] = 0.f;
+    if (t.exp_avg_sq) t.exp_avg_sq[base + i] = 0.f;
+    if (t.param_lp) ngm_stp(t.param_lp, base + i, p, t.lp_dtype);
+  }
+}
+int ngm_launch_fields_append(const ngm_fields_append_args& a, hipStream_t st) {
+  FieldsAppendK k = {};
+  int64_t mx = 1;
+  for (int i = 0; i < a.num_tensors; ++i) { k.t[i] = a.tensors[i]; mx = mx > a.tensors[i].numel ? mx : a.tensors[i].numel; }
+  k.n = a.num_tensors; k.first = a.first; k.num_new = a.num_new;
+  k.new_pos = a.new_positions; k.new_quat = a.new_orientations; k.pos = a.positions; k.quat = a.orientations;
+  k.training_iterations = a.training_iterations; k.num_fields_dev = a.num_fields_dev;
+  int64_t bx = (mx / 4 + 255) / 256 + 1;                  // one pass over the largest tensor in 16-byte accesses, at most 64 blocks
+  bx = bx > 64 ? 64 : bx;
+  hipLaunchKernelGGL(k_fields_append, dim3((unsigned)bx, (unsigned)a.num_new, (unsigned)(a.num_tensors > 0 ? a.num_tensors : 1)),
+                     dim3(256), 0, st, k);
   return 0;
 }

@@ -283,14 +283,70 @@ class NeuralFieldSet(torch.nn.Module):
             raise NotImplementedError("weight_dtype (16-bit weight storage) is not built for the triplane encoding")
         self.all_fields_params: Optional[Dict[str, torch.Tensor]] = None
         self.vmap_fields_params: Optional[Dict[str, torch.Tensor]] = None
+        # reserve_fields: dict(max=, num=, params={name: (max, ...)}, lp={name: (max, ...) 16-bit} or None); None = not reserved
+        self._reserved: Optional[dict] = None
 
     # -- parameter store -----------------------------------------------------------------------
     def field_cfg(self, field_radius=None) -> K.FieldCfg:
         r = self._field_radius if field_radius is None else field_radius
         return self._prototype_field.field_cfg(self._scale_mode, r)
 
+    def _lp_names(self):
+        """the parameters that have a 16-bit copy of their own (the others' "copy" is the master tensor itself)"""
+        return [k for k in self._prototype_field.state_dict() if not (k in K.NO_GRAD_PARAMS or k == "_neus_sd")]
+
+    def reserve_fields(self, max_fields: int) -> None:
+        """Allocate every stacked parameter (and its 16-bit copy, with `weight_dtype`) ONCE for max_fields rows; the fields
+        the set holds are copied over.  From here on all_fields_params / lp_fields_params are leading-row views of that
+        storage (their shapes stay (num, ...), their data never moves) and add_fields appends in place -- up to max_fields,
+        beyond which it raises ValueError and changes nothing.  Not in the reference (whose _add_fields concatenates); what
+        it buys is that device code holding the addresses (a captured training graph) survives the growth."""
+        max_fields = int(max_fields)
+        old = self.all_fields_params
+        num = 0 if old is None else next(iter(old.values())).shape[0]
+        if max_fields < max(num, 1):
+            raise ValueError(f"reserve_fields({max_fields}): the set already holds {num} fields (and needs room for one)")
+        proto = self._prototype_field.state_dict()
+        params = {k: torch.zeros((max_fields,) + tuple(v.shape), dtype=v.dtype, device=v.device if old is None else old[k].device)
+                  for k, v in proto.items()}
+        if old is not None:
+            for k, v in old.items():
+                params[k][:num] = v.detach()
+        lp = None
+        if self._weight_dtype is not None:
+            lp = {k: torch.zeros_like(params[k], dtype=self._weight_dtype) for k in self._lp_names()}
+        self._reserved = dict(max=max_fields, num=num, params=params, lp=lp)
+        self._set_num(num)
+        self.refresh_lp()
+
+    def _set_num(self, num: int) -> None:
+        """reserved mode: the public dictionaries as views of the first `num` rows"""
+        rs = self._reserved
+        rs["num"] = num
+        self.all_fields_params = {k: v[:num] for k, v in rs["params"].items()}
+        if rs["lp"] is not None:
+            self.lp_fields_params = {k: (rs["lp"][k][:num] if k in rs["lp"] else v) for k, v in self.all_fields_params.items()}
+
+    def _check_room(self, num_new: int) -> int:
+        rs = self._reserved
+        if num_new < 0 or rs["num"] + num_new > rs["max"]:
+            raise ValueError(f"add_fields({num_new}): {rs['num']} of the {rs['max']} reserved field rows are in use; reserve more "
+                             "(reserve_fields reallocates: anything that holds the old addresses must be rebuilt)")
+        return rs["num"]
+
     def add_fields(self, num_fields: int) -> None:
-        """Append clones of the prototype's state (models.py:245-264)."""
+        """Append clones of the prototype's state (models.py:245-264).  After reserve_fields: in place, into the next
+        reserved rows (plain slice assignment, on any device; NeuralGraphRenderer.add_fields does the same on the GPU in
+        one launch together with the optimiser state and the poses)."""
+        if self._reserved is not None:
+            first = self._check_room(num_fields)
+            rs = self._reserved
+            for k, v in self._prototype_field.state_dict().items():
+                rs["params"][k][first:first + num_fields] = v.detach().to(rs["params"][k].device)
+                if rs["lp"] is not None and k in rs["lp"]:
+                    rs["lp"][k][first:first + num_fields] = rs["params"][k][first:first + num_fields]     # copy_: round to nearest even
+            self._set_num(first + num_fields)
+            return
         new = {k: v.detach().unsqueeze(0).repeat(num_fields, *([1] * v.dim())).clone()
                for k, v in self._prototype_field.state_dict().items()}
         if self.all_fields_params is None:
@@ -303,6 +359,11 @@ class NeuralFieldSet(torch.nn.Module):
         """(re)build the reduced-precision copy from the fp32 masters (no-op without `weight_dtype`)"""
         if self._weight_dtype is None or self.all_fields_params is None:
             self.lp_fields_params = None
+            return
+        if self._reserved is not None:                     # in place: the copy's storage is part of the reservation
+            for k, dst in self._reserved["lp"].items():
+                dst[:self._reserved["num"]].copy_(self.all_fields_params[k])
+            self._set_num(self._reserved["num"])
             return
         self.lp_fields_params = {k: (v if (k in K.NO_GRAD_PARAMS or k == "_neus_sd") else v.to(self._weight_dtype))
                                  for k, v in self.all_fields_params.items()}
@@ -320,6 +381,14 @@ class NeuralFieldSet(torch.nn.Module):
 
     def _apply(self, fn, *a, **kw):
         super()._apply(fn, *a, **kw)
+        if self._reserved is not None:                     # the whole reservation moves (a new storage: re-capture what held it)
+            rs = self._reserved
+            rs["params"] = {k: fn(v) for k, v in rs["params"].items()}
+            if rs["lp"] is not None:
+                rs["lp"] = {k: torch.zeros_like(rs["params"][k], dtype=self._weight_dtype) for k in rs["lp"]}
+            self._set_num(rs["num"])
+            self.refresh_lp()
+            return self
         if self.all_fields_params is not None:
             self.all_fields_params = {k: fn(v) for k, v in self.all_fields_params.items()}
             self.refresh_lp()

@@ -1035,11 +1035,12 @@ def _target_sample_mv_empty(live, num_current, device, num_fields, num_train_fie
 
 
 def _target_sample_mv_call(current_field_ids, counts, c2ws, rgbd_store, frame_to_store, field_positions, iteration_dev, intrinsics,
-                           radius, num_fields, num_train_fields, num_rays, seed, iteration, world_size, rank):
-    """Both ops: counts = None calls ngm_target_sample_mv, counts = (current_count, num_frames) ngm_target_sample_mv_live
-    (current_field_ids / c2ws / frame_to_store are then sized for their maxima)"""
+                           radius, num_fields, num_train_fields, num_rays, seed, iteration, world_size, rank, num_fields_dev=None):
+    """All three ops: counts = None calls ngm_target_sample_mv, counts = (current_count, num_frames) ngm_target_sample_mv_live
+    (current_field_ids / c2ws / frame_to_store are then sized for their maxima); with num_fields_dev as well
+    ngm_target_sample_mv_grow (num_fields is the capacity max_fields then)"""
     live = counts is not None
-    fn = "ngm_target_sample_mv_live" if live else "ngm_target_sample_mv"
+    fn = "ngm_target_sample_mv" + ("" if not live else "_live" if num_fields_dev is None else "_grow")
     num_current, dev = current_field_ids.shape[0], field_positions.device
     n_obs, n_rand, cap, outs = _target_sample_mv_empty(live, num_current, dev, num_fields, num_train_fields, num_rays, world_size, rank)
     o = dict(zip(TARGET_SAMPLE_MV_LIVE_OUT, outs))
@@ -1060,6 +1061,8 @@ def _target_sample_mv_call(current_field_ids, counts, c2ws, rgbd_store, frame_to
         lv = K.TargetLive(_ptr(counts[0]), _ptr(counts[1]), o["num_observed"].data_ptr(), o["num_random"].data_ptr(),
                           num_train_fields, 0)
         args.insert(2, C.byref(lv))
+        if num_fields_dev is not None:
+            args.insert(3, _ptr(num_fields_dev))
     K.check(getattr(K.lib(), fn)(*args), fn)
     return outs
 
@@ -1102,15 +1105,39 @@ def _(current_field_ids, current_count, c2ws, num_frames, rgbd_store, frame_to_s
                                    num_rays, world_size, rank)[3]
 
 
+# the live sampler over reserved field rows (include/ngm_hip.h ngm_target_sample_mv_grow)
+@_op("target_sample_mv_grow", mutates_args=("iteration_dev",))
+def _target_sample_mv_grow_op(current_field_ids: torch.Tensor, current_count: torch.Tensor, c2ws: torch.Tensor,
+                              num_frames: torch.Tensor, num_fields_dev: torch.Tensor, rgbd_store: torch.Tensor,
+                              frame_to_store: torch.Tensor, field_positions: torch.Tensor, iteration_dev: Optional[torch.Tensor],
+                              intrinsics: List[float], radius: float, max_fields: int, num_train_fields: int, num_rays: int,
+                              seed: int, iteration: int, world_size: int, rank: int) -> List[torch.Tensor]:
+    """TARGET_SAMPLE_MV_LIVE_OUT at the sizes of target_sample_mv_live for a map of max_fields fields; the fields in force
+    are num_fields_dev (device int32)"""
+    return _target_sample_mv_call(current_field_ids, (current_count, num_frames), c2ws, rgbd_store, frame_to_store, field_positions,
+                                  iteration_dev, intrinsics, radius, max_fields, num_train_fields, num_rays, seed, iteration,
+                                  world_size, rank, num_fields_dev=num_fields_dev)
+
+
+@_target_sample_mv_grow_op.register_fake
+def _(current_field_ids, current_count, c2ws, num_frames, num_fields_dev, rgbd_store, frame_to_store, field_positions, iteration_dev,
+      intrinsics, radius, max_fields, num_train_fields, num_rays, seed, iteration, world_size, rank):
+    return _target_sample_mv_empty(True, current_field_ids.shape[0], field_positions.device, max_fields, num_train_fields,
+                                   num_rays, world_size, rank)[3]
+
+
 def _check_device_count(fn, name, t):
     if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.numel() != 1:
         raise TypeError(f"{fn}: {name} must be a one-element int32 tensor")
 
 
 def _target_sample_mv_checked(fn, current_field_ids, counts, c2ws, rgbd_store, frame_to_store, field_positions, intrinsics, radius,
-                              num_fields, num_train_fields, num_rays, seed, iteration, iteration_dev, world_size, rank):
+                              num_fields, num_train_fields, num_rays, seed, iteration, iteration_dev, world_size, rank,
+                              num_fields_dev=None):
     """The public wrappers' checks under the caller's name `fn`, then its op; the outputs as a dict"""
     live = counts is not None
+    if num_fields_dev is not None:
+        _check_device_count(fn, "num_fields_dev", num_fields_dev)
 
     def need(cond, msg, exc=ValueError):
         if not cond:
@@ -1140,9 +1167,12 @@ def _target_sample_mv_checked(fn, current_field_ids, counts, c2ws, rgbd_store, f
         raise ValueError(f"{fn}: iteration must be >= 0, got {iteration}")
     if not 0 <= int(seed) < 2 ** 63:
         raise ValueError(f"{fn}: seed must be in [0, 2^63), got {seed}")
-    _require_gpu(current_field_ids, *(counts or ()), c2ws, rgbd_store, frame_to_store, field_positions, iteration_dev)
+    _require_gpu(current_field_ids, *(counts or ()), c2ws, rgbd_store, frame_to_store, field_positions, iteration_dev, num_fields_dev)
     tail = (rgbd_store, frame_to_store, field_positions, iteration_dev, intrinsics, float(radius), num_fields, num_train_fields,
             num_rays, int(seed), -1 if iteration is None else int(iteration), world_size, rank)
+    if num_fields_dev is not None:
+        return dict(zip(TARGET_SAMPLE_MV_LIVE_OUT, torch.ops.ngm355.target_sample_mv_grow(current_field_ids, counts[0], c2ws,
+                                                                                          counts[1], num_fields_dev, *tail)))
     if live:
         return dict(zip(TARGET_SAMPLE_MV_LIVE_OUT, torch.ops.ngm355.target_sample_mv_live(current_field_ids, counts[0], c2ws,
                                                                                           counts[1], *tail)))
@@ -1176,25 +1206,36 @@ def target_sample_mv_live(current_field_ids, current_count, c2ws, num_frames, rg
                                      int(world_size), int(rank))
 
 
+def target_sample_mv_grow(current_field_ids, current_count, c2ws, num_frames, num_fields_dev, rgbd_store, frame_to_store,
+                          field_positions, fx, fy, cx, cy, radius, max_fields, num_train_fields, num_rays_per_field, seed=0,
+                          iteration=None, iteration_dev=None, world_size=1, rank=0):
+    """target_sample_mv_live over reserved field rows (torch.ops.ngm355.target_sample_mv_grow): field_positions has
+    (>= max_fields, 3) rows, the number of fields in force is num_fields_dev (one-element int32 device tensor, clamped to
+    [0, max_fields]).  Every size -- the row capacity K.target_sample_mv_grow_plan(...)[2] included -- follows from
+    max_fields; rows below `count` are bit for bit target_sample_mv_live's on a map of exactly that many fields."""
+    return _target_sample_mv_checked("target_sample_mv_grow", current_field_ids, (current_count, num_frames), c2ws, rgbd_store,
+                                     frame_to_store, field_positions, [float(fx), float(fy), float(cx), float(cy)], radius,
+                                     int(max_fields), int(num_train_fields), int(num_rays_per_field), seed, iteration, iteration_dev,
+                                     int(world_size), int(rank), num_fields_dev=num_fields_dev)
+
+
 # ------------------------------------------------------------------------------------------------
 # observed fields of one frame, on the device (include/ngm_hip.h ngm_target_observed_fields)
 # ------------------------------------------------------------------------------------------------
 TARGET_OBSERVED_FIELDS_OUT = ("current_field_ids", "current_count", "pixels", "num_used")
 
 
-@_op("target_observed_fields", mutates_args=("frame_dev", "ids_out", "count_out"))
-def _target_observed_fields_op(rgbd: torch.Tensor, c2w: torch.Tensor, field_positions: torch.Tensor, frame_dev: Optional[torch.Tensor],
-                               subset_in: Optional[torch.Tensor], ids_out: torch.Tensor, count_out: torch.Tensor,
-                               intrinsics: List[float], radius: float, num_fields: int, num_points: int, seed: int,
-                               frame: int) -> List[torch.Tensor]:
-    """(pixels (num_points,) int64, num_used (1,) int32); the observed ids and their count go to ids_out / count_out"""
+def _target_observed_fields_call(rgbd, c2w, field_positions, frame_dev, subset_in, ids_out, count_out, intrinsics, radius,
+                                 num_fields, num_points, seed, frame, num_fields_dev=None):
+    """Both ops: ngm_target_observed_fields, or with num_fields_dev ngm_target_observed_fields_grow (num_fields = max_fields)"""
+    fn = "ngm_target_observed_fields" + ("" if num_fields_dev is None else "_grow")
     dev = rgbd.device
     H, W = rgbd.shape[0], rgbd.shape[1]
     pixels = torch.empty(num_points, dtype=torch.int64, device=dev)
     used = torch.empty(1, dtype=torch.int32, device=dev)
-    ws_bytes = K.lib().ngm_target_observed_fields_workspace(H, W)
+    ws_bytes = getattr(K.lib(), fn + "_workspace")(H, W)
     if ws_bytes < 0:
-        raise K.NgmError("ngm_target_observed_fields_workspace: bad sizes")
+        raise K.NgmError(fn + "_workspace: bad sizes")
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     a = K.ObservedFields()
     a.rgbd, a.c2w = C.cast(rgbd.data_ptr(), K.f32p), C.cast(c2w.data_ptr(), K.f32p)
@@ -1205,8 +1246,37 @@ def _target_observed_fields_op(rgbd: torch.Tensor, c2w: torch.Tensor, field_posi
     a.frame_dev, a.subset_in = _ptr(frame_dev), _ptr(subset_in)
     a.current_field_ids, a.current_count = ids_out.data_ptr(), count_out.data_ptr()
     a.pixels, a.num_used = pixels.data_ptr(), used.data_ptr()
-    K.check(K.lib().ngm_target_observed_fields(C.byref(a), _ptr(ws), ws_bytes, _stream()), "ngm_target_observed_fields")
+    args = [C.byref(a), _ptr(ws), ws_bytes, _stream()]
+    if num_fields_dev is not None:
+        args.insert(1, _ptr(num_fields_dev))
+    K.check(getattr(K.lib(), fn)(*args), fn)
     return [pixels, used]
+
+
+@_op("target_observed_fields", mutates_args=("frame_dev", "ids_out", "count_out"))
+def _target_observed_fields_op(rgbd: torch.Tensor, c2w: torch.Tensor, field_positions: torch.Tensor, frame_dev: Optional[torch.Tensor],
+                               subset_in: Optional[torch.Tensor], ids_out: torch.Tensor, count_out: torch.Tensor,
+                               intrinsics: List[float], radius: float, num_fields: int, num_points: int, seed: int,
+                               frame: int) -> List[torch.Tensor]:
+    """(pixels (num_points,) int64, num_used (1,) int32); the observed ids and their count go to ids_out / count_out"""
+    return _target_observed_fields_call(rgbd, c2w, field_positions, frame_dev, subset_in, ids_out, count_out, intrinsics, radius,
+                                        num_fields, num_points, seed, frame)
+
+
+@_op("target_observed_fields_grow", mutates_args=("frame_dev", "ids_out", "count_out"))
+def _target_observed_fields_grow_op(rgbd: torch.Tensor, c2w: torch.Tensor, field_positions: torch.Tensor, num_fields_dev: torch.Tensor,
+                                    frame_dev: Optional[torch.Tensor], subset_in: Optional[torch.Tensor], ids_out: torch.Tensor,
+                                    count_out: torch.Tensor, intrinsics: List[float], radius: float, max_fields: int,
+                                    num_points: int, seed: int, frame: int) -> List[torch.Tensor]:
+    """target_observed_fields over reserved field rows: ids_out has max_fields entries, num_fields_dev fields are tested"""
+    return _target_observed_fields_call(rgbd, c2w, field_positions, frame_dev, subset_in, ids_out, count_out, intrinsics, radius,
+                                        max_fields, num_points, seed, frame, num_fields_dev=num_fields_dev)
+
+
+@_target_observed_fields_grow_op.register_fake
+def _(rgbd, c2w, field_positions, num_fields_dev, frame_dev, subset_in, ids_out, count_out, intrinsics, radius, max_fields, num_points,
+      seed, frame):
+    return [torch.empty(num_points, dtype=torch.int64, device=rgbd.device), torch.empty(1, dtype=torch.int32, device=rgbd.device)]
 
 
 @_target_observed_fields_op.register_fake
@@ -1215,16 +1285,21 @@ def _(rgbd, c2w, field_positions, frame_dev, subset_in, ids_out, count_out, intr
 
 
 def target_observed_fields(rgbd, c2w, field_positions, fx, fy, cx, cy, radius, num_fields, num_points=500, seed=0, frame=None,
-                           frame_dev=None, subset_in=None, ids_out=None, count_out=None):
+                           frame_dev=None, subset_in=None, ids_out=None, count_out=None, num_fields_dev=None):
     """NeuralGraphMap._get_observed_fields (rm.py:1642-1670) on the device (torch.ops.ngm355.target_observed_fields): no host
     synchronisation, fixed shapes.  rgbd (H, W, 4) and c2w (4, 4) are device tensors read when the kernels run.  frame=None:
     frame_dev (one-element int64 device tensor) is read and advanced.  subset_in: num_points linear pixel indices that
     replace the draw.  ids_out (>= num_fields,) int64 / count_out (1,) int32 are written in place when given.  Returns a
     dict keyed by TARGET_OBSERVED_FIELDS_OUT: the observed ids ascending with -1 past current_count, the chosen pixels (order
-    unspecified) with -1 past num_used."""
+    unspecified) with -1 past num_used.
+    num_fields_dev (one-element int32 device tensor): the map has reserved rows (torch.ops.ngm355.target_observed_fields_grow)
+    -- num_fields is then the capacity max_fields (rows of field_positions, entries of ids_out), the fields tested are the
+    first clamp(*num_fields_dev, 0, max_fields)."""
     def need(cond, msg, exc=ValueError):
         if not cond:
             raise exc("target_observed_fields: " + msg)
+    if num_fields_dev is not None:
+        _check_device_count("target_observed_fields", "num_fields_dev", num_fields_dev)
     num_fields, num_points = int(num_fields), int(num_points)
     for name, t in (("rgbd", rgbd), ("c2w", c2w), ("field_positions", field_positions)):
         need(isinstance(t, torch.Tensor), f"{name} must be a tensor", TypeError)
@@ -1252,15 +1327,20 @@ def target_observed_fields(rgbd, c2w, field_positions, fx, fy, cx, cy, radius, n
              f"ids_out must be a contiguous (>= {num_fields},) tensor, got {tuple(ids_out.shape)}")
     if count_out is not None:
         _check_device_count("target_observed_fields", "count_out", count_out)
-    _require_gpu(rgbd, c2w, field_positions, frame_dev, subset_in, ids_out, count_out)
+    _require_gpu(rgbd, c2w, field_positions, frame_dev, subset_in, ids_out, count_out, num_fields_dev)
     dev = rgbd.device
     if ids_out is None:
         ids_out = torch.empty(num_fields, dtype=torch.int64, device=dev)
     if count_out is None:
         count_out = torch.empty(1, dtype=torch.int32, device=dev)
-    pixels, used = torch.ops.ngm355.target_observed_fields(rgbd, c2w, field_positions, frame_dev, subset_in, ids_out, count_out,
-                                                           [float(fx), float(fy), float(cx), float(cy)], float(radius), num_fields,
-                                                           num_points, int(seed), -1 if frame is None else int(frame))
+    tail = ([float(fx), float(fy), float(cx), float(cy)], float(radius), num_fields, num_points, int(seed),
+            -1 if frame is None else int(frame))
+    if num_fields_dev is not None:
+        pixels, used = torch.ops.ngm355.target_observed_fields_grow(rgbd, c2w, field_positions, num_fields_dev, frame_dev, subset_in,
+                                                                    ids_out, count_out, *tail)
+    else:
+        pixels, used = torch.ops.ngm355.target_observed_fields(rgbd, c2w, field_positions, frame_dev, subset_in, ids_out, count_out,
+                                                               *tail)
     return dict(current_field_ids=ids_out, current_count=count_out, pixels=pixels, num_used=used)
 
 
@@ -1276,3 +1356,74 @@ def field_counts_add(field_ids, count, training_iterations, num_fields):
     _require_gpu(field_ids, count, training_iterations)
     K.check(K.lib().ngm_field_counts_add(_ptr(field_ids), _ptr(count), int(field_ids.shape[0]), _ptr(training_iterations),
                                          int(num_fields), _stream()), "ngm_field_counts_add")
+
+
+# ------------------------------------------------------------------------------------------------
+# reserved field rows: a keyframe's growth as one launch (include/ngm_hip.h ngm_fields_append)
+# ------------------------------------------------------------------------------------------------
+@_op("fields_append", mutates_args=("params", "exp_avgs", "exp_avg_sqs", "lps", "positions", "orientations", "training_iterations",
+                                    "num_fields_dev"))
+def _fields_append_op(params: List[torch.Tensor], exp_avgs: List[torch.Tensor], exp_avg_sqs: List[torch.Tensor],
+                      lps: List[torch.Tensor], lp_index: List[int], prototypes: List[torch.Tensor], new_positions: torch.Tensor,
+                      new_orientations: torch.Tensor, positions: torch.Tensor, orientations: torch.Tensor,
+                      training_iterations: Optional[torch.Tensor], num_fields_dev: torch.Tensor, first: int) -> None:
+    n = len(params)
+    arr = (K.AppendTensor * max(n, 1))()
+    lp_of = dict(zip(lp_index, lps))
+    for i, (p, m, v, proto) in enumerate(zip(params, exp_avgs, exp_avg_sqs, prototypes)):
+        lp = lp_of.get(i)
+        arr[i] = K.AppendTensor(C.cast(p.data_ptr(), K.f32p), C.cast(m.data_ptr(), K.f32p), C.cast(v.data_ptr(), K.f32p),
+                                C.cast(proto.data_ptr(), K.f32p), p.stride(0), proto.numel(), _ptr(lp),
+                                0 if lp is None else _TORCH_DT[lp.dtype], 0)
+    a = K.FieldsAppendArgs(arr, n, int(first), int(new_positions.shape[0]), int(positions.shape[0]),
+                           C.cast(new_positions.data_ptr(), K.f32p), C.cast(new_orientations.data_ptr(), K.f32p),
+                           C.cast(positions.data_ptr(), K.f32p), C.cast(orientations.data_ptr(), K.f32p),
+                           _ptr(training_iterations), num_fields_dev.data_ptr())
+    K.check(K.lib().ngm_fields_append(C.byref(a), _stream()), "ngm_fields_append")
+
+
+def fields_append(tensors, new_positions, new_orientations, positions, orientations, training_iterations, num_fields_dev, first):
+    """Fill rows [first, first + num_new) of a map with reserved rows and raise its device field count: one launch on the
+    current stream (torch.ops.ngm355.fields_append, ngm_fields_append), no host synchronisation.
+    tensors: a list of dicts(param=, exp_avg=, exp_avg_sq= (max_fields, ...) float32, prototype= (...) float32, lp= the
+    optional (max_fields, ...) bfloat16 / float16 copy); new_positions (num_new, 3), new_orientations (num_new, 4);
+    positions (max_fields, 3), orientations (max_fields, 4), training_iterations (max_fields,) int64 or None,
+    num_fields_dev a one-element int32 tensor.  Every tensor is a contiguous device tensor."""
+    def need(cond, msg, exc=ValueError):
+        if not cond:
+            raise exc("fields_append: " + msg)
+    _check_device_count("fields_append", "num_fields_dev", num_fields_dev)
+    need(len(tensors) <= K.NGM_APPEND_MAX_TENSORS, f"at most {K.NGM_APPEND_MAX_TENSORS} tensors per call")
+    for name, t, w in (("new_positions", new_positions, 3), ("new_orientations", new_orientations, 4), ("positions", positions, 3),
+                       ("orientations", orientations, 4)):
+        need(isinstance(t, torch.Tensor) and t.dtype == torch.float32, f"{name} must be a float32 tensor", TypeError)
+        need(t.dim() == 2 and t.shape[1] == w and t.is_contiguous(), f"{name} must be a contiguous (n, {w}) tensor, got {tuple(t.shape)}")
+    max_fields, num_new, first = positions.shape[0], new_positions.shape[0], int(first)
+    need(orientations.shape[0] == max_fields, f"positions has {max_fields} rows, orientations {orientations.shape[0]}")
+    need(new_orientations.shape[0] == num_new, f"{num_new} new positions but {new_orientations.shape[0]} new orientations")
+    need(first >= 0 and first + num_new <= max_fields, f"rows [{first}, {first + num_new}) do not fit the capacity of {max_fields} fields")
+    if training_iterations is not None:
+        need(training_iterations.dtype == torch.int64, "training_iterations must be int64", TypeError)
+        need(tuple(training_iterations.shape) == (max_fields,) and training_iterations.is_contiguous(),
+             f"training_iterations must be a contiguous ({max_fields},) tensor, got {tuple(training_iterations.shape)}")
+    params, ms, vs, lps, lp_index, protos = [], [], [], [], [], []
+    for i, t in enumerate(tensors):
+        p, proto, lp = t["param"], t["prototype"], t.get("lp")
+        for name in ("param", "exp_avg", "exp_avg_sq"):
+            x = t[name]
+            need(x.dtype == torch.float32, f"tensor {i}: {name} must be float32, got {x.dtype}", TypeError)
+            need(x.is_contiguous() and tuple(x.shape) == (max_fields,) + tuple(proto.shape),
+                 f"tensor {i}: {name} must be a contiguous {(max_fields,) + tuple(proto.shape)} tensor (capacity mismatch), got {tuple(x.shape)}")
+        need(proto.dtype == torch.float32 and proto.is_contiguous() and proto.numel() >= 1, f"tensor {i}: prototype must be contiguous float32")
+        if lp is not None:
+            need(lp.dtype in (torch.bfloat16, torch.float16), f"tensor {i}: the 16-bit copy must be bfloat16 or float16, got {lp.dtype}", TypeError)
+            need(lp.is_contiguous() and lp.shape == p.shape, f"tensor {i}: the 16-bit copy must have the shape of param (capacity mismatch)")
+            lps.append(lp)
+            lp_index.append(i)
+        params.append(p), ms.append(t["exp_avg"]), vs.append(t["exp_avg_sq"]), protos.append(proto)
+    _require_gpu(*params, *ms, *vs, *lps, *protos, new_positions, new_orientations, positions, orientations, training_iterations,
+                 num_fields_dev)
+    if num_new == 0:
+        return
+    torch.ops.ngm355.fields_append(params, ms, vs, lps, lp_index, protos, new_positions, new_orientations, positions, orientations,
+                                   training_iterations, num_fields_dev, first)

@@ -205,6 +205,10 @@ class NeuralGraphRenderer:
         self.track_training_iterations = False
         self._observe_frame_dev = None     # observed_fields_device's frame counter (device int64, advanced by each call)
         self.last_observed = None          # the chosen pixels / their number of the last observed_fields_device call
+        # reserve_fields: dict(max=, epoch=, state={name: {exp_avg, exp_avg_sq} (max, ...)}, positions (max, 3), orientations
+        # (max, 4), training_iterations (max,), num_fields_dev int32 (1,)); None = not reserved
+        self._reserved: Optional[dict] = None
+        self._reserve_epoch = 0
 
     def last_matmul(self, kernel: str = "forward") -> Optional[str]:
         """The arithmetic the library resolved `mlp_matmul` to in the LAST launch of the fused forward ("forward"), the
@@ -216,6 +220,18 @@ class NeuralGraphRenderer:
 
     # -- map bookkeeping supplied by the caller ------------------------------------------------
     def set_field_poses(self, positions: torch.Tensor, orientations: torch.Tensor):
+        """The poses of all fields.  After reserve_fields they are COPIED into the reserved pose rows (the loop-closure case:
+        every pose moves, the storage -- what a captured graph reads -- stays); the number of rows must then be the number
+        of fields: a map with reserved rows grows through add_fields(num_new, positions=, orientations=)."""
+        rs = self._reserved
+        if rs is not None:
+            num = self._global_map_dict["num"]
+            if positions.shape[0] != num or orientations.shape[0] != num:
+                raise ValueError(f"set_field_poses: {positions.shape[0]} / {orientations.shape[0]} poses for {num} fields (reserved "
+                                 "rows: add fields with add_fields(num_new, positions=, orientations=))")
+            rs["positions"][:num].copy_(positions)
+            rs["orientations"][:num].copy_(orientations)
+            return
         old = self._global_map_dict
         self._global_map_dict = {"positions": positions, "orientations": orientations, "num": positions.shape[0]}
         if old is not None and "training_iterations" in old:            # the counts belong to the fields, not to their poses
@@ -225,6 +241,8 @@ class NeuralGraphRenderer:
         """_global_map_dict["training_iterations"] (int64, one per field; rm.py:1188), created on first use and extended
         with zeros when fields were added, as add_fields extends the parameters"""
         md = self._global_map_dict
+        if self._reserved is not None:                     # max_fields rows, zero past `num`: never reallocated
+            return self._reserved["training_iterations"]
         ti, num = md.get("training_iterations"), md["num"]
         if ti is None or ti.shape[0] < num:
             if torch.cuda.is_current_stream_capturing():
@@ -239,7 +257,10 @@ class NeuralGraphRenderer:
     def _count_training_iteration(self, field_ids: torch.Tensor, count: Optional[torch.Tensor]) -> None:
         if self.track_training_iterations and field_ids.shape[0] > 0:
             fids = field_ids if field_ids.dtype == torch.int64 else field_ids.long()
-            ops.field_counts_add(fids.contiguous(), count, self._training_iterations(), self._global_map_dict["num"])
+            # reserved rows: the bound is the capacity -- the sampler emits no id at or beyond the device field count (its
+            # owner filter drops them), and training_iterations has a row for every id below the capacity
+            num = self._global_map_dict["num"] if self._reserved is None else self._reserved["max"]
+            ops.field_counts_add(fids.contiguous(), count, self._training_iterations(), num)
 
     def get_field_ids(self, min_iterations: Optional[int] = None) -> torch.Tensor:
         """NeuralGraphMap.get_field_ids (rm.py:2175-2181): the fields trained in at least min_iterations iterations (all
@@ -249,8 +270,96 @@ class NeuralGraphRenderer:
             return torch.arange(0, num, device=self._device)
         return torch.where(self._training_iterations()[:num] >= min_iterations)[0]
 
-    def add_fields(self, num_new: int):
-        """NeuralGraphMap._add_fields (rm.py:364-389): grow params + zero moments, keep the shared step."""
+    def reserve_fields(self, max_fields: int) -> None:
+        """Allocate the map ONCE for max_fields fields: every stacked parameter and its 16-bit copy (the model's
+        reserve_fields), both Adam moments, positions, orientations, training_iterations, and `num_fields_dev`, a
+        one-element int32 device tensor holding the number of fields.  The fields, moments, poses and counts the map holds
+        are copied over.  all_fields_params, lp_fields_params, _optim_state and the pose tensors of _global_map_dict stay
+        tensors of `num` rows -- leading-row views of the reservation -- and _global_map_dict["num"] stays the host mirror.
+        add_fields(num_new, positions=, orientations=) then appends in place (one launch, no synchronisation) and
+        sample_target_mv_device(current_count=, num_frames=), observed_fields_device and capture_training read
+        num_fields_dev on the device: one captured graph keeps replaying while the map grows up to max_fields.
+        Calling it again reallocates (a larger reservation): whatever was captured before must be captured again."""
+        max_fields = int(max_fields)
+        md = self._global_map_dict
+        self._model.reserve_fields(max_fields)              # raises if the fields held do not fit
+        num = self._model._reserved["num"]
+        if md is not None and md["num"] != num:
+            raise ValueError(f"reserve_fields: {md['num']} field poses but {num} fields")
+        caps = self._model._reserved["params"]
+        state = {k: {"exp_avg": torch.zeros_like(v), "exp_avg_sq": torch.zeros_like(v)} for k, v in caps.items()}
+        if self._optim_state is not None:
+            for k, st in self._optim_state.items():
+                state[k]["exp_avg"][:num] = st["exp_avg"]
+                state[k]["exp_avg_sq"][:num] = st["exp_avg_sq"]
+        pdev = next(iter(caps.values())).device
+        pos, quat = torch.zeros(max_fields, 3, device=pdev), torch.zeros(max_fields, 4, device=pdev)
+        quat[:, 0] = 1.0
+        ti = torch.zeros(max_fields, dtype=torch.int64, device=pdev)
+        if md is not None:
+            pos[:num], quat[:num] = md["positions"], md["orientations"]
+            if md.get("training_iterations") is not None:
+                ti[:num] = md["training_iterations"][:num]
+        nfd = torch.zeros(1, dtype=torch.int32, device=pdev)
+        nfd.fill_(num)
+        self._reserve_epoch += 1
+        self._reserved = dict(max=max_fields, epoch=self._reserve_epoch, state=state, positions=pos, orientations=quat,
+                              training_iterations=ti, num_fields_dev=nfd)
+        self._set_num(num)
+
+    def _set_num(self, num: int) -> None:
+        """reserved mode: the public state as views of the first `num` rows (the model's own views are set by the model)"""
+        rs = self._reserved
+        self._optim_state = {k: {n: t[:num] for n, t in st.items()} for k, st in rs["state"].items()}
+        self._global_map_dict = {"positions": rs["positions"][:num], "orientations": rs["orientations"][:num], "num": num,
+                                 "training_iterations": rs["training_iterations"]}
+
+    def _append_reserved(self, num_new: int, positions, orientations) -> None:
+        rs, m = self._reserved, self._model
+        first = m._check_room(num_new)                      # ValueError before anything is touched
+        pdev = rs["positions"].device
+        if positions is None:
+            positions = torch.zeros(num_new, 3, device=pdev)
+        if orientations is None:
+            orientations = torch.zeros(num_new, 4, device=pdev)
+            orientations[:, 0] = 1.0
+        if tuple(positions.shape) != (num_new, 3) or tuple(orientations.shape) != (num_new, 4):
+            raise ValueError(f"add_fields({num_new}): positions must be ({num_new}, 3) and orientations ({num_new}, 4), got "
+                             f"{tuple(positions.shape)} and {tuple(orientations.shape)}")
+        positions = positions.to(device=pdev, dtype=torch.float32).contiguous()
+        orientations = orientations.to(device=pdev, dtype=torch.float32).contiguous()
+        if not rs["positions"].is_cuda:                    # CPU tensors: the bookkeeping without a GPU, plain torch
+            m.add_fields(num_new)
+            for st in rs["state"].values():
+                st["exp_avg"][first:first + num_new] = 0.0
+                st["exp_avg_sq"][first:first + num_new] = 0.0
+            rs["positions"][first:first + num_new] = positions
+            rs["orientations"][first:first + num_new] = orientations
+            rs["training_iterations"][first:first + num_new] = 0
+            rs["num_fields_dev"].fill_(first + num_new)
+        else:                                              # one launch on the current stream (ngm_fields_append)
+            mr = m._reserved
+            proto = m._prototype_field.state_dict()
+            tensors = [dict(param=mr["params"][k], exp_avg=rs["state"][k]["exp_avg"], exp_avg_sq=rs["state"][k]["exp_avg_sq"],
+                            prototype=proto[k].detach().contiguous(), lp=None if mr["lp"] is None else mr["lp"].get(k))
+                       for k in mr["params"]]
+            ops.fields_append(tensors, positions, orientations, rs["positions"], rs["orientations"], rs["training_iterations"],
+                              rs["num_fields_dev"], first)
+            m._set_num(first + num_new)
+        self._set_num(first + num_new)
+
+    def add_fields(self, num_new: int, positions: Optional[torch.Tensor] = None, orientations: Optional[torch.Tensor] = None):
+        """NeuralGraphMap._add_fields (rm.py:364-389): grow params + zero moments, keep the shared step.
+        After reserve_fields the new fields are written IN PLACE into the next reserved rows -- parameters = the prototype,
+        their 16-bit copy, zero moments, training_iterations 0, the given poses (positions (num_new, 3), orientations
+        (num_new, 4) quaternions; omitted: origin / identity, to be followed by set_field_poses) -- and num_fields_dev is
+        raised, on the GPU as one launch on the current stream without host synchronisation; beyond max_fields it raises
+        ValueError and changes nothing."""
+        if self._reserved is not None:
+            return self._append_reserved(int(num_new), positions, orientations)
+        if positions is not None or orientations is not None:
+            raise ValueError("add_fields(positions=, orientations=) needs reserve_fields; without a reservation the poses "
+                             "are the caller's tensors (set_field_poses)")
         self._model.add_fields(num_new)
         allp = self._model.all_fields_params
         new_state = {}
@@ -268,10 +377,18 @@ class NeuralGraphRenderer:
         (optimizer moments are not saved there either).  With a peer exchange the health of every exchange so far is
         checked first: parameters trained behind a timed-out exchange are not written."""
         self.check_exchange()
-        torch.save({"map_dict": self._global_map_dict, "all_fields_params": self._model.all_fields_params,
-                    "state_dict": self._model.state_dict()}, path)
+        md, allp = self._global_map_dict, self._model.all_fields_params
+        if self._reserved is not None:
+            # torch.save of a view writes its whole storage (all max_fields rows): save contiguous copies of exactly `num` rows
+            num = md["num"]
+            md = {k: (v[:num].clone() if isinstance(v, torch.Tensor) else v) for k, v in md.items()}
+            allp = {k: v.clone() for k, v in allp.items()}
+        torch.save({"map_dict": md, "all_fields_params": allp, "state_dict": self._model.state_dict()}, path)
 
     def load_model(self, path: str) -> None:
+        """Load a checkpoint of the reference's layout.  The tensors are allocated anew at the checkpoint's size, so a map
+        with reserved rows LEAVES reserved mode (call reserve_fields again afterwards), and anything captured is stale."""
+        self._reserved = self._model._reserved = None
         ck = torch.load(path, map_location=self._device)
         self._model.load_state_dict(ck["state_dict"])
         self._model.all_fields_params = {k: v.to(self._device) for k, v in ck["all_fields_params"].items()}
@@ -694,11 +811,21 @@ class NeuralGraphRenderer:
         (ngm_target_sample_mv_live) -- current_field_ids, c_c2w and frame_cid_to_ncid are then fixed-capacity buffers
         (observed_fields_device and KeyframeStore fill such), only their first current_count / num_frames entries are read,
         and the result is bit for bit that of this call on the sliced tensors: the shapes no longer follow the frame, so a
-        captured graph outlives it.  Returns a LiveDeviceTarget."""
+        captured graph outlives it.  Returns a LiveDeviceTarget.
+        After reserve_fields the live sampler also reads the NUMBER OF FIELDS on the device (ngm_target_sample_mv_grow,
+        num_fields_dev): current_field_ids then has at most max_fields entries, the row capacity is the host-known
+        min(num_train_fields, fields this rank owns among max_fields), and rows below `count` are bit for bit those of an
+        unreserved map of exactly `num` fields.  Without current_count the call uses the host's `num` as before."""
         if (current_count is None) != (num_frames is None):
             raise ValueError("sample_target_mv_device: current_count and num_frames go together (both device tensors, or neither)")
         cam = camera or self._camera
         dev = self._device
+        rs = self._reserved if current_count is not None else None      # reserved rows + live counts: the grow entry point
+        if rs is not None:
+            if num_fields is not None and int(num_fields) != self._global_map_dict["num"]:
+                raise ValueError("sample_target_mv_device: with reserved field rows the number of fields is read on the device "
+                                 "(num_fields_dev); leave num_fields=None")
+            num_fields = rs["max"]
         num_fields = self._global_map_dict["num"] if num_fields is None else num_fields
         cur = current_field_ids if current_field_ids.device == torch.device(dev) else current_field_ids.to(dev)
         if cur.dtype != torch.int64:
@@ -716,7 +843,11 @@ class NeuralGraphRenderer:
         if current_count is not None:
             views = [views[0], current_count, views[1], num_frames]
         sampler = ops.target_sample_mv if current_count is None else ops.target_sample_mv_live
-        o = sampler(*views, nc_rgbd.contiguous(), frame_cid_to_ncid.contiguous(), self._global_map_dict["positions"].contiguous(),
+        positions = self._global_map_dict["positions"].contiguous()
+        if rs is not None:
+            sampler, positions = ops.target_sample_mv_grow, rs["positions"]
+            views.append(rs["num_fields_dev"])
+        o = sampler(*views, nc_rgbd.contiguous(), frame_cid_to_ncid.contiguous(), positions,
                     fx, fy, cx, cy, self._field_radius + 0.0, int(num_fields), int(num_train_fields), int(num_rays_per_field),
                     seed=seed, iteration=iteration, iteration_dev=counter, world_size=world_size, rank=rank)
         return DeviceTarget.from_sampler(o, world_size)
@@ -744,10 +875,13 @@ class NeuralGraphRenderer:
             counter = self._observe_frame_dev
         ids_out, count_out = out if out is not None else (None, None)
         fx, fy, cx, cy, _ = cam.get_pinhole_camera_parameters(0.0)
-        o = ops.target_observed_fields(rgbd_image, c2w, self._global_map_dict["positions"].contiguous(), fx, fy, cx, cy,
-                                       self._field_radius + 0.0, int(self._global_map_dict["num"]), num_points=num_points,
+        rs = self._reserved            # reserved rows: ids (max_fields,), the fields tested = num_fields_dev, read on the device
+        positions = self._global_map_dict["positions"].contiguous() if rs is None else rs["positions"]
+        o = ops.target_observed_fields(rgbd_image, c2w, positions, fx, fy, cx, cy, self._field_radius + 0.0,
+                                       int(self._global_map_dict["num"] if rs is None else rs["max"]), num_points=num_points,
                                        seed=seed, frame=frame, frame_dev=counter,
-                                       subset_in=None if draws is None else draws["pixels"], ids_out=ids_out, count_out=count_out)
+                                       subset_in=None if draws is None else draws["pixels"], ids_out=ids_out, count_out=count_out,
+                                       num_fields_dev=None if rs is None else rs["num_fields_dev"])
         self.last_observed = dict(pixels=o["pixels"], num_used=o["num_used"])
         return o["current_field_ids"], o["current_count"]
 
@@ -1218,7 +1352,11 @@ class NeuralGraphRenderer:
         current_count / num_frames (both or neither; one-element int32 device tensors): the live sampler, see
         sample_target_mv_device.  current_field_ids, c_c2w and frame_cid_to_ncid are then fixed-capacity buffers whose
         first current_count / num_frames entries are read at every replay, so ONE capture serves every frame (a new
-        observed set: observed_fields_device(out=...)) and every keyframe (KeyframeStore) until fields are added.
+        observed set: observed_fields_device(out=...)) and every keyframe (KeyframeStore) until fields are added -- or,
+        after reserve_fields(max_fields), beyond that: the graph then reads the number of fields on the device as well, the
+        replay check watches the reservation (storage addresses and capacities) instead of `num` and the row counts, and
+        add_fields(num_new, positions=, orientations=) between replays is legal up to max_fields.  Replacing any reserved
+        tensor, reserve_fields again or load_model still raise "capture again".
 
         Every rank must own at least one field of the map (a capacity of 0 rows raises ValueError: nothing to capture).
 
@@ -1242,20 +1380,38 @@ class NeuralGraphRenderer:
             if named[n].dtype != torch.int64:
                 raise TypeError(f"capture_training: {n} must be int64")
         num_fields = self._global_map_dict["num"]
+        grow = self._reserved is not None and current_count is not None      # the graph reads num_fields_dev
 
         def watched():
             ts = dict(named, positions=self._global_map_dict["positions"], orientations=self._global_map_dict["orientations"])
             ts.update({"param " + n: v for n, v in self._model.all_fields_params.items()})
             if self.track_training_iterations:
                 ts["training_iterations"] = self._training_iterations()
-            return {n: (t.data_ptr(), tuple(t.shape)) for n, t in ts.items()}
+            if not grow:
+                return {n: (t.data_ptr(), tuple(t.shape)) for n, t in ts.items()}
+            # reserved rows: the views the step reads (addresses; row shapes without the row count) + the reservation itself
+            seen = {n: (t.data_ptr(), tuple(t.shape) if n in named else tuple(t.shape[1:])) for n, t in ts.items()}
+            rs, mr = self._reserved, self._model._reserved
+            if rs is None or mr is None:
+                return dict(seen, reservation=None)
+            caps = {"reserved " + n: t for n, t in mr["params"].items()}
+            caps.update({"reserved lp " + n: t for n, t in (mr["lp"] or {}).items()})
+            for n, st in rs["state"].items():
+                caps["reserved exp_avg " + n], caps["reserved exp_avg_sq " + n] = st["exp_avg"], st["exp_avg_sq"]
+                seen["exp_avg " + n] = (self._optim_state[n]["exp_avg"].data_ptr(),)
+                seen["exp_avg_sq " + n] = (self._optim_state[n]["exp_avg_sq"].data_ptr(),)
+            for n in ("positions", "orientations", "training_iterations", "num_fields_dev"):
+                caps["reserved " + n] = rs[n]
+            seen.update({n: (t.data_ptr(), tuple(t.shape)) for n, t in caps.items()})
+            seen["reservation"] = (rs["max"], rs["epoch"])
+            return seen
         for n in ("positions", "orientations"):
             if not self._global_map_dict[n].is_contiguous():
                 raise ValueError(f"capture_training: the field {n} must be contiguous (read in place at every replay)")
 
         def sample():
             return self.sample_target_mv_device(current_field_ids, c_c2w, nc_rgbd, frame_cid_to_ncid, num_train_fields,
-                                                num_rays_per_field, num_fields=num_fields, camera=camera, seed=seed,
+                                                num_rays_per_field, num_fields=None if grow else num_fields, camera=camera, seed=seed,
                                                 iteration=None, world_size=world_size, rank=rank, current_count=current_count,
                                                 num_frames=num_frames)
         if self.track_training_iterations:
@@ -1292,7 +1448,7 @@ class NeuralGraphRenderer:
 
         def replay():
             now = watched()
-            if now != seen or self._global_map_dict["num"] != num_fields:
+            if now != seen or (not grow and self._global_map_dict["num"] != num_fields):
                 changed = sorted(n for n in now if now[n] != seen.get(n)) or ["number of fields"]
                 raise RuntimeError(f"capture_training: {changed} changed shape or storage since the capture; the graph "
                                    "reads the captured addresses -- capture again")
