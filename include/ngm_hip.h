@@ -24,12 +24,12 @@
 extern "C" {
 #endif
 
-#define NGM_ABI_VERSION 11 /* 11 (+ addition, number unchanged: ngm_target_sample_mv_live(_workspace) / struct ngm_target_live, ngm_target_observed_fields(_workspace) / struct ngm_observed_fields, ngm_field_counts_add: the sampler with its counts in device memory, the observed-field test and the per-field iteration counts on the device; nothing existing changed); 11 (+ addition, number unchanged: ngm_render_fwd_counted / ngm_render_bwd_counted / ngm_render_bwd_adam_counted, the training step launched at a capacity with the number of active rows in device memory; nothing existing changed); 11 (+ addition, number unchanged: ngm_target_sample_mv_workspace / ngm_target_sample_mv and struct ngm_target_sample, the device-side training-target sampler; nothing existing changed); 11: ngm_field_eval_stash_bytes / ngm_field_eval_fwd_train / ngm_field_eval_bwd_stash (training forward of the point evaluation writes the activation stash, its backward is the fused step's kernel); 10: ngm_field_cfg.activation_stash / .hash_grad_atomics (per configuration, no process-wide switch), empty loss selections report NaN like the reference; 9: ngm_sample_rays_weighted; 8: ngm_peer_set_timeout (a time-out now also poisons the sums with NaN); 7: ngm_encode_bwd; 6: ngm_render_eval_knn; 5: ngm_encode_fwd, ngm_render_bwd_seeded_vars, *_nll loss modes (+ loss-sum slot 10), peer status bits */
+#define NGM_ABI_VERSION 11 /* 11 (+ addition, number unchanged: ngm_target_sample_mv_live(_workspace) / struct ngm_target_live, ngm_target_observed_fields(_workspace) / struct ngm_observed_fields, ngm_field_counts_add: the sampler with its counts in device memory, the observed-field test and the per-field iteration counts on the device; nothing existing changed); 11 (+ addition, number unchanged: ngm_render_fwd_counted / ngm_render_bwd_counted / ngm_render_bwd_adam_counted, the training step launched at a capacity with the number of active rows in device memory; nothing existing changed); 11 (+ addition, number unchanged: ngm_target_sample_mv_workspace / ngm_target_sample_mv and struct ngm_target_sample, the device-side training-target sampler; nothing existing changed); 11: ngm_field_eval_stash_bytes / ngm_field_eval_fwd_train / ngm_field_eval_bwd_stash (training forward of the point evaluation writes the activation stash, its backward is the fused step's kernel); 10: ngm_field_cfg.activation_stash / .hash_grad_atomics (per configuration, no process-wide switch), empty loss selections report NaN like the reference; 9: ngm_sample_rays_weighted; 8: ngm_peer_set_timeout (a time-out now also poisons the sums with NaN); 7: ngm_encode_bwd; 6: ngm_render_eval_knn; 5: ngm_encode_fwd, ngm_render_bwd_seeded_vars, *_nll loss modes (+ loss-sum slot 10), peer status bits; 11 (+ addition, number unchanged: ngm_grid_eval_knn(_workspace), the kNN evaluation on a lattice given by its axes -- one block of the mesh grid as one call; nothing existing changed) */
 /* Array bound of the per-layer pointers below (hidden layers; +1 output layer).  NOT the depth every entry point takes -- the
  * kernels are compiled per depth L = num_layers and padded width class (dim_enc and dim_hidden both <= 32, or both 33..64):
  *   L = 1, 2   every entry point, both width classes (forward, backward, fused step, kNN evaluation)
  *   L = 3      forward only and 33..64-wide only: ngm_field_eval_fwd, ngm_render_fwd (no targets' backward), ngm_field_eval_knn,
- *              ngm_render_eval_knn; always exact-fp32 MFMA (NGM_MATMUL_AUTO resolves to it, an explicit NGM_MATMUL_BF16X3 is
+ *              ngm_render_eval_knn, ngm_grid_eval_knn; always exact-fp32 MFMA (NGM_MATMUL_AUTO resolves to it, an explicit NGM_MATMUL_BF16X3 is
  *              refused by the fused forward).  Every backward entry point (ngm_field_eval_bwd, ngm_render_bwd*, the *_adam and
  *              *_seeded forms) returns NGM_E_UNSUPPORTED before its first launch: workspace, gradients, parameters, Adam state
  *              and the device-side iteration counter are left as they were.
@@ -481,6 +481,22 @@ int ngm_field_eval_knn(const ngm_field_cfg* fcfg, const ngm_params* params, int3
                        const float* field_quat, int32_t num_knn, float distance_factor,
                        float outside_value, float mask_radius, float* out, void* workspace, int64_t workspace_bytes,
                        void* stream);
+
+/* ---- eval path on a lattice: one block of _extract_mesh's dense grid (rm.py:2236-2261) as one call -----------------------
+ * = ngm_field_eval_knn on torch.cartesian_prod(xs, ys, zs) followed by "take channel `channel`, reshape to (nx, ny, nz),
+ * negate when `negate`", bit for bit, without the (P,3) point array and the (P,4) output: point p is
+ * (xs[p / (ny nz)], ys[(p / nz) % ny], zs[p % nz]), formed from the three device axes inside the neighbour assignment and again
+ * inside the evaluation (the axes are read as they are: uniform or not), and the blend writes the one channel marching cubes
+ * needs into volume (nx, ny, nz) fp32.  The occupancy mode's sigmoid is the caller's (a torch op on the volume).
+ * mask_radius, K <= 16, params->field_index and the forward plan as in ngm_field_eval_knn; the workspace is that entry's for
+ * nx ny nz points.  Checked before any launch: a side < 1, a NULL axis / volume / pose, channel outside 0..3 ->
+ * NGM_E_INVALID; nx ny nz K > 2^31 - 1, num_fields < 1 or K > 16 -> NGM_E_UNSUPPORTED (the workspace query returns the same
+ * codes); workspace_bytes below the query's answer -> NGM_E_WORKSPACE. */
+int64_t ngm_grid_eval_knn_workspace(int32_t num_fields, int32_t nx, int32_t ny, int32_t nz, int32_t num_knn);
+int ngm_grid_eval_knn(const ngm_field_cfg* fcfg, const ngm_params* params, int32_t num_fields, const float* field_pos,
+                      const float* field_quat, const float* xs, int32_t nx, const float* ys, int32_t ny, const float* zs,
+                      int32_t nz, int32_t num_knn, float distance_factor, float outside_value, float mask_radius,
+                      int32_t channel, int32_t negate, float* volume, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- eval path, whole: render_image's loop over pixel blocks (rm.py:402-437) -------------------------------------------
  * = per block of `ray_block` rays: Camera.sample_ijs_uniform + transform_points (rm.py:513-547, eval-style: one stratum of

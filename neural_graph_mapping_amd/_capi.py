@@ -289,6 +289,11 @@ def lib():
     L.ngm_field_eval_knn.argtypes = [P(FieldCfg), P(Params), i32, i64, vp, vp, vp, i32, f32, f32, f32, vp, vp, i64, vp]
     L.ngm_field_eval_knn_workspace.argtypes = [i32, i64, i32]
     L.ngm_field_eval_knn_workspace.restype = i64
+    L.ngm_grid_eval_knn.argtypes = [P(FieldCfg), P(Params), i32, vp, vp, vp, i32, vp, i32, vp, i32, i32, f32, f32, f32, i32, i32,
+                                    vp, vp, i64, vp]
+    L.ngm_grid_eval_knn.restype = C.c_int
+    L.ngm_grid_eval_knn_workspace.argtypes = [i32, i32, i32, i32, i32]
+    L.ngm_grid_eval_knn_workspace.restype = i64
     L.ngm_render_eval_knn.argtypes = [P(FieldCfg), P(RenderCfg), P(Params), i32, vp, vp, P(Rays), i32, f32, f32, f32, i32,
                                       P(Prediction), vp, i64, vp]
     L.ngm_render_eval_knn.restype = C.c_int
@@ -355,7 +360,7 @@ EXPORTED = ["ngm_abi_version", "ngm_last_error", "ngm_device_info", "ngm_permuto
             "ngm_field_eval_stash_bytes", "ngm_field_eval_fwd_train", "ngm_field_eval_bwd_stash",
             "ngm_composite_fwd", "ngm_composite_bwd", "ngm_render_workspace", "ngm_render_fwd",
             "ngm_render_bwd", "ngm_render_bwd_adam", "ngm_render_bwd_seeded", "ngm_render_bwd_seeded_vars", "ngm_render_read_samples", "ngm_adam_sparse",
-            "ngm_field_eval_knn", "ngm_field_eval_knn_workspace", "ngm_render_eval_knn", "ngm_render_eval_knn_workspace", "ngm_adam_sparse_multi", "ngm_step_advance", "ngm_profile_enable", "ngm_profile_reset", "ngm_profile_read",
+            "ngm_field_eval_knn", "ngm_field_eval_knn_workspace", "ngm_grid_eval_knn", "ngm_grid_eval_knn_workspace", "ngm_render_eval_knn", "ngm_render_eval_knn_workspace", "ngm_adam_sparse_multi", "ngm_step_advance", "ngm_profile_enable", "ngm_profile_reset", "ngm_profile_read",
             "ngm_debug_phase_cycles", "ngm_debug_fwd_phase_cycles", "ngm_debug_last_bwd_variant", "ngm_debug_last_matmul", "ngm_debug_last_fwd_one_tile", "ngm_debug_last_comp_fused", "ngm_debug_disable_fused_comp", "ngm_debug_stash_mode", "ngm_debug_last_stash_mode", "ngm_debug_plan_bwd", "ngm_debug_plan_fwd", "ngm_target_visibility", "ngm_target_rays", "ngm_target_sv_intersect", "ngm_target_sv_rays",
             "ngm_target_sample_mv_workspace", "ngm_target_sample_mv",
             "ngm_target_sample_mv_live_workspace", "ngm_target_sample_mv_live", "ngm_target_observed_fields_workspace",

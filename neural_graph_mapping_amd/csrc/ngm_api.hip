@@ -31,6 +31,10 @@ int ngm_mc_copy_tables(int8_t* tri_table, int32_t* tri_count);
 int ngm_launch_knn(const ngm_field_cfg* fc, const ngm_params* pr, int num_fields, int64_t P, const float* points,
                    const float* pos, const float* quat, int K, float distance_factor, float outside_value, float mask_radius,
                    float* out, void* workspace, int64_t workspace_bytes, const FwdPlan& plan, hipStream_t st);
+int ngm_launch_grid_knn(const ngm_field_cfg* fc, const ngm_params* pr, int num_fields, const float* pos, const float* quat,
+                        const float* xs, int nx, const float* ys, int ny, const float* zs, int nz, int K, float distance_factor,
+                        float outside_value, float mask_radius, int channel, int negate, float* volume, void* workspace,
+                        int64_t workspace_bytes, const FwdPlan& plan, hipStream_t st);
 int64_t ngm_knn_workspace_bytes(int num_fields, int64_t P, int K);
 int64_t ngm_knn_render_workspace_bytes(int num_fields, int ray_block, int S, int K);
 int ngm_launch_render_eval_knn(const ngm_field_cfg* fc, const ngm_render_cfg* rc, const ngm_params* pr, int num_fields,
@@ -1390,6 +1394,50 @@ int ngm_field_eval_knn(const ngm_field_cfg* fcfg, const ngm_params* params, int3
   if (e) return fail(e, "ngm_field_eval_knn: not available for this configuration");
   g_last_fwd[NGM_FWD_KNN] = plan;
   return check_launch("ngm_field_eval_knn");
+}
+
+// the lattice entry's argument checks, shared by the workspace query and the call: 0, or the status; *K, *P on success
+static int grid_knn_shape(int32_t num_fields, int32_t nx, int32_t ny, int32_t nz, int32_t num_knn, int* K, int64_t* P) {
+  if (nx < 1 || ny < 1 || nz < 1) return fail(NGM_E_INVALID, "ngm_grid_eval_knn: every side of the lattice must be >= 1");
+  if (num_fields < 1) return fail(NGM_E_UNSUPPORTED, "ngm_grid_eval_knn: no field");
+  *K = num_knn < num_fields ? num_knn : num_fields;
+  if (*K < 1 || *K > 16) return fail(NGM_E_UNSUPPORTED, "ngm_grid_eval_knn: K must be in [1,16]");
+  const int64_t nxy = (int64_t)nx * ny;             // (two int32 factors at a time fit an int64, three at once need not)
+  *P = nxy > 0x7fffffff ? nxy : nxy * nz;
+  if (*P > 0x7fffffff / *K)
+    return fail(NGM_E_UNSUPPORTED, "ngm_grid_eval_knn: nx * ny * nz * K must stay below 2^31 (evaluate the block in parts, or with ngm_field_eval_knn)");
+  return NGM_OK;
+}
+int64_t ngm_grid_eval_knn_workspace(int32_t num_fields, int32_t nx, int32_t ny, int32_t nz, int32_t num_knn) {
+  int K = 0;
+  int64_t P = 0;
+  const int e = grid_knn_shape(num_fields, nx, ny, nz, num_knn, &K, &P);
+  return e ? e : ngm_knn_workspace_bytes(num_fields, P, K);
+}
+
+int ngm_grid_eval_knn(const ngm_field_cfg* fcfg, const ngm_params* params, int32_t num_fields, const float* field_pos,
+                      const float* field_quat, const float* xs, int32_t nx, const float* ys, int32_t ny, const float* zs,
+                      int32_t nz, int32_t num_knn, float distance_factor, float outside_value, float mask_radius,
+                      int32_t channel, int32_t negate, float* volume, void* workspace, int64_t workspace_bytes, void* stream) {
+  int e = check_field_cfg(fcfg);
+  if (e) return e;
+  e = check_params(fcfg, params);
+  if (e) return e;
+  if (!xs || !ys || !zs || !volume || !field_pos || !field_quat) return fail(NGM_E_INVALID, "ngm_grid_eval_knn: NULL axis, volume or pose");
+  if (channel < 0 || channel > 3) return fail(NGM_E_INVALID, "ngm_grid_eval_knn: channel must be 0..3");
+  int K = 0;
+  int64_t P = 0;
+  e = grid_knn_shape(num_fields, nx, ny, nz, num_knn, &K, &P);
+  if (e) return e;
+  if (!workspace || workspace_bytes < ngm_knn_workspace_bytes(num_fields, P, K)) return fail(NGM_E_WORKSPACE, "ngm_grid_eval_knn: workspace too small");
+  const FwdPlan plan = plan_knn(fcfg);         // the evaluation is planned before the grid build and the assignment launch
+  if (plan.status) return fail(plan.status, plan.why);
+  e = ngm_launch_grid_knn(fcfg, params, num_fields, field_pos, field_quat, xs, nx, ys, ny, zs, nz, K, distance_factor, outside_value,
+                          mask_radius > 0.f ? mask_radius : fcfg->field_radius, channel, negate ? 1 : 0, volume, workspace,
+                          workspace_bytes, plan, (hipStream_t)stream);
+  if (e) return fail(e, "ngm_grid_eval_knn: not available for this configuration");
+  g_last_fwd[NGM_FWD_KNN] = plan;
+  return check_launch("ngm_grid_eval_knn");
 }
 
 int64_t ngm_render_eval_knn_workspace(const ngm_render_cfg* rcfg, int32_t num_fields, int32_t ray_block, int32_t num_knn) {

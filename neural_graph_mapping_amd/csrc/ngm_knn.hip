@@ -18,6 +18,9 @@
 // ngm_render_eval_knn (render_image's block loop, rm.py:402-437) runs the same stages per block of rays with the points
 // GENERATED inside the assignment (k_knn_raytab + the sampler's arithmetic; only the sample distances are kept) and the blend
 // done inside the quadrature (k_composite_fwd* on the pair records): no point, blended output or camera-frame point in memory.
+// ngm_grid_eval_knn (one block of _extract_mesh's dense grid, rm.py:2236-2261) runs them on the points of a lattice given by its
+// three axes: point p is formed from the axes inside the assignment and again inside the evaluation, k_knn_blend_volume writes
+// one channel of the blend straight into the (nx, ny, nz) volume marching cubes reads: no point array, no (P, 4) output.
 #include "ngm_field.h"
 #include "ngm_launch.h"
 
@@ -85,6 +88,12 @@ struct KnnArgs {
   float* dist;          // (P)
   float* ray_dir;       // (P / S, 3)
   float4* ray_tab;      // (P / S) near, far - near, (far - near) / S of the ray's stratum
+  // gen == 2, ngm_grid_eval_knn: point p of the (nx, ny, nz) lattice is (lat_x[p / (ny nz)], lat_y[(p / nz) % ny], lat_z[p % nz]),
+  // torch.cartesian_prod's order; the axes are read as they are (uniform or not), so the point is the staged path's bit for bit
+  const float* lat_x; const float* lat_y; const float* lat_z;
+  uint32_t lat_nz, lat_nynz;
+  int chan, negate;     // k_knn_blend_volume: vol[p] = (negate ? -1 : 1) * channel `chan` of the blend
+  float* vol;           // (nx, ny, nz) == (P)
 };
 struct KnnGridHdr { float x0, y0, z0, c, inv_c; int nx, ny, nz, ncells, pad; };
 
@@ -287,6 +296,12 @@ __device__ __forceinline__ void knn_point_again(const KnnArgs& a, int64_t p, flo
   sample_world_point(a.rays, rg, ray, a.dist[p], x, y, z);
 }
 
+// lattice points (a.gen == 2): three loads, no arithmetic on the coordinates.  P K < 2^31, so 32-bit divisions do
+__device__ __forceinline__ void knn_point_lattice(const KnnArgs& a, int64_t p, float* x, float* y, float* z) {
+  const uint32_t q = (uint32_t)p, ix = q / a.lat_nynz, r = q - ix * a.lat_nynz, iy = r / a.lat_nz;
+  *x = a.lat_x[ix]; *y = a.lat_y[iy]; *z = a.lat_z[r - iy * a.lat_nz];
+}
+
 // K nearest centres of every point, exact.  The (2 R + 1)^3 block of cells around the point's cell holds every centre
 // within R cell edges c of it.  Phase A decides the inside test of models.py:369 from the candidate list of the point's cell
 // (k_knn_grid: every centre a point of that cell can be within the mask radius of) -- four out of five samples of an image
@@ -298,7 +313,9 @@ __device__ __forceinline__ void knn_point_again(const KnnArgs& a, int64_t p, flo
 // GL: the grid (cell offsets + centres) staged in LDS -- maps up to a few thousand fields; larger ones read it through L1 / L2.
 // KK: the number of neighbours as a compile-time constant (the list insertion is the hot code: a wave executes it for the
 // union of its lanes' candidates)
-template <bool GL, int KK>
+// SRC: 0 -- points from memory or drawn on rays (a.gen, decided at run time as before); 2 -- the lattice, in instances of its own:
+// the third run-time source cost the existing instances two to twenty-two VGPRs and one of them a wave of occupancy
+template <bool GL, int KK, int SRC = 0>
 __global__ __launch_bounds__(256) void k_knn_assign(KnnArgs a) {
   extern __shared__ __attribute__((aligned(16))) int knn_lds[];
   const KnnGridHdr h = *a.grid;
@@ -330,10 +347,11 @@ __global__ __launch_bounds__(256) void k_knn_assign(KnnArgs a) {
   const int maxR = max(h.nx, max(h.ny, h.nz));
   const float c2 = h.c * h.c;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  const uint64_t poff = a.gen ? philox_launch_offset(a.rays) : 0ull;
+  const uint64_t poff = (SRC == 0 && a.gen) ? philox_launch_offset(a.rays) : 0ull;
   for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < a.P; p += stride) {
     float x, y, z;
-    if (a.gen) knn_point_draw(a, poff, p, &x, &y, &z);
+    if constexpr (SRC == 2) knn_point_lattice(a, p, &x, &y, &z);
+    else if (a.gen) knn_point_draw(a, poff, p, &x, &y, &z);
     else { x = a.points[3 * p]; y = a.points[3 * p + 1]; z = a.points[3 * p + 2]; }
     const float gx = (x - h.x0) * h.inv_c, gy = (y - h.y0) * h.inv_c, gz = (z - h.z0) * h.inv_c;
     // cell of the point; far outside the grid (or NaN) it is clamped to two rings beyond: nothing is within c then
@@ -551,7 +569,8 @@ __global__ __launch_bounds__(256) void k_knn_scatter(KnnArgs a) {
 // field's weights once per field it meets (one or two per run), not once per tile, and the runs are equal to within one
 // small tile.  NT: threads per workgroup -- the bf16-split variant keeps 83 KB of weights per workgroup, so one workgroup
 // per CU: eight waves (two per SIMD, as in the training forward) instead of four share them.
-template <int MI, int MH, int L, bool NEED_COS, int HASH, int SKIP, bool B3 = false, int NT = NGM_BLOCK>
+// SRC: the point source, as in k_knn_assign.
+template <int MI, int MH, int L, bool NEED_COS, int HASH, int SKIP, bool B3 = false, int NT = NGM_BLOCK, int SRC = 0>
 __global__ __launch_bounds__(NT) void k_knn_eval(KnnArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int total_tiles = a.tile_off[a.NF];
@@ -601,7 +620,8 @@ __global__ __launch_bounds__(NT) void k_knn_eval(KnnArgs a) {
         pair = a.sorted[idx];
         const int64_t p = pair / a.K;
         float wx, wy, wz;
-        if (a.gen) knn_point_again(a, p, &wx, &wy, &wz);
+        if constexpr (SRC == 2) knn_point_lattice(a, p, &wx, &wy, &wz);
+        else if (a.gen) knn_point_again(a, p, &wx, &wy, &wz);
         else { wx = a.points[3 * p]; wy = a.points[3 * p + 1]; wz = a.points[3 * p + 2]; }
         const Vec3 v = scaled_local_point(Vec3{wx, wy, wz}, true, px, py, pz, qw, qx, qy, qz, div, off);   // models.py:377-381
         x = v.x; y = v.y; z = v.z;
@@ -624,6 +644,20 @@ __global__ __launch_bounds__(256) void k_knn_blend(KnnArgs a) {
       }
     }
     reinterpret_cast<float4*>(a.out)[p] = o;
+  }
+}
+
+// the blend of one channel into the lattice's volume (p in cartesian_prod order IS the row-major index of (nx, ny, nz)): the fmaf
+// chain of k_knn_blend for that channel, in its order; the negation (marching cubes takes "inside = above the level") is exact
+__global__ __launch_bounds__(256) void k_knn_blend_volume(KnnArgs a) {
+  const float* po = reinterpret_cast<const float*>(a.pair_out) + a.chan;
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < a.P; p += (int64_t)gridDim.x * blockDim.x) {
+    float o = a.outside_value;                                                                   // models.py:401
+    if (a.pair_field[p * a.K] >= 0) {
+      o = 0.f;
+      for (int k = 0; k < a.K; ++k) o = fmaf(a.pair_w[p * a.K + k], po[4 * (p * a.K + k)], o);
+    }
+    a.vol[p] = a.negate ? -o : o;
   }
 }
 
@@ -652,28 +686,28 @@ static int launch_eval_inst(Kernel kernel, const KnnArgs& a, const FwdPlan& p, i
   hipLaunchKernelGGL(kernel, dim3(std::max(1, std::min(max_tiles, p.blocks))), dim3(p.threads), (size_t)p.lds_bytes, st, a);
   return 0;
 }
-template <int MI, int MH, int L, bool NC, int HS>
+template <int MI, int MH, int L, bool NC, int HS, int SRC>
 static int launch_eval_skips(const KnnArgs& a, const FwdPlan& p, int max_tiles, hipStream_t st) {
-  return p.skip == 1   ? launch_eval_inst(k_knn_eval<MI, MH, L, NC, HS, 1>, a, p, max_tiles, st)
-         : p.skip == 2 ? launch_eval_inst(k_knn_eval<MI, MH, L, NC, HS, 2>, a, p, max_tiles, st)
-                       : launch_eval_inst(k_knn_eval<MI, MH, L, NC, HS, 0>, a, p, max_tiles, st);
+  return p.skip == 1   ? launch_eval_inst(k_knn_eval<MI, MH, L, NC, HS, 1, false, NGM_BLOCK, SRC>, a, p, max_tiles, st)
+         : p.skip == 2 ? launch_eval_inst(k_knn_eval<MI, MH, L, NC, HS, 2, false, NGM_BLOCK, SRC>, a, p, max_tiles, st)
+                       : launch_eval_inst(k_knn_eval<MI, MH, L, NC, HS, 0, false, NGM_BLOCK, SRC>, a, p, max_tiles, st);
 }
-template <int MI, int MH, int L>
+template <int MI, int MH, int L, int SRC>
 static int launch_eval(const KnnArgs& a, const FwdPlan& p, int max_tiles, hipStream_t st) {
   if (p.matmul == NGM_MATMUL_BF16X3) {
     if constexpr (ngm_fwd_split_shape(MI, MH, L)) {
       if (p.need_cos || p.hash || p.skip || p.threads != KNN_EVAL_B3_THREADS) return NGM_E_INVALID;
-      return launch_eval_inst(k_knn_eval<MI, MH, L, false, 0, 0, true, KNN_EVAL_B3_THREADS>, a, p, max_tiles, st);
+      return launch_eval_inst(k_knn_eval<MI, MH, L, false, 0, 0, true, KNN_EVAL_B3_THREADS, SRC>, a, p, max_tiles, st);
     }
     return NGM_E_INVALID;
   }
   if (p.threads != NGM_BLOCK) return NGM_E_INVALID;
   if (p.hash == 1) {
-    if constexpr (MI == 1) return launch_eval_skips<MI, MH, L, false, 1>(a, p, max_tiles, st);
+    if constexpr (MI == 1) return launch_eval_skips<MI, MH, L, false, 1, SRC>(a, p, max_tiles, st);
     return NGM_E_INVALID;
   }
-  if (p.hash == 2) return launch_eval_skips<MI, MH, L, false, 2>(a, p, max_tiles, st);
-  return p.need_cos ? launch_eval_skips<MI, MH, L, true, 0>(a, p, max_tiles, st) : launch_eval_skips<MI, MH, L, false, 0>(a, p, max_tiles, st);
+  if (p.hash == 2) return launch_eval_skips<MI, MH, L, false, 2, SRC>(a, p, max_tiles, st);
+  return p.need_cos ? launch_eval_skips<MI, MH, L, true, 0, SRC>(a, p, max_tiles, st) : launch_eval_skips<MI, MH, L, false, 0, SRC>(a, p, max_tiles, st);
 }
 
 // workspace carving shared by the two entry points; `a.NF`, `a.K`, `a.P` (the largest P of the call) are set
@@ -709,13 +743,15 @@ static int knn_stages(KnnArgs& a, const FwdPlan& p, bool build_grid, hipStream_t
   a.hist_in_lds = lds_h <= 150 * 1024 ? 1 : 0;
   static const hipError_t attr_a = [] {
     hipError_t e = hipSuccess;
-#define NGM_KA(G, KK_, B) do { const hipError_t x = hipFuncSetAttribute(reinterpret_cast<const void*>(k_knn_assign<G, KK_>), hipFuncAttributeMaxDynamicSharedMemorySize, B); if (x != hipSuccess) e = x; } while (0)
+#define NGM_KA1(G, KK_, SRC_, B) do { const hipError_t x = hipFuncSetAttribute(reinterpret_cast<const void*>(k_knn_assign<G, KK_, SRC_>), hipFuncAttributeMaxDynamicSharedMemorySize, B); if (x != hipSuccess) e = x; } while (0)
+#define NGM_KA(G, KK_, B) do { NGM_KA1(G, KK_, 0, B); NGM_KA1(G, KK_, 2, B); } while (0)
     NGM_KA(false, 1, 150 * 1024); NGM_KA(false, 2, 150 * 1024); NGM_KA(false, 3, 150 * 1024); NGM_KA(false, 4, 150 * 1024);
     NGM_KA(true, 1, 64 * 1024); NGM_KA(true, 2, 64 * 1024); NGM_KA(true, 3, 64 * 1024); NGM_KA(true, 4, 64 * 1024);
     NGM_KA(false, 5, 150 * 1024); NGM_KA(false, 6, 150 * 1024); NGM_KA(false, 7, 150 * 1024); NGM_KA(false, 8, 150 * 1024);
     NGM_KA(true, 5, 64 * 1024); NGM_KA(true, 6, 64 * 1024); NGM_KA(true, 7, 64 * 1024); NGM_KA(true, 8, 64 * 1024);
     NGM_KA(false, 16, 150 * 1024); NGM_KA(true, 16, 64 * 1024);
 #undef NGM_KA
+#undef NGM_KA1
     return e;
   }();
   // grid in LDS while histogram + centres + cell offsets stay within 64 KB (two workgroups per CU keep their latency hiding)
@@ -737,15 +773,17 @@ static int knn_stages(KnnArgs& a, const FwdPlan& p, bool build_grid, hipStream_t
         hipLaunchKernelGGL(k_knn_near_fill, dim3(nb), dim3(256), 0, st, a);
       }
     }
-#define NGM_KL(KK_)                                                                                                    \
+#define NGM_KL1(KK_, SRC_)                                                                                             \
     do {                                                                                                               \
-      if (grid_in_lds) hipLaunchKernelGGL((k_knn_assign<true, KK_>), dim3(std::max(pb, 1)), dim3(256), lds_grid, st, a);  \
-      else hipLaunchKernelGGL((k_knn_assign<false, KK_>), dim3(std::max(pb, 1)), dim3(256), a.hist_in_lds ? lds_h : 0, st, a); \
+      if (grid_in_lds) hipLaunchKernelGGL((k_knn_assign<true, KK_, SRC_>), dim3(std::max(pb, 1)), dim3(256), lds_grid, st, a);  \
+      else hipLaunchKernelGGL((k_knn_assign<false, KK_, SRC_>), dim3(std::max(pb, 1)), dim3(256), a.hist_in_lds ? lds_h : 0, st, a); \
     } while (0)
+#define NGM_KL(KK_) do { if (a.gen == 2) NGM_KL1(KK_, 2); else NGM_KL1(KK_, 0); } while (0)
     if (K == 1) NGM_KL(1); else if (K == 2) NGM_KL(2); else if (K == 3) NGM_KL(3); else if (K == 4) NGM_KL(4);
     else if (K == 5) NGM_KL(5); else if (K == 6) NGM_KL(6); else if (K == 7) NGM_KL(7); else if (K == 8) NGM_KL(8);
     else if (K <= 16) NGM_KL(16); else return NGM_E_UNSUPPORTED;
 #undef NGM_KL
+#undef NGM_KL1
   }
   if (hipGetLastError() != hipSuccess) return NGM_E_HIP;      // an over-sized LDS request fails here, not four launches later
   hipLaunchKernelGGL(k_knn_offsets, dim3(1), dim3(64), 0, st, a);
@@ -753,7 +791,7 @@ static int knn_stages(KnnArgs& a, const FwdPlan& p, bool build_grid, hipStream_t
   hipLaunchKernelGGL(k_knn_scatter, dim3(std::max(nb, 1)), dim3(256), a.hist_in_lds ? lds_h : 0, st, a);
   const int max_tiles = (int)std::min<int64_t>((n + KNN_TILE - 1) / KNN_TILE + a.NF, 0x7fffffff);
   NgmProfScope prof_eval_(NGM_K_KNN_EVAL, st);
-#define NGM_KNN_DISPATCH(MI_, MH_, L_) if (p.MI == MI_ && p.MH == MH_ && p.L == L_) return launch_eval<MI_, MH_, L_>(a, p, max_tiles, st);
+#define NGM_KNN_DISPATCH(MI_, MH_, L_) if (p.MI == MI_ && p.MH == MH_ && p.L == L_) return a.gen == 2 ? launch_eval<MI_, MH_, L_, 2>(a, p, max_tiles, st) : launch_eval<MI_, MH_, L_, 0>(a, p, max_tiles, st);
   NGM_FWD_SHAPES(NGM_KNN_DISPATCH)
 #undef NGM_KNN_DISPATCH
   return NGM_E_INVALID;
@@ -783,6 +821,29 @@ int ngm_launch_knn(const ngm_field_cfg* fc, const ngm_params* pr, int num_fields
   if (le) return le;
   const int pb = (int)std::min<int64_t>((P + 255) / 256, 4096);
   hipLaunchKernelGGL(k_knn_blend, dim3(std::max(pb, 1)), dim3(256), 0, st, a);
+  return 0;
+}
+
+// one block of the mesh grid: the stages on the lattice's points, one channel of the blend into the volume
+int ngm_launch_grid_knn(const ngm_field_cfg* fc, const ngm_params* pr, int num_fields, const float* pos, const float* quat,
+                        const float* xs, int nx, const float* ys, int ny, const float* zs, int nz, int K, float distance_factor,
+                        float outside_value, float mask_radius, int channel, int negate, float* volume, void* workspace,
+                        int64_t workspace_bytes, const FwdPlan& plan, hipStream_t st) {
+  if (nx < 1 || ny < 1 || nz < 1 || num_fields < 1 || K < 1) return NGM_E_INVALID;
+  const int64_t P = (int64_t)nx * ny * nz;
+  if (P * K > 0x7fffffff) return NGM_E_UNSUPPORTED;
+  if (workspace_bytes < ngm_knn_workspace_bytes(num_fields, P, K) || !workspace) return NGM_E_WORKSPACE;
+  KnnArgs a;
+  knn_common(a, fc, pr, num_fields, pos, quat, K, distance_factor, outside_value, mask_radius);
+  a.P = P; a.gen = 2;
+  a.lat_x = xs; a.lat_y = ys; a.lat_z = zs; a.lat_nz = (uint32_t)nz; a.lat_nynz = (uint32_t)ny * (uint32_t)nz;
+  a.chan = channel; a.negate = negate; a.vol = volume;
+  char* end;
+  knn_carve(a, workspace, &end);
+  const int le = knn_stages(a, plan, true, st);
+  if (le) return le;
+  const int pb = (int)std::min<int64_t>((P + 255) / 256, 4096);
+  hipLaunchKernelGGL(k_knn_blend_volume, dim3(std::max(pb, 1)), dim3(256), 0, st, a);
   return 0;
 }
 

@@ -144,15 +144,47 @@ def grid_to_world(v: torch.Tensor, bx: torch.Tensor, by: torch.Tensor, bz: torch
     return v / n1 * span + org
 
 
+def reachable_blocks(axes, block: int, pos: torch.Tensor, radius: float) -> torch.Tensor:
+    """Which blocks of extract_mesh's grid can hold a point inside a field: (nbx, nby, nbz) bool, block (i, j, k) being the
+    lattice axes[0][i*block : i*block + block + 1] x ... (the block loop's slices, range(0, len(axis) - 1, block) per axis:
+    a one-point axis has no block and gives an empty dimension; ascending axes).  `radius` is the radius of the INSIDE TEST
+    of the evaluation the result guards (the model's, or a call's mask_radius), not the map's.  A block is marked
+    when some centre of `pos` (F, 3) lies within radius * (1 + 1e-3) of the block's axis-aligned box, by box distance --
+    every lattice point of the block is inside the box, so an unmarked block has no point within `radius` of any centre;
+    the margin covers the fp32 arithmetic of this test and of the kernels' inside test.  Conservative the other way: a
+    marked block may hold no inside point (the box's corner region, or the lattice stepping over the cap).
+    Pure torch on the tensors' device (CPU tensors work), no host synchronisation: one (blocks x fields) computation."""
+    lo, hi = [], []
+    for a in axes:
+        n = a.shape[0]
+        st = torch.arange(0, n - 1, block, device=a.device)
+        lo.append(a[st])
+        hi.append(a[torch.clamp(st + block, max=n - 1)])
+    c = pos.to(torch.float32)
+    d2 = 0
+    for i, shape in enumerate(((-1, 1, 1, 1), (1, -1, 1, 1), (1, 1, -1, 1))):
+        l, h, ci = lo[i].view(shape), hi[i].view(shape), c[:, i].view(1, 1, 1, -1)
+        d = torch.clamp(torch.maximum(l - ci, ci - h), min=0)              # distance of the centre to the slab [l, h]
+        d2 = d2 + d * d
+    reach = float(radius) * (1.0 + 1e-3)
+    return (d2 <= reach * reach).any(-1)
+
+
 @torch.no_grad()
 def extract_mesh(renderer, mesh_file_path=None, resolution: Optional[float] = None, threshold: Optional[float] = None,
                  transform: Optional[torch.Tensor] = None, field_ids: Optional[torch.Tensor] = None, block: int = 200,
-                 debug: Optional[dict] = None):
+                 debug: Optional[dict] = None, fused: bool = True, stats: Optional[dict] = None):
     """NeuralGraphMap._extract_mesh (rm.py:2186-2384): bounding box of the field centres +- 2 r, grid of spacing
     `resolution` (default: the training sample spacing, rm.py:199-207), blocks of `block`^3 cells evaluated with the
     kNN-blended fields, marching cubes per block, vertex colours from a second evaluation with radius + 0.1
     (rm.py:2320-2340), one PLY + `<stem>_fields.txt`.  Returns (verts (V,3) world, faces (T,3), colours (V,3) in
     [0,255] as the reference stores them) or None when no block crosses the iso-surface.
+    fused (default): a block's volume comes from ONE call (ops.grid_eval_knn: the lattice's points are formed inside the
+    kernels, the geometry channel is blended -- and negated -- straight into the volume), and blocks no field can reach
+    (reachable_blocks, one device computation and one transfer before the loop) launch nothing: their volume is constant,
+    no grid edge is crossed.  fused=False: the staged path (cartesian_prod -> field_eval_knn in `block_size` chunks -> slice,
+    reshape, negate) over every block.  The mesh is bit for bit the same either way.  With `debug` nothing is skipped.
+    stats: filled with blocks_total / blocks_skipped / blocks_evaluated / blocks_with_surface.
     Vertex and face ORDER are this build's (oracle/mesh_oracle.py), not pytorch3d's: compare meshes as surfaces."""
     m = renderer._model
     dev = renderer._device
@@ -193,28 +225,59 @@ def extract_mesh(renderer, mesh_file_path=None, resolution: Optional[float] = No
                                    m._outside_value, fidx, mask_radius) for s in range(0, pts.shape[0], big)]
         return torch.cat(outs) if len(outs) > 1 else outs[0]
 
-    all_v, all_f, all_c, offset = [], [], [], 0
-    starts = [range(0, len(a) - 1, block) for a in axes]               # blocks overlap by one grid plane (rm.py:2236-2240)
-    for xs, ys, zs in itertools.product(*starts):
-        bx, by, bz = axes[0][xs:xs + block + 1], axes[1][ys:ys + block + 1], axes[2][zs:zs + block + 1]
-        xyz = torch.cartesian_prod(bx, by, bz)
-        vol = evaluate(xyz)[:, 3].reshape(len(bx), len(by), len(bz))
+    def volume_fused(bx, by, bz):
+        """the block's volume from one call, None where the block is too large for it (P K >= 2^31: the staged path takes it)"""
+        try:
+            vol = ops.grid_eval_knn(renderer._fc, params, bx, by, bz, pos, quat, m._num_knn, m._distance_factor,
+                                    m._outside_value, fidx, None, 3, low_is_inside and mode != K.GEO["occupancy"])
+        except K.NgmError as e:
+            if e.code != K.NGM_E_UNSUPPORTED:
+                raise
+            return None
         if mode == K.GEO["occupancy"]:
             vol = torch.sigmoid(gfac * vol)
-        if low_is_inside:
-            vol = -vol
+            if low_is_inside:
+                vol = -vol
+        return vol
+
+    all_v, all_f, all_c, offset = [], [], [], 0
+    starts = [range(0, len(a) - 1, block) for a in axes]               # blocks overlap by one grid plane (rm.py:2236-2240)
+    count = dict(blocks_total=0, blocks_skipped=0, blocks_evaluated=0, blocks_with_surface=0)
+    reach = None
+    if fused and debug is None:
+        # the radius the volume evaluation tests points against is the MODEL's (mask_radius is None there: the kernels take
+        # fc.field_radius), which need not be the map's `r` that pads the box and spaces the grid
+        reach = reachable_blocks(axes, block, pos, float(renderer._fc.field_radius)).cpu()   # the one transfer: (nbx, nby, nbz) bool
+    for xs, ys, zs in itertools.product(*starts):
+        count["blocks_total"] += 1
+        if reach is not None and not bool(reach[xs // block, ys // block, zs // block]):
+            count["blocks_skipped"] += 1                                # constant volume: marching cubes would return nothing
+            continue
+        count["blocks_evaluated"] += 1
+        bx, by, bz = axes[0][xs:xs + block + 1], axes[1][ys:ys + block + 1], axes[2][zs:zs + block + 1]
+        vol = volume_fused(bx, by, bz) if fused else None
+        if vol is None:
+            xyz = torch.cartesian_prod(bx, by, bz)
+            vol = evaluate(xyz)[:, 3].reshape(len(bx), len(by), len(bz))
+            if mode == K.GEO["occupancy"]:
+                vol = torch.sigmoid(gfac * vol)
+            if low_is_inside:
+                vol = -vol
         v, f = marching_cubes(vol.contiguous(), isolevel)
         if debug is not None:      # tests: what was handed to marching cubes and what came back, per block (fixture G17)
             debug.setdefault("blocks", []).append(dict(axes=(bx, by, bz), volume=vol, isolevel=isolevel, verts_grid=v, faces=f))
             debug["color_fn"] = lambda pts: torch.clamp(cfac * evaluate(pts, color_radius)[:, :3], 0, 1) * 255
         if len(v) == 0:
             continue
+        count["blocks_with_surface"] += 1
         vw = grid_to_world(v, bx, by, bz)
         col = torch.clamp(cfac * evaluate(vw, color_radius)[:, :3], 0, 1) * 255
         all_v.append(vw)
         all_f.append(f + offset)
         all_c.append(col)
         offset += len(vw)
+    if stats is not None:
+        stats.update(count)
     if not all_v:
         return None
     verts, faces, cols = torch.cat(all_v), torch.cat(all_f), torch.cat(all_c)

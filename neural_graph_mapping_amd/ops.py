@@ -379,6 +379,50 @@ def field_eval_knn(fc, params, points, pos, quat, num_knn=2, distance_factor=10.
                                            float(mask_radius) if mask_radius else 0.0)
 
 
+@_op("grid_eval_knn")
+def _grid_eval_knn_op(fcfg: torch.Tensor, xs: torch.Tensor, ys: torch.Tensor, zs: torch.Tensor, pos: torch.Tensor,
+                      quat: torch.Tensor, params: List[torch.Tensor], num_knn: int, distance_factor: float,
+                      outside_value: float, field_index: Optional[torch.Tensor], mask_radius: float, channel: int,
+                      negate: bool) -> torch.Tensor:
+    fc = _field_cfg(fcfg)
+    nx, ny, nz, NF = xs.shape[0], ys.shape[0], zs.shape[0], pos.shape[0]
+    L = K.lib()
+    wsb = L.ngm_grid_eval_knn_workspace(NF, nx, ny, nz, num_knn)
+    if wsb < 0:                # the shape is refused before anything is allocated (NGM_E_UNSUPPORTED: nx ny nz K >= 2^31)
+        K.check(int(wsb), "ngm_grid_eval_knn_workspace")
+    vol = torch.empty(nx, ny, nz, device=xs.device, dtype=torch.float32)
+    ps = params_struct(fc, dict(zip(K.param_names(fc), params)), field_index)
+    ws = torch.empty(wsb, device=xs.device, dtype=torch.uint8)
+    K.check(L.ngm_grid_eval_knn(C.byref(fc), C.byref(ps), NF, _ptr(_f32c(pos)), _ptr(_f32c(quat)), _ptr(xs), nx, _ptr(ys), ny,
+                                _ptr(zs), nz, num_knn, distance_factor, outside_value, mask_radius, channel, int(negate),
+                                _ptr(vol), _ptr(ws), wsb, _stream()), "ngm_grid_eval_knn")
+    return vol
+
+
+@_grid_eval_knn_op.register_fake
+def _(fcfg, xs, ys, zs, pos, quat, params, num_knn, distance_factor, outside_value, field_index, mask_radius, channel, negate):
+    return xs.new_empty(xs.shape[0], ys.shape[0], zs.shape[0])
+
+
+def grid_eval_knn(fc, params, xs, ys, zs, pos, quat, num_knn=2, distance_factor=10.0, outside_value=1.0,
+                  field_index=None, mask_radius=None, channel=3, negate=False):
+    """One channel of the kNN-blended fields on the lattice xs x ys x zs (three 1-D fp32 device axes, uniform or not) as a
+    (nx, ny, nz) volume: field_eval_knn(torch.cartesian_prod(xs, ys, zs))[:, channel].reshape(nx, ny, nz), negated when
+    `negate`, bit for bit, in one call that keeps neither the points nor the (P, 4) output in memory (one block of
+    _extract_mesh's grid, rm.py:2236-2261).  Raises NgmError with code NGM_E_UNSUPPORTED when nx ny nz K >= 2^31.
+    Dispatches through torch.ops.ngm355.grid_eval_knn."""
+    plist = [params[n] for n in K.param_names(fc)]
+    _require_gpu(xs, ys, zs, pos, quat, *plist)
+    for t, n in ((xs, "xs"), (ys, "ys"), (zs, "zs")):
+        if t.dim() != 1 or t.shape[0] < 1:
+            raise ValueError(f"grid_eval_knn: {n} must be a 1-D axis with at least one coordinate, got {tuple(t.shape)}")
+    if not 0 <= int(channel) <= 3:
+        raise ValueError("grid_eval_knn: channel must be 0..3")
+    return torch.ops.ngm355.grid_eval_knn(cfg_blob(fc), _f32c(xs, "xs"), _f32c(ys, "ys"), _f32c(zs, "zs"), pos, quat, plist,
+                                          int(num_knn), float(distance_factor), float(outside_value), field_index,
+                                          float(mask_radius) if mask_radius else 0.0, int(channel), bool(negate))
+
+
 # ------------------------------------------------------------------------------------------------
 # K1: sampler
 # ------------------------------------------------------------------------------------------------

@@ -413,12 +413,29 @@ class NeuralGraphRenderer:
                                    m._outside_value) for s in range(0, pts.shape[0], block)]
         return torch.cat(outs).reshape(*lead, 4)
 
+    @torch.no_grad()
+    def evaluate_grid(self, xs: torch.Tensor, ys: torch.Tensor, zs: torch.Tensor, channel: int = 3, negate: bool = False,
+                      field_ids: Optional[torch.Tensor] = None, mask_radius: Optional[float] = None) -> torch.Tensor:
+        """The lattice twin of evaluate_points: channel `channel` of the kNN-blended fields on xs x ys x zs as a
+        (nx, ny, nz) volume, in one call (ngm_grid_eval_knn) -- evaluate_points(torch.cartesian_prod(xs, ys, zs))[:, channel]
+        reshaped (and negated when `negate`), bit for bit.  `field_ids`: evaluate these fields only."""
+        num = self._global_map_dict["num"]
+        pos = self._global_map_dict["positions"][:num]
+        quat = self._global_map_dict["orientations"][:num]
+        fidx = None
+        if field_ids is not None:
+            fidx = field_ids.to(self._device).contiguous()
+            pos, quat = pos[fidx].contiguous(), quat[fidx].contiguous()
+        m = self._model
+        return ops.grid_eval_knn(self._fc, m.kernel_params(), xs, ys, zs, pos, quat, m._num_knn, m._distance_factor,
+                                 m._outside_value, fidx, mask_radius, channel, negate)
+
     def extract_mesh(self, mesh_file_path=None, resolution: Optional[float] = None, threshold: Optional[float] = None,
                      transform: Optional[torch.Tensor] = None, field_ids: Optional[torch.Tensor] = None, block: int = 200,
-                     debug: Optional[dict] = None):
+                     debug: Optional[dict] = None, fused: bool = True, stats: Optional[dict] = None):
         """_extract_mesh (rm.py:2186-2384): dense grid -> HIP marching cubes -> vertex colours -> PLY (see mesh.py)."""
         from . import mesh
-        return mesh.extract_mesh(self, mesh_file_path, resolution, threshold, transform, field_ids, block, debug)
+        return mesh.extract_mesh(self, mesh_file_path, resolution, threshold, transform, field_ids, block, debug, fused, stats)
 
     # -- reference-compatible API --------------------------------------------------------------
     def quadrature(self, sample_colors, sample_geometries, sample_distances, sample_depths, neus_isds=None):
