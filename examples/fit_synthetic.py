@@ -1,7 +1,7 @@
 """End-to-end smoke of the drop-in path on one MI355X: keyframe store -> training-target sampler -> fused
 training step (forward, losses, backward, sparse Adam) -> kNN-blended render -> PSNR.
 
-    python examples/fit_synthetic.py [--iters 300] [--device-iteration | --live [--grow]]
+    python examples/fit_synthetic.py [--iters 300] [--device-iteration | --live [--grow] [--loop-closure]]
 
 A synthetic RGB-D "scan" of a textured wall with a sphere in front of it is observed from a few keyframes; fields
 on a grid in front of the cameras are trained exactly as NeuralGraphMap._optimization_iteration would
@@ -13,6 +13,9 @@ to a KeyframeStore while training, the observed fields recomputed per frame on t
 --live --grow also GROWS the map while that one graph keeps replaying: the renderer reserves rows for the whole map
 (reserve_fields), starts with half of it and appends the rest across the keyframes (add_fields(n, positions=, orientations=):
 one launch each, the number of fields read on the device).
+--live --loop-closure anchors every field to a keyframe (anchor_fields) and, once the last keyframe is in, lets the pose graph
+move ALL keyframe poses rigidly: KeyframeStore.set_keyframe_poses + repose_fields re-pose the map on the device, the same
+graph keeps replaying, and the PSNR of keyframe 0 is reported before and right after the closure.
 """
 import argparse
 import math
@@ -61,7 +64,7 @@ def synth_keyframe(c2w):
     return torch.cat([rgb, depth[..., None]], -1)
 
 
-def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0, grow=False):
+def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0, grow=False, loop_closure=False):
     """loop: "torch" -- sample_target_mv (torch draws) -> optimization_iteration, the reference's loop;
     "device" -- capture_training: one graph replay per iteration;
     "materialize" -- the same device-drawn targets and jitter stream as "device" (sampler seed 0, iteration i; jitter
@@ -70,11 +73,13 @@ def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0, g
     "live" -- capture_training once over fixed-capacity buffers (KeyframeStore, observed_fields_device(out=...)): the
     current frame changes every 5 iterations, each camera's first visit adds a keyframe, the graph is never re-captured.
     grow (with "live"): rows are reserved for the whole map, half of it is there at the capture, every keyframe appends a
-    share of the rest in place."""
+    share of the rest in place.
+    loop_closure (with "live"): the fields are anchored to the keyframes; after the last keyframe all keyframe poses are
+    perturbed rigidly and the map is re-posed on the device between two replays of the one graph."""
     if loop not in ("torch", "device", "materialize", "live"):
         raise ValueError(loop)
-    if grow and loop != "live":
-        raise ValueError("grow goes with the live loop")
+    if (grow or loop_closure) and loop != "live":
+        raise ValueError("grow and loop_closure go with the live loop")
     torch.manual_seed(0)
     dev = torch.device(device)
     cam = Rr.Camera(W, H, FOC, FOC, (W - 1) / 2, (H - 1) / 2, pixel_center=0.0)
@@ -109,7 +114,18 @@ def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0, g
     cid = torch.arange(len(eyes), device=dev)
     cur = torch.arange(NF, device=dev)
 
-    losses = []
+    def evaluate():
+        """keyframe 0 re-rendered from its pose in force: (PSNR, median |depth error|, share of pixels compared)"""
+        r.eval()                                                    # as rm.py:1978 before an evaluation render
+        rgbd, _ = r.render_image(c2ws[0], camera=cam)
+        r.train()
+        ref = store[0]
+        valid = torch.isfinite(ref[..., 3]) & (rgbd[..., 3] > 0.1)  # pixels whose ray meets a trained field
+        mse = ((rgbd[..., :3].clamp(0, 1) - ref[..., :3]) ** 2)[valid].mean()
+        return (float(10 * torch.log10(1.0 / mse)), float((rgbd[..., 3] - ref[..., 3]).abs()[valid].median()),
+                float(valid.float().mean()))
+
+    losses, closure = [], None
     step = r.capture_training(cur, c2ws, store, cid, 32, 256, seed=jitter_seed, camera=cam) if loop == "device" else None
     if loop == "live":
         from neural_graph_mapping_amd.keyframes import KeyframeStore
@@ -119,7 +135,18 @@ def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0, g
         r.track_training_iterations = True
 
         def next_frame(f):
+            nonlocal c2ws, closure
             k = f % len(eyes)
+            if loop_closure and f == len(eyes):                     # every keyframe is in: the pose graph closes a loop
+                before = evaluate()[0]
+                r.anchor_fields(ks, [i % len(eyes) for i in range(NF)])        # keyframe f has frame id f
+                a = 0.05
+                D = torch.tensor([[math.cos(a), 0.0, math.sin(a), 0.08], [0.0, 1.0, 0.0, -0.05],
+                                  [-math.sin(a), 0.0, math.cos(a), 0.04], [0.0, 0.0, 0.0, 1.0]], device=dev)
+                c2ws = D @ c2ws                                     # all poses move rigidly, keyframes and later frames alike
+                ks.set_keyframe_poses(c2ws[ks.frame_ids])
+                r.repose_fields(ks)                                 # one launch; the graph reads the poses in place
+                closure = (before, evaluate()[0])
             ks.set_current(store[k], c2ws[k], frame_id=f)
             if f < len(eyes):
                 ks.add_keyframe(store[k], f)                        # a camera's first visit becomes a keyframe
@@ -150,20 +177,16 @@ def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0, g
             if not quiet:
                 print(f"iter {it:4d}  loss {losses[-1]:.4f}  (photo {float(out['photometric_l1']):.4f} depth {float(out['depth_huber']):.4f} "
                       f"fs {float(out['freespace']):.4f} tsdf {float(out['tsdf']):.4f})")
-    r.eval()                                                        # as rm.py:1978 before an evaluation render
-    rgbd, _ = r.render_image(c2ws[0], camera=cam)
-    r.train()
-    ref = store[0]
-    valid = torch.isfinite(ref[..., 3]) & (rgbd[..., 3] > 0.1)      # pixels whose ray meets a trained field
-    mse = ((rgbd[..., :3].clamp(0, 1) - ref[..., :3]) ** 2)[valid].mean()
-    psnr = float(10 * torch.log10(1.0 / mse))
-    derr = float((rgbd[..., 3] - ref[..., 3]).abs()[valid].median())
+    psnr, derr, share = evaluate()
     if not quiet:
         print(f"keyframe 0 re-rendered: PSNR {psnr:.2f} dB, median |depth error| {derr:.3f} m over "
-              f"{100 * float(valid.float().mean()):.0f} % of the pixels ({NF} fields)")
+              f"{100 * share:.0f} % of the pixels ({NF} fields)")
         if loop == "live":
             print(f"{ks.num_keyframes} keyframes, {int(cnt_buf)} fields observed by the last frame, "
                   f"{int(r.get_field_ids(50).numel())} fields trained in at least 50 iterations")
+            if closure is not None:
+                print(f"loop closure after the last keyframe: PSNR {closure[0]:.2f} dB before, {closure[1]:.2f} dB right after "
+                      "the re-pose, under the same graph")
             if grow:
                 print(f"the map grew from {n0} to {r._global_map_dict['num']} fields under that one graph")
     return losses, psnr, derr
@@ -178,5 +201,7 @@ if __name__ == "__main__":
                     help="one captured graph across changing frames and keyframes (KeyframeStore + observed_fields_device)")
     ap.add_argument("--grow", action="store_true",
                     help="with --live: reserve rows for the whole map, start with half of it, append the rest across keyframes")
+    ap.add_argument("--loop-closure", action="store_true",
+                    help="with --live: anchor the fields to keyframes, move all keyframe poses rigidly after the last keyframe, re-pose")
     a = ap.parse_args()
-    main(a.iters, loop="live" if a.live else "device" if a.device_iteration else "torch", grow=a.grow)
+    main(a.iters, loop="live" if a.live else "device" if a.device_iteration else "torch", grow=a.grow, loop_closure=a.loop_closure)

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define NGM_ABI_VERSION 11 /* 11 (+ addition, number unchanged: ngm_target_sample_mv_live(_workspace) / struct ngm_target_live, ngm_target_observed_fields(_workspace) / struct ngm_observed_fields, ngm_field_counts_add: the sampler with its counts in device memory, the observed-field test and the per-field iteration counts on the device; nothing existing changed); 11 (+ addition, number unchanged: ngm_render_fwd_counted / ngm_render_bwd_counted / ngm_render_bwd_adam_counted, the training step launched at a capacity with the number of active rows in device memory; nothing existing changed); 11 (+ addition, number unchanged: ngm_target_sample_mv_workspace / ngm_target_sample_mv and struct ngm_target_sample, the device-side training-target sampler; nothing existing changed); 11: ngm_field_eval_stash_bytes / ngm_field_eval_fwd_train / ngm_field_eval_bwd_stash (training forward of the point evaluation writes the activation stash, its backward is the fused step's kernel); 10: ngm_field_cfg.activation_stash / .hash_grad_atomics (per configuration, no process-wide switch), empty loss selections report NaN like the reference; 9: ngm_sample_rays_weighted; 8: ngm_peer_set_timeout (a time-out now also poisons the sums with NaN); 7: ngm_encode_bwd; 6: ngm_render_eval_knn; 5: ngm_encode_fwd, ngm_render_bwd_seeded_vars, *_nll loss modes (+ loss-sum slot 10), peer status bits; 11 (+ addition, number unchanged: ngm_grid_eval_knn(_workspace), the kNN evaluation on a lattice given by its axes -- one block of the mesh grid as one call; nothing existing changed) */
+#define NGM_ABI_VERSION 11 /* 11 (+ addition, number unchanged: ngm_fields_repose / struct ngm_fields_repose_args, the map re-posed in place after a pose-graph update; nothing existing changed); 11 (+ addition, number unchanged: ngm_target_sample_mv_live(_workspace) / struct ngm_target_live, ngm_target_observed_fields(_workspace) / struct ngm_observed_fields, ngm_field_counts_add: the sampler with its counts in device memory, the observed-field test and the per-field iteration counts on the device; nothing existing changed); 11 (+ addition, number unchanged: ngm_render_fwd_counted / ngm_render_bwd_counted / ngm_render_bwd_adam_counted, the training step launched at a capacity with the number of active rows in device memory; nothing existing changed); 11 (+ addition, number unchanged: ngm_target_sample_mv_workspace / ngm_target_sample_mv and struct ngm_target_sample, the device-side training-target sampler; nothing existing changed); 11: ngm_field_eval_stash_bytes / ngm_field_eval_fwd_train / ngm_field_eval_bwd_stash (training forward of the point evaluation writes the activation stash, its backward is the fused step's kernel); 10: ngm_field_cfg.activation_stash / .hash_grad_atomics (per configuration, no process-wide switch), empty loss selections report NaN like the reference; 9: ngm_sample_rays_weighted; 8: ngm_peer_set_timeout (a time-out now also poisons the sums with NaN); 7: ngm_encode_bwd; 6: ngm_render_eval_knn; 5: ngm_encode_fwd, ngm_render_bwd_seeded_vars, *_nll loss modes (+ loss-sum slot 10), peer status bits; 11 (+ addition, number unchanged: ngm_grid_eval_knn(_workspace), the kNN evaluation on a lattice given by its axes -- one block of the mesh grid as one call; nothing existing changed) */
 /* Array bound of the per-layer pointers below (hidden layers; +1 output layer).  NOT the depth every entry point takes -- the
  * kernels are compiled per depth L = num_layers and padded width class (dim_enc and dim_hidden both <= 32, or both 33..64):
  *   L = 1, 2   every entry point, both width classes (forward, backward, fused step, kNN evaluation)
@@ -712,6 +712,43 @@ int ngm_target_sample_mv_grow(const ngm_keyframes* kf, const ngm_target_sample* 
 int64_t ngm_target_observed_fields_grow_workspace(int32_t height, int32_t width);
 int ngm_target_observed_fields_grow(const ngm_observed_fields* a, const int32_t* num_fields_dev, void* workspace,
                                     int64_t workspace_bytes, void* stream);
+
+/* ---- fields anchored to keyframes: re-pose the map after a pose-graph update (opt-in; additive to ABI 11) ---------------
+ * NeuralGraphMap._update_field_poses (rm.py:937-952): every field belongs to a keyframe (map_dict["kf_ids"]) and moves with
+ * it.  anchor_slot[f] is the row of the two pose tables that field f follows; prev_poses holds the keyframe poses at the
+ * last re-pose, new_poses the poses in force.  Per field f with anchor a, in fp32, the reference's two steps in its order
+ * (rm.py:864-885, then :844-862; utils.transform_points / transform_quaternions, utils.py:270-286):
+ *   W = inverse(prev[a])       affine, last row (0,0,0,1): 3x3 inverse by adjugate and determinant, no orthonormality assumed
+ *   p_rel = W.R p + W.t        q_rel = quat(W.R) (x) q
+ *   p'    = new[a].R p_rel + new[a].t        q' = quat(new[a].R) (x) q_rel
+ * quat = pytorch3d's matrix_to_quaternion (the best-conditioned of its four candidates, so a rotation by pi is accurate;
+ * real part >= 0), (x) = the raw Hamilton product: no standardisation, no normalisation -- a quaternion's norm scales the
+ * field's frame here and is carried through unchanged up to rounding.
+ * Deliberately stricter than the reference, which sends every field through inverse x forward at every update:
+ *   - a field whose anchor's prev and new rows are BITWISE EQUAL is not touched: not one bit of its pose changes;
+ *   - a field with anchor -1 (unanchored), an anchor outside [0, num_poses), or a non-finite entry in either row of its
+ *     anchor is not touched (a lost pose must not poison the map); nor is a field whose result would be non-finite
+ *     (a singular prev row);
+ *   - rows at or beyond the field count in force are not touched: the count is num_fields, or with num_fields_dev
+ *     clamp(*num_fields_dev, 0, num_fields), as in the *_grow entry points.
+ * advance_prev != 0: prev_poses := new_poses after the re-pose, stream-ordered inside the same call (a second small launch:
+ * the first still reads prev); rows of new_poses with a non-finite entry are not copied, so prev keeps the pose the fields
+ * of that row still stand at.  One thread per field, the tables are read through the cache; no atomics, no host
+ * synchronisation; the result is bitwise deterministic (every rank of a field-sharded run computes the same map with no
+ * exchange).  NULL pointers and negative sizes give NGM_E_INVALID before anything is launched. */
+typedef struct ngm_fields_repose_args {
+  float* positions;                 /* (max_fields, 3), updated in place                                          */
+  float* orientations;              /* (max_fields, 4) real-first quaternions, updated in place                   */
+  const int32_t* anchor_slot;       /* (max_fields): row of the pose tables, -1 = unanchored                      */
+  float* prev_poses;                /* DEVICE (num_poses, 4, 4) row-major: poses at the last re-pose              */
+  const float* new_poses;           /* DEVICE (num_poses, 4, 4) row-major: poses in force                         */
+  const int32_t* num_fields_dev;    /* device (1) or NULL                                                         */
+  int32_t num_fields;               /* rows processed (the capacity max_fields when num_fields_dev is given)      */
+  int32_t num_poses;
+  int32_t advance_prev;
+  int32_t reserved0;
+} ngm_fields_repose_args;
+int ngm_fields_repose(const ngm_fields_repose_args* a, void* stream);
 
 /* Device part of NeuralGraphMap._sample_target_sv (rm.py:1461-1583), the single-view variant (`update_mode: single_view`):
  * hit (F,N) u8 = the segment camera origin -> point n of the (subsampled) back-projected depth image passes through the

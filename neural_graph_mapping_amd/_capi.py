@@ -190,6 +190,12 @@ class FieldsAppendArgs(C.Structure):
                 ("orientations", f32p), ("training_iterations", C.c_void_p), ("num_fields_dev", C.c_void_p)]
 
 
+class FieldsReposeArgs(C.Structure):
+    _fields_ = [("positions", f32p), ("orientations", f32p), ("anchor_slot", C.c_void_p), ("prev_poses", f32p),
+                ("new_poses", f32p), ("num_fields_dev", C.c_void_p), ("num_fields", C.c_int32), ("num_poses", C.c_int32),
+                ("advance_prev", C.c_int32), ("reserved0", C.c_int32)]
+
+
 def target_sample_mv_grow_plan(max_current, max_fields, num_train_fields, num_rays, world_size=1, rank=0):
     """Host-side sizes of ngm_target_sample_mv_grow: target_sample_mv_live_plan at the capacity max_fields -- (max_observed,
     max_random, capacity) = (min(T // 2, max_current), min(T, max_fields), min(min(T, max_fields), fields of this rank among
@@ -323,6 +329,8 @@ def lib():
     L.ngm_field_counts_add.restype = C.c_int
     L.ngm_fields_append.argtypes = [P(FieldsAppendArgs), vp]
     L.ngm_fields_append.restype = C.c_int
+    L.ngm_fields_repose.argtypes = [P(FieldsReposeArgs), vp]
+    L.ngm_fields_repose.restype = C.c_int
     L.ngm_target_sample_mv_grow_workspace.argtypes = [i32, i32, i32, i32]
     L.ngm_target_sample_mv_grow_workspace.restype = i64
     L.ngm_target_sample_mv_grow.argtypes = [P(Keyframes), P(TargetSample), P(TargetLive), vp, P(TargetOut), vp, i64, vp]
@@ -365,7 +373,7 @@ EXPORTED = ["ngm_abi_version", "ngm_last_error", "ngm_device_info", "ngm_permuto
             "ngm_target_sample_mv_workspace", "ngm_target_sample_mv",
             "ngm_target_sample_mv_live_workspace", "ngm_target_sample_mv_live", "ngm_target_observed_fields_workspace",
             "ngm_target_observed_fields", "ngm_field_counts_add",
-            "ngm_fields_append", "ngm_target_sample_mv_grow_workspace", "ngm_target_sample_mv_grow",
+            "ngm_fields_append", "ngm_fields_repose", "ngm_target_sample_mv_grow_workspace", "ngm_target_sample_mv_grow",
             "ngm_target_observed_fields_grow_workspace", "ngm_target_observed_fields_grow",
             "ngm_render_fwd_counted", "ngm_render_bwd_counted", "ngm_render_bwd_adam_counted",
             "ngm_peer_mailbox_bytes", "ngm_peer_alloc", "ngm_peer_free", "ngm_ipc_export", "ngm_ipc_open", "ngm_ipc_close", "ngm_loss_exchange", "ngm_peer_set_timeout",

@@ -608,6 +608,17 @@ int ngm_fields_append(const ngm_fields_append_args* a, void* stream) {
   return check_launch("ngm_fields_append");
 }
 
+int ngm_fields_repose(const ngm_fields_repose_args* a, void* stream) {
+  if (!a) return fail(NGM_E_INVALID, "ngm_fields_repose: NULL argument");
+  if (a->num_fields < 0 || a->num_poses < 0) return fail(NGM_E_INVALID, "ngm_fields_repose: num_fields and num_poses must be >= 0");
+  if ((a->num_fields > 0 && (!a->positions || !a->orientations || !a->anchor_slot)) ||
+      (a->num_poses > 0 && (!a->prev_poses || !a->new_poses)))
+    return fail(NGM_E_INVALID, "ngm_fields_repose: NULL array");
+  if (a->num_poses == 0) return NGM_OK;                  // no pose table: every anchor is out of range, nothing moves
+  ngm_launch_fields_repose(*a, (hipStream_t)stream);
+  return check_launch("ngm_fields_repose");
+}
+
 int ngm_field_counts_add(const int64_t* field_ids, const int32_t* count, int32_t rows, int64_t* training_iterations, int32_t num_fields,
                          void* stream) {
   if (rows < 0 || num_fields < 0 || (rows > 0 && (!field_ids || !training_iterations)))

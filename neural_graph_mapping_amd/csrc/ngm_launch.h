@@ -286,6 +286,7 @@ int64_t ngm_target_observed_fields_bytes(int height, int width);
 int ngm_launch_target_observed_fields(const ngm_observed_fields& a, void* workspace, hipStream_t st,
                                       const int32_t* num_fields_dev = nullptr);
 int ngm_launch_fields_append(const ngm_fields_append_args& a, hipStream_t st);
+int ngm_launch_fields_repose(const ngm_fields_repose_args& a, hipStream_t st);
 int ngm_launch_field_counts_add(const int64_t* field_ids, const int32_t* count, int rows, int num_fields, int64_t* training_iterations,
                                 hipStream_t st);
 

@@ -1471,3 +1471,45 @@ def fields_append(tensors, new_positions, new_orientations, positions, orientati
         return
     torch.ops.ngm355.fields_append(params, ms, vs, lps, lp_index, protos, new_positions, new_orientations, positions, orientations,
                                    training_iterations, num_fields_dev, first)
+
+
+# ------------------------------------------------------------------------------------------------
+# fields anchored to keyframes: the map re-posed in place after a pose-graph update (include/ngm_hip.h ngm_fields_repose)
+# ------------------------------------------------------------------------------------------------
+@_op("fields_repose_", mutates_args=("positions", "orientations", "prev_poses"))
+def _fields_repose_op(positions: torch.Tensor, orientations: torch.Tensor, anchor_slot: torch.Tensor, prev_poses: torch.Tensor,
+                      new_poses: torch.Tensor, num_fields_dev: Optional[torch.Tensor], num_fields: int, advance_prev: bool) -> None:
+    a = K.FieldsReposeArgs(C.cast(positions.data_ptr(), K.f32p), C.cast(orientations.data_ptr(), K.f32p), anchor_slot.data_ptr(),
+                           C.cast(prev_poses.data_ptr(), K.f32p), C.cast(new_poses.data_ptr(), K.f32p), _ptr(num_fields_dev),
+                           int(num_fields), int(new_poses.shape[0]), int(bool(advance_prev)), 0)
+    K.check(K.lib().ngm_fields_repose(C.byref(a), _stream()), "ngm_fields_repose")
+
+
+def fields_repose_(positions, orientations, anchor_slot, prev_poses, new_poses, num_fields_dev=None, num_fields=None,
+                   advance_prev=True):
+    """Move every field with the keyframe it is anchored to, in place (torch.ops.ngm355.fields_repose_, ngm_fields_repose): on
+    the current stream, no host synchronisation.  positions (n, 3), orientations (n, 4) float32; anchor_slot (n,) int32, row
+    of the pose tables or -1; prev_poses / new_poses (num_poses, 4, 4) float32.  The first num_fields rows are processed (all
+    n by default), or clamp(num_fields_dev, 0, num_fields) with the one-element int32 device tensor.  advance_prev: prev_poses
+    := new_poses afterwards.  Fields whose anchor did not move (bitwise), is -1 / out of range, or has a non-finite pose are
+    not touched."""
+    def need(cond, msg, exc=ValueError):
+        if not cond:
+            raise exc("fields_repose_: " + msg)
+    for name, t, tail in (("positions", positions, (3,)), ("orientations", orientations, (4,)), ("prev_poses", prev_poses, (4, 4)),
+                          ("new_poses", new_poses, (4, 4))):
+        need(isinstance(t, torch.Tensor) and t.dtype == torch.float32, f"{name} must be a float32 tensor", TypeError)
+        need(t.dim() == 1 + len(tail) and tuple(t.shape[1:]) == tail and t.is_contiguous(),
+             f"{name} must be a contiguous (n, {', '.join(map(str, tail))}) tensor, got {tuple(t.shape)}")
+    need(isinstance(anchor_slot, torch.Tensor) and anchor_slot.dtype == torch.int32, "anchor_slot must be an int32 tensor", TypeError)
+    n = positions.shape[0]
+    need(orientations.shape[0] == n and tuple(anchor_slot.shape) == (n,) and anchor_slot.is_contiguous(),
+         f"positions has {n} rows, orientations {orientations.shape[0]}, anchor_slot {tuple(anchor_slot.shape)}")
+    need(prev_poses.shape == new_poses.shape, f"prev_poses {tuple(prev_poses.shape)} and new_poses {tuple(new_poses.shape)} differ")
+    num_fields = n if num_fields is None else int(num_fields)
+    need(0 <= num_fields <= n, f"num_fields {num_fields} outside [0, {n}]")
+    if num_fields_dev is not None:
+        _check_device_count("fields_repose_", "num_fields_dev", num_fields_dev)
+    _require_gpu(positions, orientations, anchor_slot, prev_poses, new_poses, num_fields_dev)
+    torch.ops.ngm355.fields_repose_(positions, orientations, anchor_slot, prev_poses, new_poses, num_fields_dev, num_fields,
+                                    bool(advance_prev))

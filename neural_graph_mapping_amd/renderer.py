@@ -209,6 +209,9 @@ class NeuralGraphRenderer:
         # (max, 4), training_iterations (max,), num_fields_dev int32 (1,)); None = not reserved
         self._reserved: Optional[dict] = None
         self._reserve_epoch = 0
+        # anchor_fields: dict(kf_ids int64, slot int32), one row per field (max_fields rows after reserve_fields); None = the
+        # fields belong to no keyframe
+        self._anchor: Optional[dict] = None
 
     def last_matmul(self, kernel: str = "forward") -> Optional[str]:
         """The arithmetic the library resolved `mlp_matmul` to in the LAST launch of the fused forward ("forward"), the
@@ -236,6 +239,7 @@ class NeuralGraphRenderer:
         self._global_map_dict = {"positions": positions, "orientations": orientations, "num": positions.shape[0]}
         if old is not None and "training_iterations" in old:            # the counts belong to the fields, not to their poses
             self._global_map_dict["training_iterations"] = old["training_iterations"]
+        self._publish_kf_ids()
 
     def _training_iterations(self) -> torch.Tensor:
         """_global_map_dict["training_iterations"] (int64, one per field; rm.py:1188), created on first use and extended
@@ -305,6 +309,8 @@ class NeuralGraphRenderer:
         self._reserve_epoch += 1
         self._reserved = dict(max=max_fields, epoch=self._reserve_epoch, state=state, positions=pos, orientations=quat,
                               training_iterations=ti, num_fields_dev=nfd)
+        if self._anchor is not None:
+            self._anchor = {k: self._anchor_rows(v, max_fields) for k, v in self._anchor.items()}
         self._set_num(num)
 
     def _set_num(self, num: int) -> None:
@@ -313,6 +319,7 @@ class NeuralGraphRenderer:
         self._optim_state = {k: {n: t[:num] for n, t in st.items()} for k, st in rs["state"].items()}
         self._global_map_dict = {"positions": rs["positions"][:num], "orientations": rs["orientations"][:num], "num": num,
                                  "training_iterations": rs["training_iterations"]}
+        self._publish_kf_ids()
 
     def _append_reserved(self, num_new: int, positions, orientations) -> None:
         rs, m = self._reserved, self._model
@@ -370,12 +377,103 @@ class NeuralGraphRenderer:
                 s[:-num_new] = self._optim_state[k]["exp_avg_sq"]
             new_state[k] = {"exp_avg": m, "exp_avg_sq": s}
         self._optim_state = new_state
+        if self._anchor is not None:                        # the new fields belong to no keyframe yet
+            self._anchor = {k: self._anchor_rows(v, v.shape[0] + num_new) for k, v in self._anchor.items()}
+            self._publish_kf_ids()
+
+    # -- fields anchored to keyframes (rm.py:844-952) ---------------------------------------------
+    @staticmethod
+    def _anchor_rows(t: torch.Tensor, rows: int) -> torch.Tensor:
+        """t extended to `rows` rows, the new ones unanchored (-1)"""
+        out = torch.full((rows,), -1, dtype=t.dtype, device=t.device)
+        out[:t.shape[0]] = t
+        return out
+
+    def _publish_kf_ids(self) -> None:
+        """_global_map_dict["kf_ids"] (the reference's name): the anchors of the fields the dict describes, a view"""
+        if self._anchor is not None and self._global_map_dict is not None:
+            self._global_map_dict["kf_ids"] = self._anchor["kf_ids"][:self._global_map_dict["num"]]
+
+    def anchor_fields(self, store, frame_ids, field_ids=None) -> None:
+        """Attach fields to keyframes of `store` (a KeyframeStore): map_dict["kf_ids"] of the reference.  frame_ids: the frame
+        id of the keyframe each given field belongs to, one per entry of field_ids (None: all fields, in order).  Sets
+        _global_map_dict["kf_ids"] (int64) and the device table anchor_slot (int32: the keyframe's slot in the store, the
+        row of its pose tables), which repose_fields reads.  After reserve_fields both have max_fields rows, allocated at the
+        first call and written in place from then on; rows past `num` are unanchored (-1), and add_fields leaves new fields
+        unanchored until they are given here.  A captured training graph reads neither."""
+        md = self._global_map_dict
+        if md is None:
+            raise RuntimeError("anchor_fields: no fields yet (set_field_poses / reserve_fields first)")
+        num, dev = md["num"], md["positions"].device
+        fids = torch.arange(num) if field_ids is None else torch.as_tensor(field_ids, dtype=torch.int64).reshape(-1).cpu()
+        kfs = torch.as_tensor(frame_ids, dtype=torch.int64).reshape(-1).cpu()
+        if kfs.shape[0] != fids.shape[0]:
+            raise ValueError(f"anchor_fields: {kfs.shape[0]} frame ids for {fids.shape[0]} fields")
+        if fids.numel() and (int(fids.min()) < 0 or int(fids.max()) >= num):
+            raise ValueError(f"anchor_fields: field ids must lie in [0, {num})")
+        slot_of = {f: store.slot_of(f) for f in set(kfs.tolist())}          # ValueError for a frame that is no keyframe
+        slots = torch.tensor([slot_of[f] for f in kfs.tolist()], dtype=torch.int32)
+        if self._anchor is None:
+            rows = num if self._reserved is None else self._reserved["max"]
+            self._anchor = dict(kf_ids=torch.full((rows,), -1, dtype=torch.int64, device=dev),
+                                slot=torch.full((rows,), -1, dtype=torch.int32, device=dev))
+        elif self._anchor["kf_ids"].shape[0] < num:
+            raise RuntimeError("anchor_fields: the anchors have fewer rows than the map (fields added behind the renderer's back)")
+        idx = fids.to(dev)
+        self._anchor["kf_ids"].index_copy_(0, idx, kfs.to(dev))
+        self._anchor["slot"].index_copy_(0, idx, slots.to(dev))
+        self._publish_kf_ids()
+
+    def remove_keyframe(self, store, frame_id) -> None:
+        """The SLAM front end culled keyframes (rm.py:907-929): every field anchored to a removed keyframe is rewired by the
+        reference's rule -- to the next later keyframe that existed before this update, else to the closest earlier one
+        (rm.py:918-921) -- by an in-place device write without synchronisation, then store.remove_keyframe runs.  Positions
+        and orientations are not transformed (rm.py:928-929: the map holds absolute poses); the next repose_fields moves
+        the rewired fields with their NEW keyframe.  frame_id: one frame id, or all the frame ids one update removes.  Call it
+        before the update's own new keyframe is added to the store: every keyframe of the store counts as having existed."""
+        removed = [int(f) for f in frame_id] if isinstance(frame_id, (list, tuple, set)) else [int(frame_id)]
+        known = set(store.frame_ids)
+        for f in removed:
+            if f not in known:
+                raise ValueError(f"remove_keyframe: frame {f} is not a keyframe of the store")
+        new_kfs = known - set(removed)
+        if not new_kfs:
+            raise ValueError("remove_keyframe: no keyframe would be left to take the fields")
+        for f in removed:
+            kf_after = min((i for i in new_kfs if i >= f), default=None)
+            new_anchor = kf_after if kf_after is not None else max(i for i in new_kfs if f >= i)
+            if self._anchor is not None:
+                kf, sl = self._anchor["kf_ids"], self._anchor["slot"]
+                sl.masked_fill_(kf == f, store.slot_of(new_anchor))
+                kf.masked_fill_(kf == f, new_anchor)
+            store.remove_keyframe(f)
+
+    def repose_fields(self, store) -> None:
+        """NeuralGraphMap._update_field_poses (rm.py:937-952) after store.set_keyframe_poses: every anchored field moves with
+        its keyframe, from the pose at the last re-pose (store.slot_c2w_prev) to the pose in force (store.slot_c2w), in
+        place, as one ngm_fields_repose call on the current stream that also advances slot_c2w_prev -- no host
+        synchronisation.  Fields whose keyframe did not move are not touched, bit for bit; unanchored fields and fields of
+        a keyframe with a non-finite pose stay where they are.  With reserved rows the number of fields is read on the
+        device.  Legal between replays of a capture_training graph: it reads the poses in place, and nothing it watches
+        moves."""
+        if self._anchor is None:
+            raise RuntimeError("repose_fields: the fields belong to no keyframe (anchor_fields first)")
+        rs, md = self._reserved, self._global_map_dict
+        if rs is not None:
+            pos, quat, nfd = rs["positions"], rs["orientations"], rs["num_fields_dev"]
+        else:
+            pos, quat, nfd = md["positions"], md["orientations"], None
+        if self._anchor["slot"].shape[0] != pos.shape[0]:
+            raise RuntimeError(f"repose_fields: {self._anchor['slot'].shape[0]} anchors for {pos.shape[0]} field poses")
+        ops.fields_repose_(pos, quat, self._anchor["slot"], store.slot_c2w_prev, store.slot_c2w, num_fields_dev=nfd,
+                           advance_prev=True)
 
     # -- checkpoint interchange (rm.py:2147-2173) ------------------------------------------------
     def save_model(self, path: str) -> None:
         """torch.save of {map_dict, all_fields_params, state_dict}: the reference's checkpoint layout
-        (optimizer moments are not saved there either).  With a peer exchange the health of every exchange so far is
-        checked first: parameters trained behind a timed-out exchange are not written."""
+        (optimizer moments are not saved there either); map_dict holds "kf_ids" only when anchor_fields set them.  With a
+        peer exchange the health of every exchange so far is checked first: parameters trained behind a timed-out exchange
+        are not written."""
         self.check_exchange()
         md, allp = self._global_map_dict, self._model.all_fields_params
         if self._reserved is not None:
@@ -389,6 +487,7 @@ class NeuralGraphRenderer:
         """Load a checkpoint of the reference's layout.  The tensors are allocated anew at the checkpoint's size, so a map
         with reserved rows LEAVES reserved mode (call reserve_fields again afterwards), and anything captured is stale."""
         self._reserved = self._model._reserved = None
+        self._anchor = None                                 # a checkpoint's map_dict["kf_ids"] stays there: anchor_fields(store, them)
         ck = torch.load(path, map_location=self._device)
         self._model.load_state_dict(ck["state_dict"])
         self._model.all_fields_params = {k: v.to(self._device) for k, v in ck["all_fields_params"].items()}
