@@ -1,7 +1,7 @@
 """End-to-end smoke of the drop-in path on one MI355X: keyframe store -> training-target sampler -> fused
 training step (forward, losses, backward, sparse Adam) -> kNN-blended render -> PSNR.
 
-    python examples/fit_synthetic.py [--iters 300] [--device-iteration | --live [--grow] [--loop-closure]]
+    python examples/fit_synthetic.py [--iters 300] [--device-iteration | --live [--grow] [--loop-closure]] [--mesh-metrics]
 
 A synthetic RGB-D "scan" of a textured wall with a sphere in front of it is observed from a few keyframes; fields
 on a grid in front of the cameras are trained exactly as NeuralGraphMap._optimization_iteration would
@@ -16,6 +16,10 @@ one launch each, the number of fields read on the device).
 --live --loop-closure anchors every field to a keyframe (anchor_fields) and, once the last keyframe is in, lets the pose graph
 move ALL keyframe poses rigidly: KeyframeStore.set_keyframe_poses + repose_fields re-pose the map on the device, the same
 graph keeps replaying, and the PSNR of keyframe 0 is reported before and right after the closure.
+--mesh-metrics also scores the map as a mesh on the device (NeuralGraphRenderer.evaluate_mesh): the mesh extracted from the
+fields around the sphere against the scene's analytic sphere, triangulated here -- the ten numbers of the reference's mesh
+evaluation (accuracy, completion, their ratios at 5 cm and 1 cm, F1).  The cameras see the front of the sphere only, so
+completion counts its unseen back as missing.
 """
 import argparse
 import math
@@ -64,7 +68,19 @@ def synth_keyframe(c2w):
     return torch.cat([rgb, depth[..., None]], -1)
 
 
-def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0, grow=False, loop_closure=False):
+def sphere_mesh(centre, radius, n_lat=48, n_lon=96):
+    """the scene's sphere as a triangle mesh (n_lat bands x n_lon sectors, vertices on the sphere): (verts (V, 3), faces (T, 3))"""
+    th = torch.linspace(0, math.pi, n_lat + 1)
+    ph = torch.arange(n_lon) * (2 * math.pi / n_lon)
+    v = torch.stack([torch.sin(th)[:, None] * torch.cos(ph)[None], torch.sin(th)[:, None] * torch.sin(ph)[None],
+                     torch.cos(th)[:, None].expand(-1, n_lon)], -1).reshape(-1, 3)
+    i, j = torch.arange(n_lat)[:, None] * n_lon, torch.arange(n_lon)[None]
+    a, b = i + j, i + (j + 1) % n_lon
+    f = torch.cat([torch.stack([a, a + n_lon, b], -1).reshape(-1, 3), torch.stack([b, a + n_lon, b + n_lon], -1).reshape(-1, 3)])
+    return radius * v + torch.tensor(centre), f.to(torch.int64)
+
+
+def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0, grow=False, loop_closure=False, mesh_metrics=False):
     """loop: "torch" -- sample_target_mv (torch draws) -> optimization_iteration, the reference's loop;
     "device" -- capture_training: one graph replay per iteration;
     "materialize" -- the same device-drawn targets and jitter stream as "device" (sampler seed 0, iteration i; jitter
@@ -189,6 +205,15 @@ def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0, g
                       "the re-pose, under the same graph")
             if grow:
                 print(f"the map grew from {n0} to {r._global_map_dict['num']} fields under that one graph")
+    if mesh_metrics:
+        gv, gf = sphere_mesh([0.0, 0.0, -2.2], 0.6)
+        around = torch.arange(NF - 18, NF, device=dev)              # the 3 x 3 x 2 fields around the sphere
+        m = r.evaluate_mesh((gv.to(dev), gf.to(dev)), num_points=200000, seed=0, resolution=0.02, field_ids=around)
+        if m is None:
+            print("mesh metrics: the fields around the sphere hold no surface yet")
+        else:
+            print("mesh of the fields around the sphere against the analytic sphere (metres; ratios at 5 cm / 1 cm):")
+            print("  " + "  ".join(f"{k} {v:.4f}" for k, v in m.items()))
     return losses, psnr, derr
 
 
@@ -203,5 +228,8 @@ if __name__ == "__main__":
                     help="with --live: reserve rows for the whole map, start with half of it, append the rest across keyframes")
     ap.add_argument("--loop-closure", action="store_true",
                     help="with --live: anchor the fields to keyframes, move all keyframe poses rigidly after the last keyframe, re-pose")
+    ap.add_argument("--mesh-metrics", action="store_true",
+                    help="score the mesh of the fields around the sphere against the analytic sphere on the device (ten numbers)")
     a = ap.parse_args()
-    main(a.iters, loop="live" if a.live else "device" if a.device_iteration else "torch", grow=a.grow, loop_closure=a.loop_closure)
+    main(a.iters, loop="live" if a.live else "device" if a.device_iteration else "torch", grow=a.grow, loop_closure=a.loop_closure,
+         mesh_metrics=a.mesh_metrics)

@@ -785,6 +785,33 @@ int ngm_marching_cubes_emit(const float* volume, int32_t nx, int32_t ny, int32_t
                             int64_t workspace_bytes, void* stream);
 int ngm_marching_cubes_tables(int8_t* tri_table, int32_t* tri_count);
 
+/* ---- scoring a mesh: surface samples and exact nearest points (additive to ABI 11) --------------------------------------
+ * The device parts of evaluation._evaluate_postprocessed_meshes (evaluation.py:163-208): the two
+ * trimesh.sample.sample_surface calls (evaluation.py:190-191) and the scipy.spatial.KDTree build + query behind every one
+ * of the ten numbers (evaluation.py:75-130).  Culling, ICP alignment and subdivision are the caller's.
+ * ngm_surface_sample: verts (V,3) fp32, faces (F,3) int64 -> points (N,3) fp32, face_ids (N) int64.  trimesh's sampler
+ * restated from its public definition: a face with probability proportional to its area (fp32 area, fp64 inclusive scan,
+ * binary search for the first cum[k] > u * total), then the point v0 + u (v1 - v0) + v (v2 - v0) with (u, v) reflected to
+ * (1 - u, 1 - v) where u + v > 1.  Sample i draws Philox block i of a stream of its own under `seed`: words 0 and 1 form the
+ * 53-bit face draw, words 2 and 3 the 24-bit u and v; the result is a function of (mesh, seed, i) alone.  A face with a
+ * non-finite vertex or an index outside [0, V) has area 0, and a face of area 0 is never returned.  Nothing is read back:
+ * when the total area is not > 0 every point is NaN and every face id -1.
+ * ngm_nearest_point: refs (M,3), queries (N,3) fp32 -> dist (N) fp32, index (N) int64: the EXACT nearest reference of
+ * every query (a uniform grid over the references built per call on the device, searched ring by ring until the best
+ * distance found is provably the smallest), dist = sqrtf(dx*dx + dy*dy + dz*dz) of fp32 differences; equal distances may
+ * go to any of the tied indices.  A non-finite reference is nobody's neighbour; a non-finite query gets dist NaN, index -1;
+ * with no finite reference every dist is +inf and every index -1.  Queries need no order.
+ * Both: the caller owns the workspace (the *_workspace functions: bytes, or NGM_E_INVALID for sizes the calls refuse);
+ * no host synchronisation.  NGM_E_INVALID before anything is launched for a NULL array, a negative count, num_faces == 0,
+ * num_refs == 0, a count >= 2^31 or a workspace that is too small; num_samples == 0 / num_queries == 0 return NGM_OK and
+ * launch nothing (the outputs may be NULL then). */
+int64_t ngm_surface_sample_workspace(int64_t num_faces);
+int ngm_surface_sample(const float* verts, int64_t num_verts, const int64_t* faces, int64_t num_faces, int64_t num_samples,
+                       uint64_t seed, float* points, int64_t* face_ids, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t ngm_nearest_point_workspace(int64_t num_refs, int64_t num_queries);
+int ngm_nearest_point(const float* refs, int64_t num_refs, const float* queries, int64_t num_queries, float* dist,
+                      int64_t* index, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- measurement hooks (bench.py roofline leg) ------------------------------------------------
  * When enabled, every launch of the listed kernels is bracketed by hipEvents recorded on the launch
  * stream; ngm_profile_read() synchronises them and returns the accumulated device time. */

@@ -28,6 +28,12 @@ int ngm_launch_mc_count(const float* vol, int nx, int ny, int nz, float iso, int
 int ngm_launch_mc_emit(const float* vol, int nx, int ny, int nz, float iso, float* verts, int64_t max_verts,
                        int64_t* faces, int64_t max_faces, void* workspace, int64_t workspace_bytes, hipStream_t st);
 int ngm_mc_copy_tables(int8_t* tri_table, int32_t* tri_count);
+int64_t ngm_surface_sample_bytes(int64_t num_faces);
+int ngm_launch_surface_sample(const float* verts, int64_t V, const int64_t* faces, int64_t F, int64_t N, uint64_t seed, float* points,
+                              int64_t* face_ids, void* workspace, hipStream_t st);
+int64_t ngm_nearest_point_bytes(int64_t M, int64_t N);
+int ngm_launch_nearest_point(const float* refs, int64_t M, const float* queries, int64_t N, float* dist, int64_t* index, void* workspace,
+                             hipStream_t st);
 int ngm_launch_knn(const ngm_field_cfg* fc, const ngm_params* pr, int num_fields, int64_t P, const float* points,
                    const float* pos, const float* quat, int K, float distance_factor, float outside_value, float mask_radius,
                    float* out, void* workspace, int64_t workspace_bytes, const FwdPlan& plan, hipStream_t st);
@@ -1510,6 +1516,43 @@ int ngm_marching_cubes_emit(const float* volume, int32_t nx, int32_t ny, int32_t
 int ngm_marching_cubes_tables(int8_t* tri_table, int32_t* tri_count) {
   const int e = ngm_mc_copy_tables(tri_table, tri_count);
   return e ? fail(e, "marching cubes: table derivation failed") : NGM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// scoring a mesh: surface samples and exact nearest points (evaluation.py:75-130, 190-191; ngm_mesh_eval.hip)
+// ------------------------------------------------------------------------------------------------
+int64_t ngm_surface_sample_workspace(int64_t num_faces) {
+  if (num_faces < 1 || num_faces > 0x7fffffff) return NGM_E_INVALID;
+  return ngm_surface_sample_bytes(num_faces);
+}
+int ngm_surface_sample(const float* verts, int64_t num_verts, const int64_t* faces, int64_t num_faces, int64_t num_samples,
+                       uint64_t seed, float* points, int64_t* face_ids, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (num_verts < 0 || num_faces < 0 || num_samples < 0) return fail(NGM_E_INVALID, "ngm_surface_sample: counts must be >= 0");
+  if (num_faces == 0) return fail(NGM_E_INVALID, "ngm_surface_sample: a mesh without faces has no surface to sample");
+  if (num_verts > 0x7fffffff || num_faces > 0x7fffffff || num_samples > 0x7fffffff)
+    return fail(NGM_E_INVALID, "ngm_surface_sample: counts must be below 2^31");
+  if (!faces || (num_verts > 0 && !verts) || !workspace || (num_samples > 0 && (!points || !face_ids)))
+    return fail(NGM_E_INVALID, "ngm_surface_sample: NULL array");
+  if (workspace_bytes < ngm_surface_sample_bytes(num_faces)) return fail(NGM_E_INVALID, "ngm_surface_sample: workspace too small (ngm_surface_sample_workspace)");
+  if (num_samples == 0) return NGM_OK;
+  ngm_launch_surface_sample(verts, num_verts, faces, num_faces, num_samples, seed, points, face_ids, workspace, (hipStream_t)stream);
+  return check_launch("ngm_surface_sample");
+}
+int64_t ngm_nearest_point_workspace(int64_t num_refs, int64_t num_queries) {
+  if (num_refs < 1 || num_queries < 0 || num_refs > 0x7fffffff || num_queries > 0x7fffffff) return NGM_E_INVALID;
+  return ngm_nearest_point_bytes(num_refs, num_queries);
+}
+int ngm_nearest_point(const float* refs, int64_t num_refs, const float* queries, int64_t num_queries, float* dist, int64_t* index,
+                      void* workspace, int64_t workspace_bytes, void* stream) {
+  if (num_refs < 0 || num_queries < 0) return fail(NGM_E_INVALID, "ngm_nearest_point: counts must be >= 0");
+  if (num_refs == 0) return fail(NGM_E_INVALID, "ngm_nearest_point: no reference points");
+  if (num_refs > 0x7fffffff || num_queries > 0x7fffffff) return fail(NGM_E_INVALID, "ngm_nearest_point: counts must be below 2^31");
+  if (!refs || !workspace || (num_queries > 0 && (!queries || !dist || !index))) return fail(NGM_E_INVALID, "ngm_nearest_point: NULL array");
+  if (workspace_bytes < ngm_nearest_point_bytes(num_refs, num_queries))
+    return fail(NGM_E_INVALID, "ngm_nearest_point: workspace too small (ngm_nearest_point_workspace)");
+  if (num_queries == 0) return NGM_OK;
+  ngm_launch_nearest_point(refs, num_refs, queries, num_queries, dist, index, workspace, (hipStream_t)stream);
+  return check_launch("ngm_nearest_point");
 }
 
 // ------------------------------------------------------------------------------------------------

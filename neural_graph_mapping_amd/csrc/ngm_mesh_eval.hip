@@ -1,0 +1,425 @@
+// Scoring a mesh on the device: the two device parts of evaluation._evaluate_postprocessed_meshes (evaluation.py:163-208).
+//   surface sampler (evaluation.py:190-191, trimesh.sample.sample_surface restated from its public definition: a face with
+//   probability proportional to its area, then a uniform point in it)
+//     k_face_area       : fp32 triangle area per face, stored as fp64; 0 for a face with a non-finite vertex or an index
+//                         outside [0, V)
+//     k_scan_*          : inclusive fp64 scan over the faces, three passes (chunk sums, one workgroup over the chunk sums with
+//                         a carry, chunks again): GT meshes have millions of faces
+//     k_surface_sample  : one thread per sample: Philox block `sample index` of stream MESH_STREAM_SURFACE, words 0 and 1 a
+//                         53-bit uniform that picks the face by binary search in the scan, words 2 and 3 the point in it
+//   exact nearest point between two clouds (evaluation.py:75-130: scipy.spatial.KDTree build + query)
+//     k_np_bbox / k_np_header : bounding box of the finite references -> uniform grid of cubic cells, a few points per occupied
+//                         cell, no more than max_cells of them; the header stays in device memory (NpGridHdr, like KnnGridHdr)
+//     k_np_clear / k_np_count / k_scan_* / k_np_fill : count -> exclusive scan -> cell-sorted float4 copy (x, y, z, index)
+//     k_np_query        : one thread per query: Chebyshev rings around the query's (clamped) cell until the best distance found
+//                         is within the gap to every face of the visited block that still has cells behind it
+// No size is read back to the host; nothing here returns a status from the device.  Plain C++ and vector stores only; every
+// index that reaches memory is checked (face indices against V) or clamped (cell indices).
+#include "ngm_device.h"
+#include "ngm_launch.h"
+
+#include <algorithm>
+
+#pragma clang fp contract(off)
+
+constexpr uint32_t MESH_STREAM_SURFACE = 0x54470006u;      // next to the TSMV_STREAM_* ids of ngm_target.hip
+
+__device__ __forceinline__ bool me_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+
+// ---- scans ------------------------------------------------------------------------------------------------------------
+// Three passes over chunks of SCAN_CHUNK elements, one workgroup of SCAN_T threads per chunk, SCAN_PER contiguous elements
+// per thread: (1) chunk sums, (2) exclusive scan of the chunk sums by ONE workgroup (1024 per round, carried), (3) the chunks
+// again with their offsets.  The length is n_host, or *n_dev where the host does not know it (the grid's cell count): the
+// launch covers the host's upper bound, chunks beyond the length do nothing.  INCLUSIVE = false also leaves a[n] = total.
+constexpr int SCAN_T = 256, SCAN_PER = 8, SCAN_CHUNK = SCAN_T * SCAN_PER;
+
+template <typename T>
+__device__ __forceinline__ T scan_block_exclusive(T v, T* lds, T* total) {
+  const int t = threadIdx.x;
+  lds[t] = v;
+  __syncthreads();
+  for (int d = 1; d < SCAN_T; d <<= 1) {
+    const T o = (t >= d) ? lds[t - d] : T(0);
+    __syncthreads();
+    lds[t] += o;
+    __syncthreads();
+  }
+  *total = lds[SCAN_T - 1];
+  const T r = lds[t] - v;
+  __syncthreads();
+  return r;
+}
+
+template <typename T>
+__global__ __launch_bounds__(SCAN_T) void k_scan_reduce(const T* a, const int* n_dev, int64_t n_host, T* partial) {
+  __shared__ T lds[SCAN_T];
+  const int64_t n = n_dev ? (int64_t)*n_dev : n_host;
+  const int64_t b0 = (int64_t)blockIdx.x * SCAN_CHUNK + (int64_t)threadIdx.x * SCAN_PER;
+  T s = T(0);
+#pragma unroll
+  for (int i = 0; i < SCAN_PER; ++i)
+    if (b0 + i < n) s += a[b0 + i];
+  T total;
+  (void)scan_block_exclusive(s, lds, &total);
+  if (threadIdx.x == 0) partial[blockIdx.x] = total;
+}
+
+template <typename T>
+__global__ __launch_bounds__(1024) void k_scan_partials(T* partial, int64_t nb) {
+  __shared__ T lds[1024];
+  const int t = threadIdx.x;
+  T carry = T(0);
+  for (int64_t base = 0; base < nb; base += 1024) {
+    const T v = (base + t < nb) ? partial[base + t] : T(0);
+    lds[t] = v;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {
+      const T o = (t >= d) ? lds[t - d] : T(0);
+      __syncthreads();
+      lds[t] += o;
+      __syncthreads();
+    }
+    if (base + t < nb) partial[base + t] = carry + (lds[t] - v);
+    carry += lds[1023];
+    __syncthreads();
+  }
+}
+
+template <typename T, bool INCLUSIVE>
+__global__ __launch_bounds__(SCAN_T) void k_scan_apply(T* a, const int* n_dev, int64_t n_host, const T* partial) {
+  __shared__ T lds[SCAN_T];
+  const int64_t n = n_dev ? (int64_t)*n_dev : n_host;
+  const int64_t b0 = (int64_t)blockIdx.x * SCAN_CHUNK + (int64_t)threadIdx.x * SCAN_PER;
+  T v[SCAN_PER];
+  T s = T(0);
+#pragma unroll
+  for (int i = 0; i < SCAN_PER; ++i) { v[i] = (b0 + i < n) ? a[b0 + i] : T(0); s += v[i]; }
+  T total;
+  T run = partial[blockIdx.x] + scan_block_exclusive(s, lds, &total);
+#pragma unroll
+  for (int i = 0; i < SCAN_PER; ++i) {
+    if (b0 + i < n) {
+      if (INCLUSIVE) { run += v[i]; a[b0 + i] = run; }
+      else { a[b0 + i] = run; run += v[i]; if (b0 + i == n - 1) a[n] = run; }
+    }
+  }
+  if (!INCLUSIVE && n == 0 && blockIdx.x == 0 && threadIdx.x == 0) a[0] = T(0);
+}
+
+template <typename T, bool INCLUSIVE>
+static void launch_scan(T* a, const int* n_dev, int64_t n_max, T* partial, hipStream_t st) {
+  const int64_t nb = std::max<int64_t>((n_max + SCAN_CHUNK - 1) / SCAN_CHUNK, 1);
+  hipLaunchKernelGGL(k_scan_reduce<T>, dim3((unsigned)nb), dim3(SCAN_T), 0, st, a, n_dev, n_max, partial);
+  hipLaunchKernelGGL(k_scan_partials<T>, dim3(1), dim3(1024), 0, st, partial, nb);
+  hipLaunchKernelGGL((k_scan_apply<T, INCLUSIVE>), dim3((unsigned)nb), dim3(SCAN_T), 0, st, a, n_dev, n_max, partial);
+}
+static int64_t scan_partials(int64_t n_max) { return std::max<int64_t>((n_max + SCAN_CHUNK - 1) / SCAN_CHUNK, 1); }
+static int64_t up256(int64_t b) { return (b + 255) / 256 * 256; }
+
+// ---- surface sampler --------------------------------------------------------------------------------------------------
+struct SurfArgs {
+  const float* verts; const int64_t* faces;
+  int64_t V; int F; int N;
+  uint64_t seed;
+  double* cum;          // (F) areas, then their inclusive scan
+  float* points; int64_t* face_ids;
+};
+
+// the three corners of face f; false when an index is outside [0, V) or a coordinate is not finite
+__device__ __forceinline__ bool surf_face(const SurfArgs& a, int f, float (&p)[3][3]) {
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int64_t i = a.faces[3 * (int64_t)f + k];
+    if (i < 0 || i >= a.V) { ok = false; p[k][0] = p[k][1] = p[k][2] = 0.f; continue; }
+#pragma unroll
+    for (int d = 0; d < 3; ++d) { p[k][d] = a.verts[3 * i + d]; ok = ok && me_finite(p[k][d]); }
+  }
+  return ok;
+}
+// fp32: 0.5 |(v1 - v0) x (v2 - v0)|, every product and sum rounded on its own (tests/_mesh_metrics_host.py restates it)
+__device__ __forceinline__ float surf_area(const float (&p)[3][3]) {
+  const float ax = p[1][0] - p[0][0], ay = p[1][1] - p[0][1], az = p[1][2] - p[0][2];
+  const float bx = p[2][0] - p[0][0], by = p[2][1] - p[0][1], bz = p[2][2] - p[0][2];
+  const float cx = ay * bz - az * by, cy = az * bx - ax * bz, cz = ax * by - ay * bx;
+  const float ar = 0.5f * sqrtf((cx * cx + cy * cy) + cz * cz);
+  return me_finite(ar) ? ar : 0.f;
+}
+
+__global__ __launch_bounds__(256) void k_face_area(SurfArgs a) {
+  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= a.F) return;
+  float p[3][3];
+  a.cum[f] = surf_face(a, f, p) ? (double)surf_area(p) : 0.0;
+}
+
+__global__ __launch_bounds__(256) void k_surface_sample(SurfArgs a) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.N) return;
+  const float qnan = __int_as_float(0x7fc00000);
+  float out[3] = {qnan, qnan, qnan};
+  int64_t fid = -1;
+  const double total = a.cum[a.F - 1];
+  if (total > 0.0 && total < (double)INFINITY) {
+    uint32_t q[4];
+    philox_block(a.seed, 0ull, (uint64_t)i, MESH_STREAM_SURFACE, q);
+    // 53 bits: a 24-bit draw would quantise a mesh of millions of faces
+    const double u53 = (double)(((uint64_t)(q[0] >> 5) << 26) | (uint64_t)(q[1] >> 6)) * (1.0 / 9007199254740992.0);
+    const double target = u53 * total;
+    int lo = 0, hi = a.F;                                   // first k with cum[k] > target (F: none)
+    while (lo < hi) { const int mid = lo + ((hi - lo) >> 1); if (a.cum[mid] > target) hi = mid; else lo = mid + 1; }
+    int k = min(lo, a.F - 1);
+    // cum[k - 1] <= target < cum[k] makes face k one of positive area.  A parallel fp64 scan may be off by an ulp between
+    // neighbouring elements, and u53 * total may round up to total: where the face found has no area after all, the next
+    // one that has (forwards, then backwards) is the face the draw belongs to
+    float p[3][3];
+    bool ok = surf_face(a, k, p) && surf_area(p) > 0.f;
+    for (int j = k + 1; !ok && j < a.F; ++j) { ok = surf_face(a, j, p) && surf_area(p) > 0.f; if (ok) k = j; }
+    for (int j = k - 1; !ok && j >= 0; --j) { ok = surf_face(a, j, p) && surf_area(p) > 0.f; if (ok) k = j; }
+    if (ok) {
+      float u = philox_word_uniform(q[2]), v = philox_word_uniform(q[3]);
+      if (u + v > 1.0f) { u = 1.0f - u; v = 1.0f - v; }
+#pragma unroll
+      for (int d = 0; d < 3; ++d) out[d] = (p[0][d] + u * (p[1][d] - p[0][d])) + v * (p[2][d] - p[0][d]);
+      fid = k;
+    }
+  }
+  a.points[3 * (int64_t)i] = out[0]; a.points[3 * (int64_t)i + 1] = out[1]; a.points[3 * (int64_t)i + 2] = out[2];
+  a.face_ids[i] = fid;
+}
+
+int64_t ngm_surface_sample_bytes(int64_t num_faces) {
+  return 256 + up256(8 * num_faces) + up256(8 * (scan_partials(num_faces) + 1)) + 256;
+}
+int ngm_launch_surface_sample(const float* verts, int64_t V, const int64_t* faces, int64_t F, int64_t N, uint64_t seed, float* points,
+                              int64_t* face_ids, void* workspace, hipStream_t st) {
+  char* w = reinterpret_cast<char*>(((int64_t)workspace + 255) / 256 * 256);
+  SurfArgs a = {};
+  a.verts = verts; a.faces = faces; a.V = V; a.F = (int)F; a.N = (int)N; a.seed = seed; a.points = points; a.face_ids = face_ids;
+  a.cum = reinterpret_cast<double*>(w);
+  double* partial = reinterpret_cast<double*>(w + up256(8 * F));
+  hipLaunchKernelGGL(k_face_area, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, st, a);
+  launch_scan<double, true>(a.cum, nullptr, F, partial, st);
+  hipLaunchKernelGGL(k_surface_sample, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, a);
+  return 0;
+}
+
+// ---- exact nearest point ----------------------------------------------------------------------------------------------
+struct NpGridHdr { float x0, y0, z0, c, inv_c; int nx, ny, nz, ncells, valid, nmax, pad; };
+constexpr int NP_BBOX_BLOCKS = 1024;
+struct NpArgs {
+  const float* refs; const float* queries;
+  int M, N;
+  float* dist; int64_t* index;
+  NpGridHdr* hdr;
+  float* part;          // (NP_BBOX_BLOCKS, 6) per-workgroup bounding boxes
+  int* cell_start;      // (max_cells + 1) counts, then their exclusive prefix
+  int* cell_fill;       // (max_cells) fill cursors
+  int* scan_part;       // chunk sums of the scan
+  float4* sorted;       // (M) finite references grouped by cell: (x, y, z, original index as int bits)
+  int max_cells, bbox_blocks;
+};
+
+__global__ __launch_bounds__(256) void k_np_bbox(NpArgs a) {
+  __shared__ float red[6][256];
+  float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.M; i += (int64_t)gridDim.x * 256) {
+    const float x = a.refs[3 * i], y = a.refs[3 * i + 1], z = a.refs[3 * i + 2];
+    if (!(me_finite(x) && me_finite(y) && me_finite(z))) continue;           // a non-finite reference is nobody's neighbour
+    lo[0] = fminf(lo[0], x); hi[0] = fmaxf(hi[0], x);
+    lo[1] = fminf(lo[1], y); hi[1] = fmaxf(hi[1], y);
+    lo[2] = fminf(lo[2], z); hi[2] = fmaxf(hi[2], z);
+  }
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) { red[d][t] = lo[d]; red[3 + d][t] = hi[d]; }
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (t < s)
+#pragma unroll
+      for (int d = 0; d < 3; ++d) { red[d][t] = fminf(red[d][t], red[d][t + s]); red[3 + d][t] = fmaxf(red[3 + d][t], red[3 + d][t + s]); }
+    __syncthreads();
+  }
+  if (t < 6) a.part[6 * blockIdx.x + t] = red[t][0];
+}
+
+// One workgroup: the boxes of k_np_bbox -> the grid.  Cubic cells sized for a few points per OCCUPIED cell: 2 M cells over
+// the box's volume when it has three extents (the clouds are samples of surfaces: a cell the surface crosses then holds
+// about half a dozen), M / 4 over its area / length when it has two / one; coarsened by 2^(1/3) per step until the
+// grid fits max_cells.  A box the arithmetic cannot grid (an extent that overflows fp32) becomes one cell: brute force.
+__global__ __launch_bounds__(256) void k_np_header(NpArgs a) {
+  __shared__ float red[6][256];
+  const int t = threadIdx.x;
+  float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (int b = t; b < a.bbox_blocks; b += 256)
+#pragma unroll
+    for (int d = 0; d < 3; ++d) { lo[d] = fminf(lo[d], a.part[6 * b + d]); hi[d] = fmaxf(hi[d], a.part[6 * b + 3 + d]); }
+#pragma unroll
+  for (int d = 0; d < 3; ++d) { red[d][t] = lo[d]; red[3 + d][t] = hi[d]; }
+  __syncthreads();
+  if (t != 0) return;
+  float L[3], U[3], ext[3];
+  bool valid = true, gridable = true;
+  for (int d = 0; d < 3; ++d) {
+    L[d] = red[d][0]; U[d] = red[3 + d][0];
+    for (int j = 1; j < 256; ++j) { L[d] = fminf(L[d], red[d][j]); U[d] = fmaxf(U[d], red[3 + d][j]); }
+    valid = valid && (L[d] <= U[d]);
+  }
+  NpGridHdr h = {};
+  h.nx = h.ny = h.nz = 1; h.ncells = 1; h.nmax = 1; h.c = 1.f; h.inv_c = 0.f;
+  if (valid) {
+    int k = 0;
+    double vol = 1.0;
+    for (int d = 0; d < 3; ++d) {
+      ext[d] = U[d] - L[d];
+      if (!me_finite(ext[d])) gridable = false;
+      if (ext[d] > 0.f) { ++k; vol *= (double)ext[d]; }
+    }
+    h.x0 = L[0]; h.y0 = L[1]; h.z0 = L[2];
+    if (gridable && k > 0) {
+      double want = (k == 3) ? 2.0 * (double)a.M : fmax(0.25 * (double)a.M, 1.0);
+      want = fmin(want, (double)a.max_cells);
+      float c = (float)pow(vol / want, 1.0 / (double)k);
+      if (!(c > 0.f) || !me_finite(c)) c = fmaxf(fmaxf(ext[0], ext[1]), ext[2]);
+      int n[3] = {1, 1, 1};
+      bool fits = false;
+      for (int it = 0; it < 400 && !fits; ++it) {
+        double cells = 1.0;
+        for (int d = 0; d < 3; ++d) {
+          const float e = ext[d] / c;
+          n[d] = (e < 1.0e6f) ? (int)e + 1 : 1000001;
+          cells *= (double)n[d];
+        }
+        fits = cells <= (double)a.max_cells;
+        if (!fits) c *= 1.26f;
+      }
+      if (fits && me_finite(c) && me_finite(1.0f / c)) {
+        h.c = c; h.inv_c = 1.0f / c;
+        h.nx = n[0]; h.ny = n[1]; h.nz = n[2]; h.ncells = n[0] * n[1] * n[2]; h.nmax = max(n[0], max(n[1], n[2]));
+      }
+    }
+  }
+  h.valid = valid ? 1 : 0;
+  *a.hdr = h;
+}
+
+// cell coordinate along one axis: clamped as a float first, so neither a NaN nor a value beyond int ever becomes an index
+__device__ __forceinline__ int np_cell1(float g, int n) { return (int)fminf(fmaxf(floorf(g), 0.f), (float)(n - 1)); }
+__device__ __forceinline__ int np_cell_of(const NpGridHdr& h, float x, float y, float z) {
+  const int ix = np_cell1((x - h.x0) * h.inv_c, h.nx), iy = np_cell1((y - h.y0) * h.inv_c, h.ny), iz = np_cell1((z - h.z0) * h.inv_c, h.nz);
+  return (iz * h.ny + iy) * h.nx + ix;
+}
+
+__global__ __launch_bounds__(256) void k_np_clear(NpArgs a) {
+  const int nc = min(a.hdr->ncells, a.max_cells);
+  for (int i = blockIdx.x * 256 + threadIdx.x; i <= nc; i += gridDim.x * 256) { a.cell_start[i] = 0; if (i < nc) a.cell_fill[i] = 0; }
+}
+__global__ __launch_bounds__(256) void k_np_count(NpArgs a) {
+  const NpGridHdr h = *a.hdr;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.M; i += (int64_t)gridDim.x * 256) {
+    const float x = a.refs[3 * i], y = a.refs[3 * i + 1], z = a.refs[3 * i + 2];
+    if (me_finite(x) && me_finite(y) && me_finite(z)) atomicAdd(&a.cell_start[np_cell_of(h, x, y, z)], 1);
+  }
+}
+__global__ __launch_bounds__(256) void k_np_fill(NpArgs a) {
+  const NpGridHdr h = *a.hdr;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.M; i += (int64_t)gridDim.x * 256) {
+    const float x = a.refs[3 * i], y = a.refs[3 * i + 1], z = a.refs[3 * i + 2];
+    if (!(me_finite(x) && me_finite(y) && me_finite(z))) continue;
+    const int cidx = np_cell_of(h, x, y, z);
+    const int slot = a.cell_start[cidx] + atomicAdd(&a.cell_fill[cidx], 1);
+    if (slot >= 0 && slot < a.M) a.sorted[slot] = make_float4(x, y, z, __int_as_float((int)i));
+  }
+}
+
+// The (2 r + 1)^3 block of cells around the query's cell, clipped to the grid, has been searched after ring r.  A
+// reference not yet seen lies in a cell beyond one of the block's faces, and only a face that is not on the grid's boundary
+// has cells behind it; such a reference is at least the gap from the query to that face's plane away.  The cell
+// coordinate g(x) = (x - x0) * inv_c is monotonic in x and is computed for queries exactly as it was for the references,
+// so the gap in cell units, less the rounding of g (a few 2^-24 of its magnitude, which is at most the grid's size for a
+// plane of the grid, and relative to the gap itself where the query is far outside), times c, is a lower bound.
+__global__ __launch_bounds__(256) void k_np_query(NpArgs a) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.N) return;
+  const NpGridHdr h = *a.hdr;
+  const float x = a.queries[3 * (int64_t)i], y = a.queries[3 * (int64_t)i + 1], z = a.queries[3 * (int64_t)i + 2];
+  if (!(me_finite(x) && me_finite(y) && me_finite(z))) { a.dist[i] = __int_as_float(0x7fc00000); a.index[i] = -1; return; }
+  if (!h.valid) { a.dist[i] = INFINITY; a.index[i] = -1; return; }
+  const float gx = (x - h.x0) * h.inv_c, gy = (y - h.y0) * h.inv_c, gz = (z - h.z0) * h.inv_c;
+  const int ix = np_cell1(gx, h.nx), iy = np_cell1(gy, h.ny), iz = np_cell1(gz, h.nz);
+  const float slack = 2.0e-6f * (float)(h.nmax + 2);
+  // a lower bound, in world units, of a gap given in cell units
+  auto world_gap = [&](float cells) { return fmaxf(cells * (1.0f - 2.0e-6f) - slack, 0.f) * h.c * (1.0f - 2.0e-6f); };
+  float best = INFINITY;
+  int bi = -1;
+  auto visit = [&](int j0, int j1) __attribute__((always_inline)) {
+    for (int j = j0; j < j1; ++j) {
+      const float4 c = a.sorted[j];
+      const float dx = x - c.x, dy = y - c.y, dz = z - c.z;
+      const float d = sqrtf((dx * dx + dy * dy) + dz * dz);
+      if (d < best || bi < 0) { best = d; bi = __float_as_int(c.w); }
+    }
+  };
+  for (int r = 0;; ++r) {
+    const int xlo = max(ix - r, 0), xhi = min(ix + r, h.nx - 1);
+    const int ylo = max(iy - r, 0), yhi = min(iy + r, h.ny - 1);
+    const int zlo = max(iz - r, 0), zhi = min(iz + r, h.nz - 1);
+    for (int cz = zlo; cz <= zhi; ++cz) {
+      const float lz = fmaxf(fmaxf((float)cz - gz, gz - (float)(cz + 1)), 0.f);
+      for (int cy = ylo; cy <= yhi; ++cy) {
+        const float ly = fmaxf(fmaxf((float)cy - gy, gy - (float)(cy + 1)), 0.f);
+        if (world_gap(fmaxf(ly, lz)) > best) continue;             // nothing in this row can be closer
+        const int rowb = (cz * h.ny + cy) * h.nx;
+        if (abs(cz - iz) == r || abs(cy - iy) == r) {              // a row of the shell: its cells are one range
+          visit(a.cell_start[rowb + xlo], a.cell_start[rowb + xhi + 1]);
+        } else {                                                    // an inner row: the shell's two end cells
+          if (ix - r >= 0) visit(a.cell_start[rowb + ix - r], a.cell_start[rowb + ix - r + 1]);
+          if (ix + r <= h.nx - 1) visit(a.cell_start[rowb + ix + r], a.cell_start[rowb + ix + r + 1]);
+        }
+      }
+    }
+    float gap = INFINITY;                                          // faces with cells behind them
+    if (ix - r > 0) gap = fminf(gap, gx - (float)(ix - r));
+    if (ix + r < h.nx - 1) gap = fminf(gap, (float)(ix + r + 1) - gx);
+    if (iy - r > 0) gap = fminf(gap, gy - (float)(iy - r));
+    if (iy + r < h.ny - 1) gap = fminf(gap, (float)(iy + r + 1) - gy);
+    if (iz - r > 0) gap = fminf(gap, gz - (float)(iz - r));
+    if (iz + r < h.nz - 1) gap = fminf(gap, (float)(iz + r + 1) - gz);
+    if (gap == INFINITY) break;                                    // the grid is exhausted
+    if (best <= world_gap(gap)) break;
+  }
+  a.dist[i] = best;
+  a.index[i] = (int64_t)bi;
+}
+
+// cells of the grid over the references: 2 per reference (k_np_header), bounded
+static int np_max_cells(int64_t M) { return (int)std::min<int64_t>(std::max<int64_t>(2 * M, 64), 1 << 22); }
+int64_t ngm_nearest_point_bytes(int64_t M, int64_t N) {
+  (void)N;
+  const int64_t mc = np_max_cells(M);
+  return 256 + 256 + up256(4 * 6 * NP_BBOX_BLOCKS) + up256(4 * (mc + 1)) + up256(4 * mc) + up256(4 * (scan_partials(mc) + 1)) + up256(16 * M);
+}
+int ngm_launch_nearest_point(const float* refs, int64_t M, const float* queries, int64_t N, float* dist, int64_t* index, void* workspace,
+                             hipStream_t st) {
+  char* w = reinterpret_cast<char*>(((int64_t)workspace + 255) / 256 * 256);
+  auto carve = [&](int64_t bytes) { char* p = w; w += up256(bytes); return p; };
+  NpArgs a = {};
+  a.refs = refs; a.queries = queries; a.M = (int)M; a.N = (int)N; a.dist = dist; a.index = index;
+  a.max_cells = np_max_cells(M);
+  a.bbox_blocks = (int)std::min<int64_t>((M + 255) / 256, NP_BBOX_BLOCKS);
+  a.hdr = reinterpret_cast<NpGridHdr*>(carve(256));
+  a.part = reinterpret_cast<float*>(carve(4 * 6 * NP_BBOX_BLOCKS));
+  a.cell_start = reinterpret_cast<int*>(carve(4 * ((int64_t)a.max_cells + 1)));
+  a.cell_fill = reinterpret_cast<int*>(carve(4 * (int64_t)a.max_cells));
+  a.scan_part = reinterpret_cast<int*>(carve(4 * (scan_partials(a.max_cells) + 1)));
+  a.sorted = reinterpret_cast<float4*>(carve(16 * M));
+  const unsigned ref_blocks = (unsigned)std::min<int64_t>((M + 255) / 256, 8192);
+  hipLaunchKernelGGL(k_np_bbox, dim3((unsigned)a.bbox_blocks), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(k_np_header, dim3(1), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(k_np_clear, dim3((unsigned)std::min((a.max_cells + 256) / 256, 4096)), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(k_np_count, dim3(ref_blocks), dim3(256), 0, st, a);
+  launch_scan<int, false>(a.cell_start, &a.hdr->ncells, a.max_cells, a.scan_part, st);
+  hipLaunchKernelGGL(k_np_fill, dim3(ref_blocks), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(k_np_query, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, a);
+  return 0;
+}

@@ -536,6 +536,16 @@ class NeuralGraphRenderer:
         from . import mesh
         return mesh.extract_mesh(self, mesh_file_path, resolution, threshold, transform, field_ids, block, debug, fused, stats)
 
+    def evaluate_mesh(self, gt, num_points: int = 200000, seed: int = 0, **extract_mesh_kwargs):
+        """extract_mesh(**extract_mesh_kwargs) scored against the ground truth `gt` (a (verts, faces) pair of device tensors
+        or a PLY path) by mesh.evaluate_mesh: the ten numbers of evaluation._evaluate_postprocessed_meshes
+        (evaluation.py:163-208).  None where extract_mesh returns None (no surface)."""
+        from . import mesh
+        est = self.extract_mesh(**extract_mesh_kwargs)
+        if est is None:
+            return None
+        return mesh.evaluate_mesh((est[0], est[1]), gt, num_points=num_points, seed=seed)
+
     # -- reference-compatible API --------------------------------------------------------------
     def quadrature(self, sample_colors, sample_geometries, sample_distances, sample_depths, neus_isds=None):
         return ops.quadrature(self._rc_train, sample_colors, sample_geometries, sample_distances, sample_depths,
