@@ -215,7 +215,8 @@ def _train_case(name, F, R, n_c, n_g, seed, encoding="fourier", num_layers=2, di
         # make geometry non-trivial: larger last-layer weights
         model.all_fields_params[f"_linears.{num_layers}.weight"].mul_(2.0)
     t = synth_target(F, R, cam, pos, gen, inside=inside)
-    if color_shift:                      # pushes the photometric gaussian_nll mean over 2: the L1 branch of losses.py:34-35
+    if color_shift:                      # pushes the photometric gaussian_nll mean far over 2: the L1 branch of losses.py:34-35
+        #                                  (random target colours are over 2 without it: make_golden_nll_branch.py is the NLL side)
         t["rgbds"][..., :3] += color_shift
     fids = torch.arange(F)
     target = make_target(t, fids)
@@ -748,7 +749,10 @@ def g17_extract_mesh():
 def g20_train_nll():
     """the variance-weighted loss modes (losses.py:30-36, 64-75): gradients flow through the rendered colour / depth variances
     (rm.py:781-790).  Three configurations: gaussian_nll for both losses; l1 + laplacian_nll; and gaussian_nll photometric
-    with targets far off, where the reference's data-dependent switch (mean NLL > 2) returns the L1 loss instead."""
+    with targets far off, where the reference's data-dependent switch (mean NLL > 2) returns the L1 loss instead.
+    The FIRST configuration is on that L1 side as well (random target colours against variances of 1e-3: mean colour NLL 9.6e3;
+    its recorded photometric_gaussian_nll is the L1 value), so through the colour variances no gradient flows in any of the
+    three; the NLL side of the switch is fixture G28 (make_golden_nll_branch.py)."""
     _train_case("g20_train_gnll_gnll", F=2, R=24, n_c=8, n_g=8, seed=200, termination_weight=0.5,
                 photometric_loss="gaussian_nll", depth_loss="gaussian_nll")
     _train_case("g20_train_l1_lnll", F=2, R=24, n_c=8, n_g=8, seed=201, termination_weight=0.5,

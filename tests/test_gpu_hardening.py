@@ -214,7 +214,9 @@ def test_nll_loss_modes_ragged_vs_oracle(F, R, n_c, n_g, photo, depth, geom):
     used for these modes).  Conditioning: the NLL divides by the rendered variance, which is a cancellation (sum w (c - C)^2)
     and vanishes where one sample takes all the weight -- there e^2 / V^2 amplifies the fp32 rounding of V without bound in
     ANY implementation; rays whose variances fall below 1e-4 are therefore taken out of the loss (depth mask off): 19-39 of
-    the masked rays stay in."""
+    the masked rays stay in.  The photometric gaussian_nll instances all sit on the L1 side of its switch (random target
+    colours: mean colour NLL 434 to 750, losses.py:34-35), so here only the DEPTH variance carries gradient; the NLL side is
+    tests/test_gpu_loss_terms.py."""
     from gpu_common import kink_free_draws
     torch.manual_seed(F * 1000 + R)
     fkw = dict(FOURIER)

@@ -940,10 +940,11 @@ def test_fused_train_step_golden(name):
 
 
 @pytest.mark.parametrize("name", ["g6_train_cfg0", "g6_train_3field", "g18_train_l2", "g20_train_gnll_gnll", "g20_train_l1_lnll",
-                                  "g20_train_gnll_switch_l1"])
+                                  "g20_train_gnll_switch_l1", "g28_train_gnll_nll_branch"])
 def test_render_ijs_autograd_path_golden(name):
     """reference-style call sequence: render_ijs -> compute_losses -> backward (rm.py:1164-1186).  G20: the *_nll loss modes,
-    whose autograd reaches the parameters through Prediction.color_vars / depth_vars as well (ngm_render_bwd_seeded_vars)."""
+    whose autograd reaches the parameters through Prediction.depth_vars as well (ngm_render_bwd_seeded_vars); G28: through
+    Prediction.color_vars too (the G20 fixtures are on the L1 side of the photometric switch)."""
     g = load_golden(name)
     fkw, ckw = CASES[name]
     F = g["pos"].shape[0]
