@@ -1,7 +1,7 @@
 """End-to-end smoke of the drop-in path on one MI355X: keyframe store -> training-target sampler -> fused
 training step (forward, losses, backward, sparse Adam) -> kNN-blended render -> PSNR.
 
-    python examples/fit_synthetic.py [--iters 300] [--device-iteration | --live [--grow] [--loop-closure]] [--mesh-metrics]
+    python examples/fit_synthetic.py [--iters 300] [--device-iteration | --live [--grow] [--loop-closure]] [--mesh-metrics [--cull]]
 
 A synthetic RGB-D "scan" of a textured wall with a sphere in front of it is observed from a few keyframes; fields
 on a grid in front of the cameras are trained exactly as NeuralGraphMap._optimization_iteration would
@@ -20,6 +20,9 @@ graph keeps replaying, and the PSNR of keyframe 0 is reported before and right a
 fields around the sphere against the scene's analytic sphere, triangulated here -- the ten numbers of the reference's mesh
 evaluation (accuracy, completion, their ratios at 5 cm and 1 cm, F1).  The cameras see the front of the sphere only, so
 completion counts its unseen back as missing.
+--mesh-metrics --cull also scores the two meshes the way the reference's evaluate_raw_mesh does: both culled first by what the
+keyframes see (NeuralGraphRenderer.evaluate_raw_mesh, method "occlusion": frusta and self-occlusion from every keyframe pose),
+so the sphere's unseen back no longer counts against completion.
 """
 import argparse
 import math
@@ -80,7 +83,7 @@ def sphere_mesh(centre, radius, n_lat=48, n_lon=96):
     return radius * v + torch.tensor(centre), f.to(torch.int64)
 
 
-def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0, grow=False, loop_closure=False, mesh_metrics=False):
+def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0, grow=False, loop_closure=False, mesh_metrics=False, cull=False):
     """loop: "torch" -- sample_target_mv (torch draws) -> optimization_iteration, the reference's loop;
     "device" -- capture_training: one graph replay per iteration;
     "materialize" -- the same device-drawn targets and jitter stream as "device" (sampler seed 0, iteration i; jitter
@@ -214,6 +217,11 @@ def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0, g
         else:
             print("mesh of the fields around the sphere against the analytic sphere (metres; ratios at 5 cm / 1 cm):")
             print("  " + "  ".join(f"{k} {v:.4f}" for k, v in m.items()))
+        if cull and m is not None:
+            m = r.evaluate_raw_mesh((gv.to(dev), gf.to(dev)), c2ws, cam, "occlusion", "occlusion", num_points=200000, seed=0, resolution=0.02,
+                                    field_ids=around)
+            print("the same two meshes, both culled to what the keyframes see (frusta and self-occlusion) before they are scored:")
+            print("  " + "  ".join(f"{k} {v:.4f}" for k, v in m.items()))
     return losses, psnr, derr
 
 
@@ -230,6 +238,8 @@ if __name__ == "__main__":
                     help="with --live: anchor the fields to keyframes, move all keyframe poses rigidly after the last keyframe, re-pose")
     ap.add_argument("--mesh-metrics", action="store_true",
                     help="score the mesh of the fields around the sphere against the analytic sphere on the device (ten numbers)")
+    ap.add_argument("--cull", action="store_true",
+                    help="with --mesh-metrics: also score the two meshes after culling both to what the keyframes see (evaluate_raw_mesh)")
     a = ap.parse_args()
     main(a.iters, loop="live" if a.live else "device" if a.device_iteration else "torch", grow=a.grow, loop_closure=a.loop_closure,
-         mesh_metrics=a.mesh_metrics)
+         mesh_metrics=a.mesh_metrics, cull=a.cull)

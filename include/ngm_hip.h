@@ -788,7 +788,7 @@ int ngm_marching_cubes_tables(int8_t* tri_table, int32_t* tri_count);
 /* ---- scoring a mesh: surface samples and exact nearest points (additive to ABI 11) --------------------------------------
  * The device parts of evaluation._evaluate_postprocessed_meshes (evaluation.py:163-208): the two
  * trimesh.sample.sample_surface calls (evaluation.py:190-191) and the scipy.spatial.KDTree build + query behind every one
- * of the ten numbers (evaluation.py:75-130).  Culling, ICP alignment and subdivision are the caller's.
+ * of the ten numbers (evaluation.py:75-130).  Culling is the next block's; ICP alignment and subdivision are the caller's.
  * ngm_surface_sample: verts (V,3) fp32, faces (F,3) int64 -> points (N,3) fp32, face_ids (N) int64.  trimesh's sampler
  * restated from its public definition: a face with probability proportional to its area (fp32 area, fp64 inclusive scan,
  * binary search for the first cum[k] > u * total), then the point v0 + u (v1 - v0) + v (v2 - v0) with (u, v) reflected to
@@ -811,6 +811,47 @@ int ngm_surface_sample(const float* verts, int64_t num_verts, const int64_t* fac
 int64_t ngm_nearest_point_workspace(int64_t num_refs, int64_t num_queries);
 int ngm_nearest_point(const float* refs, int64_t num_refs, const float* queries, int64_t num_queries, float* dist,
                       int64_t* index, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- culling a mesh: depth rasteriser and per-vertex visibility (additive to ABI 11) -----------------------------------
+ * The device parts of mesh_culling._cull_mesh (mesh_culling.py:228-352), the step evaluation.evaluate_raw_mesh
+ * (evaluation.py:211-251) runs on both meshes before it scores them.
+ * ngm_mesh_depth: verts (V,3) fp32, faces (F,3) int64, c2w (P,4,4) fp32 row-major camera-to-world in the OpenGL convention
+ * (what _cull_mesh hands on), intrinsics with cx, cy in the 0.5-pixel-centre convention
+ * (Camera.get_pinhole_camera_parameters(0.5)) -> depth (P,H,W) fp32: the camera-space z of the nearest surface, 0.0 where
+ * nothing is hit.  THE RULE (the contract; tests/_mesh_cull_host.py restates it in fp64):
+ *   - columns 1 and 2 of the pose's rotation are negated (mesh_culling.py:164-167), the affine part is inverted by adjugate
+ *     and determinant (no orthonormality assumed; the last row is taken as 0 0 0 1), the three corners go to camera space;
+ *   - the triangle is clipped against z >= near: 0, 3 or 4 corners, hence at most two triangles (0 1 2 and 0 2 3; a crossing
+ *     is formed from the corner in front towards the one behind and has z = near);
+ *   - projection sx = fx X / Z + cx, sy = fy Y / Z + cy; pixel (u, v) is sampled at (u + 0.5, v + 0.5) and is covered when
+ *     the sample lies inside or ON the triangle, in either winding -- the reference's two renders with flipped winding,
+ *     merged by minimum (mesh_culling.py:102-120);
+ *   - the depth at the sample is the perspective-correct camera z (1 / z interpolated linearly on the screen); samples with
+ *     z > far are rejected; the stored value is the minimum over all faces.
+ * Skipped, as the surface sampler skips them: a face with an index outside [0, V), with a non-finite vertex, or with zero
+ * projected area (each of the two clipped triangles on its own; also one whose projection is not finite in fp32).  A pose
+ * with a non-finite entry gives an all-zero map.  Not reproduced: GL's top-left fill rule and the quantisation of its depth
+ * buffer, both far inside the eps = 0.03 the maps are compared with.
+ * The minimum is an integer atomic on the bit pattern of the positive float: independent of the order of the faces, so the
+ * map is bitwise deterministic.  A lane draws its own triangle when its bounding box holds at most 32 pixels; larger ones
+ * are drawn one at a time by all 64 lanes of the wave; a mesh of few faces is drawn in bands of rows, so that many
+ * workgroups share its screen-filling triangles.  No workspace.
+ * ngm_mesh_visibility: _cull_from_one_pose for all P poses of the call plus the accumulation of _apply_culling_strategy
+ * (mesh_culling.py:143-225).  ADDS into in_frustum (V) and observed (V) int32 (the caller zeroes them; calls over chunks
+ * of the poses add up to one call over all of them).  Per (vertex, pose), in fp32: camera space as above, uvz = K camera
+ * space, pz = z + 1e-8, px = u / pz, py = v / pz; inside = 0 <= px <= width - 1 and 0 <= py <= height - 1 (the reference's
+ * bound, kept) and pz > 0; the pixel is (clamp, then truncate) of (px, py); seen = inside and pz < depth[pose, v, u] + eps.
+ * inside counts into in_frustum for poses [0, num_frustum_poses) only (virtual cameras, mesh_culling.py:220-223), seen into
+ * observed for all.  depth == NULL: seen = inside (the frustum-only method).  One thread per vertex, no atomics.
+ * Both: no host synchronisation.  NGM_E_INVALID before anything is launched for a NULL array, a negative count, a count
+ * >= 2^31, width or height < 1, and (ngm_mesh_depth) near <= 0 or far <= near.  num_poses == 0 or num_verts == 0 return
+ * NGM_OK and launch nothing (ngm_mesh_depth then leaves `depth` untouched); num_faces == 0 gives all-zero maps. */
+int ngm_mesh_depth(const float* verts, int64_t num_verts, const int64_t* faces, int64_t num_faces, const float* c2w, int64_t num_poses,
+                   int32_t width, int32_t height, float fx, float fy, float cx, float cy, float near, float far, float* depth,
+                   void* stream);
+int ngm_mesh_visibility(const float* verts, int64_t num_verts, const float* c2w, int64_t num_poses, int32_t width, int32_t height,
+                        float fx, float fy, float cx, float cy, const float* depth, float eps, int64_t num_frustum_poses,
+                        int32_t* in_frustum, int32_t* observed, void* stream);
 
 /* ---- measurement hooks (bench.py roofline leg) ------------------------------------------------
  * When enabled, every launch of the listed kernels is bracketed by hipEvents recorded on the launch

@@ -354,6 +354,10 @@ def lib():
     L.ngm_nearest_point_workspace.restype = i64
     L.ngm_nearest_point.argtypes = [vp, i64, vp, i64, vp, vp, vp, i64, vp]
     L.ngm_nearest_point.restype = C.c_int
+    L.ngm_mesh_depth.argtypes = [vp, i64, vp, i64, vp, i64, i32, i32, f32, f32, f32, f32, f32, f32, vp, vp]
+    L.ngm_mesh_depth.restype = C.c_int
+    L.ngm_mesh_visibility.argtypes = [vp, i64, vp, i64, i32, i32, f32, f32, f32, f32, vp, f32, i64, vp, vp, vp]
+    L.ngm_mesh_visibility.restype = C.c_int
     L.ngm_debug_plan_bwd.argtypes = [P(FieldCfg), P(RenderCfg), i32, i64, i32, i32, i32, P(i32)]
     L.ngm_debug_plan_bwd.restype = C.c_int
     L.ngm_debug_plan_fwd.argtypes = [P(FieldCfg), P(RenderCfg), i32, i32, i64, i32, P(i32)]
@@ -386,7 +390,8 @@ EXPORTED = ["ngm_abi_version", "ngm_last_error", "ngm_device_info", "ngm_permuto
             "ngm_render_fwd_counted", "ngm_render_bwd_counted", "ngm_render_bwd_adam_counted",
             "ngm_peer_mailbox_bytes", "ngm_peer_alloc", "ngm_peer_free", "ngm_ipc_export", "ngm_ipc_open", "ngm_ipc_close", "ngm_loss_exchange", "ngm_peer_set_timeout",
             "ngm_marching_cubes_workspace", "ngm_marching_cubes_count", "ngm_marching_cubes_emit", "ngm_marching_cubes_tables",
-            "ngm_surface_sample_workspace", "ngm_surface_sample", "ngm_nearest_point_workspace", "ngm_nearest_point"]
+            "ngm_surface_sample_workspace", "ngm_surface_sample", "ngm_nearest_point_workspace", "ngm_nearest_point",
+            "ngm_mesh_depth", "ngm_mesh_visibility"]
 
 # parameters that never receive a gradient (the CUDA package gives none to the per-level shifts either;
 # torch.optim.Adam skips grad-less parameters, so the sparse Adam must skip them too)

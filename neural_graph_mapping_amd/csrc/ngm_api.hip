@@ -34,6 +34,11 @@ int ngm_launch_surface_sample(const float* verts, int64_t V, const int64_t* face
 int64_t ngm_nearest_point_bytes(int64_t M, int64_t N);
 int ngm_launch_nearest_point(const float* refs, int64_t M, const float* queries, int64_t N, float* dist, int64_t* index, void* workspace,
                              hipStream_t st);
+int ngm_launch_mesh_depth(const float* verts, int64_t V, const int64_t* faces, int64_t F, const float* c2w, int64_t P, int W, int H,
+                          float fx, float fy, float cx, float cy, float near, float far, float* depth, hipStream_t st);
+int ngm_launch_mesh_visibility(const float* verts, int64_t V, const float* c2w, int64_t P, int W, int H, float fx, float fy, float cx,
+                               float cy, const float* depth, float eps, int64_t num_frustum_poses, int32_t* in_frustum,
+                               int32_t* observed, hipStream_t st);
 int ngm_launch_knn(const ngm_field_cfg* fc, const ngm_params* pr, int num_fields, int64_t P, const float* points,
                    const float* pos, const float* quat, int K, float distance_factor, float outside_value, float mask_radius,
                    float* out, void* workspace, int64_t workspace_bytes, const FwdPlan& plan, hipStream_t st);
@@ -1553,6 +1558,39 @@ int ngm_nearest_point(const float* refs, int64_t num_refs, const float* queries,
   if (num_queries == 0) return NGM_OK;
   ngm_launch_nearest_point(refs, num_refs, queries, num_queries, dist, index, workspace, (hipStream_t)stream);
   return check_launch("ngm_nearest_point");
+}
+
+// ------------------------------------------------------------------------------------------------
+// culling a mesh: depth rasteriser and per-vertex visibility (mesh_culling.py:41-225; ngm_mesh_cull.hip)
+// ------------------------------------------------------------------------------------------------
+int ngm_mesh_depth(const float* verts, int64_t num_verts, const int64_t* faces, int64_t num_faces, const float* c2w, int64_t num_poses,
+                   int32_t width, int32_t height, float fx, float fy, float cx, float cy, float near, float far, float* depth,
+                   void* stream) {
+  if (num_verts < 0 || num_faces < 0 || num_poses < 0) return fail(NGM_E_INVALID, "ngm_mesh_depth: counts must be >= 0");
+  if (num_verts > 0x7fffffff || num_faces > 0x7fffffff || num_poses > 0x7fffffff)
+    return fail(NGM_E_INVALID, "ngm_mesh_depth: counts must be below 2^31");
+  if (width < 1 || height < 1) return fail(NGM_E_INVALID, "ngm_mesh_depth: width and height must be >= 1");
+  if (!(near > 0.f) || !(far > near)) return fail(NGM_E_INVALID, "ngm_mesh_depth: 0 < near < far");
+  if ((num_verts > 0 && !verts) || (num_faces > 0 && !faces) || (num_poses > 0 && (!c2w || !depth)))
+    return fail(NGM_E_INVALID, "ngm_mesh_depth: NULL array");
+  if (num_poses == 0 || num_verts == 0) return NGM_OK;
+  ngm_launch_mesh_depth(verts, num_verts, faces, num_faces, c2w, num_poses, width, height, fx, fy, cx, cy, near, far, depth,
+                        (hipStream_t)stream);
+  return check_launch("ngm_mesh_depth");
+}
+int ngm_mesh_visibility(const float* verts, int64_t num_verts, const float* c2w, int64_t num_poses, int32_t width, int32_t height,
+                        float fx, float fy, float cx, float cy, const float* depth, float eps, int64_t num_frustum_poses,
+                        int32_t* in_frustum, int32_t* observed, void* stream) {
+  if (num_verts < 0 || num_poses < 0 || num_frustum_poses < 0) return fail(NGM_E_INVALID, "ngm_mesh_visibility: counts must be >= 0");
+  if (num_verts > 0x7fffffff || num_poses > 0x7fffffff || num_frustum_poses > 0x7fffffff)
+    return fail(NGM_E_INVALID, "ngm_mesh_visibility: counts must be below 2^31");
+  if (width < 1 || height < 1) return fail(NGM_E_INVALID, "ngm_mesh_visibility: width and height must be >= 1");
+  if ((num_verts > 0 && (!verts || !in_frustum || !observed)) || (num_poses > 0 && !c2w))
+    return fail(NGM_E_INVALID, "ngm_mesh_visibility: NULL array");
+  if (num_poses == 0 || num_verts == 0) return NGM_OK;
+  ngm_launch_mesh_visibility(verts, num_verts, c2w, num_poses, width, height, fx, fy, cx, cy, depth, eps, num_frustum_poses, in_frustum,
+                             observed, (hipStream_t)stream);
+  return check_launch("ngm_mesh_visibility");
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -292,9 +292,9 @@ def extract_mesh(renderer, mesh_file_path=None, resolution: Optional[float] = No
 # scoring a mesh (evaluation._evaluate_postprocessed_meshes, evaluation.py:163-208): surface samples of the estimated and
 # the ground-truth mesh, two exact nearest-neighbour queries between the clouds, ten numbers.  The reference runs
 # trimesh.sample.sample_surface and scipy.spatial.KDTree on the host; here both are device kernels (csrc/ngm_mesh_eval.hip)
-# and the reductions are torch on the device.  OUT OF SCOPE: mesh culling (mesh_culling.py: occlusion culling needs a
-# rasteriser), ICP alignment (evaluation._align_mesh), subdivide_to_size, LPIPS / SSIM -- callers pass meshes that are already
-# culled and aligned.
+# and the reductions are torch on the device.  Culling (mesh_culling.py) is further down: render_mesh_depth, cull_mesh,
+# evaluate_raw_mesh.  OUT OF SCOPE: ICP alignment (evaluation._align_mesh), subdivide_to_size, LPIPS / SSIM -- callers pass
+# meshes that are aligned and fine enough.
 # ------------------------------------------------------------------------------------------------
 METRIC_KEYS = ("median_acc", "median_comp", "acc", "comp", "acc_ratio", "acc_ratio_1cm", "comp_ratio", "comp_ratio_1cm",
                "f1_5cm", "f1_1cm")
@@ -416,10 +416,189 @@ def _as_mesh(m, device):
 def evaluate_mesh(est, gt, num_points: int = 200000, seed: int = 0) -> dict:
     """evaluation._evaluate_postprocessed_meshes (evaluation.py:163-208): `num_points` surface samples of each mesh
     (est with `seed`, gt with `seed + 1`), then mesh_metrics.  est / gt: a (verts, faces) pair of device tensors, or the path of
-    a PLY file save_ply wrote.  The meshes are taken as they are: culling, ICP alignment and subdivision are the caller's."""
+    a PLY file save_ply wrote.  The meshes are taken as they are: culling is evaluate_raw_mesh's (below), ICP alignment and subdivision are the caller's."""
     device = next((m[0].device for m in (est, gt) if not isinstance(m, (str, os.PathLike))), torch.device("cuda"))
     ev, ef = _as_mesh(est, device)
     gv, gf = _as_mesh(gt, device)
     est_points = sample_surface(ev, ef, num_points, seed)[0]
     gt_points = sample_surface(gv, gf, num_points, seed + 1)[0]
     return mesh_metrics(gt_points, est_points)
+
+
+# ------------------------------------------------------------------------------------------------
+# culling a mesh (mesh_culling._cull_mesh, mesh_culling.py:228-352): scene bounds, camera frusta and self-occlusion seen from
+# the given poses.  The reference draws two pyrender depth maps per pose under EGL and runs about ten torch kernels per pose over
+# all vertices; here the depth maps come from a HIP rasteriser and the per-vertex decisions of all poses of a chunk from one
+# launch (csrc/ngm_mesh_cull.hip; the rule is written down in include/ngm_hip.h), selection and compaction are torch on the
+# device.  NOT BUILT: subdivide_to_size (callers pass meshes that are fine enough), ICP, reading virtual-camera files (the
+# caller appends those poses and says where they start), GL's top-left fill rule and depth-buffer quantisation (both far
+# inside eps = 0.03).
+# ------------------------------------------------------------------------------------------------
+CULLING_METHODS = ("frustum", "occlusion", "virt_cams")
+
+
+@ops._op("mesh_depth")
+def _mesh_depth_op(verts: torch.Tensor, faces: torch.Tensor, c2ws: torch.Tensor, width: int, height: int, fx: float, fy: float,
+                   cx: float, cy: float, near: float, far: float) -> torch.Tensor:
+    """depth (P, H, W) fp32"""
+    p = c2ws.shape[0]
+    depth = torch.empty(p, height, width, device=verts.device, dtype=torch.float32)
+    if verts.shape[0] == 0:
+        return depth.zero_()                                    # the entry point launches nothing for a mesh without vertices
+    K.check(K.lib().ngm_mesh_depth(verts.data_ptr(), verts.shape[0], faces.data_ptr(), faces.shape[0], c2ws.data_ptr(), p, width, height,
+                                   fx, fy, cx, cy, near, far, depth.data_ptr(), ops._stream()), "ngm_mesh_depth")
+    return depth
+
+
+@_mesh_depth_op.register_fake
+def _(verts, faces, c2ws, width, height, fx, fy, cx, cy, near, far):
+    return verts.new_empty(c2ws.shape[0], height, width)
+
+
+@ops._op("mesh_visibility")
+def _mesh_visibility_op(verts: torch.Tensor, c2ws: torch.Tensor, depth: Optional[torch.Tensor], width: int, height: int, fx: float,
+                        fy: float, cx: float, cy: float, eps: float, num_frustum_poses: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """[in_frustum (V) int32, observed (V) int32]: the counts over the poses of this call"""
+    v = verts.shape[0]
+    in_frustum = torch.empty(v, device=verts.device, dtype=torch.int32).zero_()
+    observed = torch.empty(v, device=verts.device, dtype=torch.int32).zero_()
+    K.check(K.lib().ngm_mesh_visibility(verts.data_ptr(), v, c2ws.data_ptr(), c2ws.shape[0], width, height, fx, fy, cx, cy,
+                                        ops._ptr(depth), eps, num_frustum_poses, in_frustum.data_ptr(), observed.data_ptr(),
+                                        ops._stream()), "ngm_mesh_visibility")
+    return in_frustum, observed
+
+
+@_mesh_visibility_op.register_fake
+def _(verts, c2ws, depth, width, height, fx, fy, cx, cy, eps, num_frustum_poses):
+    return verts.new_empty(verts.shape[0], dtype=torch.int32), verts.new_empty(verts.shape[0], dtype=torch.int32)
+
+
+def _cull_inputs(fn, verts, faces, c2ws, camera):
+    ops._require_gpu(verts, faces, c2ws)
+    if verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32:
+        raise ValueError(f"{fn} expects (V, 3) float32 vertices")
+    if faces is not None and (faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int64):
+        raise ValueError(f"{fn} expects (F, 3) int64 faces")
+    if c2ws.dim() != 3 or tuple(c2ws.shape[1:]) != (4, 4) or c2ws.dtype != torch.float32:
+        raise ValueError(f"{fn} expects (P, 4, 4) float32 camera-to-world poses")
+    fx, fy, cx, cy, _ = camera.get_pinhole_camera_parameters(0.5)
+    return int(camera.width), int(camera.height), float(fx), float(fy), float(cx), float(cy)
+
+
+def render_mesh_depth(verts: torch.Tensor, faces: torch.Tensor, c2ws: torch.Tensor, camera, near: float = 0.01, far: float = 10.0):
+    """Depth maps of a mesh: verts (V, 3) fp32, faces (F, 3) int64, c2ws (P, 4, 4) fp32 camera-to-world in the OpenGL
+    convention, `camera` a renderer.Camera -> (P, H, W) fp32, the camera-space z of the nearest surface at every pixel centre,
+    0.0 where nothing is hit (mesh_culling._render_depth_maps_doublesided, mesh_culling.py:41-120: either winding counts).
+    The rule is the contract of ngm_mesh_depth (include/ngm_hip.h).  Bitwise deterministic, no host synchronisation.
+    Dispatches through torch.ops.ngm355.mesh_depth."""
+    w, h, fx, fy, cx, cy = _cull_inputs("render_mesh_depth", verts, faces, c2ws, camera)
+    return torch.ops.ngm355.mesh_depth(verts.contiguous(), faces.contiguous(), c2ws.contiguous(), w, h, fx, fy, cx, cy, float(near),
+                                       float(far))
+
+
+def mesh_visibility(verts: torch.Tensor, c2ws: torch.Tensor, camera, depth: Optional[torch.Tensor] = None, eps: float = 0.03,
+                    num_frustum_poses: Optional[int] = None):
+    """_cull_from_one_pose over all poses plus the sums of _apply_culling_strategy (mesh_culling.py:143-225): (in_frustum (V),
+    observed (V)) int32, how many of the poses have the vertex inside the image and how many also see it, i.e. find it no
+    further than `eps` behind depth (P, H, W) at its pixel.  depth None: observed = in_frustum.  Poses at or beyond
+    num_frustum_poses (None: all count) add to observed only -- the virtual-camera rule.
+    Dispatches through torch.ops.ngm355.mesh_visibility."""
+    w, h, fx, fy, cx, cy = _cull_inputs("mesh_visibility", verts, None, c2ws, camera)
+    p = c2ws.shape[0]
+    if depth is not None:
+        ops._require_gpu(depth)
+        if tuple(depth.shape) != (p, h, w) or depth.dtype != torch.float32:
+            raise ValueError(f"mesh_visibility expects ({p}, {h}, {w}) float32 depth maps")
+        depth = depth.contiguous()
+    nfp = p if num_frustum_poses is None else max(0, min(int(num_frustum_poses), p))
+    return torch.ops.ngm355.mesh_visibility(verts.contiguous(), c2ws.contiguous(), depth, w, h, fx, fy, cx, cy, float(eps), nfp)
+
+
+def _take(mask: torch.Tensor, n: int) -> torch.Tensor:
+    """indices of the n set entries of `mask`, ascending, without a read-back of their number (n is known)"""
+    return torch.argsort((~mask).to(torch.uint8), stable=True)[:n]
+
+
+@torch.no_grad()
+def cull_mesh(verts: torch.Tensor, faces: torch.Tensor, c2ws: torch.Tensor, camera, method: str, bounds=None,
+              colors: Optional[torch.Tensor] = None, num_frustum_poses: Optional[int] = None, th_obs: float = 0, eps: float = 0.03,
+              bounds_eps: float = 0.02, pose_chunk: int = 16):
+    """mesh_culling._cull_mesh (mesh_culling.py:228-352) on the device, step by step:
+      1. bounds (2, 3), when given: a face stays if ANY of its vertices is inside [lo - bounds_eps, hi + bounds_eps];
+      2. method "occlusion" / "virt_cams": depth maps of the faces that are left, from every pose (render_mesh_depth);
+      3. visibility of ALL original vertices (mesh_visibility), `pose_chunk` poses at a time so that depth memory is bounded;
+      4. a face stays if any vertex has in_frustum > th_obs and -- occlusion methods -- any vertex has observed > th_obs;
+      5. vertices no face refers to any more are dropped (order kept), then faces with a repeated index.
+    Returns (verts, faces) or (verts, faces, colors) on the device.  One read-back (the two output sizes), at the end.
+    The camera and the poses are taken AS GIVEN: _cull_mesh culls with dataset.camera.scaled_camera(0.5) and every second
+    ground-truth pose (`[::2]`); the caller applies both.  "virt_cams": the caller appends the virtual poses (OpenGL convention) and
+    passes the index of the first as num_frustum_poses -- they add to `observed` only.  subdivide_to_size is not built.
+    "frustum": the reference dies in torch.from_numpy(None) (mesh_culling.py:210-215); here it runs and does what
+    remove_occlusion=False evidently means -- no depth maps, faces kept on in_frustum alone.
+    A face with an index outside [0, V) is dropped (the reference would raise)."""
+    if method not in CULLING_METHODS:
+        raise ValueError(f"Unknown culling method {method}")                     # mesh_culling.py:373 wording
+    _cull_inputs("cull_mesh", verts, faces, c2ws, camera)
+    if colors is not None:
+        ops._require_gpu(colors)
+        if colors.shape[0] != verts.shape[0]:
+            raise ValueError("cull_mesh expects one colour row per vertex")
+    if int(pose_chunk) < 1:
+        raise ValueError("cull_mesh: pose_chunk >= 1")
+    occlusion = method != "frustum"
+    nv, p = verts.shape[0], c2ws.shape[0]
+    verts, faces, c2ws = verts.contiguous(), faces.contiguous(), c2ws.contiguous()
+    keep = ((faces >= 0) & (faces < nv)).all(1)
+    idx = faces.clamp(0, max(nv - 1, 0))                                         # safe to gather with; `keep` carries validity
+    if nv == 0:
+        keep = torch.zeros_like(keep)
+        idx = torch.zeros_like(faces)
+        verts_g = verts.new_zeros(1, 3)
+    else:
+        verts_g = verts
+    if bounds is not None:
+        b = torch.as_tensor(bounds, dtype=torch.float32, device=verts.device).reshape(2, 3)
+        inside = ((verts_g >= b[0] - bounds_eps) & (verts_g <= b[1] + bounds_eps)).all(1)
+        keep = keep & inside[idx].any(1)
+    in_frustum = torch.zeros(nv, device=verts.device, dtype=torch.int32)
+    observed = torch.zeros(nv, device=verts.device, dtype=torch.int32)
+    nfp = p if num_frustum_poses is None else max(0, min(int(num_frustum_poses), p))
+    drawn = torch.where(keep[:, None], faces, torch.full_like(faces, -1)) if occlusion else None   # index -1: skipped by the kernel
+    for s in range(0, p, int(pose_chunk)):
+        chunk = c2ws[s:s + int(pose_chunk)]
+        depth = render_mesh_depth(verts, drawn, chunk, camera) if occlusion else None
+        inf, obs = mesh_visibility(verts, chunk, camera, depth, eps, nfp - s)
+        in_frustum += inf
+        observed += obs
+    if nv:
+        keep = keep & (in_frustum[idx] > th_obs).any(1)
+        if occlusion:
+            keep = keep & (observed[idx] > th_obs).any(1)
+    referenced = torch.zeros(nv + 1, device=verts.device, dtype=torch.bool)
+    referenced[torch.where(keep[:, None], idx, torch.full_like(idx, nv)).reshape(-1)] = True
+    referenced = referenced[:nv]
+    keep = keep & (idx[:, 0] != idx[:, 1]) & (idx[:, 1] != idx[:, 2]) & (idx[:, 0] != idx[:, 2])
+    n_v, n_f = torch.stack([referenced.sum(), keep.sum()]).tolist()              # the one read-back
+    new_index = torch.cumsum(referenced, 0) - 1
+    vsel, fsel = _take(referenced, n_v), _take(keep, n_f)
+    out_faces = new_index[idx[fsel]]
+    if colors is not None:
+        return verts[vsel], out_faces, colors[vsel]
+    return verts[vsel], out_faces
+
+
+def evaluate_raw_mesh(est, gt, c2ws: torch.Tensor, camera, gt_culling_method: str, est_culling_method: str, num_points: int = 200000,
+                      seed: int = 0, bounds=None, mesh_alignment: bool = False, **cull_kwargs) -> dict:
+    """evaluation.evaluate_raw_mesh (evaluation.py:211-251): both meshes culled (cull_mesh: the ground truth with
+    gt_culling_method, the estimate with est_culling_method, the same poses, camera and bounds), then evaluate_mesh on what is
+    left -- the reference's headline mesh numbers without leaving the device.  est / gt as evaluate_mesh takes them;
+    cull_kwargs go to both cull_mesh calls (num_frustum_poses, th_obs, eps, bounds_eps, pose_chunk).  mesh_alignment=True (ICP,
+    evaluation._align_mesh) is not built and raises NotImplementedError."""
+    if mesh_alignment:
+        raise NotImplementedError("evaluate_raw_mesh: mesh_alignment (ICP, evaluation._align_mesh) is not built")
+    device = next((m[0].device for m in (est, gt) if not isinstance(m, (str, os.PathLike))), c2ws.device)
+    ev, ef = _as_mesh(est, device)
+    gv, gf = _as_mesh(gt, device)
+    gt_culled = cull_mesh(gv, gf, c2ws, camera, gt_culling_method, bounds=bounds, **cull_kwargs)
+    est_culled = cull_mesh(ev, ef, c2ws, camera, est_culling_method, bounds=bounds, **cull_kwargs)
+    return evaluate_mesh(est_culled, gt_culled, num_points=num_points, seed=seed)
