@@ -788,7 +788,7 @@ int ngm_marching_cubes_tables(int8_t* tri_table, int32_t* tri_count);
 /* ---- scoring a mesh: surface samples and exact nearest points (additive to ABI 11) --------------------------------------
  * The device parts of evaluation._evaluate_postprocessed_meshes (evaluation.py:163-208): the two
  * trimesh.sample.sample_surface calls (evaluation.py:190-191) and the scipy.spatial.KDTree build + query behind every one
- * of the ten numbers (evaluation.py:75-130).  Culling is the next block's; ICP alignment and subdivision are the caller's.
+ * of the ten numbers (evaluation.py:75-130).  Culling and the subdivision before it are the next two blocks'; ICP alignment is the caller's.
  * ngm_surface_sample: verts (V,3) fp32, faces (F,3) int64 -> points (N,3) fp32, face_ids (N) int64.  trimesh's sampler
  * restated from its public definition: a face with probability proportional to its area (fp32 area, fp64 inclusive scan,
  * binary search for the first cum[k] > u * total), then the point v0 + u (v1 - v0) + v (v2 - v0) with (u, v) reflected to
@@ -852,6 +852,53 @@ int ngm_mesh_depth(const float* verts, int64_t num_verts, const int64_t* faces, 
 int ngm_mesh_visibility(const float* verts, int64_t num_verts, const float* c2w, int64_t num_poses, int32_t width, int32_t height,
                         float fx, float fy, float cx, float cy, const float* depth, float eps, int64_t num_frustum_poses,
                         int32_t* in_frustum, int32_t* observed, void* stream);
+
+/* ---- subdividing a mesh to a maximum edge length (additive to ABI 11) ----------------------------------------------------
+ * The first step of mesh_culling._cull_mesh (mesh_culling.py:260-261): trimesh's subdivide_to_size, which splits every face
+ * with an edge longer than max_edge into four by its edge midpoints and repeats on the children.  The children are similar to
+ * the parent at half its size, so they share its fate in every round and the result per INPUT face is closed-form: the face
+ * becomes the uniform split into 4^k children, n = 2^k segments per edge, k its LEVEL.  Two calls, like marching cubes:
+ * ngm_mesh_subdivide_count: verts (V,3) fp32, faces (F,3) int64 -> totals_dev, three int64 on the device: the number of new
+ *   vertices, the number of output faces, the largest level.  THE LEVEL: the three edge lengths in fp64 from the fp32
+ *   vertices, sqrt((dx*dx + dy*dy) + dz*dz), no fused multiply-add (what numpy computes on a float64 copy of the vertices);
+ *   L = the longest; k = the number of exact halvings of L until `L > max_edge` is false.  An edge equal to max_edge is not
+ *   split.  A NaN length makes L NaN, which compares false: level 0.  A +inf length never passes; it, and every length that
+ *   needs more than max_iter halvings, gets level max_iter + 1, which the caller reads from totals_dev[2] and refuses -- such
+ *   a face counts one output face and no new vertex, so the totals stay bounded.  A face with an index outside [0, V) has
+ *   level 0 and is never dereferenced.  A face that needs exactly max_iter halvings is accepted.
+ *   The workspace (ngm_mesh_subdivide_workspace(F) bytes) holds, from its first 256-byte boundary on: level (F) int32, then
+ *   -- each rounded up to 256 bytes -- the exclusive int64 scans (F + 1) of the new vertices and of the output faces per face.
+ * ngm_mesh_subdivide_emit: the same mesh and workspace, the two totals as the host read them, attrs (V,C) fp32 or NULL ->
+ *   out_verts (V + new_vertices, 3) fp32: the V originals unchanged in [0, V), then per split face, in face order, its
+ *     lattice points that are not corners.  Lattice point (i, j), i + j <= n, of face (a, b, c) is a w0 + b w1 + c w2 with
+ *     w = ((n - i - j) / n, i / n, j / n); the points of a face are numbered row by row, j = 0 .. n, i = 0 .. n - j, the
+ *     three corners (0, 0), (n, 0), (0, n) left out.  Every face that is split stores its own points: a point on an edge
+ *     two faces share is stored by both, under two indices;
+ *   out_faces_idx (out_faces, 3) int64: children in parent order; inside a parent row by row, j = 0 .. n - 1, in row j the
+ *     2 (n - j) - 1 children u = 0, 1, ..: for even u, i = u / 2, the upright ((i, j), (i + 1, j), (i, j + 1)), for odd u the
+ *     inverted ((i + 1, j), (i + 1, j + 1), (i, j + 1)).  Every child has the parent's winding; a corner of a child that is a
+ *     corner of the parent keeps the original index; a level-0 face is copied as it is, whatever its indices;
+ *   out_parent (out_faces) int64: the input face of every output face (trimesh's return_index);
+ *   out_attrs (V + new_vertices, C) fp32: attrs interpolated with the same weights (attrs NULL: not written).
+ *   EXACTNESS: a point is evaluated in fp64 and rounded once to fp32, and a term whose weight is 0 is left out of the sum.
+ *   The weights are multiples of 2^-10 (max_iter <= 10) and the inputs have 24 bits, so every product is exact in fp64.  On
+ *   an edge of the parent one weight is 0: the point is ONE fp64 rounding of the exact sum of two products that depend on
+ *   the edge's two end points and the position along it alone, then one rounding to fp32.  It is therefore bit-identical
+ *   from both faces that share the edge, whatever their levels, the order of their indices or FMA contraction (a contracted
+ *   sum of an exact product is the same single rounding) -- the rasteriser's occlusion test relies on it: cracks along shared
+ *   edges would let depth leak through.
+ *   One thread per output element finds its parent by binary search in the scans (the first and the last thread of a workgroup
+ *   over all faces, the others between those two) and its lattice coordinates by a row formula with an integer fix-up; no
+ *   thread loops over the children of a face.
+ * Both: no host synchronisation.  NGM_E_INVALID before anything is launched for a NULL array, a negative count, V or F >= 2^31,
+ * max_edge not finite or not > 0, max_iter outside [0, 10], a workspace that is too small; NGM_E_UNSUPPORTED (emit) when
+ * V + new_vertices, out_faces or C (V + new_vertices) reach 2^31.  F == 0: the totals are zero, nothing else is launched. */
+int64_t ngm_mesh_subdivide_workspace(int64_t num_faces);
+int ngm_mesh_subdivide_count(const float* verts, int64_t num_verts, const int64_t* faces, int64_t num_faces, double max_edge,
+                             int32_t max_iter, void* workspace, int64_t workspace_bytes, int64_t* totals_dev, void* stream);
+int ngm_mesh_subdivide_emit(const float* verts, int64_t num_verts, const int64_t* faces, int64_t num_faces, const float* attrs,
+                            int32_t num_channels, const void* workspace, int64_t new_vertices, int64_t out_faces, float* out_verts,
+                            int64_t* out_faces_idx, float* out_attrs, int64_t* out_parent, void* stream);
 
 /* ---- measurement hooks (bench.py roofline leg) ------------------------------------------------
  * When enabled, every launch of the listed kernels is bracketed by hipEvents recorded on the launch

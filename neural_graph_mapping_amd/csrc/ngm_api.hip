@@ -34,6 +34,12 @@ int ngm_launch_surface_sample(const float* verts, int64_t V, const int64_t* face
 int64_t ngm_nearest_point_bytes(int64_t M, int64_t N);
 int ngm_launch_nearest_point(const float* refs, int64_t M, const float* queries, int64_t N, float* dist, int64_t* index, void* workspace,
                              hipStream_t st);
+int64_t ngm_mesh_subdivide_bytes(int64_t F);
+int ngm_launch_mesh_subdivide_count(const float* verts, int64_t V, const int64_t* faces, int64_t F, double max_edge, int max_iter,
+                                    void* workspace, int64_t* totals, hipStream_t st);
+int ngm_launch_mesh_subdivide_emit(const float* verts, int64_t V, const int64_t* faces, int64_t F, const float* attrs, int C,
+                                   const void* workspace, int64_t new_vertices, int64_t out_faces, float* out_verts,
+                                   int64_t* out_faces_idx, float* out_attrs, int64_t* out_parent, hipStream_t st);
 int ngm_launch_mesh_depth(const float* verts, int64_t V, const int64_t* faces, int64_t F, const float* c2w, int64_t P, int W, int H,
                           float fx, float fy, float cx, float cy, float near, float far, float* depth, hipStream_t st);
 int ngm_launch_mesh_visibility(const float* verts, int64_t V, const float* c2w, int64_t P, int W, int H, float fx, float fy, float cx,
@@ -1591,6 +1597,48 @@ int ngm_mesh_visibility(const float* verts, int64_t num_verts, const float* c2w,
   ngm_launch_mesh_visibility(verts, num_verts, c2w, num_poses, width, height, fx, fy, cx, cy, depth, eps, num_frustum_poses, in_frustum,
                              observed, (hipStream_t)stream);
   return check_launch("ngm_mesh_visibility");
+}
+
+// ------------------------------------------------------------------------------------------------
+// subdividing a mesh to a maximum edge length before it is culled (mesh_culling.py:260-261; ngm_mesh_eval.hip)
+// ------------------------------------------------------------------------------------------------
+int64_t ngm_mesh_subdivide_workspace(int64_t num_faces) {
+  if (num_faces < 0 || num_faces > 0x7fffffff) return NGM_E_INVALID;
+  return ngm_mesh_subdivide_bytes(num_faces);
+}
+int ngm_mesh_subdivide_count(const float* verts, int64_t num_verts, const int64_t* faces, int64_t num_faces, double max_edge,
+                             int32_t max_iter, void* workspace, int64_t workspace_bytes, int64_t* totals_dev, void* stream) {
+  if (num_verts < 0 || num_faces < 0) return fail(NGM_E_INVALID, "ngm_mesh_subdivide_count: counts must be >= 0");
+  if (num_verts > 0x7fffffff || num_faces > 0x7fffffff) return fail(NGM_E_INVALID, "ngm_mesh_subdivide_count: counts must be below 2^31");
+  if (!(max_edge > 0.0) || !(max_edge < (double)INFINITY)) return fail(NGM_E_INVALID, "ngm_mesh_subdivide_count: max_edge must be finite and > 0");
+  if (max_iter < 0 || max_iter > 10) return fail(NGM_E_INVALID, "ngm_mesh_subdivide_count: 0 <= max_iter <= 10");
+  if ((num_verts > 0 && !verts) || (num_faces > 0 && (!faces || !workspace)) || !totals_dev)
+    return fail(NGM_E_INVALID, "ngm_mesh_subdivide_count: NULL array");
+  if (num_faces > 0 && workspace_bytes < ngm_mesh_subdivide_bytes(num_faces))
+    return fail(NGM_E_INVALID, "ngm_mesh_subdivide_count: workspace too small (ngm_mesh_subdivide_workspace)");
+  const int e = ngm_launch_mesh_subdivide_count(verts, num_verts, faces, num_faces, max_edge, max_iter, workspace, totals_dev,
+                                                (hipStream_t)stream);
+  if (e) return fail(e, "ngm_mesh_subdivide_count: HIP error");
+  return check_launch("ngm_mesh_subdivide_count");
+}
+int ngm_mesh_subdivide_emit(const float* verts, int64_t num_verts, const int64_t* faces, int64_t num_faces, const float* attrs,
+                            int32_t num_channels, const void* workspace, int64_t new_vertices, int64_t out_faces, float* out_verts,
+                            int64_t* out_faces_idx, float* out_attrs, int64_t* out_parent, void* stream) {
+  if (num_verts < 0 || num_faces < 0 || new_vertices < 0 || out_faces < 0 || num_channels < 0)
+    return fail(NGM_E_INVALID, "ngm_mesh_subdivide_emit: counts must be >= 0");
+  if (num_verts > 0x7fffffff || num_faces > 0x7fffffff) return fail(NGM_E_INVALID, "ngm_mesh_subdivide_emit: counts must be below 2^31");
+  if (num_verts + new_vertices > 0x7fffffff || out_faces > 0x7fffffff)
+    return fail(NGM_E_UNSUPPORTED, "ngm_mesh_subdivide_emit: the output must stay below 2^31 vertices and 2^31 faces");
+  if (attrs && (int64_t)num_channels * (num_verts + new_vertices) > 0x7fffffff)
+    return fail(NGM_E_UNSUPPORTED, "ngm_mesh_subdivide_emit: the output attributes must stay below 2^31 values");
+  const int64_t nv = num_verts + new_vertices;
+  if ((num_verts > 0 && !verts) || (num_faces > 0 && (!faces || !workspace)) || (nv > 0 && !out_verts) ||
+      (out_faces > 0 && (!out_faces_idx || !out_parent)) || (attrs && num_channels > 0 && nv > 0 && !out_attrs))
+    return fail(NGM_E_INVALID, "ngm_mesh_subdivide_emit: NULL array");
+  if (num_faces == 0 && (new_vertices > 0 || out_faces > 0)) return fail(NGM_E_INVALID, "ngm_mesh_subdivide_emit: a mesh without faces has no output faces");
+  ngm_launch_mesh_subdivide_emit(verts, num_verts, faces, num_faces, attrs, num_channels, workspace, new_vertices, out_faces, out_verts,
+                                 out_faces_idx, out_attrs, out_parent, (hipStream_t)stream);
+  return check_launch("ngm_mesh_subdivide_emit");
 }
 
 // ------------------------------------------------------------------------------------------------

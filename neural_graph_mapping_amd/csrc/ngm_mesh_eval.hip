@@ -13,6 +13,9 @@
 //     k_np_clear / k_np_count / k_scan_* / k_np_fill : count -> exclusive scan -> cell-sorted float4 copy (x, y, z, index)
 //     k_np_query        : one thread per query: Chebyshev rings around the query's (clamped) cell until the best distance found
 //                         is within the gap to every face of the visited block that still has cells behind it
+//   subdivision to a maximum edge length (mesh_culling.py:260-261: trimesh's subdivide_to_size), at the end of the file
+//     k_sub_level / k_scan_* / k_sub_totals : level, children and new vertices per face, two exclusive int64 scans, three totals
+//     k_sub_copy / k_sub_verts / k_sub_faces : one thread per output element, its parent by binary search in the scans
 // No size is read back to the host; nothing here returns a status from the device.  Plain C++ and vector stores only; every
 // index that reaches memory is checked (face indices against V) or clamped (cell indices).
 #include "ngm_device.h"
@@ -421,5 +424,232 @@ int ngm_launch_nearest_point(const float* refs, int64_t M, const float* queries,
   launch_scan<int, false>(a.cell_start, &a.hdr->ncells, a.max_cells, a.scan_part, st);
   hipLaunchKernelGGL(k_np_fill, dim3(ref_blocks), dim3(256), 0, st, a);
   hipLaunchKernelGGL(k_np_query, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, a);
+  return 0;
+}
+
+// ---- subdivision to a maximum edge length -------------------------------------------------------------------------------
+// trimesh.Trimesh.subdivide_to_size (mesh_culling.py:260-261) in closed form: a face whose longest edge L needs k exact
+// halvings until L > max_edge is false becomes the uniform split into 4^k children, n = 2^k segments per edge (the rule and
+// the orders are written down in include/ngm_hip.h).
+//   k_sub_level  : one thread per face: level, number of children, number of new vertices; the largest level by atomic max
+//   k_scan_*     : exclusive int64 scans of the two counts (the scans above); k_sub_totals: the three totals
+//   k_sub_faces  : one thread per OUTPUT face: parent by binary search in the scanned child counts, row formula -> (i, j)
+//   k_sub_verts  : one thread per OUTPUT vertex: parent by binary search in the scanned vertex counts, row formula -> (i, j)
+// A workgroup's first and last thread search all faces, the others between the two parents found: no thread loops over children.
+constexpr int SUB_MAX_ITER = 10;
+constexpr int SUB_T = 256;
+
+struct SubArgs {
+  const float* verts; const int64_t* faces; const float* attrs;
+  int64_t V, F;
+  int C;
+  int* level;           // (F)
+  int64_t* vscan;       // (F + 1) new vertices per face, then their exclusive scan; [F] = total
+  int64_t* fscan;       // (F + 1) child faces per face, likewise
+  int64_t* totals;      // [new vertices, output faces, largest level]
+  double max_edge; int max_iter;
+  int64_t new_vertices, out_faces;
+  float* out_verts; int64_t* out_faces_idx; float* out_attrs; int64_t* out_parent;
+};
+
+__device__ __forceinline__ double sub_edge(const float* p, const float* q) {
+  const double dx = (double)q[0] - (double)p[0], dy = (double)q[1] - (double)p[1], dz = (double)q[2] - (double)p[2];
+  return sqrt((dx * dx + dy * dy) + dz * dz);              // contraction is off in this file: no fused multiply-add
+}
+
+__global__ __launch_bounds__(SUB_T) void k_sub_level(SubArgs a) {
+  __shared__ int red[SUB_T];
+  const int64_t f = (int64_t)blockIdx.x * SUB_T + threadIdx.x;
+  int k = 0;
+  if (f < a.F) {
+    const int64_t i0 = a.faces[3 * f], i1 = a.faces[3 * f + 1], i2 = a.faces[3 * f + 2];
+    if (i0 >= 0 && i0 < a.V && i1 >= 0 && i1 < a.V && i2 >= 0 && i2 < a.V) {
+      const float *p0 = a.verts + 3 * i0, *p1 = a.verts + 3 * i1, *p2 = a.verts + 3 * i2;
+      const double l0 = sub_edge(p0, p1), l1 = sub_edge(p1, p2), l2 = sub_edge(p2, p0);
+      // the longest as np.max takes it: a NaN length makes it NaN, which compares false -- level 0
+      double L = l0;
+      if (l1 > L) L = l1;
+      if (l2 > L) L = l2;
+      const bool nan = l0 != l0 || l1 != l1 || l2 != l2;
+      // halving is exact; +inf never passes and ends one past max_iter, as does every length that needs more rounds
+      while (!nan && L > a.max_edge && k <= a.max_iter) { L *= 0.5; ++k; }
+    }
+    const bool ok = k <= a.max_iter;                       // beyond max_iter the caller refuses: the face counts as unsplit
+    const int64_t n = (int64_t)1 << (ok ? k : 0);
+    a.level[f] = k;
+    a.fscan[f] = n * n;
+    a.vscan[f] = (n + 1) * (n + 2) / 2 - 3;
+  }
+  red[threadIdx.x] = k;
+  __syncthreads();
+  for (int s = SUB_T / 2; s > 0; s >>= 1) {
+    if (threadIdx.x < s) red[threadIdx.x] = max(red[threadIdx.x], red[threadIdx.x + s]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && red[0] > 0) atomicMax(reinterpret_cast<unsigned long long*>(a.totals + 2), (unsigned long long)red[0]);
+}
+
+__global__ void k_sub_totals(SubArgs a) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) { a.totals[0] = a.vscan[a.F]; a.totals[1] = a.fscan[a.F]; }
+}
+
+// the face p with scan[p] <= g < scan[p + 1], searched in [lo, hi] (scan has F + 1 entries, scan[F] the total); F when
+// g is at or beyond scan[hi + 1]
+__device__ __forceinline__ int64_t sub_parent(const int64_t* scan, int64_t lo, int64_t hi, int64_t g) {
+  int64_t l = lo, h = hi + 1;                              // first index in [lo, hi + 1] with scan[index + 1] > g
+  while (l < h) { const int64_t mid = l + ((h - l) >> 1); if (scan[mid + 1] > g) h = mid; else l = mid + 1; }
+  return l;
+}
+// parent of output element g for every thread of the workgroup: threads 0 and SUB_T - 1 search [0, F - 1], the rest between them
+__device__ __forceinline__ int64_t sub_parent_block(const int64_t* scan, int64_t F, int64_t g, int64_t total, int64_t* lds) {
+  const int t = threadIdx.x;
+  const bool in = g < total;
+  int64_t p = F;
+  if (t == 0 || t == SUB_T - 1) {
+    // the last thread may stand beyond the total: it searches for the last element instead
+    p = sub_parent(scan, 0, F - 1, in ? g : total - 1);
+    lds[t == 0 ? 0 : 1] = p;
+  }
+  __syncthreads();
+  if (t != 0 && t != SUB_T - 1 && in) p = sub_parent(scan, lds[0], min(lds[1], F - 1), g);
+  return in ? p : F;
+}
+
+__device__ __forceinline__ int sub_isqrt_ceil(int m) {     // ceil(sqrt(m)), 1 <= m <= 2^20
+  int s = (int)sqrtf((float)m);
+  while (s * s < m) ++s;
+  while (s > 0 && (s - 1) * (s - 1) >= m) --s;
+  return s;
+}
+// index of lattice point (i, j) of face p in the output vertices: the corners are the originals
+__device__ __forceinline__ int64_t sub_vertex_index(const SubArgs& a, int64_t p, int n, int i, int j, const int64_t (&c)[3]) {
+  if (i == 0 && j == 0) return c[0];
+  if (i == n && j == 0) return c[1];
+  if (i == 0 && j == n) return c[2];
+  const int lin = j * (n + 1) - j * (j - 1) / 2 + i;       // row j holds i = 0 .. n - j
+  return a.V + a.vscan[p] + (lin - 1 - (lin > n ? 1 : 0));
+}
+
+__global__ __launch_bounds__(SUB_T) void k_sub_faces(SubArgs a) {
+  __shared__ int64_t lds[2];
+  const int64_t g = (int64_t)blockIdx.x * SUB_T + threadIdx.x;
+  const int64_t total = min(a.out_faces, a.fscan[a.F]);
+  if ((int64_t)blockIdx.x * SUB_T >= total) return;        // the whole workgroup: nothing before the barrier
+  const int64_t p = sub_parent_block(a.fscan, a.F, g, total, lds);
+  if (p >= a.F) return;
+  const int64_t c[3] = {a.faces[3 * p], a.faces[3 * p + 1], a.faces[3 * p + 2]};
+  const int64_t children = a.fscan[p + 1] - a.fscan[p];
+  int64_t o[3] = {c[0], c[1], c[2]};
+  if (children > 1) {
+    const int n = 1 << ((63 - __clzll((unsigned long long)children)) >> 1);   // children = n * n
+    const int t = (int)(g - a.fscan[p]);
+    // row j holds 2 (n - j) - 1 children, r (2 n - r) come before row r: j = n - ceil(sqrt(n^2 - t))
+    const int j = n - sub_isqrt_ceil(n * n - t);
+    const int u = t - j * (2 * n - j);
+    const int i = u >> 1;
+    if ((u & 1) == 0) {                                    // upright: (i, j) (i + 1, j) (i, j + 1)
+      o[0] = sub_vertex_index(a, p, n, i, j, c); o[1] = sub_vertex_index(a, p, n, i + 1, j, c); o[2] = sub_vertex_index(a, p, n, i, j + 1, c);
+    } else {                                               // inverted: (i + 1, j) (i + 1, j + 1) (i, j + 1)
+      o[0] = sub_vertex_index(a, p, n, i + 1, j, c); o[1] = sub_vertex_index(a, p, n, i + 1, j + 1, c); o[2] = sub_vertex_index(a, p, n, i, j + 1, c);
+    }
+  }
+  a.out_faces_idx[3 * g] = o[0]; a.out_faces_idx[3 * g + 1] = o[1]; a.out_faces_idx[3 * g + 2] = o[2];
+  a.out_parent[g] = p;
+}
+
+// x0 w0 + x1 w1 + x2 w2 in fp64, a term of weight 0 left out, rounded once to fp32.  The weights are multiples of 2^-10 and
+// the values have 24 bits: every product is exact.  On a parent's edge one weight is 0, so the value is ONE rounding of the
+// exact sum of two products that depend on the edge's two ends and the position along it alone -- the same bits from either
+// face that shares the edge, in either order of its corners (fp64 addition commutes), at any two levels.
+__device__ __forceinline__ float sub_mix(float x0, float x1, float x2, double w0, double w1, double w2) {
+  const double t0 = (double)x0 * w0, t1 = (double)x1 * w1, t2 = (double)x2 * w2;
+  double s;
+  if (w0 == 0.0) s = (w1 == 0.0) ? t2 : ((w2 == 0.0) ? t1 : t1 + t2);
+  else if (w1 == 0.0) s = (w2 == 0.0) ? t0 : t0 + t2;
+  else if (w2 == 0.0) s = t0 + t1;
+  else s = (t0 + t1) + t2;
+  return (float)s;
+}
+
+__global__ __launch_bounds__(SUB_T) void k_sub_verts(SubArgs a) {
+  __shared__ int64_t lds[2];
+  const int64_t g = (int64_t)blockIdx.x * SUB_T + threadIdx.x;      // over the NEW vertices
+  const int64_t total = min(a.new_vertices, a.vscan[a.F]);
+  if ((int64_t)blockIdx.x * SUB_T >= total) return;
+  const int64_t p = sub_parent_block(a.vscan, a.F, g, total, lds);
+  if (p >= a.F) return;
+  const int64_t count = a.vscan[p + 1] - a.vscan[p];                // (n + 1)(n + 2) / 2 - 3 > 0: the indices were in range
+  const int64_t children = a.fscan[p + 1] - a.fscan[p];
+  const int n = 1 << ((63 - __clzll((unsigned long long)children)) >> 1);
+  const int64_t c0 = a.faces[3 * p], c1 = a.faces[3 * p + 1], c2 = a.faces[3 * p + 2];
+  const int l = (int)(g - a.vscan[p]);
+  if (count <= 0 || n < 2 || c0 < 0 || c0 >= a.V || c1 < 0 || c1 >= a.V || c2 < 0 || c2 >= a.V) return;
+  const int lin = l + 1 + (l + 1 >= n ? 1 : 0);            // the lattice point's number with the corners counted
+  // row j starts at j (2 n + 3 - j) / 2: the largest j whose start is <= lin
+  const int b = 2 * n + 3;
+  int j = (int)(((float)b - sqrtf(fmaxf((float)(b * b - 8 * lin), 0.f))) * 0.5f);
+  j = max(0, min(j, n));
+  while (j < n && (j + 1) * (b - (j + 1)) / 2 <= lin) ++j;
+  while (j > 0 && j * (b - j) / 2 > lin) --j;
+  const int i = lin - j * (b - j) / 2;
+  const double inv = 1.0 / (double)n;                      // a power of two: every weight below is exact
+  const double w0 = (double)(n - i - j) * inv, w1 = (double)i * inv, w2 = (double)j * inv;
+  const int64_t o = a.V + g;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) a.out_verts[3 * o + d] = sub_mix(a.verts[3 * c0 + d], a.verts[3 * c1 + d], a.verts[3 * c2 + d], w0, w1, w2);
+  for (int ch = 0; ch < a.C; ++ch)
+    a.out_attrs[o * a.C + ch] = sub_mix(a.attrs[c0 * a.C + ch], a.attrs[c1 * a.C + ch], a.attrs[c2 * a.C + ch], w0, w1, w2);
+}
+
+// the V originals, unchanged and in place
+__global__ __launch_bounds__(SUB_T) void k_sub_copy(SubArgs a) {
+  const int64_t g = (int64_t)blockIdx.x * SUB_T + threadIdx.x;
+  if (g < 3 * a.V) a.out_verts[g] = a.verts[g];
+  if (a.C > 0 && g < a.V * a.C) a.out_attrs[g] = a.attrs[g];
+}
+
+struct SubLayout { int* level; int64_t* vscan; int64_t* fscan; int64_t* partial; };
+static SubLayout sub_carve(void* workspace, int64_t F) {
+  char* w = reinterpret_cast<char*>(((int64_t)workspace + 255) / 256 * 256);
+  SubLayout l;
+  l.level = reinterpret_cast<int*>(w); w += up256(4 * F);
+  l.vscan = reinterpret_cast<int64_t*>(w); w += up256(8 * (F + 1));
+  l.fscan = reinterpret_cast<int64_t*>(w); w += up256(8 * (F + 1));
+  l.partial = reinterpret_cast<int64_t*>(w);
+  return l;
+}
+int64_t ngm_mesh_subdivide_bytes(int64_t F) {
+  return 256 + up256(4 * F) + 2 * up256(8 * (F + 1)) + up256(8 * (scan_partials(F) + 1));
+}
+int ngm_launch_mesh_subdivide_count(const float* verts, int64_t V, const int64_t* faces, int64_t F, double max_edge, int max_iter,
+                                    void* workspace, int64_t* totals, hipStream_t st) {
+  if (max_iter < 0 || max_iter > SUB_MAX_ITER) return -1;
+  if (hipMemsetAsync(totals, 0, 3 * sizeof(int64_t), st) != hipSuccess) return -4;
+  if (F == 0) return 0;
+  const SubLayout l = sub_carve(workspace, F);
+  SubArgs a = {};
+  a.verts = verts; a.faces = faces; a.V = V; a.F = F; a.level = l.level; a.vscan = l.vscan; a.fscan = l.fscan; a.totals = totals;
+  a.max_edge = max_edge; a.max_iter = max_iter;
+  hipLaunchKernelGGL(k_sub_level, dim3((unsigned)((F + SUB_T - 1) / SUB_T)), dim3(SUB_T), 0, st, a);
+  launch_scan<int64_t, false>(l.vscan, nullptr, F, l.partial, st);
+  launch_scan<int64_t, false>(l.fscan, nullptr, F, l.partial, st);
+  hipLaunchKernelGGL(k_sub_totals, dim3(1), dim3(64), 0, st, a);
+  return 0;
+}
+int ngm_launch_mesh_subdivide_emit(const float* verts, int64_t V, const int64_t* faces, int64_t F, const float* attrs, int C,
+                                   const void* workspace, int64_t new_vertices, int64_t out_faces, float* out_verts,
+                                   int64_t* out_faces_idx, float* out_attrs, int64_t* out_parent, hipStream_t st) {
+  const SubLayout l = sub_carve(const_cast<void*>(workspace), F);
+  SubArgs a = {};
+  a.verts = verts; a.faces = faces; a.attrs = attrs; a.V = V; a.F = F; a.C = attrs ? C : 0;
+  a.level = l.level; a.vscan = l.vscan; a.fscan = l.fscan;
+  a.new_vertices = new_vertices; a.out_faces = out_faces;
+  a.out_verts = out_verts; a.out_faces_idx = out_faces_idx; a.out_attrs = out_attrs; a.out_parent = out_parent;
+  const int64_t copy = std::max<int64_t>(3 * V, V * a.C);
+  if (copy > 0) hipLaunchKernelGGL(k_sub_copy, dim3((unsigned)((copy + SUB_T - 1) / SUB_T)), dim3(SUB_T), 0, st, a);
+  if (F > 0 && new_vertices > 0)
+    hipLaunchKernelGGL(k_sub_verts, dim3((unsigned)((new_vertices + SUB_T - 1) / SUB_T)), dim3(SUB_T), 0, st, a);
+  if (F > 0 && out_faces > 0)
+    hipLaunchKernelGGL(k_sub_faces, dim3((unsigned)((out_faces + SUB_T - 1) / SUB_T)), dim3(SUB_T), 0, st, a);
   return 0;
 }

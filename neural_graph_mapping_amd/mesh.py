@@ -292,9 +292,9 @@ def extract_mesh(renderer, mesh_file_path=None, resolution: Optional[float] = No
 # scoring a mesh (evaluation._evaluate_postprocessed_meshes, evaluation.py:163-208): surface samples of the estimated and
 # the ground-truth mesh, two exact nearest-neighbour queries between the clouds, ten numbers.  The reference runs
 # trimesh.sample.sample_surface and scipy.spatial.KDTree on the host; here both are device kernels (csrc/ngm_mesh_eval.hip)
-# and the reductions are torch on the device.  Culling (mesh_culling.py) is further down: render_mesh_depth, cull_mesh,
-# evaluate_raw_mesh.  OUT OF SCOPE: ICP alignment (evaluation._align_mesh), subdivide_to_size, LPIPS / SSIM -- callers pass
-# meshes that are aligned and fine enough.
+# and the reductions are torch on the device.  Culling (mesh_culling.py) is further down: subdivide_to_size, render_mesh_depth,
+# cull_mesh, evaluate_raw_mesh.  OUT OF SCOPE: ICP alignment (evaluation._align_mesh), LPIPS / SSIM -- callers pass meshes that
+# are aligned.
 # ------------------------------------------------------------------------------------------------
 METRIC_KEYS = ("median_acc", "median_comp", "acc", "comp", "acc_ratio", "acc_ratio_1cm", "comp_ratio", "comp_ratio_1cm",
                "f1_5cm", "f1_1cm")
@@ -416,7 +416,7 @@ def _as_mesh(m, device):
 def evaluate_mesh(est, gt, num_points: int = 200000, seed: int = 0) -> dict:
     """evaluation._evaluate_postprocessed_meshes (evaluation.py:163-208): `num_points` surface samples of each mesh
     (est with `seed`, gt with `seed + 1`), then mesh_metrics.  est / gt: a (verts, faces) pair of device tensors, or the path of
-    a PLY file save_ply wrote.  The meshes are taken as they are: culling is evaluate_raw_mesh's (below), ICP alignment and subdivision are the caller's."""
+    a PLY file save_ply wrote.  The meshes are taken as they are: culling and the subdivision before it are evaluate_raw_mesh's (below), ICP alignment is the caller's."""
     device = next((m[0].device for m in (est, gt) if not isinstance(m, (str, os.PathLike))), torch.device("cuda"))
     ev, ef = _as_mesh(est, device)
     gv, gf = _as_mesh(gt, device)
@@ -430,9 +430,10 @@ def evaluate_mesh(est, gt, num_points: int = 200000, seed: int = 0) -> dict:
 # the given poses.  The reference draws two pyrender depth maps per pose under EGL and runs about ten torch kernels per pose over
 # all vertices; here the depth maps come from a HIP rasteriser and the per-vertex decisions of all poses of a chunk from one
 # launch (csrc/ngm_mesh_cull.hip; the rule is written down in include/ngm_hip.h), selection and compaction are torch on the
-# device.  NOT BUILT: subdivide_to_size (callers pass meshes that are fine enough), ICP, reading virtual-camera files (the
-# caller appends those poses and says where they start), GL's top-left fill rule and depth-buffer quantisation (both far
-# inside eps = 0.03).
+# device.  The reference first subdivides the mesh to a maximum edge length (mesh.subdivide_to_size(max_edge),
+# mesh_culling.py:260-261): subdivide_to_size below, two kernels of csrc/ngm_mesh_eval.hip, which cull_mesh runs when it is given
+# max_edge.  NOT BUILT: ICP, reading virtual-camera files (the caller appends those poses and says where they start), GL's
+# top-left fill rule and depth-buffer quantisation (both far inside eps = 0.03).
 # ------------------------------------------------------------------------------------------------
 CULLING_METHODS = ("frustum", "occlusion", "virt_cams")
 
@@ -471,6 +472,114 @@ def _mesh_visibility_op(verts: torch.Tensor, c2ws: torch.Tensor, depth: Optional
 @_mesh_visibility_op.register_fake
 def _(verts, c2ws, depth, width, height, fx, fy, cx, cy, eps, num_frustum_poses):
     return verts.new_empty(verts.shape[0], dtype=torch.int32), verts.new_empty(verts.shape[0], dtype=torch.int32)
+
+
+SUBDIVIDE_MAX_ITER = 10                     # include/ngm_hip.h: the weights of a lattice point have at most 10 bits
+
+
+@ops._op("mesh_subdivide_count")
+def _mesh_subdivide_count_op(verts: torch.Tensor, faces: torch.Tensor, max_edge: float, max_iter: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """[totals (3) int64 = new vertices, output faces, largest level; the workspace (uint8) the emit call reads]"""
+    L = K.lib()
+    nf = faces.shape[0]
+    wsb = L.ngm_mesh_subdivide_workspace(nf)
+    if wsb < 0:
+        raise K.NgmError(f"mesh_subdivide_count: {nf} faces not supported (faces < 2^31)", code=int(wsb))
+    dev = verts.device
+    ws = torch.empty(wsb, device=dev, dtype=torch.uint8)
+    totals = torch.empty(3, device=dev, dtype=torch.int64)
+    K.check(L.ngm_mesh_subdivide_count(verts.data_ptr(), verts.shape[0], faces.data_ptr(), nf, float(max_edge), int(max_iter), ws.data_ptr(),
+                                       wsb, totals.data_ptr(), ops._stream()), "ngm_mesh_subdivide_count")
+    return totals, ws
+
+
+@_mesh_subdivide_count_op.register_fake
+def _(verts, faces, max_edge, max_iter):
+    nf = faces.shape[0]
+    chunks = max((nf + 2047) // 2048, 1)                   # the layout of ngm_mesh_subdivide_workspace, restated for shape inference
+    up = lambda b: (b + 255) // 256 * 256
+    return faces.new_empty(3), verts.new_empty(256 + up(4 * nf) + 2 * up(8 * (nf + 1)) + up(8 * (chunks + 1)), dtype=torch.uint8)
+
+
+@ops._op("mesh_subdivide_emit")
+def _mesh_subdivide_emit_op(verts: torch.Tensor, faces: torch.Tensor, attrs: Optional[torch.Tensor], workspace: torch.Tensor,
+                            new_vertices: int, out_faces: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """[verts (V + new_vertices, 3) fp32, faces (out_faces, 3) int64, attrs (V + new_vertices, C) fp32 -- C = 0 without attrs --,
+    parent (out_faces) int64]"""
+    nv, dev = verts.shape[0], verts.device
+    if nv + new_vertices >= 2 ** 31 or out_faces >= 2 ** 31:                       # before anything is allocated
+        raise K.NgmError(f"mesh_subdivide_emit: {nv + new_vertices} vertices, {out_faces} faces: the output must stay below 2^31 "
+                         "vertices and 2^31 faces", code=K.NGM_E_UNSUPPORTED)
+    c = 0 if attrs is None else attrs.shape[1]
+    out_v = torch.empty(nv + new_vertices, 3, device=dev, dtype=torch.float32)
+    out_f = torch.empty(out_faces, 3, device=dev, dtype=torch.int64)
+    out_a = torch.empty(nv + new_vertices, c, device=dev, dtype=torch.float32)
+    parent = torch.empty(out_faces, device=dev, dtype=torch.int64)
+    K.check(K.lib().ngm_mesh_subdivide_emit(verts.data_ptr(), nv, faces.data_ptr(), faces.shape[0], ops._ptr(attrs), c, workspace.data_ptr(),
+                                            new_vertices, out_faces, out_v.data_ptr(), out_f.data_ptr(), out_a.data_ptr() if c else None,
+                                            parent.data_ptr(), ops._stream()), "ngm_mesh_subdivide_emit")
+    return out_v, out_f, out_a, parent
+
+
+@_mesh_subdivide_emit_op.register_fake
+def _(verts, faces, attrs, workspace, new_vertices, out_faces):
+    n = verts.shape[0] + new_vertices
+    return (verts.new_empty(n, 3), faces.new_empty(out_faces, 3), verts.new_empty(n, 0 if attrs is None else attrs.shape[1]),
+            faces.new_empty(out_faces))
+
+
+@torch.no_grad()
+def subdivide_to_size(verts: torch.Tensor, faces: torch.Tensor, max_edge: float, max_iter: int = 10, attrs: Optional[torch.Tensor] = None,
+                      return_index: bool = False):
+    """trimesh.Trimesh.subdivide_to_size (the first step of mesh_culling._cull_mesh, mesh_culling.py:260-261) on the device:
+    verts (V, 3) fp32, faces (F, 3) int64 -> (verts, faces[, attrs][, parent]) in which no edge is longer than max_edge.
+    trimesh splits every face with an edge above max_edge into four by its edge midpoints and repeats on the children; the
+    children are similar to the parent, so the result per input face is the uniform split into 4^k, k the number of halvings of
+    its longest edge until `L > max_edge` is false (an edge equal to max_edge is not split).  Two kernels -- count and scan,
+    then emit -- with ONE read-back between them, of the three totals; the rule, the orders and why points on shared edges are
+    bit-identical from both faces (no cracks for the rasteriser) are written down in include/ngm_hip.h.
+    attrs (V, C) fp32: per-vertex attributes, interpolated with the same weights.  return_index: parent (F_out,) int64, the
+    input face of every output face (trimesh's return_index).
+    A face that needs more than max_iter halvings (a +inf edge always does) raises ValueError("max_iter exceeded") and nothing
+    is returned; a face that needs EXACTLY max_iter is accepted (whether trimesh accepts it is not pinned by any
+    fixture of this repository).  When nothing has to be split the INPUT tensors themselves are returned, uncopied.
+    A face with a NaN edge or an index outside [0, V) is copied unchanged.  max_iter > 10 is refused: the exactness argument
+    uses at most 10 weight bits.  A result of 2^31 vertices or faces or more is refused (NgmError, NGM_E_UNSUPPORTED) before
+    it is allocated.
+    Differences from trimesh: the outputs are fp32 (trimesh works on a float64 copy); the V input vertices stay in place and
+    every split face appends its own new vertices, so a vertex on an edge shared by two split faces is stored once per face
+    -- bit-identical positions, two indices.  trimesh duplicates vertices across its rounds too, and _cull_mesh loads with
+    process=False: vertex counts and orders differ, the triangles do not.
+    Dispatches through torch.ops.ngm355.mesh_subdivide_count / mesh_subdivide_emit."""
+    ops._require_gpu(verts, faces, attrs)
+    if verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32:
+        raise ValueError("subdivide_to_size expects (V, 3) float32 vertices")
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int64:
+        raise ValueError("subdivide_to_size expects (F, 3) int64 faces")
+    if attrs is not None and (attrs.dim() != 2 or attrs.shape[0] != verts.shape[0] or attrs.dtype != torch.float32):
+        raise ValueError("subdivide_to_size expects (V, C) float32 attrs")
+    if isinstance(max_edge, bool) or not isinstance(max_edge, (int, float)) or not (0 < max_edge < float("inf")):
+        raise ValueError("subdivide_to_size: max_edge must be a finite number > 0")
+    if isinstance(max_iter, bool) or not isinstance(max_iter, int) or not 0 <= max_iter <= SUBDIVIDE_MAX_ITER:
+        raise ValueError(f"subdivide_to_size: 0 <= max_iter <= {SUBDIVIDE_MAX_ITER}")
+
+    def result(v, f, a, parent):
+        return (v, f) + ((a,) if attrs is not None else ()) + ((parent(),) if return_index else ())
+
+    nf = faces.shape[0]
+    unsplit = lambda: torch.arange(nf, device=faces.device, dtype=torch.int64)
+    if nf == 0:
+        return result(verts, faces, attrs, unsplit)
+    cv, cf = verts.contiguous(), faces.contiguous()
+    totals, ws = torch.ops.ngm355.mesh_subdivide_count(cv, cf, float(max_edge), max_iter)
+    new_vertices, out_faces, max_level = (int(t) for t in totals.tolist())        # the one read-back
+    if max_level > max_iter:
+        raise ValueError("max_iter exceeded")
+    if new_vertices == 0:
+        return result(verts, faces, attrs, unsplit)
+    ca = None if attrs is None else attrs.contiguous()
+    out_v, out_f, out_a, parent = torch.ops.ngm355.mesh_subdivide_emit(cv, cf, ca, ws, new_vertices, out_faces)
+    return result(out_v, out_f, out_a, lambda: parent)
 
 
 def _cull_inputs(fn, verts, faces, c2ws, camera):
@@ -522,8 +631,12 @@ def _take(mask: torch.Tensor, n: int) -> torch.Tensor:
 @torch.no_grad()
 def cull_mesh(verts: torch.Tensor, faces: torch.Tensor, c2ws: torch.Tensor, camera, method: str, bounds=None,
               colors: Optional[torch.Tensor] = None, num_frustum_poses: Optional[int] = None, th_obs: float = 0, eps: float = 0.03,
-              bounds_eps: float = 0.02, pose_chunk: int = 16):
+              bounds_eps: float = 0.02, pose_chunk: int = 16, max_edge: Optional[float] = None, max_iter: int = 10):
     """mesh_culling._cull_mesh (mesh_culling.py:228-352) on the device, step by step:
+      0. max_edge, when given: the mesh and its colours are subdivided first (subdivide_to_size(max_edge, max_iter)) and
+         everything below runs on the result -- the reference's `subdivide=True, max_edge=0.1` (mesh_culling.py:260-261).  The
+         decisions below are per vertex: they mean something only on faces that are small against the frusta.  Colours that
+         are not fp32 are interpolated in fp32 and rounded back to their type.  None (default): the mesh is taken as it is;
       1. bounds (2, 3), when given: a face stays if ANY of its vertices is inside [lo - bounds_eps, hi + bounds_eps];
       2. method "occlusion" / "virt_cams": depth maps of the faces that are left, from every pose (render_mesh_depth);
       3. visibility of ALL original vertices (mesh_visibility), `pose_chunk` poses at a time so that depth memory is bounded;
@@ -532,7 +645,7 @@ def cull_mesh(verts: torch.Tensor, faces: torch.Tensor, c2ws: torch.Tensor, came
     Returns (verts, faces) or (verts, faces, colors) on the device.  One read-back (the two output sizes), at the end.
     The camera and the poses are taken AS GIVEN: _cull_mesh culls with dataset.camera.scaled_camera(0.5) and every second
     ground-truth pose (`[::2]`); the caller applies both.  "virt_cams": the caller appends the virtual poses (OpenGL convention) and
-    passes the index of the first as num_frustum_poses -- they add to `observed` only.  subdivide_to_size is not built.
+    passes the index of the first as num_frustum_poses -- they add to `observed` only.
     "frustum": the reference dies in torch.from_numpy(None) (mesh_culling.py:210-215); here it runs and does what
     remove_occlusion=False evidently means -- no depth maps, faces kept on in_frustum alone.
     A face with an index outside [0, V) is dropped (the reference would raise)."""
@@ -545,6 +658,15 @@ def cull_mesh(verts: torch.Tensor, faces: torch.Tensor, c2ws: torch.Tensor, came
             raise ValueError("cull_mesh expects one colour row per vertex")
     if int(pose_chunk) < 1:
         raise ValueError("cull_mesh: pose_chunk >= 1")
+    if max_edge is not None:
+        if colors is None:
+            verts, faces = subdivide_to_size(verts, faces, max_edge, max_iter)
+        else:
+            attrs = colors.reshape(colors.shape[0], -1).to(torch.float32)
+            verts, faces, attrs = subdivide_to_size(verts, faces, max_edge, max_iter, attrs=attrs)
+            if not colors.dtype.is_floating_point:
+                attrs = torch.round(attrs)
+            colors = attrs.to(colors.dtype).reshape(attrs.shape[0], *colors.shape[1:])
     occlusion = method != "frustum"
     nv, p = verts.shape[0], c2ws.shape[0]
     verts, faces, c2ws = verts.contiguous(), faces.contiguous(), c2ws.contiguous()
@@ -592,7 +714,8 @@ def evaluate_raw_mesh(est, gt, c2ws: torch.Tensor, camera, gt_culling_method: st
     """evaluation.evaluate_raw_mesh (evaluation.py:211-251): both meshes culled (cull_mesh: the ground truth with
     gt_culling_method, the estimate with est_culling_method, the same poses, camera and bounds), then evaluate_mesh on what is
     left -- the reference's headline mesh numbers without leaving the device.  est / gt as evaluate_mesh takes them;
-    cull_kwargs go to both cull_mesh calls (num_frustum_poses, th_obs, eps, bounds_eps, pose_chunk).  mesh_alignment=True (ICP,
+    cull_kwargs go to both cull_mesh calls (num_frustum_poses, th_obs, eps, bounds_eps, pose_chunk, max_edge, max_iter:
+    max_edge=0.1 is the reference's default, both meshes subdivided before they are culled).  mesh_alignment=True (ICP,
     evaluation._align_mesh) is not built and raises NotImplementedError."""
     if mesh_alignment:
         raise NotImplementedError("evaluate_raw_mesh: mesh_alignment (ICP, evaluation._align_mesh) is not built")

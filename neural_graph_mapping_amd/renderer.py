@@ -551,7 +551,8 @@ class NeuralGraphRenderer:
                           **extract_mesh_kwargs):
         """extract_mesh(**extract_mesh_kwargs) and the ground truth `gt`, both culled from the poses `c2ws` (OpenGL convention)
         seen through `camera`, then scored: mesh.evaluate_raw_mesh (evaluation.evaluate_raw_mesh, evaluation.py:211-251).
-        cull_kwargs go to both mesh.cull_mesh calls.  None where extract_mesh returns None (no surface)."""
+        cull_kwargs go to both mesh.cull_mesh calls (dict(max_edge=0.1): both meshes are subdivided first, as the reference
+        does by default).  None where extract_mesh returns None (no surface)."""
         from . import mesh
         est = self.extract_mesh(**extract_mesh_kwargs)
         if est is None:

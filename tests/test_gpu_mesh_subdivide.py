@@ -1,0 +1,459 @@
+"""-m gpu: subdividing a mesh to a maximum edge length on the device (include/ngm_hip.h ngm_mesh_subdivide_count / _emit;
+mesh.subdivide_to_size, cull_mesh(max_edge=...), evaluate_raw_mesh(max_edge=...)) against the fp64 closed-form mirror of
+tests/_mesh_subdivide_host.py, which tests/test_mesh_subdivide_cpu.py holds to trimesh's loop.
+
+Positions: within 2^-24 M (1 + 2^-20) per coordinate of the mirror's fp64 value, M the largest absolute corner coordinate of the
+parent -- half an fp32 ulp of a convex combination of the corners (the one rounding to fp32), plus slack for the fp64 sum.  Derived,
+not measured.  Levels, parents, indices and the order of vertices and faces: equal."""
+import os
+import sys
+from contextlib import contextmanager
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _mesh_cull_host as CH  # noqa: E402
+import _mesh_subdivide_host as SH  # noqa: E402
+from gpu_common import DEV  # noqa: E402
+from neural_graph_mapping_amd import _capi as K  # noqa: E402
+from neural_graph_mapping_amd import mesh as Mh  # noqa: E402
+from neural_graph_mapping_amd.renderer import Camera  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+EYE = np.eye(4, dtype=np.float32)
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def gpu_levels(verts, faces, max_edge, max_iter=10):
+    """the count call alone -> (totals [new vertices, output faces, largest level], levels (F,) read from the workspace: int32 at its
+    first 256-byte boundary)"""
+    totals, ws = torch.ops.ngm355.mesh_subdivide_count(dev(verts), dev(faces), float(max_edge), max_iter)
+    off = (-ws.data_ptr()) % 256
+    lv = ws[off:off + 4 * len(faces)].view(torch.int32).cpu().numpy()
+    return totals.tolist(), lv
+
+
+def gpu_subdivide(verts, faces, max_edge, max_iter=10, attrs=None):
+    out = Mh.subdivide_to_size(dev(verts), dev(faces), max_edge, max_iter, attrs=None if attrs is None else dev(attrs), return_index=True)
+    assert out[0].dtype == torch.float32 and out[1].dtype == torch.int64 and out[-1].dtype == torch.int64
+    return tuple(t.cpu().numpy() for t in out)
+
+
+def bar(verts, faces, parent):
+    """2^-24 M (1 + 2^-20) per output face, M the largest absolute corner coordinate of its parent"""
+    ok = ((faces >= 0) & (faces < len(verts))).all(1)
+    m = np.abs(verts.astype(np.float64)[np.where(ok[:, None], faces, 0)]).max((1, 2))
+    return (2.0 ** -24 * m * (1 + 2.0 ** -20))[parent]
+
+
+def check_against_mirror(verts, faces, max_edge, max_iter=10, attrs=None, label=""):
+    """everything the issue asks of one mesh -> (gpu outputs, mirror)"""
+    want = SH.closed_form(verts, faces, max_edge, max_iter, attrs)
+    totals, lv = gpu_levels(verts, faces, max_edge, max_iter)
+    assert np.array_equal(lv, want["levels"])                                            # the level of EVERY face
+    assert totals == [len(want["verts"]) - len(verts), len(want["faces"]), int(want["levels"].max(initial=0))]
+    out = gpu_subdivide(verts, faces, max_edge, max_iter, attrs)
+    v, f, parent = out[0], out[1], out[-1]
+    assert v.shape == want["verts"].shape and f.shape == want["faces"].shape
+    assert np.array_equal(parent, want["parent"])
+    assert np.array_equal(v[:len(verts)].view(np.uint32), verts.view(np.uint32))         # the inputs, bit for bit, in place
+    ok = ((faces >= 0) & (faces < len(verts))).all(1)[parent]
+    assert np.array_equal(f, want["faces"])                                              # the documented order, index by index
+    assert f[ok].min(initial=0) >= 0 and f[ok].max(initial=0) < len(v)
+    tol = bar(verts, faces, parent)
+    got_soup = v.astype(np.float64)[np.where(ok[:, None], f, 0)]
+    # a face with a corner that is not finite is level 0: copied, which the index comparison above has settled; positions are
+    # compared on the others
+    ok = ok & np.isfinite(tol)
+    a, oa = SH.canonical(got_soup[ok], f32_keys=True)                                   # both sorted by their fp32 values: the mirror's
+    b, ob = SH.canonical(want["soup"][ok], f32_keys=True)                               # rounded once, as the kernel rounds
+    err = np.abs(a - b).max((1, 2)) if len(a) else np.zeros(0)
+    worst = float((err / np.maximum(tol[ok][oa], 1e-300)).max(initial=0.0))
+    print(f"subdivide {label}: {len(faces)} -> {len(f)} faces, levels {np.bincount(lv).tolist()}, worst error / bar {worst:.3f}")
+    assert np.array_equal(parent[ok][oa], want["parent"][ok][ob])
+    assert (err <= tol[ok][oa]).all()
+    # vertex by vertex as well: the new vertices are in the documented order
+    vtol = bar(verts, faces, want["vert_parent"])
+    assert (np.abs(v[len(verts):].astype(np.float64) - want["verts"][len(verts):]).max(1, initial=0.0) <= vtol).all()
+    if attrs is not None:
+        got_a = out[2]
+        assert got_a.dtype == np.float32 and got_a.shape == want["attrs"].shape
+        assert np.array_equal(got_a[:len(verts)].view(np.uint32), np.asarray(attrs, np.float32).view(np.uint32))
+        corner = np.abs(np.asarray(attrs, np.float64)[np.where(((faces >= 0) & (faces < len(verts))).all(1)[:, None], faces, 0)]).max((1, 2))
+        atol = 4 * np.spacing(corner.astype(np.float32)).astype(np.float64)[want["vert_parent"]]       # 4 fp32 ulps of the largest corner attribute
+        assert (np.abs(got_a[len(verts):].astype(np.float64) - want["attrs"][len(verts):]).max(1, initial=0.0) <= atol).all()
+    return out, want
+
+
+# ------------------------------------------------------------------------------------------------ against the closed form
+@pytest.mark.parametrize("num_faces", [1, 63, 64, 65, 5000])
+def test_against_the_mirror_face_counts_and_mixed_levels(num_faces):
+    """1, 63, 64, 65 faces; 5000: more than one chunk (2048) of the scans.  Edges from a few centimetres to most of a metre at
+    max_edge 0.1: levels 0 to 3 mixed in one mesh, every one of them present from 63 faces on"""
+    verts, faces = SH.random_mesh(num_faces, 500 + num_faces, lo=0.03, hi=0.25)
+    (v, f, parent), want = check_against_mirror(verts, faces, 0.1, label=f"F={num_faces}")
+    if num_faces >= 63:
+        assert set(np.unique(want["levels"])) >= {0, 1, 2, 3}
+    # winding: every child's normal points the way its parent's does
+    pn = np.cross(*(verts.astype(np.float64)[faces[:, k]] - verts.astype(np.float64)[faces[:, 0]] for k in (1, 2)))
+    c = v.astype(np.float64)[f]
+    cn = np.cross(c[:, 1] - c[:, 0], c[:, 2] - c[:, 0])
+    assert ((cn * pn[parent]).sum(1) > 0).all()
+    # no edge is longer than max_edge (+ the rounding of its two ends)
+    e = np.linalg.norm(c - np.roll(c, 1, axis=1), axis=2).max(1)
+    assert (e <= 0.1 + 2.0 ** -21 * np.abs(c).max((1, 2))).all()
+
+
+def test_special_faces_degenerate_exactly_max_edge_exactly_twice():
+    for max_edge in (0.125, 0.37109375):
+        v, f = SH.special_faces(max_edge)
+        _, want = check_against_mirror(v, f, max_edge, label=f"special {max_edge}")
+        assert want["levels"].tolist() == [0, 0, 1]
+
+
+def long_face(length, ratio=0.375):
+    """one face whose longest edge has the given length, corners with all 24 bits in use"""
+    return np.array([(0.1, 0.2, 0.3), (0.1 + length, 0.2, 0.3), (0.1 + 0.3 * length, 0.2 + ratio * length, 0.3 + 0.01 * length)], np.float32)
+
+
+def test_one_level_7_face_among_300_small_ones():
+    """16 384 children between faces of 1 and 4: the parent search crosses many workgroups inside one face and many faces inside
+    one workgroup"""
+    sv, sf = SH.random_mesh(300, 77, lo=0.01, hi=0.03)
+    verts = np.concatenate([sv, long_face(8.0)])
+    faces = np.concatenate([sf[:100], [[len(sv), len(sv) + 1, len(sv) + 2]], sf[100:]])
+    _, want = check_against_mirror(verts, faces, 0.1, label="level 7 among 300")
+    assert want["levels"][100] == 7 and want["levels"].max() == 7 and set(np.unique(np.delete(want["levels"], 100))) == {0, 1}
+
+
+def test_one_level_8_face_in_full():
+    v = long_face(20.0)
+    _, want = check_against_mirror(v, np.array([[0, 1, 2]]), 0.1, label="level 8")
+    assert want["levels"].tolist() == [8] and len(want["faces"]) == 4 ** 8
+
+
+def test_one_level_10_face():
+    v = long_face(100.0)
+    f = np.array([[0, 1, 2]], np.int64)
+    totals, lv = gpu_levels(v, f, 0.1)
+    assert lv.tolist() == [10] and totals == [1025 * 1026 // 2 - 3, 4 ** 10, 10]
+    ov, of, parent = gpu_subdivide(v, f, 0.1)
+    assert len(of) == 4 ** 10 and len(ov) == 3 + 1025 * 1026 // 2 - 3 and not parent.any()
+    assert of.min() == 0 and of.max() == len(ov) - 1 and len(np.unique(of)) == len(ov)
+    c = ov.astype(np.float64)[of]
+    area = 0.5 * np.linalg.norm(np.cross(c[:, 1] - c[:, 0], c[:, 2] - c[:, 0]), axis=1).sum()
+    p = v.astype(np.float64)
+    parent_area = 0.5 * np.linalg.norm(np.cross(p[1] - p[0], p[2] - p[0]))
+    assert abs(area - parent_area) <= 1e-6 * parent_area
+    e = np.linalg.norm(c - np.roll(c, 1, axis=1), axis=2)
+    assert e.max() <= 0.1 + 2.0 ** -21 * np.abs(p).max()
+    pn = np.cross(p[1] - p[0], p[2] - p[0])
+    assert (np.cross(c[:, 1] - c[:, 0], c[:, 2] - c[:, 0]) @ pn > 0).all()
+
+
+# ------------------------------------------------------------------------------------------------ watertightness
+def edge_points(out_v, want, num_verts, face, a, b):
+    """bit patterns of the new vertices face `face` emitted ON its edge between corners a and b (0, 1, 2), as a set of bytes"""
+    sel = want["vert_parent"] == face
+    ij, n = want["vert_ij"][sel], want["vert_n"][sel]
+    w = np.stack([n - ij[:, 0] - ij[:, 1], ij[:, 0], ij[:, 1]], -1)
+    on = w[:, 3 - a - b] == 0
+    pts = out_v[num_verts:][sel][on]
+    return {p.tobytes() for p in pts}, int(on.sum())
+
+
+@pytest.mark.parametrize("flip", [False, True])
+@pytest.mark.parametrize("apart", [0, 1, 3])
+def test_shared_edges_are_watertight(apart, flip):
+    """two faces on one edge, the second 2^apart times as large: every position the coarser face puts on the edge is, bit for bit,
+    one of the finer face's.  flip: the second face runs along the edge the same way as the first (an inconsistent winding) instead
+    of the opposite way"""
+    rng = np.random.default_rng(40 + apart)
+    p = rng.uniform(-3, 3, 3)
+    d = rng.normal(size=3)
+    d /= np.linalg.norm(d)
+    q = p + 0.35 * d                                                                     # the shared edge: level 2 at 0.1
+    side = np.cross(d, rng.normal(size=3))
+    side /= np.linalg.norm(side)
+    r_small = (p + q) / 2 + 0.2 * side                                                   # longest edge: the shared one
+    r_large = (p + q) / 2 - (0.25 if apart == 0 else 0.3 * 2 ** apart) * side            # longest edge in (0.2, 0.4] 2^apart: `apart` levels more
+    verts = np.array([p, q, r_small, r_large], np.float32)
+    second = (0, 1, 3) if flip else (1, 0, 3)
+    faces = np.array([(0, 1, 2), second], np.int64)
+    (v, f, parent), want = check_against_mirror(verts, faces, 0.1, label=f"shared edge, levels {apart} apart, flip={flip}")
+    assert want["levels"][1] - want["levels"][0] == apart and want["levels"][0] >= 2
+    coarse, n_coarse = edge_points(v, want, 4, 0, 0, 1)
+    fine, n_fine = edge_points(v, want, 4, 1, 0, 1)
+    assert n_coarse == 2 ** want["levels"][0] - 1 and n_fine == 2 ** want["levels"][1] - 1
+    assert len(coarse) == n_coarse and len(fine) == n_fine and coarse <= fine
+    if apart == 0:
+        assert coarse == fine
+
+
+# ------------------------------------------------------------------------------------------------ attributes
+def test_attributes_are_interpolated_with_the_same_weights():
+    verts, faces = SH.random_mesh(65, 9, lo=0.03, hi=0.25)
+    rng = np.random.default_rng(3)
+    attrs = (rng.uniform(0, 255, (len(verts), 3)) * rng.choice([1.0, 1e-3, 1e3], (len(verts), 1))).astype(np.float32)
+    check_against_mirror(verts, faces, 0.1, attrs=attrs, label="attrs C=3")
+    check_against_mirror(verts, faces, 0.1, attrs=attrs[:, :1], label="attrs C=1")
+    out, _ = check_against_mirror(verts, faces, 0.1, attrs=np.concatenate([attrs, attrs[:, :2]], 1), label="attrs C=5")
+    # the position as an attribute is the position
+    got = gpu_subdivide(verts, faces, 0.1, attrs=verts)
+    assert np.array_equal(got[0].view(np.uint32), got[2].view(np.uint32))
+
+
+# ------------------------------------------------------------------------------------------------ edge cases
+def test_nan_inf_and_indices_out_of_range():
+    v = np.array([(0, 0, 0), (1, 0, 0), (0, 1, 0), (np.nan, 0, 0), (0.05, 0, 0), (0, 0.05, 0), (np.inf, 0, 0)], np.float32)
+    # a NaN vertex: level 0, copied; an index out of range: level 0, copied and never dereferenced; next to a face that is split
+    faces = np.array([(0, 1, 3), (0, 1, 2), (0, 7, 2), (-1, 1, 2), (2 ** 40, 1, 2), (0, 4, 5)], np.int64)
+    (ov, of, parent), want = check_against_mirror(v, faces, 0.1, label="NaN and bad indices")
+    assert want["levels"].tolist() == [0, 4, 0, 0, 0, 0]
+    for k in (0, 2, 3, 4, 5):
+        assert of[parent == k].tolist() == [faces[k].tolist()]
+    assert np.isnan(ov[3, 0]) and np.isfinite(np.delete(ov, [3, 6], axis=0)).all()
+    # an inf vertex: no number of halvings is enough
+    with pytest.raises(ValueError, match="max_iter exceeded"):
+        gpu_subdivide(v, np.array([(0, 1, 2), (0, 1, 6)], np.int64), 0.1)
+    totals, lv = gpu_levels(v, np.array([(0, 1, 2), (0, 1, 6)], np.int64), 0.1)
+    assert lv.tolist() == [4, 11] and totals == [17 * 18 // 2 - 3, 4 ** 4 + 1, 11]
+    # no faces, no vertices
+    out = Mh.subdivide_to_size(dev(v), dev(np.zeros((0, 3), np.int64)), 0.1, return_index=True)
+    assert out[0].shape == (7, 3) and out[1].shape == (0, 3) and out[2].shape == (0,)
+    out = Mh.subdivide_to_size(dev(np.zeros((0, 3), np.float32)), dev(np.array([(0, 1, 2)], np.int64)), 0.1)
+    assert out[0].shape == (0, 3) and out[1].tolist() == [[0, 1, 2]]
+
+
+def test_nothing_to_split_returns_the_very_same_tensors():
+    verts, faces = SH.random_mesh(500, 5, lo=0.005, hi=0.02)
+    tv, tf, ta = dev(verts), dev(faces), dev(verts[:, :2].copy())
+    assert SH.levels(verts, faces, 0.1).max() == 0
+    v, f, a, parent = Mh.subdivide_to_size(tv, tf, 0.1, attrs=ta, return_index=True)
+    assert v is tv and f is tf and a is ta and torch.equal(parent, torch.arange(500, device=DEV))
+    v, f = Mh.subdivide_to_size(tv, tf, 0.1)
+    assert v is tv and f is tf
+    # max_iter = 0: nothing may be split -- fine here, refused for a mesh with one long face
+    assert Mh.subdivide_to_size(tv, tf, 0.1, max_iter=0)[0] is tv
+    with pytest.raises(ValueError, match="max_iter exceeded"):
+        Mh.subdivide_to_size(dev(long_face(0.15)), dev(np.array([[0, 1, 2]])), 0.1, max_iter=0)
+
+
+def test_a_face_that_needs_level_11_raises_and_leaves_nothing_allocated():
+    v, f = dev(long_face(110.0)), dev(np.array([[0, 1, 2]], np.int64))
+    assert SH.levels(long_face(110.0), [[0, 1, 2]], 0.1).tolist() == [11]
+    torch.cuda.synchronize()
+    before = torch.cuda.memory_allocated()
+    with pytest.raises(ValueError, match="max_iter exceeded"):
+        Mh.subdivide_to_size(v, f, 0.1)
+    torch.cuda.synchronize()
+    assert torch.cuda.memory_allocated() == before
+    # exactly max_iter is accepted: level 7 with max_iter = 7, refused with 6
+    assert len(gpu_subdivide(long_face(8.0), np.array([[0, 1, 2]]), 0.1, max_iter=7)[1]) == 4 ** 7
+    with pytest.raises(ValueError, match="max_iter exceeded"):
+        gpu_subdivide(long_face(8.0), np.array([[0, 1, 2]]), 0.1, max_iter=6)
+    # totals of 2^31 or more are refused before the emit call allocates anything
+    with pytest.raises(K.NgmError) as e:
+        torch.ops.ngm355.mesh_subdivide_emit(v, f, None, torch.zeros(4096, dtype=torch.uint8, device=DEV), 2 ** 31, 5)
+    assert e.value.code == K.NGM_E_UNSUPPORTED
+    with pytest.raises(K.NgmError) as e:
+        torch.ops.ngm355.mesh_subdivide_emit(v, f, None, torch.zeros(4096, dtype=torch.uint8, device=DEV), 5, 2 ** 31)
+    assert e.value.code == K.NGM_E_UNSUPPORTED
+
+
+# ------------------------------------------------------------------------------------------------ safety and repeatability
+GUARD, PATTERN = 4096, 0xA5
+
+
+@contextmanager
+def guard_bands():
+    """tests/test_gpu_mesh_cull.py's guard bands: 4 KiB of pattern on either side of every torch.empty on the device -- every output
+    of the two ops and the workspace --, checked after a device synchronisation"""
+    real = torch.empty
+    raws = []
+
+    def empty(*shape, dtype=None, device=None, **kw):
+        if device is None or torch.device(device).type != "cuda" or kw:
+            return real(*shape, dtype=dtype, device=device, **kw)
+        shape = tuple(shape[0]) if len(shape) == 1 and isinstance(shape[0], (tuple, list, torch.Size)) else shape
+        dtype = dtype or torch.get_default_dtype()
+        nbytes = int(np.prod(shape, dtype=np.int64)) * real((), dtype=dtype).element_size()
+        raw = real(GUARD + nbytes + (-nbytes) % 256 + GUARD, dtype=torch.uint8, device=device)
+        raw.fill_(PATTERN)
+        raws.append((raw, nbytes))
+        return raw[GUARD:GUARD + nbytes].view(dtype).view(*shape)
+
+    torch.empty = empty
+    try:
+        yield raws
+    finally:
+        torch.empty = real
+    torch.cuda.synchronize()
+    assert raws
+    for raw, nbytes in raws:
+        assert bool((raw[:GUARD] == PATTERN).all()) and bool((raw[GUARD + nbytes:] == PATTERN).all()), nbytes
+
+
+def test_guard_bands_around_every_output_and_the_workspace():
+    big = np.concatenate([SH.random_mesh(300, 77, lo=0.01, hi=0.03)[0], long_face(8.0)])
+    big_f = np.concatenate([SH.random_mesh(300, 77, lo=0.01, hi=0.03)[1], [[len(big) - 3, len(big) - 2, len(big) - 1]]])
+    with guard_bands() as raws:
+        for n in (1, 63, 64, 65, 2049):
+            verts, faces = SH.random_mesh(n, 500 + n, lo=0.03, hi=0.25)
+            out = Mh.subdivide_to_size(dev(verts), dev(faces), 0.1, attrs=dev(verts[:, :2].copy()), return_index=True)
+            assert out[1].shape[0] == (4 ** SH.levels(verts, faces, 0.1)).sum()
+        Mh.subdivide_to_size(dev(big), dev(big_f), 0.1)
+        Mh.subdivide_to_size(dev(long_face(20.0)), dev(np.array([[0, 1, 2]])), 0.1, attrs=dev(long_face(20.0)))
+        bad = np.array([(0, 1, 2), (0, 9, 2), (-4, 1, 2)], np.int64)
+        Mh.subdivide_to_size(dev(long_face(1.0)), dev(bad), 0.1)
+    assert len(raws) >= 40                                                               # per call that splits: workspace, totals, four outputs
+
+
+def test_two_calls_are_bit_identical():
+    verts, faces = SH.random_mesh(2049, 21, lo=0.03, hi=0.25)
+    args = (dev(verts), dev(faces), 0.1)
+    a = Mh.subdivide_to_size(*args, attrs=dev(verts), return_index=True)
+    b = Mh.subdivide_to_size(*args, attrs=dev(verts), return_index=True)
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        c = Mh.subdivide_to_size(*args, attrs=dev(verts), return_index=True)
+    side.synchronize()
+    for x, y, z in zip(a, b, c):
+        bits = (lambda t: t.view(torch.int32)) if x.dtype == torch.float32 else (lambda t: t)
+        assert torch.equal(bits(x), bits(y)) and torch.equal(bits(x), bits(z))
+    assert a[1].shape[0] > 2049
+
+
+# ------------------------------------------------------------------------------------------------ cull_mesh(max_edge=...)
+WALL_CAM = CH.make_cam(160, 120, 140.0, 138.0, 80.3, 60.2)
+WALL = (np.array([(-4, -1.5, -2.5), (4, -1.5, -2.5), (4, 1.5, -2.5), (-4, 1.5, -2.5)], np.float32), np.array([(0, 1, 2), (0, 2, 3)], np.int64))
+WALL_AREA = 24.0
+PAIR_CAP, FACE_CAP = 0.01, 0.05                      # tests/test_gpu_mesh_cull.py's caps on what the mirror may call doubtful
+
+
+def wall_poses():
+    """three poses 2.5 m in front of the wall, at x = -2, 0 and 1: each sees about 2.9 x 2.2 m of it, none sees a corner"""
+    poses = np.stack([EYE, EYE, EYE]).copy()
+    poses[:, 0, 3] = (-2.0, 0.0, 1.0)
+    return poses
+
+
+def camera_of(cam):
+    return Camera(cam["W"], cam["H"], cam["fx"], cam["fy"], cam["cx"], cam["cy"], pixel_center=0.5)
+
+
+def soup_keys(verts, faces):
+    """every triangle as the bytes of its three fp32 corners, sorted (-0 -> +0)"""
+    c = (np.asarray(verts, np.float32)[faces] + np.float32(0)).astype(np.float32)
+    return [b"".join(sorted(p.tobytes() for p in t)) for t in c]
+
+
+def soup_area(verts, faces):
+    c = np.asarray(verts, np.float64)[faces]
+    return float(0.5 * np.linalg.norm(np.cross(c[:, 1] - c[:, 0], c[:, 2] - c[:, 0]), axis=1).sum())
+
+
+@pytest.mark.parametrize("method", ["frustum", "occlusion"])
+def test_cull_mesh_subdivides_first_an_8_by_3_m_wall_of_two_triangles(method):
+    verts, faces = WALL
+    poses, cam = wall_poses(), WALL_CAM
+    mirror = SH.closed_form(verts, faces, 0.1)
+    assert mirror["levels"].tolist() == [7, 7]
+    sub_v = mirror["verts"].astype(np.float32)
+    want = CH.cull(sub_v, mirror["faces"], poses, cam, method)
+    share = want["face_doubt"].sum() / len(mirror["faces"])
+    assert share <= FACE_CAP and want["pair_doubt"].mean() <= PAIR_CAP
+    v, f = Mh.cull_mesh(dev(verts), dev(faces), dev(poses), camera_of(cam), method, max_edge=0.1)
+    v, f = v.cpu().numpy(), f.cpu().numpy()
+    keys = soup_keys(sub_v, mirror["faces"])
+    got, kept = set(soup_keys(v, f)), {keys[k] for k in np.nonzero(want["keep"])[0]}
+    doubtful = {keys[k] for k in np.nonzero(want["face_doubt"])[0]}
+    assert len(got) == len(f) and got <= set(keys)                                       # triangles of the subdivided wall, bit for bit
+    area = soup_area(v, f)
+    print(f"cull_mesh {method} max_edge=0.1: {len(f)} of {len(keys)} faces kept (mirror {len(kept)}), {len(got ^ kept)} differ, "
+          f"{len(doubtful)} doubtful; area kept {area:.3f} of {WALL_AREA}")
+    assert (got ^ kept) <= doubtful
+    assert 0.0 < area < WALL_AREA and 0.3 * WALL_AREA < area < 0.9 * WALL_AREA           # strictly part of the wall
+    assert np.array_equal(np.unique(f), np.arange(len(v)))
+    # the same call without max_edge: per-vertex decisions on two triangles keep all of the wall or none of it
+    v0, f0 = Mh.cull_mesh(dev(verts), dev(faces), dev(poses), camera_of(cam), method)
+    assert len(f0) in (0, 2) and (len(f0) == 0 or soup_area(v0.cpu().numpy(), f0.cpu().numpy()) == WALL_AREA)
+    # max_edge None is the default
+    v1, f1 = Mh.cull_mesh(dev(verts), dev(faces), dev(poses), camera_of(cam), method, max_edge=None)
+    assert torch.equal(v1, v0) and torch.equal(f1, f0)
+
+
+def test_cull_mesh_subdivides_the_colours_with_the_mesh():
+    verts, faces = WALL
+    poses, cam = wall_poses(), camera_of(WALL_CAM)
+    ramp = np.stack([verts[:, 0] * 10 + 100, verts[:, 1] * 10 + 100, np.full(4, 7.0)], -1)
+    ref = Mh.cull_mesh(dev(verts), dev(faces), dev(poses), cam, "frustum", max_edge=0.1, colors=dev(ramp.astype(np.float32)))
+    assert ref[2].dtype == torch.float32 and ref[2].shape == ref[0].shape
+    # an affine ramp is reproduced by interpolation: colour = 10 position + 100, to the rounding of both
+    assert torch.allclose(ref[2][:, :2], ref[0][:, :2] * 10 + 100, rtol=0, atol=1e-4) and bool((ref[2][:, 2] == 7).all())
+    for dtype in (torch.uint8, torch.float64, torch.float16, torch.int64):
+        out = Mh.cull_mesh(dev(verts), dev(faces), dev(poses), cam, "frustum", max_edge=0.1, colors=dev(ramp).to(dtype))
+        assert out[2].dtype == dtype and torch.equal(out[0], ref[0]) and torch.equal(out[1], ref[1])
+        want = torch.round(ref[2]) if dtype in (torch.uint8, torch.int64) else ref[2]
+        assert torch.equal(out[2], want.to(dtype))
+    ids = Mh.cull_mesh(dev(verts), dev(faces), dev(poses), cam, "frustum", max_edge=0.1, colors=torch.arange(4, device=DEV))
+    assert ids[2].shape == (ref[0].shape[0],) and ids[2].dtype == torch.int64
+
+
+# ------------------------------------------------------------------------------------------------ evaluate_raw_mesh(max_edge=...)
+def icosphere(radius, centre, rounds):
+    t = (1 + 5 ** 0.5) / 2
+    v = np.array([(-1, t, 0), (1, t, 0), (-1, -t, 0), (1, -t, 0), (0, -1, t), (0, 1, t), (0, -1, -t), (0, 1, -t), (t, 0, -1), (t, 0, 1),
+                  (-t, 0, -1), (-t, 0, 1)], np.float64)
+    f = np.array([(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
+                  (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)], np.int64)
+    v /= np.linalg.norm(v, axis=1, keepdims=True)
+    for _ in range(rounds):
+        edges = np.sort(f[:, [0, 1, 1, 2, 2, 0]].reshape(-1, 2), axis=1)
+        unique, inverse = np.unique(edges, axis=0, return_inverse=True)
+        mid = v[unique].mean(1)
+        mid /= np.linalg.norm(mid, axis=1, keepdims=True)
+        m = inverse.reshape(-1, 3) + len(v)
+        f = np.column_stack([f[:, 0], m[:, 0], m[:, 2], m[:, 0], f[:, 1], m[:, 1], m[:, 2], m[:, 1], f[:, 2], m[:, 0], m[:, 1], m[:, 2]]).reshape(-1, 3)
+        v = np.vstack([v, mid])
+    return (radius * v + np.asarray(centre)).astype(np.float32), f
+
+
+SPHERE_CENTRE = (0.11, -0.05, -1.75)
+SPHERE_CAM = CH.make_cam(160, 120, 140.0, 138.0, 80.3, 60.2)
+SPHERE_POSES = np.stack([EYE, EYE]).copy()
+SPHERE_POSES[1, :3, 3] = (0.4, 0.25, 0.1)
+
+
+def test_evaluate_raw_mesh_subdivides_both_meshes_first():
+    """the two concentric spheres of tests/test_gpu_mesh_cull.py as icospheres of 320 faces, edges of about 0.2 m: with max_edge = 0.1
+    the ten numbers are those of evaluate_mesh on the two meshes subdivided and then culled one call at a time"""
+    est, gt = icosphere(0.62, SPHERE_CENTRE, 2), icosphere(0.6, SPHERE_CENTRE, 2)
+    cam, poses = camera_of(SPHERE_CAM), dev(SPHERE_POSES)
+    assert SH.edge_lengths(est[0].astype(np.float64), est[1]).min() > 0.1 and SH.levels(*gt, 0.1).min() >= 1
+    m = Mh.evaluate_raw_mesh((dev(est[0]), dev(est[1])), (dev(gt[0]), dev(gt[1])), poses, cam, "occlusion", "occlusion", num_points=20000, seed=0,
+                             max_edge=0.1)
+    assert tuple(m) == Mh.METRIC_KEYS and len(m) == 10 and all(np.isfinite(x) for x in m.values())
+    culled = []
+    for v, f in (est, gt):
+        sv, sf = Mh.subdivide_to_size(dev(v), dev(f), 0.1)
+        assert sf.shape[0] >= 4 * len(f)
+        cv, cf = Mh.cull_mesh(sv, sf, poses, cam, "occlusion")
+        assert 0.1 * sf.shape[0] < cf.shape[0] < 0.8 * sf.shape[0]
+        culled.append((cv, cf))
+    ref = Mh.evaluate_mesh(culled[0], culled[1], num_points=20000, seed=0)
+    print("subdivided half-visible spheres:", {k: round(x, 5) for k, x in m.items()})
+    for k in m:
+        assert m[k] == ref[k], (k, m[k], ref[k])
+    coarse = Mh.evaluate_raw_mesh((dev(est[0]), dev(est[1])), (dev(gt[0]), dev(gt[1])), poses, cam, "occlusion", "occlusion", num_points=20000, seed=0)
+    assert coarse != m                                                                    # the rims are cut elsewhere on the coarse faces
+    with pytest.raises(NotImplementedError):
+        Mh.evaluate_raw_mesh((dev(est[0]), dev(est[1])), (dev(gt[0]), dev(gt[1])), poses, cam, "occlusion", "occlusion", mesh_alignment=True,
+                             max_edge=0.1)
