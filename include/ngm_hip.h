@@ -125,7 +125,10 @@ enum ngm_activation_stash { NGM_STASH_FULL = 0, NGM_STASH_HALF = 1 };
 /* NGM_HASH_ATOMICS_EXACT (default): Q23.40 fixed-point integer LDS atomics -- order-independent, the table gradient is
  * bitwise reproducible.  NGM_HASH_ATOMICS_FLOAT (opt-in): fp32 LDS atomics, what the reference's CUDA package does with its
  * global float atomics -- the same sums up to the rounding of the order the adds happen to land in (NOT reproducible run
- * to run), half the LDS per workgroup, no fixed-point conversion. */
+ * to run), half the LDS per workgroup, no fixed-point conversion.
+ * The table gradient keeps one level's accumulators in LDS: every backward (ngm_encode_bwd, ngm_field_eval_bwd*, the render
+ * backward) takes log2_hashmap_size <= 13 with EXACT, <= 14 with FLOAT, and returns NGM_E_UNSUPPORTED before it launches
+ * anything for a larger table.  The forward entry points take every table size check_field_cfg accepts. */
 enum ngm_hash_grad_atomics { NGM_HASH_ATOMICS_EXACT = 0, NGM_HASH_ATOMICS_FLOAT = 1 };
 
 /* fills cfg->level_scale from nr_levels / coarsest_scale / finest_scale (double precision) */

@@ -340,6 +340,9 @@ static BwdPlan plan_mlp_bwd(const ngm_field_cfg* fc, const BwdAsk& q) {
   auto refuse = [&](int status, const char* why) { p.status = status; p.why = why; return p; };
   if (L > 2)
     return refuse(NGM_E_UNSUPPORTED, "num_layers = 3 is forward only (point evaluation, fused render forward, kNN evaluation): no backward kernel");
+  // the table gradient follows the MLP backward in every backward: a table it does not take is refused here, not after that launch
+  if (fc->encoding == NGM_ENC_PERMUTO && !ngm_hash_grad_takes(*fc))
+    return refuse(NGM_E_UNSUPPORTED, "permutohedral backward: hash table too large for the LDS-staged scatter");
   // Compositing backward inside the MLP backward: the loss (not explicit seeds) in a pointwise geometry mode, per-ray seeds
   // the forward wrote for these targets, ray indices that fit 24 bits, and a stash kernel that takes the fused problem.  The
   // variance-weighted loss modes (gradients through the rendered variances) are k_stash_bwd's.
@@ -781,6 +784,8 @@ int ngm_encode_bwd(const ngm_field_cfg* fcfg, const ngm_params* params, int32_t 
     return check_launch("ngm_encode_bwd");
   }
   if (!grads->lattice) return fail(NGM_E_INVALID, "ngm_encode_bwd: grads->lattice is NULL");
+  // refused before the preparation kernel is launched, not after it
+  if (!ngm_hash_grad_takes(*fcfg)) return fail(NGM_E_UNSUPPORTED, "ngm_encode_bwd: table size not supported by the table-gradient kernel");
   FieldBwdArgs a;
   memset(&a, 0, sizeof(a));
   a.fc = *fcfg; a.pr = *params; a.F = F; a.P = P;

@@ -231,7 +231,9 @@ struct HashCtx {
 // Simplex search of one level (Adams et al. 2010, as restated in oracle/ngm_oracle.py:encode_permuto, whose operation order
 // the comments below refer to as "the restatement").  Round 3 rewrite, bit-identical to the literal transcription it
 // replaces (tools/micro/simplex_check.hip: 1.07e9 random and tie-provoking points, 0 differences; 122 instead of 175 VALU
-// instructions per call, 1182 -> 835 ns per call and wave at four waves per SIMD):
+// instructions per call, 1182 -> 835 ns per call and wave at four waves per SIMD).  Against the restatement itself, run in
+// float32 on the same float32 points, tests/test_gpu_permuto_exact.py holds every kernel that calls this at rounding-level
+// bars (equal indices; weights equal now that bw[0] is associated as the restatement associates it, see below):
 //  * nearest remainder-0 point: the restatement takes ceil / floor of el / 4 and compares the two distances (the lower one
 //    wins a tie); that is round-half-down of v = el / 4 = rint(v), minus one where rint went UP at an exact tie
 //    (rint(v) - v is exact, so the tie test is);
@@ -288,7 +290,10 @@ __device__ __forceinline__ void permuto_simplex(float x, float y, float z, const
     d[kk] = e0 ? delta[0] : e1 ? delta[1] : e2 ? delta[2] : delta[3];
     q[kk] = e0 ? 4u * P3 : e1 ? 4u * P2 : e2 ? 4u * P1 : 0u;
   }
-  bw[0] = d[3] + (1.0f + (0.f - d[0]));
+  // the restatement's association, (bary[0] + 1) + bary[4] with bary[0] = d[3], bary[4] = -d[0].  d[3] + (1 + (0 - d[0])) is as
+  // accurate but rounds differently: up to an ulp of 1 apart in ABSOLUTE terms, which is unbounded relative to a small weight
+  // and showed in the table gradient (d * bw[0]) at several times its rounding-level bar (tests/test_gpu_permuto_exact.py)
+  bw[0] = (d[3] + 1.0f) - d[0];
   bw[1] = d[2] - d[3];
   bw[2] = d[1] - d[2];
   bw[3] = d[0] - d[1];

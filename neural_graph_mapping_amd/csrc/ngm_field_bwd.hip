@@ -1079,6 +1079,12 @@ __global__ void k_hash_reduce(HashGradArgs a) {
   }
 }
 
+static size_t hash_grad_lds(const ngm_field_cfg& fc) {
+  const bool flt = fc.hash_grad_atomics == NGM_HASH_ATOMICS_FLOAT;
+  return ((size_t)2 << fc.log2_hashmap_size) * (flt ? sizeof(float) : sizeof(unsigned long long));
+}
+bool ngm_hash_grad_takes(const ngm_field_cfg& fc) { return hash_grad_lds(fc) <= 150 * 1024; }
+
 int ngm_launch_hash_grad(const FieldBwdArgs& fb, hipStream_t st, bool* adam_applied, const GradReduceArgs* mlp_reduce,
                          bool* mlp_reduced) {
   HashGradArgs a;
@@ -1090,8 +1096,8 @@ int ngm_launch_hash_grad(const FieldBwdArgs& fb, hipStream_t st, bool* adam_appl
   a.num_active = fb.num_active;
   const int T = 1 << fb.fc.log2_hashmap_size;
   const bool flt = fb.fc.hash_grad_atomics == NGM_HASH_ATOMICS_FLOAT;
-  const size_t lds = (size_t)2 * T * (flt ? sizeof(float) : sizeof(unsigned long long));
-  if (lds > 150 * 1024) return NGM_E_UNSUPPORTED;
+  const size_t lds = hash_grad_lds(fb.fc);
+  if (!ngm_hash_grad_takes(fb.fc)) return NGM_E_UNSUPPORTED;
   const int units = (int)fb.F * fb.fc.nr_levels;      // (field, level)
   constexpr int NT = 512;                              // threads per workgroup (table gradient and the riding MLP reduction)
   // One level per workgroup: 2 blocks per CU = exactly what is resident at a time (64 KB of LDS each), one round: with the

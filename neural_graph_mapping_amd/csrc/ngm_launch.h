@@ -134,6 +134,10 @@ bool ngm_field_bwd16s_takes(const ngm_field_cfg& fc, const BwdProblem& q);   // 
 bool ngm_field_bwd16_takes(const ngm_field_cfg& fc, const BwdProblem& q);    // variant 1
 bool ngm_field_bwd_takes(const ngm_field_cfg& fc, const BwdProblem& q);      // variant 0
 struct GradReduceArgs;
+// The table-gradient kernel keeps one level's table in LDS (2 T accumulators of 8 bytes, 4 with float atomics): it takes
+// log2_hashmap_size <= 13, 14 with NGM_HASH_ATOMICS_FLOAT.  Asked by the entry points before they launch anything; the launcher
+// returns NGM_E_UNSUPPORTED for what this rejects.
+bool ngm_hash_grad_takes(const ngm_field_cfg& fc);
 // mlp_reduce (optional): the MLP's gradient reduction (+ Adam) to run as extra workgroups of the same launch; *mlp_reduced tells
 // the caller that it did (no ngm_launch_grad_reduce needed then)
 int ngm_launch_hash_grad(const FieldBwdArgs& a, hipStream_t st, bool* adam_applied = nullptr, const GradReduceArgs* mlp_reduce = nullptr,

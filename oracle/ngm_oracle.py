@@ -306,21 +306,13 @@ def permuto_scale_factors(fs: FieldSpec, dtype=torch.float32):
     return (ax[None, :] / sig[:, None]).to(dtype)
 
 
-def encode_permuto(x, lattice, shift, fs: FieldSpec):
-    """Multi-resolution permutohedral-lattice hash encoding; x (F,P,3) in the field frame, lattice
-    (F,L,T,2), shift (F,L,3) -> (F,P,2L).
-
-    *** PARITY UNPINNED *** The reference only wraps `permutohedral_encoding.PermutoEncoding`
-    (roym899 fork @ bf445adb, pyproject.toml:21), a CUDA package that is not vendored and cannot be
-    built or run here, and the reference has no tests for it.  This is a restatement of the published
-    algorithm (Adams, Baek, Davis 2010 "Fast high-dimensional filtering using the permutohedral
-    lattice"; Rosu & Behnke 2023 "PermutoSDF"): elevate the scaled point onto the hyperplane
-    sum = 0 of R^4, round to the nearest remainder-0 lattice point, rank the residuals to find the
-    enclosing simplex, barycentric weights, hash every simplex vertex key into a table of T entries per
-    level, blend the F=2 features.  It is the definition the HIP kernels are tested against.
-    Differentiable w.r.t. `lattice` only (as the CUDA package: no gradient to positions/shifts here)."""
+def permuto_simplex(x, shift, fs: FieldSpec, T: int):
+    """The simplex search of `encode_permuto`, in the dtype of `x`: x (F,P,3) in the field frame, shift (F,L,3) ->
+    (idx int64 (F,P,L,4): the table entries of the four vertices of the enclosing simplex at every level, in a table of T
+    entries; bary (F,P,L,4): their barycentric weights).  Elevate the scaled point onto the hyperplane sum = 0 of R^4, round
+    to the nearest remainder-0 lattice point, rank the residuals, barycentric weights, hash every vertex key."""
     F, P, _ = x.shape
-    L, T = lattice.shape[1], lattice.shape[2]
+    L = shift.shape[1]
     d = 3
     scale = permuto_scale_factors(fs, x.dtype)                                   # (L,3)
     cf = (x[:, :, None, :] + shift[:, None, :, :]) * scale[None, None]           # (F,P,L,3)
@@ -351,16 +343,36 @@ def encode_permuto(x, lattice, shift, fs: FieldSpec):
     bary.scatter_add_(-1, d - rank, delta)
     bary.scatter_add_(-1, d + 1 - rank, -delta)
     bary[..., 0] = bary[..., 0] + 1.0 + bary[..., d + 1]
-    out = x.new_zeros(F, P, L, lattice.shape[-1])
-    fi = torch.arange(F)[:, None, None].expand(F, P, L)
-    li = torch.arange(L)[None, None, :].expand(F, P, L)
+    idx = []
     for r in range(d + 1):
         key = rem0[..., :d] + r - (rank[..., :d] > d - r) * (d + 1)               # (F,P,L,3) int64
         h = torch.zeros(F, P, L, dtype=torch.int64)
         for i in range(d):
             h = ((h + key[..., i]) * 2531011) & 0xFFFFFFFF                        # uint32 wrap-around
-        idx = h % T
-        out = out + lattice[fi, li, idx] * bary[..., r:r + 1]
+        idx.append(h % T)
+    return torch.stack(idx, -1), bary[..., :d + 1]
+
+
+def encode_permuto(x, lattice, shift, fs: FieldSpec):
+    """Multi-resolution permutohedral-lattice hash encoding; x (F,P,3) in the field frame, lattice
+    (F,L,T,2), shift (F,L,3) -> (F,P,2L).
+
+    *** PARITY UNPINNED *** The reference only wraps `permutohedral_encoding.PermutoEncoding`
+    (roym899 fork @ bf445adb, pyproject.toml:21), a CUDA package that is not vendored and cannot be
+    built or run here, and the reference has no tests for it.  This is a restatement of the published
+    algorithm (Adams, Baek, Davis 2010 "Fast high-dimensional filtering using the permutohedral
+    lattice"; Rosu & Behnke 2023 "PermutoSDF"): `permuto_simplex` finds the enclosing simplex of every
+    level, its barycentric weights and the table entries of its four vertices; the F=2 features of the
+    vertices are blended here.  It is the definition the HIP kernels are tested against.
+    Differentiable w.r.t. `lattice` only (as the CUDA package: no gradient to positions/shifts here)."""
+    F, P, _ = x.shape
+    L, T = lattice.shape[1], lattice.shape[2]
+    idx, bary = permuto_simplex(x, shift, fs, T)
+    out = x.new_zeros(F, P, L, lattice.shape[-1])
+    fi = torch.arange(F)[:, None, None].expand(F, P, L)
+    li = torch.arange(L)[None, None, :].expand(F, P, L)
+    for r in range(idx.shape[-1]):
+        out = out + lattice[fi, li, idx[..., r]] * bary[..., r:r + 1]
     return out.reshape(F, P, L * lattice.shape[-1])
 
 
