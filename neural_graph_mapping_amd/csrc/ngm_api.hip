@@ -7,6 +7,7 @@
 
 #include "../../include/ngm_hip.h"
 #include "ngm_launch.h"
+#include "ngm_workspace.h"
 
 int ngm_launch_sampler_weighted(const ngm_render_cfg* rc, const ngm_rays* rays, int S, int B, const float* boundaries,
                                 const float* weights, float* points_cam, float* distances, float* dirs, hipStream_t st);
@@ -30,13 +31,13 @@ int ngm_launch_mc_emit(const float* vol, int nx, int ny, int nz, float iso, floa
 int ngm_mc_copy_tables(int8_t* tri_table, int32_t* tri_count);
 int64_t ngm_surface_sample_bytes(int64_t num_faces);
 int ngm_launch_surface_sample(const float* verts, int64_t V, const int64_t* faces, int64_t F, int64_t N, uint64_t seed, float* points,
-                              int64_t* face_ids, void* workspace, hipStream_t st);
+                              int64_t* face_ids, void* workspace, int64_t workspace_bytes, hipStream_t st);
 int64_t ngm_nearest_point_bytes(int64_t M, int64_t N);
 int ngm_launch_nearest_point(const float* refs, int64_t M, const float* queries, int64_t N, float* dist, int64_t* index, void* workspace,
-                             hipStream_t st);
+                             int64_t workspace_bytes, hipStream_t st);
 int64_t ngm_mesh_subdivide_bytes(int64_t F);
 int ngm_launch_mesh_subdivide_count(const float* verts, int64_t V, const int64_t* faces, int64_t F, double max_edge, int max_iter,
-                                    void* workspace, int64_t* totals, hipStream_t st);
+                                    void* workspace, int64_t workspace_bytes, int64_t* totals, hipStream_t st);
 int ngm_launch_mesh_subdivide_emit(const float* verts, int64_t V, const int64_t* faces, int64_t F, const float* attrs, int C,
                                    const void* workspace, int64_t new_vertices, int64_t out_faces, float* out_verts,
                                    int64_t* out_faces_idx, float* out_attrs, int64_t* out_parent, hipStream_t st);
@@ -172,7 +173,6 @@ static int num_cus() {
   (void)hipGetLastError();
   return cached;
 }
-static inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 // ---- the forward plan ----------------------------------------------------------------------------------------------------------
 // Which forward instance a call runs -- shape, arithmetic, wave step -- and how it is launched: plan_fwd fills one FwdPlan
 // (ngm_launch.h) from plain values, before anything is carved or launched; the launchers switch on it.
@@ -543,9 +543,8 @@ static int target_sample_mv(const char* fn, bool is_live, const ngm_keyframes* k
       !out->term_mask)
     return refuse(NGM_E_INVALID, "NULL output array");
   if ((int64_t)s->capacity * s->num_rays > INT32_MAX) return refuse(NGM_E_UNSUPPORTED, "capacity x num_rays >= 2^31");
-  const int64_t need = ngm_target_sample_mv_bytes(kf->num_frames, s->num_current, s->num_fields, s->capacity);
-  if (!workspace || workspace_bytes < need) return refuse(NGM_E_WORKSPACE, "workspace too small");
-  ngm_launch_target_sample_mv(*kf, *s, is_live ? live : nullptr, *out, workspace, (hipStream_t)stream, num_fields_dev);
+  if (ngm_launch_target_sample_mv(*kf, *s, is_live ? live : nullptr, *out, workspace, workspace_bytes, (hipStream_t)stream, num_fields_dev))
+    return refuse(NGM_E_WORKSPACE, "workspace too small");
   return check_launch(fn);
 }
 int64_t ngm_target_sample_mv_workspace(int32_t num_frames, int32_t num_current, int32_t num_fields, int32_t capacity) {
@@ -602,9 +601,8 @@ static int observed_fields(const ngm_observed_fields* a, const int32_t* num_fiel
   if (!a->rgbd || !a->c2w || (a->num_fields > 0 && (!a->field_positions || !a->current_field_ids)) || !a->current_count || !a->pixels ||
       !a->num_used || (a->frame < 0 && !a->frame_dev))
     return fail(NGM_E_INVALID, "ngm_target_observed_fields: NULL array (frame < 0 needs frame_dev)");
-  const int64_t need = ngm_target_observed_fields_bytes(a->height, a->width);
-  if (!workspace || workspace_bytes < need) return fail(NGM_E_WORKSPACE, "ngm_target_observed_fields: workspace too small");
-  ngm_launch_target_observed_fields(*a, workspace, (hipStream_t)stream, num_fields_dev);
+  if (ngm_launch_target_observed_fields(*a, workspace, workspace_bytes, (hipStream_t)stream, num_fields_dev))
+    return fail(NGM_E_WORKSPACE, "ngm_target_observed_fields: workspace too small");
   return check_launch("ngm_target_observed_fields");
 }
 
@@ -746,14 +744,29 @@ int ngm_encode_fwd(const ngm_field_cfg* fcfg, const ngm_params* params, int32_t 
   return check_launch("ngm_encode_fwd");
 }
 
-static int64_t hash_scratch_bytes(const ngm_field_cfg* fc, int F, int64_t P);
-static void carve_hash_scratch(const ngm_field_cfg* fc, int F, int64_t P, char* base, FieldBwdArgs& a);
+static int64_t tri_numel(const ngm_field_cfg* fc) {       // floats of one field's planes (3, C, res, res)
+  const int64_t C = fc->tri_mode == NGM_TRI_CONCAT ? fc->dim_enc / 3 : fc->dim_enc;
+  return 3 * C * fc->tri_resolution * fc->tri_resolution;
+}
+// The encoding's backward scratch, continuing its holder's arena (render, field-eval backward, encode backward): permutohedral
+// dL/dE per sample and level, scaled local positions, per-workgroup table partials; triplane the Q23.40 accumulators
+static void hash_scratch_layout(const ngm_field_cfg* fc, int F, int64_t P, FieldBwdArgs& a, WsArena& ws) {
+  if (fc->encoding == NGM_ENC_TRIPLANE) { a.tri_numel = tri_numel(fc); a.tri_acc = ws.take<long long>((int64_t)F * a.tri_numel); return; }
+  if (fc->encoding != NGM_ENC_PERMUTO) return;
+  a.hash_dE = ws.take<float2>((int64_t)fc->nr_levels * F * P);
+  a.hash_xyz = ws.take<float4>((int64_t)F * P);
+  a.hash_part = ws.take<float>((int64_t)F * fc->nr_levels * 8 * 2 * ((int64_t)1 << fc->log2_hashmap_size));
+}
 
+// the standalone encoding backward: the Fourier kernel's per-workgroup partials, or the permutohedral scratch
+static void encode_bwd_layout(const ngm_field_cfg* fc, int F, int64_t P, float** fourier_part, FieldBwdArgs& a, WsArena& ws) {
+  if (fc->encoding == NGM_ENC_FOURIER) *fourier_part = ws.take<float>(ngm_encode_bwd_fourier_scratch(F, P) / 4);
+  if (fc->encoding == NGM_ENC_PERMUTO) hash_scratch_layout(fc, F, P, a, ws);
+}
 int64_t ngm_encode_bwd_workspace(const ngm_field_cfg* fcfg, int32_t F, int64_t P) {
   if (!fcfg || F < 1 || P < 0) return NGM_E_INVALID;
-  if (fcfg->encoding == NGM_ENC_PERMUTO) return hash_scratch_bytes(fcfg, F, P) + 512;
-  if (fcfg->encoding == NGM_ENC_FOURIER) return ngm_encode_bwd_fourier_scratch(F, P) + 512;
-  return 256;
+  float* fourier_part;
+  return ws_bytes(encode_bwd_layout, fcfg, F, P, &fourier_part, FieldBwdArgs());
 }
 
 int ngm_encode_bwd(const ngm_field_cfg* fcfg, const ngm_params* params, int32_t F, int64_t P, const float* points,
@@ -768,8 +781,12 @@ int ngm_encode_bwd(const ngm_field_cfg* fcfg, const ngm_params* params, int32_t 
   if (fcfg->encoding == NGM_ENC_TRIPLANE)
     return fail(NGM_E_UNSUPPORTED, "ngm_encode_bwd: the triplane encoding has no standalone backward stage (ngm_field_eval_bwd)");
   if (fcfg->encoding != NGM_ENC_PERMUTO && fcfg->encoding != NGM_ENC_FOURIER) return NGM_OK;     // no parameters
-  if (!workspace || workspace_bytes < ngm_encode_bwd_workspace(fcfg, F, P)) return fail(NGM_E_WORKSPACE, "ngm_encode_bwd: workspace too small");
-  char* base = reinterpret_cast<char*>(align_up((int64_t)workspace, 256));
+  FieldBwdArgs a;
+  memset(&a, 0, sizeof(a));
+  float* fourier_part = nullptr;
+  WsArena ws(workspace);
+  encode_bwd_layout(fcfg, F, P, &fourier_part, a, ws);
+  if (!workspace || !ws.covers(workspace_bytes)) return fail(NGM_E_WORKSPACE, "ngm_encode_bwd: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   if (fcfg->encoding == NGM_ENC_FOURIER) {
     if (!grads->enc_w) return fail(NGM_E_INVALID, "ngm_encode_bwd: grads->enc_w is NULL");
@@ -779,17 +796,14 @@ int ngm_encode_bwd(const ngm_field_cfg* fcfg, const ngm_params* params, int32_t 
       return check_launch("ngm_encode_bwd");
     }
     rc = ngm_launch_encode_bwd_fourier(*fcfg, *params, F, P, points, field_pos, field_quat, d_enc, grads->enc_w, grads->enc_w_stride,
-                                       reinterpret_cast<float*>(base), st);
+                                       fourier_part, st);
     if (rc) return fail(rc, "ngm_encode_bwd: launch failed");
     return check_launch("ngm_encode_bwd");
   }
   if (!grads->lattice) return fail(NGM_E_INVALID, "ngm_encode_bwd: grads->lattice is NULL");
   // refused before the preparation kernel is launched, not after it
   if (!ngm_hash_grad_takes(*fcfg)) return fail(NGM_E_UNSUPPORTED, "ngm_encode_bwd: table size not supported by the table-gradient kernel");
-  FieldBwdArgs a;
-  memset(&a, 0, sizeof(a));
   a.fc = *fcfg; a.pr = *params; a.F = F; a.P = P;
-  carve_hash_scratch(fcfg, F, P, base, a);
   a.lattice_grad = grads->lattice; a.lattice_grad_stride = grads->lattice_stride;
   if (P == 0) {
     const int64_t n = (int64_t)fcfg->nr_levels * ((int64_t)1 << fcfg->log2_hashmap_size) * 2;
@@ -802,34 +816,23 @@ int ngm_encode_bwd(const ngm_field_cfg* fcfg, const ngm_params* params, int32_t 
   return check_launch("ngm_encode_bwd");
 }
 
-// permutohedral backward scratch: dL/dE per sample and level (8 B) + scaled local position (16 B)
-static int64_t tri_numel(const ngm_field_cfg* fc) {       // floats of one field's planes (3, C, res, res)
-  const int64_t C = fc->tri_mode == NGM_TRI_CONCAT ? fc->dim_enc / 3 : fc->dim_enc;
-  return 3 * C * fc->tri_resolution * fc->tri_resolution;
-}
-static int64_t hash_scratch_bytes(const ngm_field_cfg* fc, int F, int64_t P) {
-  if (fc->encoding == NGM_ENC_TRIPLANE) return align_up((int64_t)F * tri_numel(fc) * 8, 256);   // Q23.40 accumulators
-  if (fc->encoding != NGM_ENC_PERMUTO) return 0;
-  const int64_t part = (int64_t)F * fc->nr_levels * 8 * 2 * ((int64_t)1 << fc->log2_hashmap_size) * 4;
-  return align_up((int64_t)fc->nr_levels * F * P * 8, 256) + align_up((int64_t)F * P * 16, 256) + align_up(part, 256);
-}
-static void carve_hash_scratch(const ngm_field_cfg* fc, int F, int64_t P, char* base, FieldBwdArgs& a) {
-  if (fc->encoding == NGM_ENC_TRIPLANE) { a.tri_acc = reinterpret_cast<long long*>(base); a.tri_numel = tri_numel(fc); return; }
-  if (fc->encoding != NGM_ENC_PERMUTO) return;
-  a.hash_dE = reinterpret_cast<float2*>(base);
-  a.hash_xyz = reinterpret_cast<float4*>(base + align_up((int64_t)fc->nr_levels * F * P * 8, 256));
-  a.hash_part = reinterpret_cast<float*>(base + align_up((int64_t)fc->nr_levels * F * P * 8, 256) + align_up((int64_t)F * P * 16, 256));
-}
 static int64_t param_pad(const ngm_field_cfg* fc) {
   int64_t e, w[NGM_MAX_LAYERS + 1], b[NGM_MAX_LAYERS + 1];
   return align_up(ngm_param_offsets(fc, &e, w, b), 64);
 }
 
+// point-mode backward (a.F, a.blocks_per_field, a.p_pad are set): per-workgroup gradient partials (+ 64 floats), the scratch
+static void field_eval_bwd_layout(const ngm_field_cfg* fc, int64_t P, FieldBwdArgs& a, WsArena& ws) {
+  a.partials = ws.take<float>((int64_t)a.F * a.blocks_per_field * a.p_pad + 64);
+  hash_scratch_layout(fc, a.F, P, a, ws);
+}
 int64_t ngm_field_eval_bwd_workspace(const ngm_field_cfg* fcfg, int32_t F, int64_t P) {
   if (check_field_cfg(fcfg)) return NGM_E_INVALID;
-  int64_t per; int bpf;
-  plan_bwd(F, P, &per, &bpf);
-  return align_up((int64_t)F * bpf * param_pad(fcfg) * 4 + 256, 256) + hash_scratch_bytes(fcfg, F, P) + 256;
+  FieldBwdArgs a = FieldBwdArgs();
+  int64_t per;
+  a.F = F; a.p_pad = param_pad(fcfg);
+  plan_bwd(F, P, &per, &a.blocks_per_field);
+  return ws_bytes(field_eval_bwd_layout, fcfg, P, a);
 }
 
 // ---- point evaluation: forward, training forward and backward ------------------------------------------------------------------
@@ -837,11 +840,16 @@ int64_t ngm_field_eval_bwd_workspace(const ngm_field_cfg* fcfg, int32_t F, int64
 // offered (ABI 11: ngm_field_eval_fwd_train / ngm_field_eval_bwd_stash) the forward writes what the fused step's forward writes
 // (ActStash, 256 B per sample and hidden layer) and k_field_bwd_b3 reads it in point mode; without one the backward recomputes.
 static BwdPlan plan_points(const ngm_field_cfg* fc, int32_t F, int64_t P, bool stash_offered) { return plan_mlp_bwd(fc, BwdAsk{nullptr, F, P, false, stash_offered}); }
-static int64_t field_eval_stash_stride(int32_t F, int64_t P) { return align_up((int64_t)F * P, 32) * 64 + 2048; }   // floats per layer
+// the point-mode stash: per layer whole 32-sample tiles (+1: a field may start mid-tile) of 64 activations, + 16 floats
+static float* field_eval_stash_layout(const ngm_field_cfg* fc, int32_t F, int64_t P, int64_t* layer_stride, WsArena& ws) {
+  *layer_stride = align_up((int64_t)F * P, 32) * 64 + 2048;
+  return ws.take<float>(fc->num_layers * *layer_stride + 16);
+}
 int64_t ngm_field_eval_stash_bytes(const ngm_field_cfg* fcfg, int32_t F, int64_t P) {
   if (check_field_cfg(fcfg) || F < 1 || P < 0) return NGM_E_INVALID;
   if (P == 0 || !plan_points(fcfg, F, P, true).stash_kind) return 0;
-  return align_up(fcfg->num_layers * field_eval_stash_stride(F, P) * 4 + 64, 256) + 256;
+  int64_t stride;
+  return ws_bytes(field_eval_stash_layout, fcfg, F, P, &stride);
 }
 // stash_offered: ngm_field_eval_fwd_train, which writes the stash or refuses
 static int field_eval_fwd(const ngm_field_cfg* fcfg, const ngm_params* params, int32_t F, int64_t P,
@@ -862,10 +870,10 @@ static int field_eval_fwd(const ngm_field_cfg* fcfg, const ngm_params* params, i
   memset(&a, 0, sizeof(a));
   a.fc = *fcfg; a.pr = *params; a.F = F; a.P = P; a.points = points; a.pos = field_pos; a.quat = field_quat; a.out = out;
   if (stash_offered) {
-    const int64_t need = ngm_field_eval_stash_bytes(fcfg, F, P);
-    if (need <= 0) return fail(NGM_E_UNSUPPORTED, "ngm_field_eval_fwd_train: no stash-reading backward for this configuration (ngm_field_eval_stash_bytes == 0): use ngm_field_eval_fwd / ngm_field_eval_bwd");
-    if (!stash || stash_bytes < need) return fail(NGM_E_WORKSPACE, "ngm_field_eval_fwd_train: stash too small (ngm_field_eval_stash_bytes)");
-    a.act = reinterpret_cast<float*>(align_up((int64_t)stash, 256)); a.act_layer_stride = field_eval_stash_stride(F, P);
+    if (ngm_field_eval_stash_bytes(fcfg, F, P) <= 0) return fail(NGM_E_UNSUPPORTED, "ngm_field_eval_fwd_train: no stash-reading backward for this configuration (ngm_field_eval_stash_bytes == 0): use ngm_field_eval_fwd / ngm_field_eval_bwd");
+    WsArena ss(stash);
+    a.act = field_eval_stash_layout(fcfg, F, P, &a.act_layer_stride, ss);
+    if (!stash || !ss.covers(stash_bytes)) return fail(NGM_E_WORKSPACE, "ngm_field_eval_fwd_train: stash too small (ngm_field_eval_stash_bytes)");
   }
   a.per_block = plan.per_block;
   rc = ngm_launch_points_fwd(a, plan, (hipStream_t)stream);
@@ -900,17 +908,18 @@ static int field_eval_bwd(const ngm_field_cfg* fcfg, const ngm_params* params, i
   memset(&a, 0, sizeof(a));
   if (stash_offered) {
     if (!plan.stash_kind) return fail(NGM_E_UNSUPPORTED, "ngm_field_eval_bwd_stash: no stash-reading backward for this configuration");
-    if (!stash || stash_bytes < ngm_field_eval_stash_bytes(fcfg, F, P)) return fail(NGM_E_WORKSPACE, "ngm_field_eval_bwd_stash: stash too small");
-    a.act = reinterpret_cast<const float*>(align_up((int64_t)stash, 256)); a.act_layer_stride = field_eval_stash_stride(F, P);
+    WsArena ss(stash);
+    a.act = field_eval_stash_layout(fcfg, F, P, &a.act_layer_stride, ss);
+    if (!stash || !ss.covers(stash_bytes)) return fail(NGM_E_WORKSPACE, "ngm_field_eval_bwd_stash: stash too small");
   }
-  if (workspace_bytes < ngm_field_eval_bwd_workspace(fcfg, F, P) || !workspace) return fail(NGM_E_WORKSPACE, "workspace too small");
+  a.F = F; a.blocks_per_field = plan.blocks_per_field; a.p_pad = param_pad(fcfg);
+  WsArena ws(workspace);
+  field_eval_bwd_layout(fcfg, P, a, ws);
+  if (!ws.covers(workspace_bytes) || !workspace) return fail(NGM_E_WORKSPACE, "workspace too small");
   hipStream_t st = (hipStream_t)stream;
   a.fc = *fcfg; a.pr = *params; a.F = F; a.P = P; a.points = points; a.pos = field_pos; a.quat = field_quat;
   a.d_out = reinterpret_cast<const float4*>(d_out);
-  a.per_block = plan.per_block; a.blocks_per_field = plan.blocks_per_field;
-  a.p_pad = param_pad(fcfg);
-  a.partials = reinterpret_cast<float*>(align_up((int64_t)workspace, 256));
-  carve_hash_scratch(fcfg, F, P, reinterpret_cast<char*>(a.partials) + align_up((int64_t)F * a.blocks_per_field * a.p_pad * 4 + 256, 256), a);
+  a.per_block = plan.per_block;
   rc = check_enc_grads(fcfg, grads, a);
   if (rc) return rc;
   if (a.tri_acc) (void)hipMemsetAsync(a.tri_acc, 0, (size_t)F * a.tri_numel * 8, st);
@@ -993,38 +1002,44 @@ struct RenderPlan {
   int64_t off_rayseed;             // (F*R, 8) per-ray loss derivatives without the normalisers (fused compositing backward)
   int64_t off_raytab, off_stashA, off_stashB, off_losspart, off_gradpart, off_hash, off_act, act_layer_stride, total;
   int64_t off_dout, off_disd;      // neus: separate per-sample gradient buffer, per-ray d loss / d isd
+  char* base;                      // the workspace's aligned base the offsets count from (null when only sizing)
 };
-// ask: the backward's seed mode and the forward's per-workspace records (ngm_render_bwd*); the forward and the sizing leave it empty
+// ask: the backward's seed mode and the forward's per-workspace records (ngm_render_bwd*); the forward and the sizing leave it empty.
+// workspace: the caller's, or null for the size query; enc: the backward's record, which receives the encoding's scratch
 static RenderPlan plan_render(const ngm_field_cfg* fc, const ngm_render_cfg* rc, int F, int R, bool guided, bool train,
-                              BwdAsk ask = BwdAsk(), bool counted = false) {
+                              BwdAsk ask = BwdAsk(), bool counted = false, const void* workspace = nullptr,
+                              FieldBwdArgs* enc = nullptr) {
   RenderPlan p = RenderPlan();
   p.S = rc->num_samples_coarse + (guided ? rc->num_samples_guided : 0);
   FwdAsk fq;
   fq.rc = rc; fq.F = F; fq.n = R; fq.S = p.S; fq.counted = counted;
   p.fwd = plan_fwd(fc, fq);
   p.p_pad = param_pad(fc);
-  int64_t o = 0;
+  WsArena ws(workspace);
+  p.base = ws.base();
   if (train) {
     const int64_t NR = (int64_t)F * R, NS = NR * p.S;
-    p.off_raytab = o; o = align_up(o + NR * 8 * 4, 256);
-    p.off_rayseed = o; o = align_up(o + NR * 8 * 4, 256);
-    p.off_stashA = o; o = align_up(o + NS * 16, 256);
-    p.off_stashB = o; o = align_up(o + NS * 8, 256);
-    p.off_losspart = o; o = align_up(o + (int64_t)p.fwd.blocks * NGM_NUM_LOSS_SUMS * 4, 256);
+    p.off_raytab = ws.offset(); ws.take<float>(NR * 8);
+    p.off_rayseed = ws.offset(); ws.take<float>(NR * 8);
+    p.off_stashA = ws.offset(); ws.take<float4>(NS);
+    p.off_stashB = ws.offset(); ws.take<float2>(NS);
+    p.off_losspart = ws.offset(); ws.take<float>((int64_t)p.fwd.blocks * NGM_NUM_LOSS_SUMS);
     if (rc->geometry_mode == NGM_GEO_NEUS) {
-      p.off_dout = o; o = align_up(o + NS * 16, 256);
-      p.off_disd = o; o = align_up(o + NR * 4, 256);
+      p.off_dout = ws.offset(); ws.take<float4>(NS);
+      p.off_disd = ws.offset(); ws.take<float>(NR);
     }
     ask.rc = rc; ask.F = F; ask.P = (int64_t)R * p.S;
     p.bwd = plan_mlp_bwd(fc, ask);
-    p.off_gradpart = o; o = align_up(o + (int64_t)F * p.bwd.blocks_per_field * p.p_pad * 4, 256);
-    p.off_hash = o; o = align_up(o + hash_scratch_bytes(fc, F, (int64_t)R * p.S), 256);
+    p.off_gradpart = ws.offset(); ws.take<float>((int64_t)F * p.bwd.blocks_per_field * p.p_pad);
+    p.off_hash = ws.offset();
+    FieldBwdArgs none;
+    hash_scratch_layout(fc, F, (int64_t)R * p.S, enc ? *enc : none, ws);
     if (p.bwd.stash_kind) {     // floats per layer: whole 32-sample tiles (+1: a field may start mid-tile) of 64 activations / 32 features
       p.act_layer_stride = p.bwd.stash_kind == 1 ? align_up(NS, 32) * 64 + 2048 : align_up(NS, 32) * 32 + 1024;
-      p.off_act = o; o = align_up(o + p.bwd.stash_layers * p.act_layer_stride * 4 + 64, 256);
+      p.off_act = ws.offset(); ws.take<float>(p.bwd.stash_layers * p.act_layer_stride + 16);
     }
   }
-  p.total = o + 256;
+  p.total = ws.bytes();
   return p;
 }
 
@@ -1101,10 +1116,10 @@ static int render_fwd_impl(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcfg
   if (has_tg && targets->term_mask && !targets->term_probs) return fail(NGM_E_INVALID, "render_fwd: term_mask without term_probs");
   if (has_tg && !save) return fail(NGM_E_WORKSPACE, "render_fwd: targets need a workspace");
   if (save && (!pred->rgbds || !pred->term_probs)) return fail(NGM_E_INVALID, "render_fwd(save): pred.rgbds/term_probs required");
-  const RenderPlan p = plan_render(fcfg, rcfg, rays->F, rays->R, rays->gt != nullptr, save, BwdAsk(), num_active != nullptr);
+  const RenderPlan p = plan_render(fcfg, rcfg, rays->F, rays->R, rays->gt != nullptr, save, BwdAsk(), num_active != nullptr, workspace);
   if (p.fwd.status) return fail(p.fwd.status, p.fwd.why);
   if (save && workspace_bytes < p.total) return fail(NGM_E_WORKSPACE, "render_fwd: workspace too small");
-  char* ws = reinterpret_cast<char*>(align_up((int64_t)workspace, 256));
+  char* ws = p.base;
   RenderFwdArgs a;
   memset(&a, 0, sizeof(a));
   a.fc = *fcfg; a.pr = *params; a.rc = *rcfg; a.rays = *rays; a.pred = *pred;
@@ -1166,18 +1181,17 @@ static int render_bwd_common(const ngm_field_cfg* fcfg, const ngm_render_cfg* rc
   // the plan and every argument check first: a refusal launches nothing
   BwdAsk ask;      // with what the forward on THIS workspace wrote
   ask.seeded = sb.seed_mode != 0; ask.rec_layers = forward_stash_layers(workspace); ask.seeds_written = forward_wrote_seeds_for(workspace, sb.tg.rgbds);
-  const RenderPlan p = plan_render(fcfg, rcfg, rays->F, rays->R, rays->gt != nullptr, true, ask);
+  FieldBwdArgs a;
+  memset(&a, 0, sizeof(a));
+  const RenderPlan p = plan_render(fcfg, rcfg, rays->F, rays->R, rays->gt != nullptr, true, ask, false, workspace, &a);
   if (p.bwd.status) return fail(p.bwd.status, p.bwd.why);
   if (!workspace || workspace_bytes < p.total) return fail(NGM_E_WORKSPACE, "render_bwd: workspace too small");
   const bool nll_loss = rcfg->photometric_mode == NGM_PHOTO_GAUSSIAN_NLL || rcfg->depth_mode != NGM_DEPTH_HUBER;
   if (nll_loss && sb.seed_mode == 0 && (!sb.pred.color_vars || !sb.pred.depth_vars))
     return fail(NGM_E_INVALID, "render_bwd: the *_nll loss modes need pred.color_vars and pred.depth_vars");
-  char* ws = reinterpret_cast<char*>(align_up((int64_t)workspace, 256));
-  FieldBwdArgs a;
-  memset(&a, 0, sizeof(a));
+  char* ws = p.base;
   a.fc = *fcfg; a.pr = *params; a.F = rays->F; a.P = (int64_t)rays->R * p.S; a.S = p.S;
   a.num_active = num_active;
-  carve_hash_scratch(fcfg, rays->F, a.P, ws + p.off_hash, a);
   int e = check_enc_grads(fcfg, grads, a);
   if (e) return e;
   sb.rc = *rcfg; sb.F = rays->F; sb.R = rays->R; sb.S = p.S;
@@ -1360,8 +1374,8 @@ int ngm_render_read_samples(const ngm_field_cfg* fcfg, const ngm_render_cfg* rcf
   const bool guided = S != rcfg->num_samples_coarse;
   if (S != rcfg->num_samples_coarse + (guided ? rcfg->num_samples_guided : 0))
     return fail(NGM_E_INVALID, "render_read_samples: S is neither S_c nor S_c + S_g of this render cfg");
-  const RenderPlan p = plan_render(fcfg, rcfg, F, R, guided, true);
-  const char* ws = reinterpret_cast<const char*>(align_up((int64_t)workspace, 256));
+  const RenderPlan p = plan_render(fcfg, rcfg, F, R, guided, true, BwdAsk(), false, workspace);
+  const char* ws = p.base;
   ngm_launch_read_stash(reinterpret_cast<const float4*>(ws + p.off_stashA), reinterpret_cast<const float2*>(ws + p.off_stashB),
                         (int64_t)F * R * p.S, geoms, dists, (hipStream_t)stream);
   return check_launch("ngm_render_read_samples");
@@ -1462,12 +1476,12 @@ int ngm_grid_eval_knn(const ngm_field_cfg* fcfg, const ngm_params* params, int32
   int64_t P = 0;
   e = grid_knn_shape(num_fields, nx, ny, nz, num_knn, &K, &P);
   if (e) return e;
-  if (!workspace || workspace_bytes < ngm_knn_workspace_bytes(num_fields, P, K)) return fail(NGM_E_WORKSPACE, "ngm_grid_eval_knn: workspace too small");
   const FwdPlan plan = plan_knn(fcfg);         // the evaluation is planned before the grid build and the assignment launch
-  if (plan.status) return fail(plan.status, plan.why);
   e = ngm_launch_grid_knn(fcfg, params, num_fields, field_pos, field_quat, xs, nx, ys, ny, zs, nz, K, distance_factor, outside_value,
                           mask_radius > 0.f ? mask_radius : fcfg->field_radius, channel, negate ? 1 : 0, volume, workspace,
                           workspace_bytes, plan, (hipStream_t)stream);
+  if (e == NGM_E_WORKSPACE) return fail(e, "ngm_grid_eval_knn: workspace too small");
+  if (plan.status) return fail(plan.status, plan.why);
   if (e) return fail(e, "ngm_grid_eval_knn: not available for this configuration");
   g_last_fwd[NGM_FWD_KNN] = plan;
   return check_launch("ngm_grid_eval_knn");
@@ -1549,9 +1563,10 @@ int ngm_surface_sample(const float* verts, int64_t num_verts, const int64_t* fac
     return fail(NGM_E_INVALID, "ngm_surface_sample: counts must be below 2^31");
   if (!faces || (num_verts > 0 && !verts) || !workspace || (num_samples > 0 && (!points || !face_ids)))
     return fail(NGM_E_INVALID, "ngm_surface_sample: NULL array");
-  if (workspace_bytes < ngm_surface_sample_bytes(num_faces)) return fail(NGM_E_INVALID, "ngm_surface_sample: workspace too small (ngm_surface_sample_workspace)");
+  if (ngm_launch_surface_sample(verts, num_verts, faces, num_faces, num_samples, seed, points, face_ids, workspace, workspace_bytes,
+                                (hipStream_t)stream))
+    return fail(NGM_E_INVALID, "ngm_surface_sample: workspace too small (ngm_surface_sample_workspace)");
   if (num_samples == 0) return NGM_OK;
-  ngm_launch_surface_sample(verts, num_verts, faces, num_faces, num_samples, seed, points, face_ids, workspace, (hipStream_t)stream);
   return check_launch("ngm_surface_sample");
 }
 int64_t ngm_nearest_point_workspace(int64_t num_refs, int64_t num_queries) {
@@ -1564,10 +1579,9 @@ int ngm_nearest_point(const float* refs, int64_t num_refs, const float* queries,
   if (num_refs == 0) return fail(NGM_E_INVALID, "ngm_nearest_point: no reference points");
   if (num_refs > 0x7fffffff || num_queries > 0x7fffffff) return fail(NGM_E_INVALID, "ngm_nearest_point: counts must be below 2^31");
   if (!refs || !workspace || (num_queries > 0 && (!queries || !dist || !index))) return fail(NGM_E_INVALID, "ngm_nearest_point: NULL array");
-  if (workspace_bytes < ngm_nearest_point_bytes(num_refs, num_queries))
+  if (ngm_launch_nearest_point(refs, num_refs, queries, num_queries, dist, index, workspace, workspace_bytes, (hipStream_t)stream))
     return fail(NGM_E_INVALID, "ngm_nearest_point: workspace too small (ngm_nearest_point_workspace)");
   if (num_queries == 0) return NGM_OK;
-  ngm_launch_nearest_point(refs, num_refs, queries, num_queries, dist, index, workspace, (hipStream_t)stream);
   return check_launch("ngm_nearest_point");
 }
 
@@ -1619,10 +1633,9 @@ int ngm_mesh_subdivide_count(const float* verts, int64_t num_verts, const int64_
   if (max_iter < 0 || max_iter > 10) return fail(NGM_E_INVALID, "ngm_mesh_subdivide_count: 0 <= max_iter <= 10");
   if ((num_verts > 0 && !verts) || (num_faces > 0 && (!faces || !workspace)) || !totals_dev)
     return fail(NGM_E_INVALID, "ngm_mesh_subdivide_count: NULL array");
-  if (num_faces > 0 && workspace_bytes < ngm_mesh_subdivide_bytes(num_faces))
-    return fail(NGM_E_INVALID, "ngm_mesh_subdivide_count: workspace too small (ngm_mesh_subdivide_workspace)");
-  const int e = ngm_launch_mesh_subdivide_count(verts, num_verts, faces, num_faces, max_edge, max_iter, workspace, totals_dev,
-                                                (hipStream_t)stream);
+  const int e = ngm_launch_mesh_subdivide_count(verts, num_verts, faces, num_faces, max_edge, max_iter, workspace, workspace_bytes,
+                                                totals_dev, (hipStream_t)stream);
+  if (e == NGM_E_WORKSPACE) return fail(NGM_E_INVALID, "ngm_mesh_subdivide_count: workspace too small (ngm_mesh_subdivide_workspace)");
   if (e) return fail(e, "ngm_mesh_subdivide_count: HIP error");
   return check_launch("ngm_mesh_subdivide_count");
 }

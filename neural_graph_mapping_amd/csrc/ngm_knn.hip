@@ -23,6 +23,7 @@
 // one channel of the blend straight into the (nx, ny, nz) volume marching cubes reads: no point array, no (P, 4) output.
 #include "ngm_field.h"
 #include "ngm_launch.h"
+#include "ngm_workspace.h"
 
 #include <algorithm>
 #include <cstring>
@@ -664,17 +665,6 @@ __global__ __launch_bounds__(256) void k_knn_blend_volume(KnnArgs a) {
 // cells of the uniform grid over the centres: ~8 per field (the cover grid of rm.py:299 puts about one centre per cell; rooms
 // are not cubes), bounded so that the build stays a one-workgroup job
 static int knn_max_cells(int num_fields) { return (int)std::min<int64_t>(std::max<int64_t>(8 * (int64_t)num_fields, 512), 1 << 18); }
-int64_t ngm_knn_workspace_bytes(int num_fields, int64_t P, int K) {
-  const int64_t n = P * K;
-  const int64_t mc = knn_max_cells(num_fields);
-  return 256 * 12 + 4 * (n + 255) + 4 * (n + 255) + 4 * (int64_t)((3 + KNN_COUNT_REPL) * num_fields + 64) + 4 * (n + 255) + 16 * (n + 16) +
-         256 + 4 * (2 * mc + 2) + 16 * ((int64_t)num_fields + 16) + 16 * KNN_SUB * KNN_SUB * KNN_SUB * mc + 16 * KNN_NEAR_PER_FIELD * (int64_t)num_fields + 1024;
-}
-// + the distances of the generated samples and the ray directions of one block of rays (ngm_render_eval_knn)
-int64_t ngm_knn_render_workspace_bytes(int num_fields, int ray_block, int S, int K) {
-  const int64_t P = (int64_t)ray_block * S;
-  return ngm_knn_workspace_bytes(num_fields, P, K) + 4 * (P + 64) + 28 * ((int64_t)ray_block + 64) + 1024;
-}
 
 // The persistent evaluation kernel: the instances of the point evaluation (every compiled shape x encoding x skip class; the
 // bf16 split at its shape).  plan_fwd sizes the grid: one workgroup per CU in the 83 KB split variant (eight waves), four per CU
@@ -710,27 +700,39 @@ static int launch_eval(const KnnArgs& a, const FwdPlan& p, int max_tiles, hipStr
   return p.need_cos ? launch_eval_skips<MI, MH, L, true, 0, SRC>(a, p, max_tiles, st) : launch_eval_skips<MI, MH, L, false, 0, SRC>(a, p, max_tiles, st);
 }
 
-// workspace carving shared by the two entry points; `a.NF`, `a.K`, `a.P` (the largest P of the call) are set
-static void knn_carve(KnnArgs& a, void* workspace, char** end) {
+// the workspace of the entry points; `a.NF`, `a.K`, `a.P` (the largest P of the call) are set.  ray_block > 0
+// (ngm_render_eval_knn): + the distances of the generated samples and the ray-level tables of one block of rays
+static void knn_layout(KnnArgs& a, int ray_block, WsArena& ws) {
   const int64_t n = a.P * a.K;
-  char* w = reinterpret_cast<char*>(((int64_t)workspace + 255) / 256 * 256);
-  auto carve = [&](int64_t bytes) { char* p = w; w += (bytes + 255) / 256 * 256; return p; };
-  a.pair_field = reinterpret_cast<int*>(carve(4 * n));
-  a.pair_w = reinterpret_cast<float*>(carve(4 * n));
-  a.counts = reinterpret_cast<int*>(carve(4 * (int64_t)KNN_COUNT_REPL * a.NF));
-  a.cursor = reinterpret_cast<int*>(carve(4 * a.NF));
-  a.seg_off = reinterpret_cast<int*>(carve(4 * (a.NF + 1)));
-  a.tile_off = reinterpret_cast<int*>(carve(4 * (a.NF + 1)));
-  a.sorted = reinterpret_cast<int*>(carve(4 * n));
-  a.pair_out = reinterpret_cast<float4*>(carve(16 * n));
+  a.pair_field = ws.take<int>(n);
+  a.pair_w = ws.take<float>(n);
+  a.counts = ws.take<int>((int64_t)KNN_COUNT_REPL * a.NF);
+  a.cursor = ws.take<int>(a.NF);
+  a.seg_off = ws.take<int>(a.NF + 1);
+  a.tile_off = ws.take<int>(a.NF + 1);
+  a.sorted = ws.take<int>(n);
+  a.pair_out = ws.take<float4>(n);
   a.max_cells = knn_max_cells(a.NF);
-  a.grid = reinterpret_cast<KnnGridHdr*>(carve(256));
-  a.cell_start = reinterpret_cast<int*>(carve(4 * ((int64_t)a.max_cells + 1)));
-  a.cell_fill = reinterpret_cast<int*>(carve(4 * (int64_t)a.max_cells));
-  a.cell_c = reinterpret_cast<float4*>(carve(16 * (int64_t)a.NF));
-  a.near_start = reinterpret_cast<int*>(carve(4 * (KNN_SUB * KNN_SUB * KNN_SUB * 4 * (int64_t)a.max_cells + 1)));
-  a.near_c = reinterpret_cast<float4*>(carve(16 * KNN_NEAR_PER_FIELD * (int64_t)a.NF));
-  *end = w;
+  a.grid = ws.take<KnnGridHdr>(1);
+  a.cell_start = ws.take<int>((int64_t)a.max_cells + 1);
+  a.cell_fill = ws.take<int>(a.max_cells);
+  a.cell_c = ws.take<float4>(a.NF);
+  a.near_start = ws.take<int>(KNN_SUB * KNN_SUB * KNN_SUB * 4 * (int64_t)a.max_cells + 1);
+  a.near_c = ws.take<float4>(KNN_NEAR_PER_FIELD * (int64_t)a.NF);
+  if (ray_block > 0) {
+    a.dist = ws.take<float>(a.P);
+    a.ray_dir = ws.take<float>(3 * (int64_t)ray_block);
+    a.ray_tab = ws.take<float4>(ray_block);
+  }
+}
+static int64_t knn_bytes(int num_fields, int64_t P, int K, int ray_block) {
+  KnnArgs a = {};
+  a.NF = num_fields; a.K = K; a.P = P;
+  return ws_bytes(knn_layout, a, ray_block);
+}
+int64_t ngm_knn_workspace_bytes(int num_fields, int64_t P, int K) { return knn_bytes(num_fields, P, K, 0); }
+int64_t ngm_knn_render_workspace_bytes(int num_fields, int ray_block, int S, int K) {
+  return knn_bytes(num_fields, (int64_t)ray_block * S, K, ray_block);
 }
 
 // grid build (optional) -> assignment -> offsets -> scatter -> per-field evaluation of the pairs; the blend is the caller's
@@ -810,13 +812,13 @@ static void knn_common(KnnArgs& a, const ngm_field_cfg* fc, const ngm_params* pr
 int ngm_launch_knn(const ngm_field_cfg* fc, const ngm_params* pr, int num_fields, int64_t P, const float* points,
                    const float* pos, const float* quat, int K, float distance_factor, float outside_value, float mask_radius,
                    float* out, void* workspace, int64_t workspace_bytes, const FwdPlan& plan, hipStream_t st) {
-  if (workspace_bytes < ngm_knn_workspace_bytes(num_fields, P, K) || !workspace) return NGM_E_WORKSPACE;
-  if (num_fields < 1 || P * K > 0x7fffffff) return NGM_E_UNSUPPORTED;
   KnnArgs a;
   knn_common(a, fc, pr, num_fields, pos, quat, K, distance_factor, outside_value, mask_radius);
   a.P = P; a.points = points; a.out = out;
-  char* end;
-  knn_carve(a, workspace, &end);
+  WsArena ws(workspace);
+  knn_layout(a, 0, ws);
+  if (!ws.covers(workspace_bytes) || !workspace) return NGM_E_WORKSPACE;
+  if (num_fields < 1 || P * K > 0x7fffffff) return NGM_E_UNSUPPORTED;
   const int le = knn_stages(a, plan, true, st);
   if (le) return le;
   const int pb = (int)std::min<int64_t>((P + 255) / 256, 4096);
@@ -832,14 +834,15 @@ int ngm_launch_grid_knn(const ngm_field_cfg* fc, const ngm_params* pr, int num_f
   if (nx < 1 || ny < 1 || nz < 1 || num_fields < 1 || K < 1) return NGM_E_INVALID;
   const int64_t P = (int64_t)nx * ny * nz;
   if (P * K > 0x7fffffff) return NGM_E_UNSUPPORTED;
-  if (workspace_bytes < ngm_knn_workspace_bytes(num_fields, P, K) || !workspace) return NGM_E_WORKSPACE;
   KnnArgs a;
   knn_common(a, fc, pr, num_fields, pos, quat, K, distance_factor, outside_value, mask_radius);
   a.P = P; a.gen = 2;
+  WsArena ws(workspace);
+  knn_layout(a, 0, ws);
+  if (!ws.covers(workspace_bytes) || !workspace) return NGM_E_WORKSPACE;
+  if (plan.status) return plan.status;         // reported by the caller, after the workspace's refusal
   a.lat_x = xs; a.lat_y = ys; a.lat_z = zs; a.lat_nz = (uint32_t)nz; a.lat_nynz = (uint32_t)ny * (uint32_t)nz;
   a.chan = channel; a.negate = negate; a.vol = volume;
-  char* end;
-  knn_carve(a, workspace, &end);
   const int le = knn_stages(a, plan, true, st);
   if (le) return le;
   const int pb = (int)std::min<int64_t>((P + 255) / 256, 4096);
@@ -859,15 +862,12 @@ int ngm_launch_render_eval_knn(const ngm_field_cfg* fc, const ngm_render_cfg* rc
   const int S = rc->num_samples_coarse;
   const int64_t total = (int64_t)rays->F * rays->R;
   if (ray_block < 1 || S < 1 || S > CQ_MAXS_EVAL || (int64_t)ray_block * S * K > 0x7fffffff || num_fields < 1) return NGM_E_UNSUPPORTED;
-  if (workspace_bytes < ngm_knn_render_workspace_bytes(num_fields, ray_block, S, K) || !workspace) return NGM_E_WORKSPACE;
   KnnArgs a;
   knn_common(a, fc, pr, num_fields, pos, quat, K, distance_factor, outside_value, mask_radius);
   a.P = (int64_t)ray_block * S;
-  char* w;
-  knn_carve(a, workspace, &w);
-  a.dist = reinterpret_cast<float*>(w); w += (4 * a.P + 255) / 256 * 256;
-  a.ray_dir = reinterpret_cast<float*>(w); w += (12 * (int64_t)ray_block + 255) / 256 * 256;
-  a.ray_tab = reinterpret_cast<float4*>(w);
+  WsArena ws(workspace);
+  knn_layout(a, ray_block, ws);
+  if (!ws.covers(workspace_bytes) || !workspace) return NGM_E_WORKSPACE;
   a.gen = 1; a.S = S; a.rc = *rc;
   for (int64_t r0 = 0; r0 < total; r0 += ray_block) {
     const int nr = (int)std::min<int64_t>(ray_block, total - r0);

@@ -284,10 +284,10 @@ int ngm_launch_target_rays(const ngm_keyframes& kf, int F, int R, const float* f
                            const int64_t* frame_cids, const float* u_xy, const ngm_target_out& o, hipStream_t st);
 int64_t ngm_target_sample_mv_bytes(int num_frames, int num_current, int num_fields, int capacity);
 int ngm_launch_target_sample_mv(const ngm_keyframes& kf, const ngm_target_sample& s, const ngm_target_live* live /* or NULL */,
-                                const ngm_target_out& o, void* workspace, hipStream_t st,
+                                const ngm_target_out& o, void* workspace, int64_t workspace_bytes, hipStream_t st,
                                 const int32_t* num_fields_dev = nullptr /* the grow variant: s.num_fields is the capacity */);
 int64_t ngm_target_observed_fields_bytes(int height, int width);
-int ngm_launch_target_observed_fields(const ngm_observed_fields& a, void* workspace, hipStream_t st,
+int ngm_launch_target_observed_fields(const ngm_observed_fields& a, void* workspace, int64_t workspace_bytes, hipStream_t st,
                                       const int32_t* num_fields_dev = nullptr);
 int ngm_launch_fields_append(const ngm_fields_append_args& a, hipStream_t st);
 int ngm_launch_fields_repose(const ngm_fields_repose_args& a, hipStream_t st);

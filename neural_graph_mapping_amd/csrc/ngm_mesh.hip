@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "ngm_launch.h"
+#include "ngm_workspace.h"
 
 namespace {
 
@@ -379,36 +380,38 @@ static void exclusive_scan_inplace(int32_t* d, int64_t n, int32_t* chunk_sums, h
   hipLaunchKernelGGL(k_scan_apply, dim3(nc), dim3(SCAN_T), 0, st, d, n, chunk_sums);
 }
 
-// workspace: vflag (3N+1) + tcnt (cells+1) int32 + the scans' chunk sums
-static int64_t mc_scan_temp_bytes(int64_t n) { return 4 * ((n + SCAN_CHUNK - 1) / SCAN_CHUNK) + 256; }
-static inline int64_t up256(int64_t x) { return (x + 255) / 256 * 256; }
-
+// workspace (a.nx, a.ny, a.nz are set): vflag (3N+1) + tcnt (cells+1) int32 + one buffer of chunk sums that serves both scans in
+// turn, so it is sized for the longer one, vflag's (cells + 1 < 3N + 1); the scan kernels touch chunk_sums[0 .. chunks) only
+static void mc_layout(McArgs& a, int32_t** chunk_sums, WsArena& ws) {
+  const int64_t N = (int64_t)a.nx * a.ny * a.nz, cells = (int64_t)(a.nx - 1) * (a.ny - 1) * (a.nz - 1);
+  a.vflag = ws.take<int32_t>(3 * N + 1);
+  a.tcnt = ws.take<int32_t>(cells + 1);
+  *chunk_sums = ws.take<int32_t>((3 * N + 1 + SCAN_CHUNK - 1) / SCAN_CHUNK);
+}
 int64_t ngm_mc_workspace_bytes(int nx, int ny, int nz) {
-  const int64_t N = (int64_t)nx * ny * nz, cells = (int64_t)(nx - 1) * (ny - 1) * (nz - 1);
-  return 256 + up256(4 * (3 * N + 1)) + up256(4 * (cells + 1)) + up256(mc_scan_temp_bytes(3 * N + 1));
+  McArgs a = {};
+  a.nx = nx; a.ny = ny; a.nz = nz;
+  int32_t* chunk_sums;
+  return ws_bytes(mc_layout, a, &chunk_sums);
 }
 
-static int mc_setup(McArgs& a, void** temp, int64_t* temp_bytes, const float* vol, int nx, int ny, int nz, float iso,
-                    void* workspace, int64_t workspace_bytes) {
+static int mc_setup(McArgs& a, int32_t** chunk_sums, const float* vol, int nx, int ny, int nz, float iso, void* workspace,
+                    int64_t workspace_bytes) {
   if (!vol || nx < 2 || ny < 2 || nz < 2 || !workspace) return NGM_E_INVALID;
-  const int64_t N = (int64_t)nx * ny * nz, cells = (int64_t)(nx - 1) * (ny - 1) * (nz - 1);
-  if (3 * N + 1 > 0x7fffffff) return NGM_E_UNSUPPORTED;
-  if (workspace_bytes < ngm_mc_workspace_bytes(nx, ny, nz)) return NGM_E_WORKSPACE;
-  char* w = reinterpret_cast<char*>(up256((int64_t)workspace));
+  if (3 * (int64_t)nx * ny * nz + 1 > 0x7fffffff) return NGM_E_UNSUPPORTED;
   memset(&a, 0, sizeof(a));
   a.vol = vol; a.nx = nx; a.ny = ny; a.nz = nz; a.iso = iso;
-  a.vflag = reinterpret_cast<int32_t*>(w); w += up256(4 * (3 * N + 1));
-  a.tcnt = reinterpret_cast<int32_t*>(w); w += up256(4 * (cells + 1));
-  *temp = w; *temp_bytes = mc_scan_temp_bytes(3 * N + 1);
-  return NGM_OK;
+  WsArena ws(workspace);
+  mc_layout(a, chunk_sums, ws);
+  return ws.covers(workspace_bytes) ? NGM_OK : NGM_E_WORKSPACE;
 }
 
 // pass 1: classify + scans; counts (device int64[2]) = number of vertices, number of faces.  Leaves the offsets in
 // the workspace for ngm_launch_mc_emit.
 int ngm_launch_mc_count(const float* vol, int nx, int ny, int nz, float iso, int64_t* counts, void* workspace,
                         int64_t workspace_bytes, hipStream_t st) {
-  McArgs a; void* temp; int64_t tb;
-  int e = mc_setup(a, &temp, &tb, vol, nx, ny, nz, iso, workspace, workspace_bytes);
+  McArgs a; int32_t* chunk_sums;
+  int e = mc_setup(a, &chunk_sums, vol, nx, ny, nz, iso, workspace, workspace_bytes);
   if (e) return e;
   if (!counts) return NGM_E_INVALID;
   e = upload_tables();
@@ -416,9 +419,8 @@ int ngm_launch_mc_count(const float* vol, int nx, int ny, int nz, float iso, int
   a.counts = counts;
   const int64_t N = (int64_t)nx * ny * nz, cells = (int64_t)(nx - 1) * (ny - 1) * (nz - 1);
   hipLaunchKernelGGL(k_mc_classify, dim3((unsigned)((N + 1 + 255) / 256)), dim3(256), 0, st, a);
-  (void)tb;
-  exclusive_scan_inplace(a.vflag, 3 * N + 1, reinterpret_cast<int32_t*>(temp), st);
-  exclusive_scan_inplace(a.tcnt, cells + 1, reinterpret_cast<int32_t*>(temp), st);
+  exclusive_scan_inplace(a.vflag, 3 * N + 1, chunk_sums, st);
+  exclusive_scan_inplace(a.tcnt, cells + 1, chunk_sums, st);
   hipLaunchKernelGGL(k_mc_totals, dim3(1), dim3(1), 0, st, a);
   return NGM_OK;
 }
@@ -426,8 +428,8 @@ int ngm_launch_mc_count(const float* vol, int nx, int ny, int nz, float iso, int
 // pass 2: emit (same volume / isolevel / workspace as pass 1)
 int ngm_launch_mc_emit(const float* vol, int nx, int ny, int nz, float iso, float* verts, int64_t max_verts,
                        int64_t* faces, int64_t max_faces, void* workspace, int64_t workspace_bytes, hipStream_t st) {
-  McArgs a; void* temp; int64_t tb;
-  int e = mc_setup(a, &temp, &tb, vol, nx, ny, nz, iso, workspace, workspace_bytes);
+  McArgs a; int32_t* chunk_sums;
+  int e = mc_setup(a, &chunk_sums, vol, nx, ny, nz, iso, workspace, workspace_bytes);
   if (e) return e;
   if ((max_verts > 0 && !verts) || (max_faces > 0 && !faces)) return NGM_E_INVALID;
   a.verts = verts; a.faces = faces; a.max_verts = max_verts; a.max_faces = max_faces;

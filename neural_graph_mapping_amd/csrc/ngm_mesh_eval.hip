@@ -20,6 +20,7 @@
 // index that reaches memory is checked (face indices against V) or clamped (cell indices).
 #include "ngm_device.h"
 #include "ngm_launch.h"
+#include "ngm_workspace.h"
 
 #include <algorithm>
 
@@ -117,7 +118,6 @@ static void launch_scan(T* a, const int* n_dev, int64_t n_max, T* partial, hipSt
   hipLaunchKernelGGL((k_scan_apply<T, INCLUSIVE>), dim3((unsigned)nb), dim3(SCAN_T), 0, st, a, n_dev, n_max, partial);
 }
 static int64_t scan_partials(int64_t n_max) { return std::max<int64_t>((n_max + SCAN_CHUNK - 1) / SCAN_CHUNK, 1); }
-static int64_t up256(int64_t b) { return (b + 255) / 256 * 256; }
 
 // ---- surface sampler --------------------------------------------------------------------------------------------------
 struct SurfArgs {
@@ -191,16 +191,24 @@ __global__ __launch_bounds__(256) void k_surface_sample(SurfArgs a) {
   a.face_ids[i] = fid;
 }
 
+// workspace: the areas / their scan, the scan's chunk sums
+static void surf_layout(int64_t F, double** cum, double** partial, WsArena& ws) {
+  *cum = ws.take<double>(F);
+  *partial = ws.take<double>(scan_partials(F) + 1);
+}
 int64_t ngm_surface_sample_bytes(int64_t num_faces) {
-  return 256 + up256(8 * num_faces) + up256(8 * (scan_partials(num_faces) + 1)) + 256;
+  double *cum, *partial;
+  return ws_bytes(surf_layout, num_faces, &cum, &partial);
 }
 int ngm_launch_surface_sample(const float* verts, int64_t V, const int64_t* faces, int64_t F, int64_t N, uint64_t seed, float* points,
-                              int64_t* face_ids, void* workspace, hipStream_t st) {
-  char* w = reinterpret_cast<char*>(((int64_t)workspace + 255) / 256 * 256);
+                              int64_t* face_ids, void* workspace, int64_t workspace_bytes, hipStream_t st) {
   SurfArgs a = {};
   a.verts = verts; a.faces = faces; a.V = V; a.F = (int)F; a.N = (int)N; a.seed = seed; a.points = points; a.face_ids = face_ids;
-  a.cum = reinterpret_cast<double*>(w);
-  double* partial = reinterpret_cast<double*>(w + up256(8 * F));
+  double* partial;
+  WsArena ws(workspace);
+  surf_layout(F, &a.cum, &partial, ws);
+  if (!ws.covers(workspace_bytes)) return NGM_E_WORKSPACE;
+  if (N == 0) return 0;
   hipLaunchKernelGGL(k_face_area, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, st, a);
   launch_scan<double, true>(a.cum, nullptr, F, partial, st);
   hipLaunchKernelGGL(k_surface_sample, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, a);
@@ -397,25 +405,31 @@ __global__ __launch_bounds__(256) void k_np_query(NpArgs a) {
 
 // cells of the grid over the references: 2 per reference (k_np_header), bounded
 static int np_max_cells(int64_t M) { return (int)std::min<int64_t>(std::max<int64_t>(2 * M, 64), 1 << 22); }
+// workspace: the grid over the references and the references grouped by its cells (a.M is set; the queries take none)
+static void np_layout(NpArgs& a, WsArena& ws) {
+  a.max_cells = np_max_cells(a.M);
+  a.hdr = ws.take<NpGridHdr>(1);
+  a.part = ws.take<float>(6 * NP_BBOX_BLOCKS);
+  a.cell_start = ws.take<int>((int64_t)a.max_cells + 1);
+  a.cell_fill = ws.take<int>(a.max_cells);
+  a.scan_part = ws.take<int>(scan_partials(a.max_cells) + 1);
+  a.sorted = ws.take<float4>(a.M);
+}
 int64_t ngm_nearest_point_bytes(int64_t M, int64_t N) {
   (void)N;
-  const int64_t mc = np_max_cells(M);
-  return 256 + 256 + up256(4 * 6 * NP_BBOX_BLOCKS) + up256(4 * (mc + 1)) + up256(4 * mc) + up256(4 * (scan_partials(mc) + 1)) + up256(16 * M);
+  NpArgs a = {};
+  a.M = (int)M;
+  return ws_bytes(np_layout, a);
 }
 int ngm_launch_nearest_point(const float* refs, int64_t M, const float* queries, int64_t N, float* dist, int64_t* index, void* workspace,
-                             hipStream_t st) {
-  char* w = reinterpret_cast<char*>(((int64_t)workspace + 255) / 256 * 256);
-  auto carve = [&](int64_t bytes) { char* p = w; w += up256(bytes); return p; };
+                             int64_t workspace_bytes, hipStream_t st) {
   NpArgs a = {};
   a.refs = refs; a.queries = queries; a.M = (int)M; a.N = (int)N; a.dist = dist; a.index = index;
-  a.max_cells = np_max_cells(M);
   a.bbox_blocks = (int)std::min<int64_t>((M + 255) / 256, NP_BBOX_BLOCKS);
-  a.hdr = reinterpret_cast<NpGridHdr*>(carve(256));
-  a.part = reinterpret_cast<float*>(carve(4 * 6 * NP_BBOX_BLOCKS));
-  a.cell_start = reinterpret_cast<int*>(carve(4 * ((int64_t)a.max_cells + 1)));
-  a.cell_fill = reinterpret_cast<int*>(carve(4 * (int64_t)a.max_cells));
-  a.scan_part = reinterpret_cast<int*>(carve(4 * (scan_partials(a.max_cells) + 1)));
-  a.sorted = reinterpret_cast<float4*>(carve(16 * M));
+  WsArena ws(workspace);
+  np_layout(a, ws);
+  if (!ws.covers(workspace_bytes)) return NGM_E_WORKSPACE;
+  if (N == 0) return 0;
   const unsigned ref_blocks = (unsigned)std::min<int64_t>((M + 255) / 256, 8192);
   hipLaunchKernelGGL(k_np_bbox, dim3((unsigned)a.bbox_blocks), dim3(256), 0, st, a);
   hipLaunchKernelGGL(k_np_header, dim3(1), dim3(256), 0, st, a);
@@ -609,24 +623,24 @@ __global__ __launch_bounds__(SUB_T) void k_sub_copy(SubArgs a) {
 }
 
 struct SubLayout { int* level; int64_t* vscan; int64_t* fscan; int64_t* partial; };
-static SubLayout sub_carve(void* workspace, int64_t F) {
-  char* w = reinterpret_cast<char*>(((int64_t)workspace + 255) / 256 * 256);
+// workspace: count and emit see the same layout from F alone
+static SubLayout sub_layout(int64_t F, WsArena& ws) {
   SubLayout l;
-  l.level = reinterpret_cast<int*>(w); w += up256(4 * F);
-  l.vscan = reinterpret_cast<int64_t*>(w); w += up256(8 * (F + 1));
-  l.fscan = reinterpret_cast<int64_t*>(w); w += up256(8 * (F + 1));
-  l.partial = reinterpret_cast<int64_t*>(w);
+  l.level = ws.take<int>(F);
+  l.vscan = ws.take<int64_t>(F + 1);
+  l.fscan = ws.take<int64_t>(F + 1);
+  l.partial = ws.take<int64_t>(scan_partials(F) + 1);
   return l;
 }
-int64_t ngm_mesh_subdivide_bytes(int64_t F) {
-  return 256 + up256(4 * F) + 2 * up256(8 * (F + 1)) + up256(8 * (scan_partials(F) + 1));
-}
+int64_t ngm_mesh_subdivide_bytes(int64_t F) { return ws_bytes(sub_layout, F); }
 int ngm_launch_mesh_subdivide_count(const float* verts, int64_t V, const int64_t* faces, int64_t F, double max_edge, int max_iter,
-                                    void* workspace, int64_t* totals, hipStream_t st) {
+                                    void* workspace, int64_t workspace_bytes, int64_t* totals, hipStream_t st) {
   if (max_iter < 0 || max_iter > SUB_MAX_ITER) return -1;
+  WsArena ws(workspace);
+  const SubLayout l = sub_layout(F, ws);
+  if (F > 0 && !ws.covers(workspace_bytes)) return NGM_E_WORKSPACE;
   if (hipMemsetAsync(totals, 0, 3 * sizeof(int64_t), st) != hipSuccess) return -4;
   if (F == 0) return 0;
-  const SubLayout l = sub_carve(workspace, F);
   SubArgs a = {};
   a.verts = verts; a.faces = faces; a.V = V; a.F = F; a.level = l.level; a.vscan = l.vscan; a.fscan = l.fscan; a.totals = totals;
   a.max_edge = max_edge; a.max_iter = max_iter;
@@ -639,7 +653,8 @@ int ngm_launch_mesh_subdivide_count(const float* verts, int64_t V, const int64_t
 int ngm_launch_mesh_subdivide_emit(const float* verts, int64_t V, const int64_t* faces, int64_t F, const float* attrs, int C,
                                    const void* workspace, int64_t new_vertices, int64_t out_faces, float* out_verts,
                                    int64_t* out_faces_idx, float* out_attrs, int64_t* out_parent, hipStream_t st) {
-  const SubLayout l = sub_carve(const_cast<void*>(workspace), F);
+  WsArena ws(workspace);
+  const SubLayout l = sub_layout(F, ws);
   SubArgs a = {};
   a.verts = verts; a.faces = faces; a.attrs = attrs; a.V = V; a.F = F; a.C = attrs ? C : 0;
   a.level = l.level; a.vscan = l.vscan; a.fscan = l.fscan;

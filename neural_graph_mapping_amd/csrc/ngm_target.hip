@@ -9,6 +9,7 @@
 // HBM-bound gathers; one thread per (field, keyframe) resp. per ray.
 #include "ngm_device.h"
 #include "ngm_launch.h"
+#include "ngm_workspace.h"
 
 #pragma clang fp contract(off)
 
@@ -212,22 +213,19 @@ struct tsmv_ws {
   int* list;           // capacity x num_frames visible-keyframe lists, only when num_frames > TSMV_LDS_FRAMES
 };
 
-static int64_t tsmv_layout(int num_frames, int num_current, int num_fields, int capacity, char* base, tsmv_ws* w) {
-  int64_t off = 0;
-  auto take = [&](int64_t bytes) { char* p = base ? base + off : nullptr; off += (bytes + 255) / 256 * 256; return p; };
+static tsmv_ws tsmv_layout(int num_frames, int num_current, int num_fields, int capacity, WsArena& ws) {
   const int64_t pairs = (int64_t)capacity * num_frames;
   tsmv_ws t;
-  t.hdr = (int64_t*)take(2 * sizeof(int64_t));
-  t.keys = (uint64_t*)take((int64_t)(num_current > num_fields ? num_current : num_fields) * sizeof(uint64_t));
-  t.slot_ids = (int64_t*)take((int64_t)capacity * sizeof(int64_t));
-  t.slot_pos = (float*)take((int64_t)capacity * 3 * sizeof(float));
-  t.flags = (int*)take((int64_t)capacity * sizeof(int));
-  t.offsets = (float*)take(TSMV_NUM_OFFSETS * 3 * sizeof(float));
-  t.kf_mask = (uint8_t*)take(pairs);
-  t.bbox = (float4*)take(pairs * sizeof(float4));
-  t.list = num_frames > TSMV_LDS_FRAMES ? (int*)take(pairs * sizeof(int)) : nullptr;
-  if (w) *w = t;
-  return off;
+  t.hdr = ws.take<int64_t>(2);
+  t.keys = ws.take<uint64_t>(num_current > num_fields ? num_current : num_fields);
+  t.slot_ids = ws.take<int64_t>(capacity);
+  t.slot_pos = ws.take<float>((int64_t)capacity * 3);
+  t.flags = ws.take<int>(capacity);
+  t.offsets = ws.take<float>(TSMV_NUM_OFFSETS * 3);
+  t.kf_mask = ws.take<uint8_t>(pairs);
+  t.bbox = ws.take<float4>(pairs);
+  t.list = num_frames > TSMV_LDS_FRAMES ? ws.take<int>(pairs) : nullptr;
+  return t;
 }
 
 // Exact-rounding stand-ins for logf / sincosf (only +, -, *, / and bit operations, fp contraction off): the host restates the
@@ -544,7 +542,7 @@ __global__ __launch_bounds__(TSMV_RAY_THREADS) void k_tsmv_rays(ngm_keyframes kf
 }
 
 int64_t ngm_target_sample_mv_bytes(int num_frames, int num_current, int num_fields, int capacity) {
-  return tsmv_layout(num_frames, num_current, num_fields, capacity, nullptr, nullptr);
+  return ws_bytes(tsmv_layout, num_frames, num_current, num_fields, capacity);
 }
 // live == nullptr: the sizes of kf / s are the counts in force.  Otherwise kf.num_frames = max_frames, s.num_current =
 // max_current, s.num_observed / s.num_random = their maxima (include/ngm_hip.h) and the kernels read the counts from `live`.
@@ -559,9 +557,11 @@ static void tsmv_launch(const ngm_keyframes& kf, const ngm_target_sample& s, con
                      dim3(TSMV_RAY_THREADS), 0, st, kf, s, o, w, lv);
 }
 int ngm_launch_target_sample_mv(const ngm_keyframes& kf, const ngm_target_sample& s, const ngm_target_live* live,
-                                const ngm_target_out& o, void* workspace, hipStream_t st, const int32_t* num_fields_dev) {
-  tsmv_ws w;
-  tsmv_layout(kf.num_frames, s.num_current, s.num_fields, s.capacity, (char*)workspace, &w);
+                                const ngm_target_out& o, void* workspace, int64_t workspace_bytes, hipStream_t st,
+                                const int32_t* num_fields_dev) {
+  WsArena ws(workspace);
+  const tsmv_ws w = tsmv_layout(kf.num_frames, s.num_current, s.num_fields, s.capacity, ws);
+  if (!workspace || !ws.covers(workspace_bytes)) return NGM_E_WORKSPACE;
   if (!live)
     tsmv_launch<false>(kf, s, tsmv_live{nullptr, nullptr, nullptr, nullptr, 0, nullptr}, o, w, st);
   else
@@ -608,15 +608,12 @@ struct obs_ws {
   int* hist;          // OBS_PASSES x 256
   int* counters;      // [0] slots handed out by k_obs_collect
 };
-static int64_t obs_layout(int64_t pixels, char* base, obs_ws* w) {
-  int64_t off = 0;
-  auto take = [&](int64_t bytes) { char* p = base ? base + off : nullptr; off += (bytes + 255) / 256 * 256; return p; };
+static obs_ws obs_layout(int64_t pixels, WsArena& ws) {
   obs_ws t;
-  t.keys = (uint64_t*)take(pixels * (int64_t)sizeof(uint64_t));
-  t.hist = (int*)take(OBS_PASSES * 256 * sizeof(int));
-  t.counters = (int*)take(4 * sizeof(int));
-  if (w) *w = t;
-  return off;
+  t.keys = ws.take<uint64_t>(pixels);
+  t.hist = ws.take<int>(OBS_PASSES * 256);
+  t.counters = ws.take<int>(4);
+  return t;
 }
 
 __global__ __launch_bounds__(OBS_THREADS) void k_obs_keys(ngm_observed_fields a, obs_ws w) {
@@ -815,10 +812,12 @@ __global__ __launch_bounds__(OBS_FIELD_THREADS) void k_obs_fields(ngm_observed_f
   }
 }
 
-int64_t ngm_target_observed_fields_bytes(int height, int width) { return obs_layout((int64_t)height * width, nullptr, nullptr); }
-int ngm_launch_target_observed_fields(const ngm_observed_fields& a, void* workspace, hipStream_t st, const int32_t* num_fields_dev) {
-  obs_ws w;
-  obs_layout((int64_t)a.height * a.width, (char*)workspace, &w);
+int64_t ngm_target_observed_fields_bytes(int height, int width) { return ws_bytes(obs_layout, (int64_t)height * width); }
+int ngm_launch_target_observed_fields(const ngm_observed_fields& a, void* workspace, int64_t workspace_bytes, hipStream_t st,
+                                      const int32_t* num_fields_dev) {
+  WsArena ws(workspace);
+  const obs_ws w = obs_layout((int64_t)a.height * a.width, ws);
+  if (!workspace || !ws.covers(workspace_bytes)) return NGM_E_WORKSPACE;
   const int64_t n = (int64_t)a.height * a.width;
   int blocks = (int)((n + OBS_THREADS - 1) / OBS_THREADS);
   blocks = blocks < OBS_PASSES ? OBS_PASSES : blocks > OBS_MAX_BLOCKS ? OBS_MAX_BLOCKS : blocks;

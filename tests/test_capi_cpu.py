@@ -102,6 +102,85 @@ def test_workspace_sizing_and_validation_without_gpu(capi):
     assert L.ngm_field_eval_fwd(C.byref(fc), None, 1, 10, None, None, None, None, None) == -1
 
 
+def test_workspace_boundary_without_a_device(capi):
+    """One byte short of what the size query reports is refused as too small; the reported size gets past that check, to a later
+    refusal that launches nothing either (no pointer below is ever read)."""
+    L, fake = capi.lib(), 0x1000
+    WS, INV, UNS = capi.NGM_E_WORKSPACE, capi.NGM_E_INVALID, capi.NGM_E_UNSUPPORTED
+    err = lambda: L.ngm_last_error().decode()
+
+    def params(fc):
+        ptrs = {n: fake for n in capi.param_shapes(fc)}
+        return capi.params_struct(fc, ptrs, {n: 1 for n in ptrs}, None, 0)
+
+    # marching cubes: the count without `counts`, the emit without `verts`
+    need = L.ngm_marching_cubes_workspace(5, 4, 3)
+    assert need > 0
+    assert L.ngm_marching_cubes_count(fake, 5, 4, 3, 0.0, None, fake, need - 1, None) == WS and "too small" in err()
+    assert L.ngm_marching_cubes_count(fake, 5, 4, 3, 0.0, None, fake, need, None) == INV
+    assert L.ngm_marching_cubes_emit(fake, 5, 4, 3, 0.0, None, 1, fake, 1, fake, need - 1, None) == WS and "too small" in err()
+    assert L.ngm_marching_cubes_emit(fake, 5, 4, 3, 0.0, None, 1, fake, 1, fake, need, None) == INV
+    # kNN evaluation of points: P * K = 2^31 pairs are refused as unsupported, after the workspace
+    fc = capi.field_cfg(encoding="nerf", num_octaves=2, num_layers=1, dim_hidden=16)
+    ps = params(fc)
+    NF, P, K_ = 7, 2 ** 30, 2
+    need = L.ngm_field_eval_knn_workspace(NF, P, K_)
+    knn = lambda wsb: L.ngm_field_eval_knn(C.byref(fc), C.byref(ps), NF, P, fake, fake, fake, K_, 10.0, 1.0, 0.0, fake, fake, wsb, None)
+    assert need > 0 and knn(need - 1) == WS and err() == "ngm_field_eval_knn: workspace too small"
+    assert knn(need) == UNS
+    # the standalone encoding backward (Fourier partials, permutohedral scratch) without the gradient tensor
+    gr = capi.Grads()
+    F, P = 3, 257
+    for enc, why in ((dict(encoding="fourier", dim_enc=64, num_layers=2), "enc_w is NULL"), (dict(encoding="permuto", num_layers=1), "lattice is NULL")):
+        fc = capi.field_cfg(**enc)
+        ps = params(fc)
+        need = L.ngm_encode_bwd_workspace(C.byref(fc), F, P)
+        enc_bwd = lambda wsb: L.ngm_encode_bwd(C.byref(fc), C.byref(ps), F, P, fake, fake, fake, fake, C.byref(gr), fake, wsb, None)
+        assert need > 256 and enc_bwd(need - 1) == WS and err() == "ngm_encode_bwd: workspace too small", enc
+        assert enc_bwd(need) == INV and why in err(), (enc, err())
+    # the point-mode backward (partials, then the encoding's scratch) without the encoding's gradient tensor
+    for enc, why in ((dict(encoding="permuto", num_layers=1), "lattice is NULL"),
+                     (dict(encoding="triplane", num_layers=1, resolution=16, num_components=32), "planes missing")):
+        fc = capi.field_cfg(**enc)
+        ps = params(fc)
+        need = L.ngm_field_eval_bwd_workspace(C.byref(fc), F, P)
+        bwd = lambda wsb: L.ngm_field_eval_bwd(C.byref(fc), C.byref(ps), F, P, fake, fake, fake, fake, C.byref(gr), fake, wsb, None)
+        assert need > 256 and bwd(need - 1) == WS and err() == "workspace too small", enc
+        assert bwd(need) == INV and why in err(), (enc, err())
+    # its stash: one byte short is the stash's refusal, the reported size reaches the workspace's
+    fc = capi.field_cfg(encoding="fourier", dim_enc=64, num_layers=2, matmul_mode="auto")
+    ps = params(fc)
+    sb, wsb = L.ngm_field_eval_stash_bytes(C.byref(fc), F, P), L.ngm_field_eval_bwd_workspace(C.byref(fc), F, P)
+    stash_bwd = lambda s, w: L.ngm_field_eval_bwd_stash(C.byref(fc), C.byref(ps), F, P, fake, fake, fake, fake, C.byref(gr), fake, s, fake, w, None)
+    assert sb > 256 and stash_bwd(sb - 1, wsb) == WS and err() == "ngm_field_eval_bwd_stash: stash too small"
+    assert stash_bwd(sb, wsb - 1) == WS and err() == "workspace too small"
+    # the fused backward, every wrapper of it (loss, counted, Adam, counted Adam, seeded, seeded with variances): a
+    # permutohedral network without the table's gradient tensor
+    fc, rc = capi.field_cfg(encoding="permuto", num_layers=1), capi.render_cfg(num_samples_coarse=9, num_samples_guided=5)
+    ps, fp = params(fc), C.cast(fake, capi.f32p)
+    rays = capi.Rays()
+    rays.F, rays.R, rays.ijs, rays.c2ws, rays.gt, rays.field_pos, rays.field_quat = 3, 41, fake, fp, fp, fp, fp
+    tg, pred = capi.Targets(fp, fake, None, None), capi.Prediction(fp, None, None, fp)
+    at = capi.AdamTensor(fp, fp, fp, fp, 1, 1, 1)
+    head = (C.byref(fc), C.byref(rc), C.byref(ps), C.byref(rays))
+    loss = head + (C.byref(tg), C.byref(pred), None, C.byref(gr))
+    adam = loss + (C.byref(at), 1, C.byref(at), None, 1, None, 1e-3, 0.9, 0.999, 1e-15, 0.0)
+    need = L.ngm_render_workspace(C.byref(fc), C.byref(rc), rays.F, rays.R, 1)
+    wrappers = {
+        "ngm_render_bwd": lambda w: L.ngm_render_bwd(*loss, None, fake, w, None),
+        "ngm_render_bwd_counted": lambda w: L.ngm_render_bwd_counted(*loss, None, fake, w, None, fake),
+        "ngm_render_bwd_adam": lambda w: L.ngm_render_bwd_adam(*adam, None, fake, w, None),
+        "ngm_render_bwd_adam_counted": lambda w: L.ngm_render_bwd_adam_counted(*adam, None, fake, w, None, fake),
+        "ngm_render_bwd_seeded": lambda w: L.ngm_render_bwd_seeded(*head, fake, None, None, C.byref(gr), fake, w, None),
+        "ngm_render_bwd_seeded_vars": lambda w: L.ngm_render_bwd_seeded_vars(*head, C.byref(pred), fake, fake, None, None, None,
+                                                                             C.byref(gr), fake, w, None),
+    }
+    assert need > 4096
+    for name, call in wrappers.items():
+        assert call(need - 1) == WS and err() == "render_bwd: workspace too small", name
+        assert call(need) == INV and err() == "permutohedral: grads.lattice is NULL", (name, err())
+
+
 def test_param_names_and_shapes_follow_reference(capi):
     fc = capi.field_cfg(encoding="fourier", dim_enc=64, num_layers=2)
     shapes = capi.param_shapes(fc)

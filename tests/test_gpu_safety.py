@@ -36,7 +36,7 @@ PATTERN = 0xA5
 
 class Bands:
     def __init__(self):
-        self.raw = []            # (raw uint8 tensor, payload bytes)
+        self.raw = []            # (raw uint8 tensor, payload offset, payload bytes)
         self.bytes = 0
 
     def alloc(self, shape, dtype, device, zero):
@@ -44,12 +44,17 @@ class Bands:
         for d in shape:
             n *= int(d)
         nbytes = n * torch.empty((), dtype=dtype).element_size()
-        pad = (-nbytes) % 256                       # the payload keeps the allocator's 256-byte alignment on both ends
-        raw = _REAL["empty"](GUARD + nbytes + pad + GUARD, dtype=torch.uint8, device=device)
+        # A flat byte buffer is a workspace or a stash: the library aligns its base up to 256 itself and sizes it for that, so
+        # it starts 255 bytes past a boundary here, the alignment uses up all but one byte of its allowance and the band behind
+        # it begins one byte (+ the last region's rounding to 256) behind the last region.  Everything else keeps the allocator's
+        # 256-byte alignment on both ends.
+        lo = GUARD + (255 if dtype == torch.uint8 and len(shape) == 1 and nbytes >= 512 else 0)
+        pad = (-(lo + nbytes)) % 256
+        raw = _REAL["empty"](lo + nbytes + pad + GUARD, dtype=torch.uint8, device=device)
         raw.fill_(PATTERN)
-        self.raw.append((raw, nbytes))
+        self.raw.append((raw, lo, nbytes))
         self.bytes += nbytes
-        out = raw[GUARD:GUARD + nbytes].view(dtype).view(*shape) if n else _REAL["empty"](*shape, dtype=dtype, device=device)
+        out = raw[lo:lo + nbytes].view(dtype).view(*shape) if n else _REAL["empty"](*shape, dtype=dtype, device=device)
         if zero and n:
             out.zero_()
         return out
@@ -57,10 +62,10 @@ class Bands:
     def check(self):
         torch.cuda.synchronize()
         bad = []
-        for i, (raw, nbytes) in enumerate(self.raw):
-            lo, hi = raw[:GUARD], raw[GUARD + nbytes:]
+        for i, (raw, start, nbytes) in enumerate(self.raw):
+            lo, hi = raw[:start], raw[start + nbytes:]
             if not bool((lo == PATTERN).all()):
-                bad.append((i, nbytes, "before", int((lo != PATTERN).nonzero()[-1]) - GUARD))
+                bad.append((i, nbytes, "before", int((lo != PATTERN).nonzero()[-1]) - start))
             if not bool((hi == PATTERN).all()):
                 bad.append((i, nbytes, "after", int((hi != PATTERN).nonzero()[0])))
         assert not bad, f"writes outside caller-owned buffers (index, payload bytes, side, byte offset): {bad[:8]}"
@@ -284,6 +289,134 @@ def test_guard_bands_mesh_target_sampler_and_adam():
             ops.adam_sparse_(v, st["exp_avg"], st["exp_avg_sq"], torch.randn(3, *v.shape[1:], device=DEV), ids, 3)
         n = bands.check()
     assert n > 5
+    _small_ragged_workspaces()
+
+
+def _small_ragged_workspaces():
+    """Every workspace-taking entry point once more at a small ragged shape, each workspace of exactly the size the library
+    reports (the host layer allocates that and no more), so the band starts one byte + the last region's rounding to 256
+    behind that region's last byte (Bands.alloc places a workspace 255 bytes past a boundary): the point stages of the
+    encodings with a scratch or stash of their own (F = 3, P = 257), 7 fields / K = 3 / 500 points, a 9 x 7 x 5 lattice and its
+    marching cubes, ray blocks of 64, a mesh of ten faces, the observed-fields select plain and over reserved rows."""
+    from neural_graph_mapping_amd import mesh as Mh
+    gen = torch.Generator().manual_seed(5)
+    small = dict(num_samples_coarse=4, num_samples_depth_guided=4)
+    with guard_bands() as bands:
+        F, P = 3, 257
+        pos = torch.randn(F, 3, generator=gen)
+        quat = torch.nn.functional.normalize(torch.randn(F, 4, generator=gen), dim=-1).to(DEV)
+        pts = (pos[:, None] + 0.4 * torch.randn(F, P, 3, generator=gen)).to(DEV)
+        pos = pos.to(DEV)
+        for fkw in (FOURIER, HASH, dict(encoding="triplane", num_layers=1, resolution=16, num_components=32)):
+            r = make_renderer(fkw, small, F)
+            params = {k: v.detach().clone().requires_grad_() for k, v in r._model.all_fields_params.items() if k != "_neus_sd"}
+            ops.field_eval(r._fc, params, pts, pos, quat).sum().backward()
+            if fkw["encoding"] != "triplane":                      # (no standalone encoding stage)
+                enc = ops.encode(r._fc, params, pts, pos, quat)
+                ops.encode_bwd(r._fc, params, pts, torch.ones_like(enc), pos, quat)
+        n = bands.check()
+    assert n > 20
+    with guard_bands() as bands:
+        NF, N = 7, 500
+        r = make_renderer(FOURIER, dict(eval_num_samples=33, eval_far_distance=4.0, pixel_block_size=64, eval_ray_block=64, block_size=5000,
+                                        **small), NF)
+        r._model._num_knn = 3
+        _perturb(r)
+        pos = torch.rand(NF, 3, generator=gen) * 2 - 1 + torch.tensor([0.0, 0.0, -1.7])
+        quat = torch.nn.functional.normalize(torch.randn(NF, 4, generator=gen), dim=-1)
+        r.set_field_poses(pos.to(DEV), quat.to(DEV))
+        ijs = torch.stack([torch.randint(0, 480, (N,), generator=gen), torch.randint(0, 640, (N,), generator=gen)], -1).to(DEV)
+        r.eval()
+        r.render_ijs(ijs, torch.eye(4, device=DEV).expand(N, 4, 4), seed=3)                     # 7 full blocks of 64 rays and one of 52
+        assert r.last_eval_path == "fused, ray_block 64"
+        r.evaluate_points(torch.rand(N, 3, generator=gen).to(DEV) * 3 - torch.tensor([1.5, 1.5, 3.2], device=DEV), block_size=N)
+        params = {k: v for k, v in r._model.kernel_params().items() if k != "_neus_sd"}
+        xs, ys, zs = (torch.linspace(lo, lo + 3.0, n, device=DEV) for lo, n in ((-1.5, 9), (-1.5, 7), (-3.2, 5)))
+        vol = ops.grid_eval_knn(r._fc, params, xs, ys, zs, pos.to(DEV), quat.to(DEV), num_knn=3, negate=True)
+        assert tuple(vol.shape) == (9, 7, 5)
+        Mh.marching_cubes(vol, float(vol.median()))
+        n = bands.check()
+    assert n > 8
+    with guard_bands() as bands:
+        verts = torch.randn(12, 3, generator=gen).to(DEV)
+        faces = torch.tensor([[0, i, i + 1] for i in range(1, 11)], dtype=torch.int64, device=DEV)       # a fan of ten faces
+        pts, _ = Mh.sample_surface(verts, faces, 257, 1)
+        Mh.nearest_distances(pts, verts)
+        Mh.subdivide_to_size(verts, faces, 0.3, attrs=verts[:, :2].contiguous())
+        rgbd = torch.rand(17, 33, 4, generator=gen).to(DEV) + 0.5
+        fpos = (torch.rand(NF, 3, generator=gen) * 2 - 1 + torch.tensor([0.0, 0.0, 1.0])).to(DEV)
+        o = ops.target_observed_fields(rgbd, torch.eye(4, device=DEV), fpos, 30.0, 30.0, 16.0, 8.0, 0.5, NF, num_points=64, seed=1, frame=0)
+        g = ops.target_observed_fields(rgbd, torch.eye(4, device=DEV), fpos, 30.0, 30.0, 16.0, 8.0, 0.5, NF, num_points=64, seed=1, frame=0,
+                                       num_fields_dev=torch.tensor([5], dtype=torch.int32, device=DEV))
+        assert 0 < int(o["num_used"]) <= 64 and int(g["current_count"]) <= int(o["current_count"]) <= NF
+        n = bands.check()
+    assert n > 12
+
+
+@contextmanager
+def one_byte_short(query):
+    """the size query `query` answers one byte less: the host layer allocates that and passes it on as workspace_bytes"""
+    L = K.lib()
+    real = getattr(L, query)
+    setattr(L, query, lambda *a: real(*a) - 1)
+    try:
+        yield
+    finally:
+        setattr(L, query, real)
+
+
+def test_one_byte_short_of_the_reported_size_is_refused():
+    """The entry points whose next step after the workspace check is a launch (the others: tests/test_capi_cpu.py and its
+    neighbours, without a device): one byte short of the reported size is refused with the entry point's own code and
+    message, the reported size itself runs (every other test of this file, and the plain calls below)."""
+    from neural_graph_mapping_amd import mesh as Mh
+    gen = torch.Generator().manual_seed(9)
+
+    def refused(query, code, msg, call):
+        call()                                                        # the reported size: accepted
+        with one_byte_short(query):
+            with pytest.raises(K.NgmError, match=msg) as e:
+                call()
+        assert e.value.code == code, (query, e.value.code)
+        torch.cuda.synchronize()
+
+    verts = torch.randn(12, 3, generator=gen).to(DEV)
+    faces = torch.tensor([[0, i, i + 1] for i in range(1, 11)], dtype=torch.int64, device=DEV)
+    refused("ngm_mesh_subdivide_workspace", K.NGM_E_INVALID, "ngm_mesh_subdivide_count: workspace too small",
+            lambda: Mh.subdivide_to_size(verts, faces, 0.3))
+    NF = 7
+    rgbd = torch.rand(17, 33, 4, generator=gen).to(DEV) + 0.5
+    fpos = (torch.rand(NF, 3, generator=gen) * 2 - 1 + torch.tensor([0.0, 0.0, 1.0])).to(DEV)
+    obs = lambda **kw: ops.target_observed_fields(rgbd, torch.eye(4, device=DEV), fpos, 30.0, 30.0, 16.0, 8.0, 0.5, NF, num_points=64,
+                                                  seed=1, frame=0, **kw)
+    refused("ngm_target_observed_fields_workspace", K.NGM_E_WORKSPACE, "ngm_target_observed_fields: workspace too small", obs)
+    refused("ngm_target_observed_fields_grow_workspace", K.NGM_E_WORKSPACE, "ngm_target_observed_fields: workspace too small",
+            lambda: obs(num_fields_dev=torch.tensor([5], dtype=torch.int32, device=DEV)))
+    r = make_renderer(FOURIER, dict(num_samples_coarse=4, num_samples_depth_guided=4), NF)
+    pos = (torch.rand(NF, 3, generator=gen) * 2 - 1 + torch.tensor([0.0, 0.0, -1.7])).to(DEV)
+    quat = torch.nn.functional.normalize(torch.randn(NF, 4, generator=gen), dim=-1).to(DEV)
+    params = {k: v for k, v in r._model.kernel_params().items() if k != "_neus_sd"}
+    ijs = torch.stack([torch.randint(0, 480, (130,), generator=gen), torch.randint(0, 640, (130,), generator=gen)], -1).to(DEV)
+    rc = K.render_cfg(num_samples_coarse=33, num_samples_guided=0)
+    refused("ngm_render_eval_knn_workspace", K.NGM_E_WORKSPACE, "ngm_render_eval_knn: workspace too small",
+            lambda: ops.render_eval_knn(r._fc, rc, params, ijs, torch.eye(4, device=DEV), pos, quat, num_knn=3, far_const=4.0, ray_block=64))
+    F, P = 3, 257
+    pts = torch.randn(F, P, 3, generator=gen).to(DEV)
+    grad_params = {k: v[:F].detach().clone().requires_grad_() for k, v in r._model.all_fields_params.items() if k != "_neus_sd"}
+    fc = K.field_cfg(**FOURIER, matmul_mode="auto")                   # (the arithmetic that has a stash-reading backward)
+    assert K.lib().ngm_field_eval_stash_bytes(K.C.byref(fc), F, P) > 0
+    refused("ngm_field_eval_stash_bytes", K.NGM_E_WORKSPACE, "ngm_field_eval_fwd_train: stash too small",
+            lambda: ops.field_eval(fc, grad_params, pts))
+    t3 = make_renderer(FOURIER, dict(num_samples_coarse=9, num_samples_depth_guided=5), F)
+    p3, q3, t = synth_target(F, 41, seed=1)
+    t3.set_field_poses(p3.to(DEV), q3.to(DEV))
+    tgt = make_target(t, torch.arange(F))
+
+    def step():
+        t3._ws_cache.clear()
+        t3.optimization_iteration(tgt, seed=3, update=False)
+
+    refused("ngm_render_workspace", K.NGM_E_WORKSPACE, "render_fwd: workspace too small", step)
 
 
 # ------------------------------------------------------------------------------------------------ (b) two streams

@@ -54,19 +54,22 @@ def _call(capi, live, edits):
         else:
             r[key] = val
     s, kf = r["s"], r["kf"]
-    plan = L.ngm_target_sample_mv_live_workspace if live else L.ngm_target_sample_mv_workspace
+    plan = (L.ngm_target_sample_mv_grow_workspace if live == "grow" else L.ngm_target_sample_mv_live_workspace if live
+            else L.ngm_target_sample_mv_workspace)
     need = plan(kf.num_frames if kf is not None else 1, s.num_current if s is not None else 1,
                 s.num_fields if s is not None else 1, min(max(s.capacity, 0), MAX_DRAW) if s is not None else 0)
     need = max(need, 1)
     ref = lambda x: None if x is None else C.byref(x)
-    if live:
+    if live == "grow":                                           # the live records over reserved rows + the device field count
+        rc = L.ngm_target_sample_mv_grow(ref(kf), ref(s), ref(r["live"]), r.get("num_fields_dev", PTR), ref(r["out"]), ws, need - short, None)
+    elif live:
         rc = L.ngm_target_sample_mv_live(ref(kf), ref(s), ref(r["live"]), ref(r["out"]), ws, need - short, None)
     else:
         rc = L.ngm_target_sample_mv(ref(kf), ref(s), ref(r["out"]), ws, need - short, None)
     return rc, L.ngm_last_error().decode()
 
 
-S, LV = "ngm_target_sample_mv: ", "ngm_target_sample_mv_live: "
+S, LV, GR = "ngm_target_sample_mv: ", "ngm_target_sample_mv_live: ", "ngm_target_sample_mv_grow: "
 NULL_ARRAY = "NULL array (iteration < 0 needs iteration_dev)"
 BIG = dict([("s.num_fields", 5000), ("s.num_current", 3000)])
 
@@ -162,11 +165,16 @@ ROWS = [
      LV + "capacity must be min(min(T, num_fields), fields of this rank)"),
     ("order_counts_before_arrays", True, {"live.num_current": None, "s.count": None}, INVALID, LV + "NULL device count"),
     ("order_outputs_before_workspace", True, {"out.far": None, "ws_short": 1}, INVALID, LV + "NULL output array"),
+    # ---- ngm_target_sample_mv_grow: the live entry point's checks behind its own ----
+    ("num_fields_dev_null", "grow", {"num_fields_dev": None}, INVALID, GR + "NULL num_fields_dev"),
+    ("ws_null", "grow", {"ws": None}, WORKSPACE, GR + "workspace too small"),
+    ("ws_one_byte_short", "grow", {"ws_short": 1}, WORKSPACE, GR + "workspace too small"),
+    ("order_outputs_before_workspace", "grow", {"out.far": None, "ws_short": 1}, INVALID, GR + "NULL output array"),
 ]
 
 
 @pytest.mark.parametrize("live,edits,status,message", [r[1:] for r in ROWS],
-                         ids=[("live-" if r[1] else "static-") + r[0] for r in ROWS])
+                         ids=[("grow-" if r[1] == "grow" else "live-" if r[1] else "static-") + r[0] for r in ROWS])
 def test_sampler_refuses_before_any_launch(capi, live, edits, status, message):
     rc, err = _call(capi, live, edits)
     assert (rc, err) == (status, message)
