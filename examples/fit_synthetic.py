@@ -19,7 +19,8 @@ graph keeps replaying, and the PSNR of keyframe 0 is reported before and right a
 --mesh-metrics also scores the map as a mesh on the device (NeuralGraphRenderer.evaluate_mesh): the mesh extracted from the
 fields around the sphere against the scene's analytic sphere, triangulated here -- the ten numbers of the reference's mesh
 evaluation (accuracy, completion, their ratios at 5 cm and 1 cm, F1).  The cameras see the front of the sphere only, so
-completion counts its unseen back as missing.
+completion counts its unseen back as missing.  The ten numbers are printed twice: for the mesh as extracted, and for the mesh
+aligned to the sphere by point-to-plane ICP on the device first (mesh.align_mesh), the reference's eval_mesh_alignment.
 --mesh-metrics --cull also scores the two meshes the way the reference's evaluate_raw_mesh does: both culled first by what the
 keyframes see (NeuralGraphRenderer.evaluate_raw_mesh, method "occlusion": frusta and self-occlusion from every keyframe pose),
 so the sphere's unseen back no longer counts against completion.
@@ -217,6 +218,15 @@ def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0, g
         else:
             print("mesh of the fields around the sphere against the analytic sphere (metres; ratios at 5 cm / 1 cm):")
             print("  " + "  ".join(f"{k} {v:.4f}" for k, v in m.items()))
+            # once more as the reference's eval_mesh_alignment scores it: the extracted mesh aligned to the ground truth by
+            # point-to-plane ICP on the device first (mesh.align_mesh; evaluate_raw_mesh(align="icp") does it between its two cullings)
+            from neural_graph_mapping_amd import mesh as ngm_mesh
+            est = r.extract_mesh(resolution=0.02, field_ids=around)
+            aligned, icp = ngm_mesh.align_mesh((est[0], est[1]), (gv.to(dev), gf.to(dev)))
+            ma = ngm_mesh.evaluate_mesh(aligned, (gv.to(dev), gf.to(dev)), num_points=200000, seed=0)
+            print(f"the same after ICP alignment ({int(icp.iterations)} iterations, converged {bool(icp.converged)}, fitness {float(icp.fitness):.4f}, "
+                  f"inlier rmse {float(icp.inlier_rmse):.4f} m):")
+            print("  " + "  ".join(f"{k} {v:.4f}" for k, v in ma.items()))
         if cull and m is not None:
             m = r.evaluate_raw_mesh((gv.to(dev), gf.to(dev)), c2ws, cam, "occlusion", "occlusion", num_points=200000, seed=0, resolution=0.02,
                                     field_ids=around)

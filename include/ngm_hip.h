@@ -791,7 +791,7 @@ int ngm_marching_cubes_tables(int8_t* tri_table, int32_t* tri_count);
 /* ---- scoring a mesh: surface samples and exact nearest points (additive to ABI 11) --------------------------------------
  * The device parts of evaluation._evaluate_postprocessed_meshes (evaluation.py:163-208): the two
  * trimesh.sample.sample_surface calls (evaluation.py:190-191) and the scipy.spatial.KDTree build + query behind every one
- * of the ten numbers (evaluation.py:75-130).  Culling and the subdivision before it are the next two blocks'; ICP alignment is the caller's.
+ * of the ten numbers (evaluation.py:75-130).  Culling and the subdivision before it are the next two blocks', ICP alignment the one after them.
  * ngm_surface_sample: verts (V,3) fp32, faces (F,3) int64 -> points (N,3) fp32, face_ids (N) int64.  trimesh's sampler
  * restated from its public definition: a face with probability proportional to its area (fp32 area, fp64 inclusive scan,
  * binary search for the first cum[k] > u * total), then the point v0 + u (v1 - v0) + v (v2 - v0) with (u, v) reflected to
@@ -902,6 +902,58 @@ int ngm_mesh_subdivide_count(const float* verts, int64_t num_verts, const int64_
 int ngm_mesh_subdivide_emit(const float* verts, int64_t num_verts, const int64_t* faces, int64_t num_faces, const float* attrs,
                             int32_t num_channels, const void* workspace, int64_t new_vertices, int64_t out_faces, float* out_verts,
                             int64_t* out_faces_idx, float* out_attrs, int64_t* out_parent, void* stream);
+
+/* ---- aligning a mesh to the ground truth: vertex normals and point-to-plane ICP (additive to ABI 11) ---------------------
+ * evaluation._align_mesh (evaluation.py:133-160), the step evaluation.evaluate_raw_mesh runs between culling the ground truth
+ * and culling the estimate: Open3D's registration_icp from the estimate's vertices to the culled ground truth's vertices and
+ * vertex normals, threshold 0.1, identity start, TransformationEstimationPointToPlane, at most 100 iterations.
+ * PARITY UNPINNED against Open3D (not installed here): both entry points are restated from Open3D's public definitions, and
+ * the yardstick is the fp64 host mirror tests/_mesh_align_host.py, written to the rules below.
+ * ngm_mesh_vertex_normals: verts (V,3) fp32, faces (F,3) int64 -> normals (V,3) fp32, Open3D's compute_vertex_normals: every
+ *   face adds its unnormalised normal (v1 - v0) x (v2 - v0) (fp64 from the fp32 vertices: area weighting) to its three vertices,
+ *   the sum is normalised in fp64 and rounded to fp32.  A vertex whose sum has length 0 (no face refers to it, or exact
+ *   cancellation) gets (0, 0, 1); so does a vertex with a non-finite coordinate.  A face with an index outside [0, V) or a
+ *   non-finite vertex adds nothing.  The sums are int64 fixed-point sums at a per-vertex scale (the largest exponent among the
+ *   vertex's incident normals and its valence, found by a first pass, make 2^62 the bound of the sum): integer addition is
+ *   associative, so the result does not depend on the order of the faces and is bitwise equal from call to call; the
+ *   fixed-point rounding is below 2^-40 of the largest term.  One atomic per (face, corner, component) and pass; no thread
+ *   loops over the faces of a vertex.
+ * ngm_icp_point_to_plane: source (N,3), target (M,3), target_normals (M,3) fp32; init: 16 doubles, row-major, on the HOST
+ *   (read before the call returns; NULL = identity; its last row is taken as 0 0 0 1); state: 64 doubles on the DEVICE.
+ *   Pass k = 0 .. max_iteration works at the current transformation T_k (fp64, in `state`):
+ *   - p = R s + t in fp64, ((R0 sx + R1 sy) + R2 sz) + t per row, no fused multiply-add; the search runs from (float)p on a
+ *     uniform grid over the finite target points, built ONCE per call, ring by ring as ngm_nearest_point does, with fp32
+ *     distances; EQUAL DISTANCES GO TO THE SMALLEST TARGET INDEX; the search stops where no unseen point can be within
+ *     `threshold` (plus rounding slack) of p;
+ *   - the found target q is a correspondence iff d = sqrt((dx dx + dy dy) + dz dz) < threshold, in fp64 from the fp64 p;
+ *   - a non-finite source point (or p), a call without a finite target, and a correspondence whose normal n is not finite take no part;
+ *   - with r = (p - q) . n and J = [p x n, n]: the 21 upper entries of J^T J (row by row), the 6 of J^T r, sum d^2 and the
+ *     count are summed in fp64: per thread over a grid-stride loop of a fixed grid, per wave, per workgroup, then over the
+ *     workgroups' rows, every step in a fixed order -- bitwise equal from call to call;
+ *   - fitness_k = count / N (the denominator is always N), rmse_k = sqrt(sum d^2 / count), 0 without correspondences;
+ *   - k >= 1 and |fitness_k - fitness_{k-1}| < relative_fitness and |rmse_k - rmse_{k-1}| < relative_rmse: converged, stop at T_k;
+ *     else k == max_iteration: stop, not converged; else J^T J x = -J^T r by Cholesky in fp64,
+ *     U = Rz(x2) Ry(x1) Rx(x0) with translation (x3, x4, x5), T_{k+1} = U T_k.
+ *   - No correspondence gives the identity update.  SINGULAR SYSTEMS (OUR RULE -- Open3D's LDLT has no check): a Cholesky pivot
+ *     that is not above 1e-12 x the largest diagonal entry of J^T J, or a solution that is not finite, gives the identity update
+ *     (a planar target leaves three columns of J^T J exactly zero; the next pass then converges at the unchanged T).
+ *   All max_iteration + 1 passes (two launches each) are enqueued at once; a `done` flag in `state` turns the launches after
+ *   the stop into immediate exits.  No host synchronisation: the call can be captured in a graph (init is read at capture).
+ *   state: [0, 16) T row-major; [16] fitness; [17] inlier rmse; [18] iterations = the k it stopped at = updates applied; [19]
+ *   converged (0 / 1); [20, 49) the last pass's sums -- J^T J upper (21), J^T r (6), sum d^2, count (with max_iteration = 0:
+ *   the sums at init); [49] done (internal); [50, 64) zero.
+ * Both: the caller owns the workspace (the *_workspace functions: bytes, or NGM_E_INVALID for sizes the calls refuse; stale
+ * contents are never read).  NGM_E_INVALID before anything is launched for a NULL array, a negative count, a count >= 2^31, a
+ * workspace that is too small, and (ICP) M == 0, a threshold that is not finite or not > 0, max_iteration outside [0, 1000].
+ * V == 0 launches nothing; N == 0 writes state (T = init, fitness 0, converged 0) and returns NGM_OK. */
+int64_t ngm_mesh_vertex_normals_workspace(int64_t num_verts);
+int ngm_mesh_vertex_normals(const float* verts, int64_t num_verts, const int64_t* faces, int64_t num_faces, float* normals,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+int64_t ngm_icp_point_to_plane_workspace(int64_t num_target, int64_t num_source);
+int ngm_icp_point_to_plane(const float* source, int64_t num_source, const float* target, const float* target_normals,
+                           int64_t num_target, double threshold, int32_t max_iteration, double relative_fitness,
+                           double relative_rmse, const double* init, double* state, void* workspace, int64_t workspace_bytes,
+                           void* stream);
 
 /* ---- measurement hooks (bench.py roofline leg) ------------------------------------------------
  * When enabled, every launch of the listed kernels is bracketed by hipEvents recorded on the launch

@@ -364,6 +364,14 @@ def lib():
     L.ngm_mesh_subdivide_count.restype = C.c_int
     L.ngm_mesh_subdivide_emit.argtypes = [vp, i64, vp, i64, vp, i32, vp, i64, i64, vp, vp, vp, vp, vp]
     L.ngm_mesh_subdivide_emit.restype = C.c_int
+    L.ngm_mesh_vertex_normals_workspace.argtypes = [i64]
+    L.ngm_mesh_vertex_normals_workspace.restype = i64
+    L.ngm_mesh_vertex_normals.argtypes = [vp, i64, vp, i64, vp, vp, i64, vp]
+    L.ngm_mesh_vertex_normals.restype = C.c_int
+    L.ngm_icp_point_to_plane_workspace.argtypes = [i64, i64]
+    L.ngm_icp_point_to_plane_workspace.restype = i64
+    L.ngm_icp_point_to_plane.argtypes = [vp, i64, vp, vp, i64, C.c_double, i32, C.c_double, C.c_double, vp, vp, vp, i64, vp]
+    L.ngm_icp_point_to_plane.restype = C.c_int
     L.ngm_debug_plan_bwd.argtypes = [P(FieldCfg), P(RenderCfg), i32, i64, i32, i32, i32, P(i32)]
     L.ngm_debug_plan_bwd.restype = C.c_int
     L.ngm_debug_plan_fwd.argtypes = [P(FieldCfg), P(RenderCfg), i32, i32, i64, i32, P(i32)]
@@ -398,7 +406,8 @@ EXPORTED = ["ngm_abi_version", "ngm_last_error", "ngm_device_info", "ngm_permuto
             "ngm_marching_cubes_workspace", "ngm_marching_cubes_count", "ngm_marching_cubes_emit", "ngm_marching_cubes_tables",
             "ngm_surface_sample_workspace", "ngm_surface_sample", "ngm_nearest_point_workspace", "ngm_nearest_point",
             "ngm_mesh_depth", "ngm_mesh_visibility",
-            "ngm_mesh_subdivide_workspace", "ngm_mesh_subdivide_count", "ngm_mesh_subdivide_emit"]
+            "ngm_mesh_subdivide_workspace", "ngm_mesh_subdivide_count", "ngm_mesh_subdivide_emit",
+            "ngm_mesh_vertex_normals_workspace", "ngm_mesh_vertex_normals", "ngm_icp_point_to_plane_workspace", "ngm_icp_point_to_plane"]
 
 # parameters that never receive a gradient (the CUDA package gives none to the per-level shifts either;
 # torch.optim.Adam skips grad-less parameters, so the sparse Adam must skip them too)

@@ -35,6 +35,13 @@ int ngm_launch_surface_sample(const float* verts, int64_t V, const int64_t* face
 int64_t ngm_nearest_point_bytes(int64_t M, int64_t N);
 int ngm_launch_nearest_point(const float* refs, int64_t M, const float* queries, int64_t N, float* dist, int64_t* index, void* workspace,
                              int64_t workspace_bytes, hipStream_t st);
+int64_t ngm_mesh_vertex_normals_bytes(int64_t V);
+int ngm_launch_mesh_vertex_normals(const float* verts, int64_t V, const int64_t* faces, int64_t F, float* normals, void* workspace,
+                                   int64_t workspace_bytes, hipStream_t st);
+int64_t ngm_icp_point_to_plane_bytes(int64_t M, int64_t N);
+int ngm_launch_icp_point_to_plane(const float* source, int64_t N, const float* target, const float* target_normals, int64_t M,
+                                  double threshold, int max_iteration, double relative_fitness, double relative_rmse, const double* init,
+                                  double* state, void* workspace, int64_t workspace_bytes, hipStream_t st);
 int64_t ngm_mesh_subdivide_bytes(int64_t F);
 int ngm_launch_mesh_subdivide_count(const float* verts, int64_t V, const int64_t* faces, int64_t F, double max_edge, int max_iter,
                                     void* workspace, int64_t workspace_bytes, int64_t* totals, hipStream_t st);
@@ -1657,6 +1664,44 @@ int ngm_mesh_subdivide_emit(const float* verts, int64_t num_verts, const int64_t
   ngm_launch_mesh_subdivide_emit(verts, num_verts, faces, num_faces, attrs, num_channels, workspace, new_vertices, out_faces, out_verts,
                                  out_faces_idx, out_attrs, out_parent, (hipStream_t)stream);
   return check_launch("ngm_mesh_subdivide_emit");
+}
+
+// ------------------------------------------------------------------------------------------------
+// aligning a mesh to the ground truth: vertex normals and point-to-plane ICP (evaluation.py:133-160; ngm_mesh_eval.hip)
+// ------------------------------------------------------------------------------------------------
+int64_t ngm_mesh_vertex_normals_workspace(int64_t num_verts) {
+  if (num_verts < 0 || num_verts > 0x7fffffff) return NGM_E_INVALID;
+  return ngm_mesh_vertex_normals_bytes(num_verts);
+}
+int ngm_mesh_vertex_normals(const float* verts, int64_t num_verts, const int64_t* faces, int64_t num_faces, float* normals,
+                            void* workspace, int64_t workspace_bytes, void* stream) {
+  if (num_verts < 0 || num_faces < 0) return fail(NGM_E_INVALID, "ngm_mesh_vertex_normals: counts must be >= 0");
+  if (num_verts > 0x7fffffff || num_faces > 0x7fffffff) return fail(NGM_E_INVALID, "ngm_mesh_vertex_normals: counts must be below 2^31");
+  if ((num_verts > 0 && (!verts || !normals || !workspace)) || (num_faces > 0 && !faces))
+    return fail(NGM_E_INVALID, "ngm_mesh_vertex_normals: NULL array");
+  if (ngm_launch_mesh_vertex_normals(verts, num_verts, faces, num_faces, normals, workspace, workspace_bytes, (hipStream_t)stream))
+    return fail(NGM_E_INVALID, "ngm_mesh_vertex_normals: workspace too small (ngm_mesh_vertex_normals_workspace)");
+  if (num_verts == 0) return NGM_OK;
+  return check_launch("ngm_mesh_vertex_normals");
+}
+int64_t ngm_icp_point_to_plane_workspace(int64_t num_target, int64_t num_source) {
+  if (num_target < 1 || num_source < 0 || num_target > 0x7fffffff || num_source > 0x7fffffff) return NGM_E_INVALID;
+  return ngm_icp_point_to_plane_bytes(num_target, num_source);
+}
+int ngm_icp_point_to_plane(const float* source, int64_t num_source, const float* target, const float* target_normals, int64_t num_target,
+                           double threshold, int32_t max_iteration, double relative_fitness, double relative_rmse, const double* init,
+                           double* state, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (num_source < 0 || num_target < 0) return fail(NGM_E_INVALID, "ngm_icp_point_to_plane: counts must be >= 0");
+  if (num_target == 0) return fail(NGM_E_INVALID, "ngm_icp_point_to_plane: no target points");
+  if (num_source > 0x7fffffff || num_target > 0x7fffffff) return fail(NGM_E_INVALID, "ngm_icp_point_to_plane: counts must be below 2^31");
+  if (!(threshold > 0.0) || !(threshold < (double)INFINITY)) return fail(NGM_E_INVALID, "ngm_icp_point_to_plane: threshold must be finite and > 0");
+  if (max_iteration < 0 || max_iteration > 1000) return fail(NGM_E_INVALID, "ngm_icp_point_to_plane: 0 <= max_iteration <= 1000");
+  if (!target || !target_normals || !state || !workspace || (num_source > 0 && !source))
+    return fail(NGM_E_INVALID, "ngm_icp_point_to_plane: NULL array");
+  if (ngm_launch_icp_point_to_plane(source, num_source, target, target_normals, num_target, threshold, max_iteration, relative_fitness,
+                                    relative_rmse, init, state, workspace, workspace_bytes, (hipStream_t)stream))
+    return fail(NGM_E_INVALID, "ngm_icp_point_to_plane: workspace too small (ngm_icp_point_to_plane_workspace)");
+  return check_launch("ngm_icp_point_to_plane");
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -421,6 +421,16 @@ int64_t ngm_nearest_point_bytes(int64_t M, int64_t N) {
   a.M = (int)M;
   return ws_bytes(np_layout, a);
 }
+// the grid over a.refs, built once: bounding box -> header -> counts -> exclusive scan -> cell-sorted copy
+static void np_build_grid(const NpArgs& a, hipStream_t st) {
+  const unsigned ref_blocks = (unsigned)std::min<int64_t>(((int64_t)a.M + 255) / 256, 8192);
+  hipLaunchKernelGGL(k_np_bbox, dim3((unsigned)a.bbox_blocks), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(k_np_header, dim3(1), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(k_np_clear, dim3((unsigned)std::min((a.max_cells + 256) / 256, 4096)), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(k_np_count, dim3(ref_blocks), dim3(256), 0, st, a);
+  launch_scan<int, false>(a.cell_start, &a.hdr->ncells, a.max_cells, a.scan_part, st);
+  hipLaunchKernelGGL(k_np_fill, dim3(ref_blocks), dim3(256), 0, st, a);
+}
 int ngm_launch_nearest_point(const float* refs, int64_t M, const float* queries, int64_t N, float* dist, int64_t* index, void* workspace,
                              int64_t workspace_bytes, hipStream_t st) {
   NpArgs a = {};
@@ -430,13 +440,7 @@ int ngm_launch_nearest_point(const float* refs, int64_t M, const float* queries,
   np_layout(a, ws);
   if (!ws.covers(workspace_bytes)) return NGM_E_WORKSPACE;
   if (N == 0) return 0;
-  const unsigned ref_blocks = (unsigned)std::min<int64_t>((M + 255) / 256, 8192);
-  hipLaunchKernelGGL(k_np_bbox, dim3((unsigned)a.bbox_blocks), dim3(256), 0, st, a);
-  hipLaunchKernelGGL(k_np_header, dim3(1), dim3(256), 0, st, a);
-  hipLaunchKernelGGL(k_np_clear, dim3((unsigned)std::min((a.max_cells + 256) / 256, 4096)), dim3(256), 0, st, a);
-  hipLaunchKernelGGL(k_np_count, dim3(ref_blocks), dim3(256), 0, st, a);
-  launch_scan<int, false>(a.cell_start, &a.hdr->ncells, a.max_cells, a.scan_part, st);
-  hipLaunchKernelGGL(k_np_fill, dim3(ref_blocks), dim3(256), 0, st, a);
+  np_build_grid(a, st);
   hipLaunchKernelGGL(k_np_query, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, a);
   return 0;
 }
@@ -450,6 +454,7 @@ int ngm_launch_nearest_point(const float* refs, int64_t M, const float* queries,
 //   k_sub_faces  : one thread per OUTPUT face: parent by binary search in the scanned child counts, row formula -> (i, j)
 //   k_sub_verts  : one thread per OUTPUT vertex: parent by binary search in the scanned vertex counts, row formula -> (i, j)
 // A workgroup's first and last thread search all faces, the others between the two parents found: no thread loops over children.
+// After it: vertex normals (k_vn_*) and point-to-plane ICP (k_icp_*) -- evaluation._align_mesh, evaluation.py:133-160.
 constexpr int SUB_MAX_ITER = 10;
 constexpr int SUB_T = 256;
 
@@ -666,5 +671,363 @@ int ngm_launch_mesh_subdivide_emit(const float* verts, int64_t V, const int64_t*
     hipLaunchKernelGGL(k_sub_verts, dim3((unsigned)((new_vertices + SUB_T - 1) / SUB_T)), dim3(SUB_T), 0, st, a);
   if (F > 0 && out_faces > 0)
     hipLaunchKernelGGL(k_sub_faces, dim3((unsigned)((out_faces + SUB_T - 1) / SUB_T)), dim3(SUB_T), 0, st, a);
+  return 0;
+}
+
+// ---- vertex normals ---------------------------------------------------------------------------------------------------
+// Open3D's compute_vertex_normals: every face adds (v1 - v0) x (v2 - v0) to its three vertices, the sums are normalised.
+// The sums are EXACT integer sums, so neither the order of the faces nor the order of the atomics shows:
+//   k_vn_clear : exponent, valence and the three int64 sums of every vertex
+//   k_vn_scale : per face: atomic max of the largest binary exponent among its normal's components, valence + 1, per corner
+//   k_vn_add   : per face: the normal again (fp64 from the fp32 vertices), times 2^(62 - e_v - ceil(log2(valence + 1))), rounded
+//                to int64 and added: |term| <= 2^(62 - L) and valence < 2^L, so the sum stays below 2^62
+//   k_vn_finish: per vertex: normalise in fp64, round to fp32; (0, 0, 1) for a sum of length 0 or a non-finite vertex
+// No thread loops over the faces of a vertex: a fan of any valence costs its faces one atomic each per pass.
+constexpr int VN_EMPTY = -(1 << 20);
+struct VnArgs {
+  const float* verts; const int64_t* faces;
+  int64_t V, F;
+  int* emax;                       // (V)
+  unsigned long long* valence;     // (V)
+  unsigned long long* acc;         // (V, 3) int64 sums, two's complement
+  float* normals;
+};
+
+// the corners' indices and the unnormalised normal of face f; false when the face adds nothing
+__device__ __forceinline__ bool vn_face(const VnArgs& a, int64_t f, int64_t (&ix)[3], double (&n)[3]) {
+  float p[3][3];
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int64_t i = a.faces[3 * f + k];
+    ix[k] = i;
+    if (i < 0 || i >= a.V) { ok = false; p[k][0] = p[k][1] = p[k][2] = 0.f; continue; }
+#pragma unroll
+    for (int d = 0; d < 3; ++d) { p[k][d] = a.verts[3 * i + d]; ok = ok && me_finite(p[k][d]); }
+  }
+  const double ax = (double)p[1][0] - (double)p[0][0], ay = (double)p[1][1] - (double)p[0][1], az = (double)p[1][2] - (double)p[0][2];
+  const double bx = (double)p[2][0] - (double)p[0][0], by = (double)p[2][1] - (double)p[0][1], bz = (double)p[2][2] - (double)p[0][2];
+  n[0] = ay * bz - az * by; n[1] = az * bx - ax * bz; n[2] = ax * by - ay * bx;       // finite: |products| < 2^258
+  return ok;
+}
+// e with |v| < 2^e for a finite v != 0 (frexp's exponent); VN_EMPTY for 0.  The products of fp32 differences are never subnormal.
+__device__ __forceinline__ int vn_exponent(double v) {
+  if (v == 0.0) return VN_EMPTY;
+  return (int)((__double_as_longlong(v) >> 52) & 0x7ff) - 1022;
+}
+
+__global__ __launch_bounds__(256) void k_vn_clear(VnArgs a) {
+  const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (v >= a.V) return;
+  a.emax[v] = VN_EMPTY; a.valence[v] = 0ull;
+  a.acc[3 * v] = 0ull; a.acc[3 * v + 1] = 0ull; a.acc[3 * v + 2] = 0ull;
+}
+__global__ __launch_bounds__(256) void k_vn_scale(VnArgs a) {
+  const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (f >= a.F) return;
+  int64_t ix[3];
+  double n[3];
+  if (!vn_face(a, f, ix, n)) return;
+  const int e = max(vn_exponent(n[0]), max(vn_exponent(n[1]), vn_exponent(n[2])));
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    if (e != VN_EMPTY) atomicMax(&a.emax[ix[k]], e);
+    atomicAdd(&a.valence[ix[k]], 1ull);
+  }
+}
+__global__ __launch_bounds__(256) void k_vn_add(VnArgs a) {
+  const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (f >= a.F) return;
+  int64_t ix[3];
+  double n[3];
+  if (!vn_face(a, f, ix, n)) return;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int e = a.emax[ix[k]];
+    if (e == VN_EMPTY) continue;                                     // every normal at this vertex is exactly zero
+    const int L = 64 - __clzll((long long)a.valence[ix[k]]);          // ceil(log2(valence + 1)), valence >= 1 here
+    const int shift = 62 - e - L;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      const long long q = llrint(ldexp(n[d], shift));
+      if (q != 0) atomicAdd(&a.acc[3 * ix[k] + d], (unsigned long long)q);
+    }
+  }
+}
+__global__ __launch_bounds__(256) void k_vn_finish(VnArgs a) {
+  const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (v >= a.V) return;
+  float o[3] = {0.f, 0.f, 1.f};
+  if (me_finite(a.verts[3 * v]) && me_finite(a.verts[3 * v + 1]) && me_finite(a.verts[3 * v + 2])) {
+    const double sx = (double)(long long)a.acc[3 * v], sy = (double)(long long)a.acc[3 * v + 1], sz = (double)(long long)a.acc[3 * v + 2];
+    const double len = sqrt((sx * sx + sy * sy) + sz * sz);          // the common scale 2^shift cancels
+    if (len > 0.0) { o[0] = (float)(sx / len); o[1] = (float)(sy / len); o[2] = (float)(sz / len); }
+  }
+  a.normals[3 * v] = o[0]; a.normals[3 * v + 1] = o[1]; a.normals[3 * v + 2] = o[2];
+}
+
+static void vn_layout(VnArgs& a, WsArena& ws) {
+  a.emax = ws.take<int>(a.V);
+  a.valence = ws.take<unsigned long long>(a.V);
+  a.acc = ws.take<unsigned long long>(3 * a.V);
+}
+int64_t ngm_mesh_vertex_normals_bytes(int64_t V) {
+  VnArgs a = {};
+  a.V = V;
+  return ws_bytes(vn_layout, a);
+}
+int ngm_launch_mesh_vertex_normals(const float* verts, int64_t V, const int64_t* faces, int64_t F, float* normals, void* workspace,
+                                   int64_t workspace_bytes, hipStream_t st) {
+  VnArgs a = {};
+  a.verts = verts; a.faces = faces; a.V = V; a.F = F; a.normals = normals;
+  WsArena ws(workspace);
+  vn_layout(a, ws);
+  if (!ws.covers(workspace_bytes)) return NGM_E_WORKSPACE;
+  if (V == 0) return 0;
+  const unsigned vb = (unsigned)((V + 255) / 256), fb = (unsigned)((F + 255) / 256);
+  hipLaunchKernelGGL(k_vn_clear, dim3(vb), dim3(256), 0, st, a);
+  if (F > 0) {
+    hipLaunchKernelGGL(k_vn_scale, dim3(fb), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_vn_add, dim3(fb), dim3(256), 0, st, a);
+  }
+  hipLaunchKernelGGL(k_vn_finish, dim3(vb), dim3(256), 0, st, a);
+  return 0;
+}
+
+// ---- point-to-plane ICP -------------------------------------------------------------------------------------------------
+// Open3D's registration_icp with TransformationEstimationPointToPlane (evaluation._align_mesh, evaluation.py:133-160); the
+// rules are written down in include/ngm_hip.h.  The grid over the target is built ONCE (np_build_grid); then per pass
+//   k_icp_accumulate : a FIXED grid of ICP_BLOCKS x ICP_T threads strides over the source points: p = R s + t in fp64, the ring
+//                      search of k_np_query from (float)p -- ties to the smallest original index, stopped where the proven gap
+//                      is beyond the threshold --, the correspondence test in fp64, 29 fp64 sums in registers; reduced per
+//                      wave (shuffles), per workgroup (LDS), one row of ICP_ROW doubles per workgroup, written on every pass
+//   k_icp_solve      : one workgroup: the rows in a fixed order, fitness / rmse / convergence, 6 x 6 Cholesky by one thread,
+//                      T <- U T.  Once it sets `done` in the state both kernels of the remaining passes return at once.
+// Nothing is read back; all passes are enqueued at once.
+constexpr int ICP_BLOCKS = 1024, ICP_T = 256, ICP_SUMS = 29, ICP_ROW = 32;
+constexpr int ICP_S_FITNESS = 16, ICP_S_RMSE = 17, ICP_S_ITER = 18, ICP_S_CONV = 19, ICP_S_SUMS = 20, ICP_S_DONE = 49, ICP_STATE = 64;
+struct IcpArgs {
+  NpArgs np;                 // the grid over the target
+  const float* source; const float* normals;
+  int N, max_iteration;
+  double threshold, relative_fitness, relative_rmse;
+  double* state;             // (64) on the device
+  double* partial;           // (ICP_BLOCKS, ICP_ROW)
+};
+struct IcpInit { double t[16]; };
+
+__global__ void k_icp_init(double* state, IcpInit init) {
+  const int t = threadIdx.x;
+  if (t < ICP_STATE) state[t] = t < 16 ? init.t[t] : 0.0;
+}
+
+// k_np_query's search with three differences: equal distances go to the smallest original index (and the search goes on
+// while an unseen point could TIE), rows and rings whose proven gap exceeds `stop` are left out, and the coordinates of the
+// point found come back with its index.  -1: no finite target within `stop`.
+__device__ __forceinline__ int icp_search(const NpArgs& a, const NpGridHdr& h, float x, float y, float z, float stop, float (&q)[3]) {
+  const float gx = (x - h.x0) * h.inv_c, gy = (y - h.y0) * h.inv_c, gz = (z - h.z0) * h.inv_c;
+  const int ix = np_cell1(gx, h.nx), iy = np_cell1(gy, h.ny), iz = np_cell1(gz, h.nz);
+  const float slack = 2.0e-6f * (float)(h.nmax + 2);
+  auto world_gap = [&](float cells) { return fmaxf(cells * (1.0f - 2.0e-6f) - slack, 0.f) * h.c * (1.0f - 2.0e-6f); };
+  float best = INFINITY;
+  int bi = -1;
+  auto visit = [&](int j0, int j1) __attribute__((always_inline)) {
+    for (int j = j0; j < j1; ++j) {
+      const float4 c = a.sorted[j];
+      const float dx = x - c.x, dy = y - c.y, dz = z - c.z;
+      const float d = sqrtf((dx * dx + dy * dy) + dz * dz);
+      const int id = __float_as_int(c.w);
+      if (bi < 0 || d < best || (d == best && id < bi)) { best = d; bi = id; q[0] = c.x; q[1] = c.y; q[2] = c.z; }
+    }
+  };
+  for (int r = 0;; ++r) {
+    const int xlo = max(ix - r, 0), xhi = min(ix + r, h.nx - 1);
+    const int ylo = max(iy - r, 0), yhi = min(iy + r, h.ny - 1);
+    const int zlo = max(iz - r, 0), zhi = min(iz + r, h.nz - 1);
+    for (int cz = zlo; cz <= zhi; ++cz) {
+      const float lz = fmaxf(fmaxf((float)cz - gz, gz - (float)(cz + 1)), 0.f);
+      for (int cy = ylo; cy <= yhi; ++cy) {
+        const float ly = fmaxf(fmaxf((float)cy - gy, gy - (float)(cy + 1)), 0.f);
+        if (world_gap(fmaxf(ly, lz)) > fminf(best, stop)) continue; // nothing in this row can be closer, or as close as `stop`
+        const int rowb = (cz * h.ny + cy) * h.nx;
+        if (abs(cz - iz) == r || abs(cy - iy) == r) {
+          visit(a.cell_start[rowb + xlo], a.cell_start[rowb + xhi + 1]);
+        } else {
+          if (ix - r >= 0) visit(a.cell_start[rowb + ix - r], a.cell_start[rowb + ix - r + 1]);
+          if (ix + r <= h.nx - 1) visit(a.cell_start[rowb + ix + r], a.cell_start[rowb + ix + r + 1]);
+        }
+      }
+    }
+    float gap = INFINITY;
+    if (ix - r > 0) gap = fminf(gap, gx - (float)(ix - r));
+    if (ix + r < h.nx - 1) gap = fminf(gap, (float)(ix + r + 1) - gx);
+    if (iy - r > 0) gap = fminf(gap, gy - (float)(iy - r));
+    if (iy + r < h.ny - 1) gap = fminf(gap, (float)(iy + r + 1) - gy);
+    if (iz - r > 0) gap = fminf(gap, gz - (float)(iz - r));
+    if (iz + r < h.nz - 1) gap = fminf(gap, (float)(iz + r + 1) - gz);
+    if (gap == INFINITY) break;
+    const float wg = world_gap(gap);
+    if (best < wg || wg > stop) break;                             // strictly: a point at exactly `best` may carry a smaller index
+  }
+  return bi;
+}
+
+__global__ __launch_bounds__(ICP_T) void k_icp_accumulate(IcpArgs a) {
+  __shared__ double red[ICP_T / 64][ICP_ROW];
+  if (a.state[ICP_S_DONE] != 0.0) return;                           // the same for every thread: nobody reaches the barrier
+  double T[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) T[i] = a.state[i];
+  const NpGridHdr h = *a.np.hdr;
+  double acc[ICP_SUMS];
+#pragma unroll
+  for (int i = 0; i < ICP_SUMS; ++i) acc[i] = 0.0;
+  const float thr_f = (float)a.threshold * 1.0001f;
+  for (int64_t i = (int64_t)blockIdx.x * ICP_T + threadIdx.x; i < a.N; i += (int64_t)ICP_BLOCKS * ICP_T) {
+    const float sx = a.source[3 * i], sy = a.source[3 * i + 1], sz = a.source[3 * i + 2];
+    if (!(me_finite(sx) && me_finite(sy) && me_finite(sz)) || !h.valid) continue;
+    const double px = ((T[0] * (double)sx + T[1] * (double)sy) + T[2] * (double)sz) + T[3];
+    const double py = ((T[4] * (double)sx + T[5] * (double)sy) + T[6] * (double)sz) + T[7];
+    const double pz = ((T[8] * (double)sx + T[9] * (double)sy) + T[10] * (double)sz) + T[11];
+    const float x = (float)px, y = (float)py, z = (float)pz;
+    if (!(me_finite(x) && me_finite(y) && me_finite(z))) continue;
+    // beyond `stop` from (float)p means beyond the threshold from p: the rounding of p is 2^-24 of each coordinate
+    const float stop = thr_f + 4.0e-7f * ((fabsf(x) + fabsf(y)) + fabsf(z));
+    float q[3];
+    const int bi = icp_search(a.np, h, x, y, z, stop, q);
+    if (bi < 0) continue;
+    const double dx = px - (double)q[0], dy = py - (double)q[1], dz = pz - (double)q[2];
+    const double d2 = (dx * dx + dy * dy) + dz * dz;
+    if (!(sqrt(d2) < a.threshold)) continue;
+    const float nxf = a.normals[3 * (int64_t)bi], nyf = a.normals[3 * (int64_t)bi + 1], nzf = a.normals[3 * (int64_t)bi + 2];
+    if (!(me_finite(nxf) && me_finite(nyf) && me_finite(nzf))) continue;
+    const double nx = (double)nxf, ny = (double)nyf, nz = (double)nzf;
+    const double rr = (dx * nx + dy * ny) + dz * nz;
+    const double J[6] = {py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz};
+    int k = 0;
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+      for (int c = r; c < 6; ++c) acc[k++] += J[r] * J[c];
+#pragma unroll
+    for (int r = 0; r < 6; ++r) acc[21 + r] += J[r] * rr;
+    acc[27] += d2;
+    acc[28] += 1.0;
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int s = 0; s < ICP_SUMS; ++s) {
+    double v = acc[s];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+    if (lane == 0) red[wave][s] = v;
+  }
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t < ICP_ROW) a.partial[(int64_t)blockIdx.x * ICP_ROW + t] = t < ICP_SUMS ? ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t] : 0.0;
+}
+
+// x of A x = b by Cholesky, A the 21 upper entries row by row; false (nothing written) where a pivot is not above
+// 1e-12 x the largest diagonal entry or the solution is not finite
+__device__ bool icp_cholesky(const double* up, const double* b, double (&x)[6]) {
+  double A[6][6], Lm[6][6];
+  int k = 0;
+  for (int r = 0; r < 6; ++r) for (int c = r; c < 6; ++c) { A[r][c] = up[k]; A[c][r] = up[k]; ++k; }
+  double dmax = 0.0;
+  for (int r = 0; r < 6; ++r) dmax = fmax(dmax, A[r][r]);
+  for (int j = 0; j < 6; ++j) {
+    double piv = A[j][j];
+    for (int m = 0; m < j; ++m) piv -= Lm[j][m] * Lm[j][m];
+    if (!(piv > 1e-12 * dmax)) return false;
+    const double l = sqrt(piv);
+    Lm[j][j] = l;
+    for (int i = j + 1; i < 6; ++i) {
+      double s = A[i][j];
+      for (int m = 0; m < j; ++m) s -= Lm[i][m] * Lm[j][m];
+      Lm[i][j] = s / l;
+    }
+  }
+  double y[6];
+  for (int i = 0; i < 6; ++i) { double s = b[i]; for (int m = 0; m < i; ++m) s -= Lm[i][m] * y[m]; y[i] = s / Lm[i][i]; }
+  for (int i = 5; i >= 0; --i) { double s = y[i]; for (int m = i + 1; m < 6; ++m) s -= Lm[m][i] * x[m]; x[i] = s / Lm[i][i]; }
+  for (int i = 0; i < 6; ++i) if (!(fabs(x[i]) < (double)INFINITY)) return false;
+  return true;
+}
+
+__global__ __launch_bounds__(256) void k_icp_solve(IcpArgs a, int pass) {
+  __shared__ double red[8][ICP_ROW];
+  double* S = a.state;
+  if (S[ICP_S_DONE] != 0.0) return;
+  const int t = threadIdx.x, col = t & (ICP_ROW - 1), seg = t / ICP_ROW;
+  constexpr int SEG = ICP_BLOCKS / 8;
+  double v = 0.0;
+  for (int b = seg * SEG; b < (seg + 1) * SEG; ++b) v += a.partial[(int64_t)b * ICP_ROW + col];
+  red[seg][col] = v;
+  __syncthreads();
+  if (t != 0) return;
+  double sum[ICP_SUMS];
+  for (int s = 0; s < ICP_SUMS; ++s) {
+    double w = red[0][s];
+    for (int j = 1; j < 8; ++j) w += red[j][s];
+    sum[s] = w;
+    S[ICP_S_SUMS + s] = w;
+  }
+  const double count = sum[28];
+  const double fitness = count / (double)a.N, rmse = count > 0.0 ? sqrt(sum[27] / count) : 0.0;
+  const double fitness0 = S[ICP_S_FITNESS], rmse0 = S[ICP_S_RMSE];
+  S[ICP_S_FITNESS] = fitness; S[ICP_S_RMSE] = rmse; S[ICP_S_ITER] = (double)pass;
+  if (pass >= 1 && fabs(fitness - fitness0) < a.relative_fitness && fabs(rmse - rmse0) < a.relative_rmse) {
+    S[ICP_S_CONV] = 1.0; S[ICP_S_DONE] = 1.0;
+    return;
+  }
+  if (pass >= a.max_iteration) { S[ICP_S_DONE] = 1.0; return; }
+  double b[6], x[6];
+  for (int i = 0; i < 6; ++i) b[i] = -sum[21 + i];
+  if (!(count > 0.0) || !icp_cholesky(sum, b, x)) return;           // identity update: T stays
+  const double ca = cos(x[0]), sa = sin(x[0]), cb = cos(x[1]), sb = sin(x[1]), cg = cos(x[2]), sg = sin(x[2]);
+  // U = Rz(x2) Ry(x1) Rx(x0), translation x3..x5
+  const double U[3][4] = {{cg * cb, cg * sb * sa - sg * ca, cg * sb * ca + sg * sa, x[3]},
+                          {sg * cb, sg * sb * sa + cg * ca, sg * sb * ca - cg * sa, x[4]},
+                          {-sb, cb * sa, cb * ca, x[5]}};
+  double Tn[12];
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 4; ++c) {
+      double w = (U[r][0] * S[c] + U[r][1] * S[4 + c]) + U[r][2] * S[8 + c];
+      if (c == 3) w += U[r][3];                                      // the last row of T is 0 0 0 1
+      Tn[4 * r + c] = w;
+    }
+  for (int i = 0; i < 12; ++i) S[i] = Tn[i];
+}
+
+static void icp_layout(IcpArgs& a, WsArena& ws) {
+  np_layout(a.np, ws);
+  a.partial = ws.take<double>((int64_t)ICP_BLOCKS * ICP_ROW);
+}
+int64_t ngm_icp_point_to_plane_bytes(int64_t M, int64_t N) {
+  (void)N;
+  IcpArgs a = {};
+  a.np.M = (int)M;
+  return ws_bytes(icp_layout, a);
+}
+int ngm_launch_icp_point_to_plane(const float* source, int64_t N, const float* target, const float* target_normals, int64_t M,
+                                  double threshold, int max_iteration, double relative_fitness, double relative_rmse, const double* init,
+                                  double* state, void* workspace, int64_t workspace_bytes, hipStream_t st) {
+  IcpArgs a = {};
+  a.np.refs = target; a.np.M = (int)M;
+  a.np.bbox_blocks = (int)std::min<int64_t>((M + 255) / 256, NP_BBOX_BLOCKS);
+  a.source = source; a.normals = target_normals; a.N = (int)N; a.max_iteration = max_iteration;
+  a.threshold = threshold; a.relative_fitness = relative_fitness; a.relative_rmse = relative_rmse; a.state = state;
+  WsArena ws(workspace);
+  icp_layout(a, ws);
+  if (!ws.covers(workspace_bytes)) return NGM_E_WORKSPACE;
+  IcpInit in;
+  for (int i = 0; i < 16; ++i) in.t[i] = init ? init[i] : (i % 5 == 0 ? 1.0 : 0.0);
+  hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, st, state, in);
+  if (N == 0) return 0;
+  np_build_grid(a.np, st);
+  for (int pass = 0; pass <= max_iteration; ++pass) {
+    hipLaunchKernelGGL(k_icp_accumulate, dim3(ICP_BLOCKS), dim3(ICP_T), 0, st, a);
+    hipLaunchKernelGGL(k_icp_solve, dim3(1), dim3(256), 0, st, a, pass);
+  }
   return 0;
 }

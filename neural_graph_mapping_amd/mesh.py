@@ -293,8 +293,8 @@ def extract_mesh(renderer, mesh_file_path=None, resolution: Optional[float] = No
 # the ground-truth mesh, two exact nearest-neighbour queries between the clouds, ten numbers.  The reference runs
 # trimesh.sample.sample_surface and scipy.spatial.KDTree on the host; here both are device kernels (csrc/ngm_mesh_eval.hip)
 # and the reductions are torch on the device.  Culling (mesh_culling.py) is further down: subdivide_to_size, render_mesh_depth,
-# cull_mesh, evaluate_raw_mesh.  OUT OF SCOPE: ICP alignment (evaluation._align_mesh), LPIPS / SSIM -- callers pass meshes that
-# are aligned.
+# cull_mesh, evaluate_raw_mesh; ICP alignment (evaluation._align_mesh) is at the end: vertex_normals, icp_point_to_plane,
+# align_mesh.  OUT OF SCOPE: LPIPS / SSIM.
 # ------------------------------------------------------------------------------------------------
 METRIC_KEYS = ("median_acc", "median_comp", "acc", "comp", "acc_ratio", "acc_ratio_1cm", "comp_ratio", "comp_ratio_1cm",
                "f1_5cm", "f1_1cm")
@@ -416,7 +416,7 @@ def _as_mesh(m, device):
 def evaluate_mesh(est, gt, num_points: int = 200000, seed: int = 0) -> dict:
     """evaluation._evaluate_postprocessed_meshes (evaluation.py:163-208): `num_points` surface samples of each mesh
     (est with `seed`, gt with `seed + 1`), then mesh_metrics.  est / gt: a (verts, faces) pair of device tensors, or the path of
-    a PLY file save_ply wrote.  The meshes are taken as they are: culling and the subdivision before it are evaluate_raw_mesh's (below), ICP alignment is the caller's."""
+    a PLY file save_ply wrote.  The meshes are taken as they are: culling, the subdivision before it and ICP alignment are evaluate_raw_mesh's (below; align_mesh on its own)."""
     device = next((m[0].device for m in (est, gt) if not isinstance(m, (str, os.PathLike))), torch.device("cuda"))
     ev, ef = _as_mesh(est, device)
     gv, gf = _as_mesh(gt, device)
@@ -432,7 +432,7 @@ def evaluate_mesh(est, gt, num_points: int = 200000, seed: int = 0) -> dict:
 # launch (csrc/ngm_mesh_cull.hip; the rule is written down in include/ngm_hip.h), selection and compaction are torch on the
 # device.  The reference first subdivides the mesh to a maximum edge length (mesh.subdivide_to_size(max_edge),
 # mesh_culling.py:260-261): subdivide_to_size below, two kernels of csrc/ngm_mesh_eval.hip, which cull_mesh runs when it is given
-# max_edge.  NOT BUILT: ICP, reading virtual-camera files (the caller appends those poses and says where they start), GL's
+# max_edge.  ICP alignment is align_mesh (further down).  NOT BUILT: reading virtual-camera files (the caller appends those poses and says where they start), GL's
 # top-left fill rule and depth-buffer quantisation (both far inside eps = 0.03).
 # ------------------------------------------------------------------------------------------------
 CULLING_METHODS = ("frustum", "occlusion", "virt_cams")
@@ -710,18 +710,173 @@ def cull_mesh(verts: torch.Tensor, faces: torch.Tensor, c2ws: torch.Tensor, came
 
 
 def evaluate_raw_mesh(est, gt, c2ws: torch.Tensor, camera, gt_culling_method: str, est_culling_method: str, num_points: int = 200000,
-                      seed: int = 0, bounds=None, mesh_alignment: bool = False, **cull_kwargs) -> dict:
+                      seed: int = 0, bounds=None, mesh_alignment: bool = False, align: Optional[str] = None, **cull_kwargs) -> dict:
     """evaluation.evaluate_raw_mesh (evaluation.py:211-251): both meshes culled (cull_mesh: the ground truth with
     gt_culling_method, the estimate with est_culling_method, the same poses, camera and bounds), then evaluate_mesh on what is
     left -- the reference's headline mesh numbers without leaving the device.  est / gt as evaluate_mesh takes them;
     cull_kwargs go to both cull_mesh calls (num_frustum_poses, th_obs, eps, bounds_eps, pose_chunk, max_edge, max_iter:
-    max_edge=0.1 is the reference's default, both meshes subdivided before they are culled).  mesh_alignment=True (ICP,
-    evaluation._align_mesh) is not built and raises NotImplementedError."""
+    max_edge=0.1 is the reference's default, both meshes subdivided before they are culled).
+    align="icp": the reference's eval_mesh_alignment, in its order -- the ground truth is culled, the UNCULLED estimate is
+    aligned to the culled ground truth (align_mesh: point-to-plane ICP, threshold 0.1, at most 100 iterations), the aligned
+    estimate is culled, then scored.  None (default): no alignment; any other string is a ValueError.
+    mesh_alignment=True is the reference's spelling and raises NotImplementedError: ask with align="icp"."""
+    _check_align(align)
     if mesh_alignment:
-        raise NotImplementedError("evaluate_raw_mesh: mesh_alignment (ICP, evaluation._align_mesh) is not built")
+        raise NotImplementedError('evaluate_raw_mesh: mesh_alignment is the reference\'s flag; here ICP alignment is asked for '
+                                  'with align="icp"')
     device = next((m[0].device for m in (est, gt) if not isinstance(m, (str, os.PathLike))), c2ws.device)
     ev, ef = _as_mesh(est, device)
     gv, gf = _as_mesh(gt, device)
     gt_culled = cull_mesh(gv, gf, c2ws, camera, gt_culling_method, bounds=bounds, **cull_kwargs)
+    if align == "icp":
+        (ev, ef), _ = align_mesh((ev, ef), gt_culled)
     est_culled = cull_mesh(ev, ef, c2ws, camera, est_culling_method, bounds=bounds, **cull_kwargs)
     return evaluate_mesh(est_culled, gt_culled, num_points=num_points, seed=seed)
+
+
+# ------------------------------------------------------------------------------------------------
+# aligning a mesh to the ground truth (evaluation._align_mesh, evaluation.py:133-160): Open3D's compute_vertex_normals and
+# registration_icp with TransformationEstimationPointToPlane, restated from their public definitions as device kernels
+# (csrc/ngm_mesh_eval.hip; the rules are the contract of ngm_mesh_vertex_normals / ngm_icp_point_to_plane in
+# include/ngm_hip.h).  PARITY UNPINNED against Open3D; tests/_mesh_align_host.py is the fp64 mirror.
+# ------------------------------------------------------------------------------------------------
+ICP_STATE_DOUBLES = 64                      # include/ngm_hip.h: the layout of `state`
+ICP_MAX_ITERATION = 1000
+
+
+def _check_align(align):
+    if align is not None and align != "icp":
+        raise ValueError(f'Unknown alignment {align!r}: None or "icp"')
+
+
+@ops._op("mesh_vertex_normals")
+def _mesh_vertex_normals_op(verts: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
+    """normals (V, 3) fp32"""
+    L = K.lib()
+    nv = verts.shape[0]
+    wsb = L.ngm_mesh_vertex_normals_workspace(nv)
+    if wsb < 0:
+        raise K.NgmError(f"mesh_vertex_normals: {nv} vertices not supported (vertices < 2^31)", code=int(wsb))
+    ws = torch.empty(wsb, device=verts.device, dtype=torch.uint8)
+    normals = torch.empty(nv, 3, device=verts.device, dtype=torch.float32)
+    K.check(L.ngm_mesh_vertex_normals(verts.data_ptr(), nv, faces.data_ptr(), faces.shape[0], normals.data_ptr(), ws.data_ptr(), wsb,
+                                      ops._stream()), "ngm_mesh_vertex_normals")
+    return normals
+
+
+@_mesh_vertex_normals_op.register_fake
+def _(verts, faces):
+    return verts.new_empty(verts.shape[0], 3)
+
+
+@ops._op("icp_point_to_plane")
+def _icp_point_to_plane_op(source: torch.Tensor, target: torch.Tensor, target_normals: torch.Tensor, threshold: float,
+                           max_iteration: int, relative_fitness: float, relative_rmse: float, init: List[float]) -> torch.Tensor:
+    """state (64) fp64: the layout of include/ngm_hip.h"""
+    L = K.lib()
+    n, m = source.shape[0], target.shape[0]
+    wsb = L.ngm_icp_point_to_plane_workspace(m, n)
+    if wsb < 0:
+        raise K.NgmError(f"icp_point_to_plane: {n} source and {m} target points not supported (1 <= target, both < 2^31)", code=int(wsb))
+    ws = torch.empty(wsb, device=source.device, dtype=torch.uint8)
+    state = torch.empty(ICP_STATE_DOUBLES, device=source.device, dtype=torch.float64)
+    init_c = (C.c_double * 16)(*init)
+    K.check(L.ngm_icp_point_to_plane(source.data_ptr(), n, target.data_ptr(), target_normals.data_ptr(), m, float(threshold),
+                                     int(max_iteration), float(relative_fitness), float(relative_rmse), init_c, state.data_ptr(),
+                                     ws.data_ptr(), wsb, ops._stream()), "ngm_icp_point_to_plane")
+    return state
+
+
+@_icp_point_to_plane_op.register_fake
+def _(source, target, target_normals, threshold, max_iteration, relative_fitness, relative_rmse, init):
+    return source.new_empty(ICP_STATE_DOUBLES, dtype=torch.float64)
+
+
+def vertex_normals(verts: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
+    """Open3D's compute_vertex_normals on the device: verts (V, 3) fp32, faces (F, 3) int64 -> (V, 3) fp32 unit normals, every
+    face's unnormalised normal (v1 - v0) x (v2 - v0) added to its three vertices (area weighting) and the sum normalised.
+    (0, 0, 1) for a vertex whose sum has length 0 (no face, exact cancellation) or that is not finite; a face with an
+    out-of-range index or a non-finite vertex adds nothing.  Exact integer sums: independent of the order of the faces, bitwise
+    equal from call to call.  No host synchronisation.  Dispatches through torch.ops.ngm355.mesh_vertex_normals."""
+    ops._require_gpu(verts, faces)
+    if verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32:
+        raise ValueError("vertex_normals expects (V, 3) float32 vertices")
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int64:
+        raise ValueError("vertex_normals expects (F, 3) int64 faces")
+    return torch.ops.ngm355.mesh_vertex_normals(verts.contiguous(), faces.contiguous())
+
+
+class IcpResult:
+    """What icp_point_to_plane returns, every field a DEVICE tensor (nothing has been read back): transformation (4, 4) fp64,
+    fitness and inlier_rmse (fp64 scalars), iterations (int64 scalar: updates applied), converged (bool scalar); `state`
+    is the raw (64,) record of ngm_icp_point_to_plane (the last pass's sums are state[20:49])."""
+
+    def __init__(self, state: torch.Tensor):
+        self.state = state
+        self.transformation = state[:16].view(4, 4)
+        self.fitness = state[16]
+        self.inlier_rmse = state[17]
+        self.iterations = state[18].to(torch.int64)
+        self.converged = state[19] != 0
+
+    def __repr__(self):
+        return "IcpResult(device tensors: transformation, fitness, inlier_rmse, iterations, converged)"
+
+
+def icp_point_to_plane(source: torch.Tensor, target: torch.Tensor, target_normals: torch.Tensor, threshold: float = 0.1,
+                       max_iteration: int = 100, init=None, relative_fitness: float = 1e-6, relative_rmse: float = 1e-6) -> IcpResult:
+    """Open3D's registration_icp(source, target, threshold, init, TransformationEstimationPointToPlane(),
+    ICPConvergenceCriteria(relative_fitness, relative_rmse, max_iteration)) on the device: source (N, 3), target (M, 3),
+    target_normals (M, 3) fp32 -> IcpResult.  init: None (identity) or a (4, 4) HOST array (numpy, nested lists, CPU tensor).
+    The grid over the target is built once, every iteration is two launches, all of them enqueued at once: no host
+    synchronisation, and the call can be captured in a graph.  Deterministic: equal distances go to the smallest target index,
+    every sum has a fixed order.  A system that is singular by the rule of include/ngm_hip.h (a planar target) leaves the
+    transformation unchanged.  M == 0 is refused (NgmError, NGM_E_INVALID).
+    Dispatches through torch.ops.ngm355.icp_point_to_plane."""
+    ops._require_gpu(source, target, target_normals)
+    for name, t in (("source", source), ("target", target), ("target_normals", target_normals)):
+        if t.dim() != 2 or t.shape[1] != 3 or t.dtype != torch.float32:
+            raise ValueError(f"icp_point_to_plane expects (n, 3) float32 {name}")
+    if target_normals.shape[0] != target.shape[0]:
+        raise ValueError("icp_point_to_plane expects one normal per target point")
+    threshold = float(threshold)
+    if not (0 < threshold < float("inf")):
+        raise ValueError("icp_point_to_plane: threshold must be a finite number > 0")
+    if isinstance(max_iteration, bool) or not isinstance(max_iteration, int) or not 0 <= max_iteration <= ICP_MAX_ITERATION:
+        raise ValueError(f"icp_point_to_plane: 0 <= max_iteration <= {ICP_MAX_ITERATION}")
+    if init is None:
+        init_l = [1.0 if i % 5 == 0 else 0.0 for i in range(16)]
+    else:
+        if isinstance(init, torch.Tensor) and init.is_cuda:
+            raise ValueError("icp_point_to_plane: init is a host array (a device tensor would have to be read back)")
+        init_l = [float(x) for x in np.asarray(init, dtype=np.float64).reshape(-1)]
+        if len(init_l) != 16:
+            raise ValueError("icp_point_to_plane: init must be a (4, 4) transformation")
+    state = torch.ops.ngm355.icp_point_to_plane(source.contiguous(), target.contiguous(), target_normals.contiguous(), threshold,
+                                                max_iteration, float(relative_fitness), float(relative_rmse), init_l)
+    return IcpResult(state)
+
+
+def transform_vertices(verts: torch.Tensor, transformation: torch.Tensor) -> torch.Tensor:
+    """R v + t in fp64, ((R0 x + R1 y) + R2 z) + t per row, rounded once to fp32: verts (V, 3) fp32, transformation (4, 4) fp64"""
+    v = verts.double()
+    T = transformation.to(device=verts.device, dtype=torch.float64)
+    x, y, z = v[:, 0:1], v[:, 1:2], v[:, 2:3]
+    return (((x * T[:3, 0] + y * T[:3, 1]) + z * T[:3, 2]) + T[:3, 3]).float()
+
+
+@torch.no_grad()
+def align_mesh(est, gt, threshold: float = 0.1, max_iteration: int = 100, init=None, relative_fitness: float = 1e-6,
+               relative_rmse: float = 1e-6):
+    """evaluation._align_mesh (evaluation.py:133-160) on the device: the vertex normals of `gt` (vertex_normals), point-to-plane
+    ICP from est's vertices to gt's vertices (icp_point_to_plane with the reference's threshold 0.1, identity start and at most
+    100 iterations by default), and est moved by the result.  est / gt as evaluate_mesh takes them; a third element of est
+    (colours) is handed through.  Returns (est with its vertices at R v + t -- fp64, rounded to fp32; faces and colours are
+    the SAME tensors --, IcpResult).  Nothing is read back."""
+    device = next((m[0].device for m in (est, gt) if not isinstance(m, (str, os.PathLike))), torch.device("cuda"))
+    rest = () if isinstance(est, (str, os.PathLike)) else tuple(est[2:])
+    ev, ef = _as_mesh(est, device)
+    gv, gf = _as_mesh(gt, device)
+    result = icp_point_to_plane(ev, gv, vertex_normals(gv, gf), threshold=threshold, max_iteration=max_iteration, init=init,
+                                relative_fitness=relative_fitness, relative_rmse=relative_rmse)
+    return (transform_vertices(ev, result.transformation), ef) + rest, result

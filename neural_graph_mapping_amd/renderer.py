@@ -548,17 +548,19 @@ class NeuralGraphRenderer:
 
     def evaluate_raw_mesh(self, gt, c2ws, camera, gt_culling_method: str, est_culling_method: str, num_points: int = 200000,
                           seed: int = 0, bounds=None, mesh_alignment: bool = False, cull_kwargs: Optional[dict] = None,
-                          **extract_mesh_kwargs):
+                          align: Optional[str] = None, **extract_mesh_kwargs):
         """extract_mesh(**extract_mesh_kwargs) and the ground truth `gt`, both culled from the poses `c2ws` (OpenGL convention)
         seen through `camera`, then scored: mesh.evaluate_raw_mesh (evaluation.evaluate_raw_mesh, evaluation.py:211-251).
         cull_kwargs go to both mesh.cull_mesh calls (dict(max_edge=0.1): both meshes are subdivided first, as the reference
-        does by default).  None where extract_mesh returns None (no surface)."""
+        does by default).  align="icp": the extracted mesh is aligned to the culled ground truth by point-to-plane ICP before
+        it is culled (the reference's eval_mesh_alignment; mesh.align_mesh).  None where extract_mesh returns None (no surface)."""
         from . import mesh
+        mesh._check_align(align)
         est = self.extract_mesh(**extract_mesh_kwargs)
         if est is None:
             return None
         return mesh.evaluate_raw_mesh((est[0], est[1]), gt, c2ws, camera, gt_culling_method, est_culling_method, num_points=num_points,
-                                      seed=seed, bounds=bounds, mesh_alignment=mesh_alignment, **(cull_kwargs or {}))
+                                      seed=seed, bounds=bounds, mesh_alignment=mesh_alignment, align=align, **(cull_kwargs or {}))
 
     # -- reference-compatible API --------------------------------------------------------------
     def quadrature(self, sample_colors, sample_geometries, sample_distances, sample_depths, neus_isds=None):
