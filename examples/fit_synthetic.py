@@ -2,6 +2,7 @@
 training step (forward, losses, backward, sparse Adam) -> kNN-blended render -> PSNR.
 
     python examples/fit_synthetic.py [--iters 300] [--device-iteration | --live [--grow] [--loop-closure]] [--mesh-metrics [--cull]]
+                                     [--frame-metrics]
 
 A synthetic RGB-D "scan" of a textured wall with a sphere in front of it is observed from a few keyframes; fields
 on a grid in front of the cameras are trained exactly as NeuralGraphMap._optimization_iteration would
@@ -24,6 +25,8 @@ aligned to the sphere by point-to-plane ICP on the device first (mesh.align_mesh
 --mesh-metrics --cull also scores the two meshes the way the reference's evaluate_raw_mesh does: both culled first by what the
 keyframes see (NeuralGraphRenderer.evaluate_raw_mesh, method "occlusion": frusta and self-occlusion from every keyframe pose),
 so the sphere's unseen back no longer counts against completion.
+--frame-metrics also scores keyframe 0 the way the reference's _evaluate_frame does (NeuralGraphRenderer.evaluate_frame): the
+frame re-rendered in eval mode against the keyframe's image, PSNR, SSIM and depth L1 over the whole frame, in fp64 on the device.
 """
 import argparse
 import math
@@ -84,7 +87,7 @@ def sphere_mesh(centre, radius, n_lat=48, n_lon=96):
     return radius * v + torch.tensor(centre), f.to(torch.int64)
 
 
-def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0, grow=False, loop_closure=False, mesh_metrics=False, cull=False):
+def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0, grow=False, loop_closure=False, mesh_metrics=False, cull=False, frame_metrics=False):
     """loop: "torch" -- sample_target_mv (torch draws) -> optimization_iteration, the reference's loop;
     "device" -- capture_training: one graph replay per iteration;
     "materialize" -- the same device-drawn targets and jitter stream as "device" (sampler seed 0, iteration i; jitter
@@ -209,6 +212,10 @@ def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0, g
                       "the re-pose, under the same graph")
             if grow:
                 print(f"the map grew from {n0} to {r._global_map_dict['num']} fields under that one graph")
+    if frame_metrics:
+        fm = r.evaluate_frame(c2ws[0], store[0], camera=cam, metrics=["psnr", "ssim", "depthl1"], crop=10)
+        print(f"keyframe 0 as the reference's _evaluate_frame scores it (whole frame, crop 10): PSNR {fm['psnr']:.2f} dB, "
+              f"SSIM {fm['ssim']:.4f}, depth L1 {fm['depthl1']:.4f} m")
     if mesh_metrics:
         gv, gf = sphere_mesh([0.0, 0.0, -2.2], 0.6)
         around = torch.arange(NF - 18, NF, device=dev)              # the 3 x 3 x 2 fields around the sphere
@@ -250,6 +257,8 @@ if __name__ == "__main__":
                     help="score the mesh of the fields around the sphere against the analytic sphere on the device (ten numbers)")
     ap.add_argument("--cull", action="store_true",
                     help="with --mesh-metrics: also score the two meshes after culling both to what the keyframes see (evaluate_raw_mesh)")
+    ap.add_argument("--frame-metrics", action="store_true",
+                    help="score keyframe 0 with PSNR, SSIM and depth L1 on the device (evaluate_frame)")
     a = ap.parse_args()
     main(a.iters, loop="live" if a.live else "device" if a.device_iteration else "torch", grow=a.grow, loop_closure=a.loop_closure,
-         mesh_metrics=a.mesh_metrics, cull=a.cull)
+         mesh_metrics=a.mesh_metrics, cull=a.cull, frame_metrics=a.frame_metrics)

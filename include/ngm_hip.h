@@ -955,6 +955,42 @@ int ngm_icp_point_to_plane(const float* source, int64_t num_source, const float*
                            double relative_rmse, const double* init, double* state, void* workspace, int64_t workspace_bytes,
                            void* stream);
 
+/* ---- scoring rendered frames: PSNR, SSIM and depth L1 in fp64 (additive to ABI 11) ---------------------------------------
+ * The per-frame render metrics of NeuralGraphMap._evaluate_frame (run_mapping.py:1977-2020): evaluation.psnr, evaluation.ssim
+ * and evaluation.depthl1 (evaluation.py:20-30, 46-62) over a batch of frames in one call.  LPIPS is not built (its network
+ * weights are not part of this project).
+ * PARITY UNPINNED against torchmetrics (not installed here): the definitions below restate its public algorithm
+ * (structural_similarity_index_measure and peak_signal_noise_ratio with data_range = 1.0 and their defaults), evaluated in
+ * fp64 where torchmetrics works in fp32; the yardstick is the fp64 host mirror tests/_image_metrics_host.py.
+ * pred, target: (batch, height, width, 4) fp32, contiguous, 16-byte aligned, r g b depth interleaved (what render_image returns
+ * and a keyframe holds).  crop is the reference's eval_crop.  EVERY OPERATION AFTER THE LOAD IS IN fp64; "clamped" keeps NaN as
+ * torch.clamp does (v < 0 ? 0 : v > 1 ? 1 : v).  Per frame:
+ * - depth L1 over the WHOLE image (the reference's depthl1 takes crop and never uses it): a pixel takes part iff
+ *   target depth != 0 (a NaN target depth takes part, -0.0 does not); depth_l1 = sum |pred - target| / count, NaN without one.
+ * - PSNR over the region R = rows and columns crop .. size - crop - 1: x = clamped pred rgb, y = clamped target rgb,
+ *   mse = sum (x - y)^2 / (3 |R|), psnr = 10 log10(1 / mse): +inf where mse == 0, NaN where R is empty (2 crop >= height or width).
+ * - SSIM: weights g_i proportional to exp(-((i - 5) / 1.5)^2 / 2), i = 0..10, normalised to sum 1 in fp64 on the host; the 2-D
+ *   weights are g_i g_j.  For every channel and every 11 x 11 window that lies wholly inside R the five weighted sums mu_x, mu_y,
+ *   E[xx], E[yy], E[xy] (separable: 11 taps along the row, then 11 down the column, each sum = fma(g, value, sum) from 0);
+ *   var_x = max(E[xx] - mu_x^2, 0), likewise var_y (NaN kept), cov = E[xy] - mu_x mu_y; c1 = 1e-4, c2 = 9e-4;
+ *   s = ((2 mu_x mu_y + c1)(2 cov + c2)) / ((mu_x^2 + mu_y^2 + c1)(var_x + var_y + c2)), formed without fused multiply-add:
+ *   identical finite images with var > 0 give exactly 1.0 per window.  ssim = mean of s over the 3 (h - 10)(w - 10) windows, h, w
+ *   the sides of R.  OUR RULE: fewer than 11 rows or columns in R gives NaN (torchmetrics fails or returns an empty mean
+ *   there).  torchmetrics pads by reflection and cuts the padded border off again, which equals the valid windows: no padding.
+ * out: (batch, 8) doubles on the device: [0] psnr, [1] ssim, [2] depth_l1, [3] mse, [4] colour terms 3 |R|, [5] SSIM windows,
+ *   [6] depth pixels, [7] 0.
+ * At most three launches (pixel sums, SSIM tiles with their 5-pixel halo staged in LDS, a closing kernel), no host
+ * synchronisation, capturable in a graph.  No floating-point atomics: per-wave, then per-workgroup sums land as rows in the
+ * caller's workspace and are added in a fixed order, so two calls on the same inputs agree bit for bit, and frame b of a batch
+ * equals the same frame scored alone (a frame's grid depends on height, width and crop only).
+ * ngm_image_metrics_workspace: bytes, or NGM_E_INVALID for what the call refuses; stale contents are never read.
+ * NGM_E_INVALID before anything is launched for a NULL or misaligned array, batch, height, width or crop < 0,
+ * batch * height * width >= 2^31, and a workspace that is too small.  batch == 0 launches nothing and returns NGM_OK;
+ * height * width == 0 reads no pixel: only the closing kernel runs and writes every row as NaN with zero counts. */
+int64_t ngm_image_metrics_workspace(int32_t batch, int32_t height, int32_t width, int32_t crop);
+int ngm_image_metrics(const float* pred, const float* target, int32_t batch, int32_t height, int32_t width, int32_t crop,
+                      double* out, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- measurement hooks (bench.py roofline leg) ------------------------------------------------
  * When enabled, every launch of the listed kernels is bracketed by hipEvents recorded on the launch
  * stream; ngm_profile_read() synchronises them and returns the accumulated device time. */

@@ -372,6 +372,10 @@ def lib():
     L.ngm_icp_point_to_plane_workspace.restype = i64
     L.ngm_icp_point_to_plane.argtypes = [vp, i64, vp, vp, i64, C.c_double, i32, C.c_double, C.c_double, vp, vp, vp, i64, vp]
     L.ngm_icp_point_to_plane.restype = C.c_int
+    L.ngm_image_metrics_workspace.argtypes = [i32, i32, i32, i32]
+    L.ngm_image_metrics_workspace.restype = i64
+    L.ngm_image_metrics.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, i64, vp]
+    L.ngm_image_metrics.restype = C.c_int
     L.ngm_debug_plan_bwd.argtypes = [P(FieldCfg), P(RenderCfg), i32, i64, i32, i32, i32, P(i32)]
     L.ngm_debug_plan_bwd.restype = C.c_int
     L.ngm_debug_plan_fwd.argtypes = [P(FieldCfg), P(RenderCfg), i32, i32, i64, i32, P(i32)]
@@ -407,7 +411,8 @@ EXPORTED = ["ngm_abi_version", "ngm_last_error", "ngm_device_info", "ngm_permuto
             "ngm_surface_sample_workspace", "ngm_surface_sample", "ngm_nearest_point_workspace", "ngm_nearest_point",
             "ngm_mesh_depth", "ngm_mesh_visibility",
             "ngm_mesh_subdivide_workspace", "ngm_mesh_subdivide_count", "ngm_mesh_subdivide_emit",
-            "ngm_mesh_vertex_normals_workspace", "ngm_mesh_vertex_normals", "ngm_icp_point_to_plane_workspace", "ngm_icp_point_to_plane"]
+            "ngm_mesh_vertex_normals_workspace", "ngm_mesh_vertex_normals", "ngm_icp_point_to_plane_workspace", "ngm_icp_point_to_plane",
+            "ngm_image_metrics_workspace", "ngm_image_metrics"]
 
 # parameters that never receive a gradient (the CUDA package gives none to the per-level shifts either;
 # torch.optim.Adam skips grad-less parameters, so the sparse Adam must skip them too)

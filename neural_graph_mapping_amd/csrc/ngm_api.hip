@@ -42,6 +42,9 @@ int64_t ngm_icp_point_to_plane_bytes(int64_t M, int64_t N);
 int ngm_launch_icp_point_to_plane(const float* source, int64_t N, const float* target, const float* target_normals, int64_t M,
                                   double threshold, int max_iteration, double relative_fitness, double relative_rmse, const double* init,
                                   double* state, void* workspace, int64_t workspace_bytes, hipStream_t st);
+int64_t ngm_image_metrics_bytes(int B, int H, int W, int crop);
+int ngm_launch_image_metrics(const float* pred, const float* target, int B, int H, int W, int crop, double* out, void* workspace,
+                             int64_t workspace_bytes, hipStream_t st);
 int64_t ngm_mesh_subdivide_bytes(int64_t F);
 int ngm_launch_mesh_subdivide_count(const float* verts, int64_t V, const int64_t* faces, int64_t F, double max_edge, int max_iter,
                                     void* workspace, int64_t workspace_bytes, int64_t* totals, hipStream_t st);
@@ -1702,6 +1705,29 @@ int ngm_icp_point_to_plane(const float* source, int64_t num_source, const float*
                                     relative_rmse, init, state, workspace, workspace_bytes, (hipStream_t)stream))
     return fail(NGM_E_INVALID, "ngm_icp_point_to_plane: workspace too small (ngm_icp_point_to_plane_workspace)");
   return check_launch("ngm_icp_point_to_plane");
+}
+
+// ------------------------------------------------------------------------------------------------
+// scoring rendered frames: PSNR, SSIM and depth L1 in fp64 (evaluation.py:20-30, 46-62; ngm_image_metrics.hip)
+// ------------------------------------------------------------------------------------------------
+static bool image_metrics_shape_ok(int32_t batch, int32_t height, int32_t width, int32_t crop) {
+  return batch >= 0 && height >= 0 && width >= 0 && crop >= 0 && (int64_t)batch * height * width < ((int64_t)1 << 31);
+}
+int64_t ngm_image_metrics_workspace(int32_t batch, int32_t height, int32_t width, int32_t crop) {
+  if (!image_metrics_shape_ok(batch, height, width, crop)) return NGM_E_INVALID;
+  return ngm_image_metrics_bytes(batch, height, width, crop);
+}
+int ngm_image_metrics(const float* pred, const float* target, int32_t batch, int32_t height, int32_t width, int32_t crop, double* out,
+                      void* workspace, int64_t workspace_bytes, void* stream) {
+  if (batch < 0 || height < 0 || width < 0) return fail(NGM_E_INVALID, "ngm_image_metrics: batch, height and width must be >= 0");
+  if (crop < 0) return fail(NGM_E_INVALID, "ngm_image_metrics: crop must be >= 0");
+  if (!image_metrics_shape_ok(batch, height, width, crop)) return fail(NGM_E_INVALID, "ngm_image_metrics: batch * height * width must be below 2^31");
+  if (!pred || !target || !out || !workspace) return fail(NGM_E_INVALID, "ngm_image_metrics: NULL array");
+  if (((uintptr_t)pred | (uintptr_t)target) & 15) return fail(NGM_E_INVALID, "ngm_image_metrics: pred and target must be 16-byte aligned");
+  if (ngm_launch_image_metrics(pred, target, batch, height, width, crop, out, workspace, workspace_bytes, (hipStream_t)stream))
+    return fail(NGM_E_INVALID, "ngm_image_metrics: workspace too small (ngm_image_metrics_workspace)");
+  if (batch == 0) return NGM_OK;
+  return check_launch("ngm_image_metrics");
 }
 
 // ------------------------------------------------------------------------------------------------

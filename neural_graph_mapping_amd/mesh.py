@@ -294,7 +294,7 @@ def extract_mesh(renderer, mesh_file_path=None, resolution: Optional[float] = No
 # trimesh.sample.sample_surface and scipy.spatial.KDTree on the host; here both are device kernels (csrc/ngm_mesh_eval.hip)
 # and the reductions are torch on the device.  Culling (mesh_culling.py) is further down: subdivide_to_size, render_mesh_depth,
 # cull_mesh, evaluate_raw_mesh; ICP alignment (evaluation._align_mesh) is at the end: vertex_normals, icp_point_to_plane,
-# align_mesh.  OUT OF SCOPE: LPIPS / SSIM.
+# align_mesh.  The per-frame render metrics (PSNR, SSIM, depth L1) are evaluation.py's.  OUT OF SCOPE: LPIPS.
 # ------------------------------------------------------------------------------------------------
 METRIC_KEYS = ("median_acc", "median_comp", "acc", "comp", "acc_ratio", "acc_ratio_1cm", "comp_ratio", "comp_ratio_1cm",
                "f1_5cm", "f1_1cm")

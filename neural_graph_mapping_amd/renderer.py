@@ -1159,6 +1159,63 @@ class NeuralGraphRenderer:
         mse = ((prediction.clamp(0.0, 1.0) - target.clamp(0.0, 1.0)) ** 2).mean()
         return float(10.0 * torch.log10(1.0 / mse))
 
+    def _eval_request(self, metrics, crop):
+        from . import evaluation
+        cfg = self._config
+        metrics = evaluation.check_metrics(cfg.get("eval_metrics") or [] if metrics is None else metrics)
+        return metrics, evaluation._check_crop(cfg.get("eval_crop", 0) if crop is None else crop)
+
+    @torch.no_grad()
+    def evaluate_frame(self, c2w: torch.Tensor, target_rgbd: torch.Tensor, camera: Optional[Camera] = None, metrics=None,
+                       crop: Optional[int] = None, seed: int = 0) -> dict:
+        """NeuralGraphMap._evaluate_frame (rm.py:1977-2020): eval(), render_image(c2w, camera), the frame scored against
+        `target_rgbd` (H, W, 4) on the device by one evaluation.image_metrics call, train() afterwards as rm.py:2019 does.
+        metrics: names out of "psnr", "ssim", "depthl1" (default: config `eval_metrics`, which defaults to []); "lpips" raises
+        NotImplementedError.  crop defaults to config `eval_crop`.  Returns {metric: float} for the metrics asked for, in
+        that order: one transfer."""
+        from . import evaluation
+        metrics, crop = self._eval_request(metrics, crop)
+        cam = camera or self._camera
+        ops._require_gpu(target_rgbd)
+        if tuple(target_rgbd.shape) != (cam.height, cam.width, 4) or target_rgbd.dtype != torch.float32:
+            raise ValueError(f"evaluate_frame expects target_rgbd as ({cam.height}, {cam.width}, 4) float32, got "
+                             f"{tuple(target_rgbd.shape)} {target_rgbd.dtype}")
+        self.eval()
+        try:
+            rgbd, _ = self.render_image(c2w, camera, seed=seed)
+            row = evaluation.image_metrics_raw(rgbd[None], target_rgbd[None], crop)[0].cpu()
+        finally:
+            self.train()
+        return {m: float(row[evaluation.OUT_COLUMNS.index(m)]) for m in metrics}
+
+    @torch.no_grad()
+    def evaluate_frames(self, c2ws, target_rgbds, camera: Optional[Camera] = None, metrics=None, crop: Optional[int] = None,
+                        seed: int = 0, batch: int = 16):
+        """_evaluate_frame over the frames of a chunk or a sequence (rm.py:1897-1906, 1930-1936): frame i is rendered from
+        c2ws[i] with `seed` and scored against target_rgbds[i]; the frames are scored `batch` at a time and everything is
+        read back once at the end.  Returns (mean_dict, per_frame): the reference's _mean_metric_dict (rm.py:82-92) of the
+        metrics asked for, and the (N, 8) host array of ngm_image_metrics rows (evaluation.OUT_COLUMNS).  No frame: ({}, (0, 8))."""
+        from . import evaluation
+        metrics, crop = self._eval_request(metrics, crop)
+        if len(c2ws) != len(target_rgbds):
+            raise ValueError(f"evaluate_frames: {len(c2ws)} poses and {len(target_rgbds)} targets")
+        if isinstance(batch, bool) or not isinstance(batch, int) or batch < 1:
+            raise ValueError(f"evaluate_frames: batch must be an integer >= 1, got {batch!r}")
+        rows = []
+        self.eval()
+        try:
+            for s0 in range(0, len(c2ws), batch):
+                pred = torch.stack([self.render_image(c2ws[i], camera, seed=seed)[0] for i in range(s0, min(s0 + batch, len(c2ws)))])
+                tgt = torch.stack([target_rgbds[i].to(pred.device) for i in range(s0, s0 + pred.shape[0])])
+                rows.append(evaluation.image_metrics_raw(pred, tgt, crop))
+        finally:
+            self.train()
+        import numpy as np
+        if not rows:
+            return {}, np.zeros((0, 8))
+        per_frame = torch.cat(rows).cpu().numpy()
+        return evaluation.mean_metric_dict(per_frame, metrics), per_frame
+
     # -- fused fast path -----------------------------------------------------------------------
     def _workspace(self, F, R):
         key = (F, R)
