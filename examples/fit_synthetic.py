@@ -1,7 +1,7 @@
 """End-to-end smoke of the drop-in path on one MI355X: keyframe store -> training-target sampler -> fused
 training step (forward, losses, backward, sparse Adam) -> kNN-blended render -> PSNR.
 
-    python examples/fit_synthetic.py [--iters 300] [--device-iteration | --live [--grow] [--loop-closure]] [--mesh-metrics [--cull]]
+    python examples/fit_synthetic.py [--iters 300] [--device-iteration | --live [--grow [--cover]] [--loop-closure]] [--mesh-metrics [--cull]]
                                      [--frame-metrics]
 
 A synthetic RGB-D "scan" of a textured wall with a sphere in front of it is observed from a few keyframes; fields
@@ -14,6 +14,9 @@ to a KeyframeStore while training, the observed fields recomputed per frame on t
 --live --grow also GROWS the map while that one graph keeps replaying: the renderer reserves rows for the whole map
 (reserve_fields), starts with half of it and appends the rest across the keyframes (add_fields(n, positions=, orientations=):
 one launch each, the number of fields read on the device).
+--live --grow --cover takes each keyframe's fields not from that prepared list but from extend_map on the keyframe's depth
+(the reference's _extend_global_map_dict on the device: grid cells that hold uncovered points and no field yet), anchored to
+the keyframe; the same run with the prepared list follows, and both final PSNRs are printed (the two maps differ by construction).
 --live --loop-closure anchors every field to a keyframe (anchor_fields) and, once the last keyframe is in, lets the pose graph
 move ALL keyframe poses rigidly: KeyframeStore.set_keyframe_poses + repose_fields re-pose the map on the device, the same
 graph keeps replaying, and the PSNR of keyframe 0 is reported before and right after the closure.
@@ -87,7 +90,8 @@ def sphere_mesh(centre, radius, n_lat=48, n_lon=96):
     return radius * v + torch.tensor(centre), f.to(torch.int64)
 
 
-def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0, grow=False, loop_closure=False, mesh_metrics=False, cull=False, frame_metrics=False):
+def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0, grow=False, loop_closure=False, mesh_metrics=False, cull=False, frame_metrics=False,
+         cover=False):
     """loop: "torch" -- sample_target_mv (torch draws) -> optimization_iteration, the reference's loop;
     "device" -- capture_training: one graph replay per iteration;
     "materialize" -- the same device-drawn targets and jitter stream as "device" (sampler seed 0, iteration i; jitter
@@ -97,12 +101,19 @@ def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0, g
     current frame changes every 5 iterations, each camera's first visit adds a keyframe, the graph is never re-captured.
     grow (with "live"): rows are reserved for the whole map, half of it is there at the capture, every keyframe appends a
     share of the rest in place.
+    cover (with "live" and grow): the fields a keyframe brings are not taken from the prepared list but placed by
+    extend_map on that keyframe's depth (the reference's _extend_global_map_dict), anchored to it; the reservation is larger,
+    since the number of fields is then the scene's and the grid's business.
     loop_closure (with "live"): the fields are anchored to the keyframes; after the last keyframe all keyframe poses are
     perturbed rigidly and the map is re-posed on the device between two replays of the one graph."""
     if loop not in ("torch", "device", "materialize", "live"):
         raise ValueError(loop)
     if (grow or loop_closure) and loop != "live":
         raise ValueError("grow and loop_closure go with the live loop")
+    if cover and not (grow and loop == "live"):
+        raise ValueError("cover goes with the live loop and grow")
+    if cover and (loop_closure or mesh_metrics):
+        raise ValueError("cover places its own fields: the loop-closure and mesh-metrics legs index the prepared map")
     torch.manual_seed(0)
     dev = torch.device(device)
     cam = Rr.Camera(W, H, FOC, FOC, (W - 1) / 2, (H - 1) / 2, pixel_center=0.0)
@@ -129,7 +140,8 @@ def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0, g
     r.add_fields(n0)
     r.set_field_poses(pos[:n0].to(dev), quat[:n0].to(dev))
     if grow:
-        r.reserve_fields(NF)                                        # once; from here on nothing of the map is reallocated
+        CAP = NF + 512 if cover else NF                             # cover: as many fields as the keyframes' depth asks for
+        r.reserve_fields(CAP)                                       # once; from here on nothing of the map is reallocated
     eyes = torch.tensor([[0.0, 0.0, 0.0], [0.7, 0.2, 0.1], [-0.7, -0.1, 0.2], [0.2, 0.5, 0.3]])
     c2ws = torch.stack([look_at(e, torch.tensor([0.0, 0.0, -2.6])) for e in eyes])
     store = torch.stack([synth_keyframe(T) for T in c2ws]).contiguous().to(dev)
@@ -153,9 +165,10 @@ def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0, g
     if loop == "live":
         from neural_graph_mapping_amd.keyframes import KeyframeStore
         ks = KeyframeStore(len(eyes) + 1, H, W, device=dev)
-        ids_buf = torch.full((NF,), -1, dtype=torch.int64, device=dev)
+        ids_buf = torch.full((CAP if grow else NF,), -1, dtype=torch.int64, device=dev)
         cnt_buf = torch.zeros(1, dtype=torch.int32, device=dev)
         r.track_training_iterations = True
+        cover_gen = torch.Generator(device=dev).manual_seed(0)      # extend_map draws the grid's shift from it
 
         def next_frame(f):
             nonlocal c2ws, closure
@@ -173,7 +186,9 @@ def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0, g
             ks.set_current(store[k], c2ws[k], frame_id=f)
             if f < len(eyes):
                 ks.add_keyframe(store[k], f)                        # a camera's first visit becomes a keyframe
-                if grow:                                            # ... and brings its share of the fields still missing
+                if cover:                                           # ... and is covered with new fields where the map has none
+                    r.extend_map(ks.nc_rgbd[ks.slot_of(f)], f, c2ws[k], store=ks, generator=cover_gen, camera=cam)
+                elif grow:                                          # ... or brings its share of the fields still missing
                     new = torch.tensor_split(torch.arange(n0, NF), len(eyes))[k]
                     r.add_fields(len(new), positions=pos[new].to(dev), orientations=quat[new].to(dev))
             r.observed_fields_device(ks.nc_rgbd[0], ks.c_c2w[0], seed=0, frame=f, out=(ids_buf, cnt_buf), camera=cam)
@@ -203,7 +218,7 @@ def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0, g
     psnr, derr, share = evaluate()
     if not quiet:
         print(f"keyframe 0 re-rendered: PSNR {psnr:.2f} dB, median |depth error| {derr:.3f} m over "
-              f"{100 * share:.0f} % of the pixels ({NF} fields)")
+              f"{100 * share:.0f} % of the pixels ({r._global_map_dict['num']} fields)")
         if loop == "live":
             print(f"{ks.num_keyframes} keyframes, {int(cnt_buf)} fields observed by the last frame, "
                   f"{int(r.get_field_ids(50).numel())} fields trained in at least 50 iterations")
@@ -251,6 +266,8 @@ if __name__ == "__main__":
                     help="one captured graph across changing frames and keyframes (KeyframeStore + observed_fields_device)")
     ap.add_argument("--grow", action="store_true",
                     help="with --live: reserve rows for the whole map, start with half of it, append the rest across keyframes")
+    ap.add_argument("--cover", action="store_true",
+                    help="with --live --grow: each keyframe's fields come from extend_map on its depth, not from the prepared list")
     ap.add_argument("--loop-closure", action="store_true",
                     help="with --live: anchor the fields to keyframes, move all keyframe poses rigidly after the last keyframe, re-pose")
     ap.add_argument("--mesh-metrics", action="store_true",
@@ -260,5 +277,10 @@ if __name__ == "__main__":
     ap.add_argument("--frame-metrics", action="store_true",
                     help="score keyframe 0 with PSNR, SSIM and depth L1 on the device (evaluate_frame)")
     a = ap.parse_args()
-    main(a.iters, loop="live" if a.live else "device" if a.device_iteration else "torch", grow=a.grow, loop_closure=a.loop_closure,
-         mesh_metrics=a.mesh_metrics, cull=a.cull, frame_metrics=a.frame_metrics)
+    loop = "live" if a.live else "device" if a.device_iteration else "torch"
+    res = main(a.iters, loop=loop, grow=a.grow, loop_closure=a.loop_closure, mesh_metrics=a.mesh_metrics, cull=a.cull,
+               frame_metrics=a.frame_metrics, cover=a.cover)
+    if a.cover:                                                    # the two maps differ by construction: no bar, both numbers
+        prepared = main(a.iters, loop=loop, grow=True, quiet=True)
+        print(f"final PSNR of keyframe 0: {res[1]:.2f} dB with the fields extend_map placed, {prepared[1]:.2f} dB with the prepared "
+              "list (--grow)")

@@ -991,6 +991,56 @@ int64_t ngm_image_metrics_workspace(int32_t batch, int32_t height, int32_t width
 int ngm_image_metrics(const float* pred, const float* target, int32_t batch, int32_t height, int32_t width, int32_t crop,
                       double* out, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- covering a keyframe's depth with new fields (additive to ABI 11) ------------------------------------------------------
+ * NeuralGraphMap._extend_global_map_dict (run_mapping.py:265-345) up to the positions of the new fields: where do new fields
+ * go so that every back-projected pixel of a keyframe lies inside one?  fp32, operations in the reference's order.
+ * - pixel (i, j) is valid iff its depth d = depth[(i width + j) pixel_stride] is finite and != 0 (camera.py:374; OUR RULE: a
+ *   non-finite depth is skipped, the reference would carry NaN on);
+ * - camera point (OpenGL frame, pixel centre 0): x = (j - cx) d / fx, y = -(i - cy) d / fy, z = -d (camera.py:382-384); world
+ *   point p = R (x y z) + t of c2w, row r as ((R_r0 x + R_r1 y) + R_r2 z) + t_r without fused multiply-add (utils.py:283-286;
+ *   the reference's einsum does not define its order).  OUR RULE: a pixel whose p is non-finite (a lost pose) is skipped;
+ * - p is covered iff an ACTIVE field centre c has |p - c|^2 < radius^2, strictly, both sides in fp32, the squares added x, y, z
+ *   (pytorch3d's ball_query with K = 1, restated from its public definition).  Active fields: rows 0 .. num_active - 1 of
+ *   field_positions, or with field_ids the rows it names; entries < 0 or >= rows are skipped (padded lists pass as they are);
+ * - the cell of a point v is floor((v + shift) / cell) per axis, IEEE division; `cell` is (float)(2 radius / sqrt 3) formed in
+ *   double by the caller.  A cell is WANTED when an uncovered valid pixel falls into it, OCCUPIED when an active centre does
+ *   (whether or not that field covers anything there, rm.py:303-311); the new cells are wanted and not occupied;
+ * - new_positions rows 0 .. num_new - 1 = ((ijk - shift) + 0.5) cell (rm.py:325), the cells in ascending lexicographic
+ *   (i, j, k) order, the order torch.unique(dim=0) gives the reference.
+ * counts (4) int32 = {num_new, status, uncovered valid pixels, valid pixels}.  status 0: rows 0 .. num_new - 1 written, rows
+ * past them untouched.  status 1: more than max_new new cells; num_new holds the number needed and NO row is written.
+ * status 2: an uncovered valid pixel's cell index is outside (-2^20, 2^20) on some axis (or shift is not finite): num_new is 0
+ * and no row is written.  The call returns NGM_OK in all three cases: the status lives on the device.
+ * The set of cells is exact and the output bitwise identical from call to call: integer atomics only, nothing depends on the
+ * order of arrival.  One memset and five launches on `stream`, no host synchronisation, capturable in a graph.
+ * NGM_E_INVALID before anything is launched for a NULL argument or array (field_positions may be NULL iff num_active == 0),
+ * height, width < 1 or height * width >= 2^31, pixel_stride < 1, rows or num_active < 0, num_active > rows without field_ids,
+ * radius or cell not finite or <= 0, max_new < 1; NGM_E_UNSUPPORTED for max_new > NGM_COVER_MAX_NEW (every new field's rank is
+ * found by counting the keys below its own: quadratic in num_new, 2^32 comparisons at the limit); NGM_E_WORKSPACE for a
+ * workspace below ngm_cover_depth_workspace (bytes; the same refusals as negative codes); stale contents are never read. */
+#define NGM_COVER_MAX_NEW 65536
+typedef struct ngm_cover_depth_args {
+  const float* depth;               /* (height, width) pixels, pixel_stride floats apart                           */
+  const float* c2w;                 /* DEVICE (4, 4) row-major camera-to-world pose; the first three rows are read */
+  const float* shift;               /* DEVICE (3): the grid's shift, drawn from [0, cell) by the caller            */
+  const float* field_positions;     /* (rows, 3) field centres; NULL with num_active == 0                          */
+  const int64_t* field_ids;         /* (num_active) rows of the active fields, or NULL: rows 0 .. num_active - 1   */
+  float* new_positions;             /* (max_new, 3)                                                                */
+  int32_t* counts;                  /* (4)                                                                         */
+  int32_t pixel_stride;             /* 1: a depth image; 4: the depth channel of an (H, W, 4) RGB-D image          */
+  int32_t rows, num_active;
+  int32_t height, width;
+  int32_t max_new;
+  float fx, fy, cx, cy;
+  float radius, cell;
+} ngm_cover_depth_args;
+int64_t ngm_cover_depth_workspace(int32_t height, int32_t width, int32_t num_active, int32_t max_new);
+int ngm_cover_depth(const ngm_cover_depth_args* a, void* workspace, int64_t workspace_bytes, void* stream);
+/* Measurement only: copies the five device counters of the LAST call on this workspace to out5 (host) after synchronising
+ * `stream`: new cells before the max_new cut, range flag, uncovered valid pixels, valid pixels, insertions into the global set. */
+int ngm_cover_depth_counters(int32_t height, int32_t width, int32_t num_active, int32_t max_new, void* workspace, int32_t* out5,
+                             void* stream);
+
 /* ---- measurement hooks (bench.py roofline leg) ------------------------------------------------
  * When enabled, every launch of the listed kernels is bracketed by hipEvents recorded on the launch
  * stream; ngm_profile_read() synchronises them and returns the accumulated device time. */

@@ -196,6 +196,18 @@ class FieldsReposeArgs(C.Structure):
                 ("advance_prev", C.c_int32), ("reserved0", C.c_int32)]
 
 
+class CoverDepthArgs(C.Structure):
+    """ngm_cover_depth_args"""
+    _fields_ = [("depth", f32p), ("c2w", f32p), ("shift", f32p), ("field_positions", f32p), ("field_ids", C.c_void_p),
+                ("new_positions", f32p), ("counts", C.c_void_p), ("pixel_stride", C.c_int32), ("rows", C.c_int32),
+                ("num_active", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("max_new", C.c_int32),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("radius", C.c_float),
+                ("cell", C.c_float)]
+
+
+NGM_COVER_MAX_NEW = 65536                    # include/ngm_hip.h
+
+
 def target_sample_mv_grow_plan(max_current, max_fields, num_train_fields, num_rays, world_size=1, rank=0):
     """Host-side sizes of ngm_target_sample_mv_grow: target_sample_mv_live_plan at the capacity max_fields -- (max_observed,
     max_random, capacity) = (min(T // 2, max_current), min(T, max_fields), min(min(T, max_fields), fields of this rank among
@@ -376,6 +388,12 @@ def lib():
     L.ngm_image_metrics_workspace.restype = i64
     L.ngm_image_metrics.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, i64, vp]
     L.ngm_image_metrics.restype = C.c_int
+    L.ngm_cover_depth_workspace.argtypes = [i32, i32, i32, i32]
+    L.ngm_cover_depth_workspace.restype = i64
+    L.ngm_cover_depth.argtypes = [P(CoverDepthArgs), vp, i64, vp]
+    L.ngm_cover_depth.restype = C.c_int
+    L.ngm_cover_depth_counters.argtypes = [i32, i32, i32, i32, vp, P(i32), vp]
+    L.ngm_cover_depth_counters.restype = C.c_int
     L.ngm_debug_plan_bwd.argtypes = [P(FieldCfg), P(RenderCfg), i32, i64, i32, i32, i32, P(i32)]
     L.ngm_debug_plan_bwd.restype = C.c_int
     L.ngm_debug_plan_fwd.argtypes = [P(FieldCfg), P(RenderCfg), i32, i32, i64, i32, P(i32)]
@@ -412,7 +430,8 @@ EXPORTED = ["ngm_abi_version", "ngm_last_error", "ngm_device_info", "ngm_permuto
             "ngm_mesh_depth", "ngm_mesh_visibility",
             "ngm_mesh_subdivide_workspace", "ngm_mesh_subdivide_count", "ngm_mesh_subdivide_emit",
             "ngm_mesh_vertex_normals_workspace", "ngm_mesh_vertex_normals", "ngm_icp_point_to_plane_workspace", "ngm_icp_point_to_plane",
-            "ngm_image_metrics_workspace", "ngm_image_metrics"]
+            "ngm_image_metrics_workspace", "ngm_image_metrics",
+            "ngm_cover_depth_workspace", "ngm_cover_depth", "ngm_cover_depth_counters"]
 
 # parameters that never receive a gradient (the CUDA package gives none to the per-level shifts either;
 # torch.optim.Adam skips grad-less parameters, so the sparse Adam must skip them too)

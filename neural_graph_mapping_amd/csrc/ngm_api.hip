@@ -45,6 +45,9 @@ int ngm_launch_icp_point_to_plane(const float* source, int64_t N, const float* t
 int64_t ngm_image_metrics_bytes(int B, int H, int W, int crop);
 int ngm_launch_image_metrics(const float* pred, const float* target, int B, int H, int W, int crop, double* out, void* workspace,
                              int64_t workspace_bytes, hipStream_t st);
+int64_t ngm_cover_bytes(int H, int W, int num_active, int max_new);
+const int32_t* ngm_cover_counters(int H, int W, int num_active, int max_new, void* workspace);
+int ngm_launch_cover(const ngm_cover_depth_args& a, void* workspace, int64_t workspace_bytes, hipStream_t st);
 int64_t ngm_mesh_subdivide_bytes(int64_t F);
 int ngm_launch_mesh_subdivide_count(const float* verts, int64_t V, const int64_t* faces, int64_t F, double max_edge, int max_iter,
                                     void* workspace, int64_t workspace_bytes, int64_t* totals, hipStream_t st);
@@ -1728,6 +1731,48 @@ int ngm_image_metrics(const float* pred, const float* target, int32_t batch, int
     return fail(NGM_E_INVALID, "ngm_image_metrics: workspace too small (ngm_image_metrics_workspace)");
   if (batch == 0) return NGM_OK;
   return check_launch("ngm_image_metrics");
+}
+
+// covering a keyframe's depth with new fields (run_mapping.py:265-345; ngm_cover.hip)
+static int cover_shape(int32_t height, int32_t width, int32_t num_active, int32_t max_new) {
+  if (height < 1 || width < 1 || (int64_t)height * width >= ((int64_t)1 << 31))
+    return fail(NGM_E_INVALID, "ngm_cover_depth: height and width must be >= 1 and height * width below 2^31");
+  if (num_active < 0) return fail(NGM_E_INVALID, "ngm_cover_depth: num_active must be >= 0");
+  if (max_new < 1) return fail(NGM_E_INVALID, "ngm_cover_depth: max_new must be >= 1");
+  if (max_new > NGM_COVER_MAX_NEW) return fail(NGM_E_UNSUPPORTED, "ngm_cover_depth: max_new above NGM_COVER_MAX_NEW");
+  return NGM_OK;
+}
+int64_t ngm_cover_depth_workspace(int32_t height, int32_t width, int32_t num_active, int32_t max_new) {
+  const int rc = cover_shape(height, width, num_active, max_new);
+  if (rc != NGM_OK) return rc;
+  return ngm_cover_bytes(height, width, num_active, max_new);
+}
+int ngm_cover_depth(const ngm_cover_depth_args* a, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!a) return fail(NGM_E_INVALID, "ngm_cover_depth: NULL argument");
+  if (!a->depth || !a->c2w || !a->shift || !a->new_positions || !a->counts || !workspace)
+    return fail(NGM_E_INVALID, "ngm_cover_depth: NULL array");
+  const int rc = cover_shape(a->height, a->width, a->num_active, a->max_new);
+  if (rc == NGM_E_INVALID) return rc;
+  if (a->pixel_stride < 1 || a->rows < 0) return fail(NGM_E_INVALID, "ngm_cover_depth: pixel_stride must be >= 1 and rows >= 0");
+  if (a->num_active > 0 && !a->field_positions) return fail(NGM_E_INVALID, "ngm_cover_depth: active fields without field_positions");
+  if (!a->field_ids && a->num_active > a->rows) return fail(NGM_E_INVALID, "ngm_cover_depth: num_active above rows");
+  if (!(a->radius > 0.f) || !(a->cell > 0.f) || !(a->radius < INFINITY) || !(a->cell < INFINITY))
+    return fail(NGM_E_INVALID, "ngm_cover_depth: radius and cell must be finite and > 0");
+  if (rc != NGM_OK) return rc;                                               // NGM_E_UNSUPPORTED: after every NGM_E_INVALID
+  if (ngm_launch_cover(*a, workspace, workspace_bytes, (hipStream_t)stream))
+    return fail(NGM_E_WORKSPACE, "ngm_cover_depth: workspace too small (ngm_cover_depth_workspace)");
+  return check_launch("ngm_cover_depth");
+}
+int ngm_cover_depth_counters(int32_t height, int32_t width, int32_t num_active, int32_t max_new, void* workspace, int32_t* out5,
+                             void* stream) {
+  if (!workspace || !out5) return fail(NGM_E_INVALID, "ngm_cover_depth_counters: NULL argument");
+  const int rc = cover_shape(height, width, num_active, max_new);
+  if (rc != NGM_OK) return rc;
+  const int32_t* ctr = ngm_cover_counters(height, width, num_active, max_new, workspace);
+  if (hipMemcpyAsync(out5, ctr, 5 * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess ||
+      hipStreamSynchronize((hipStream_t)stream) != hipSuccess)
+    return check_launch("ngm_cover_depth_counters") == NGM_OK ? fail(NGM_E_HIP, "ngm_cover_depth_counters: copy failed") : NGM_E_HIP;
+  return NGM_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1513,3 +1513,98 @@ def fields_repose_(positions, orientations, anchor_slot, prev_poses, new_poses, 
     _require_gpu(positions, orientations, anchor_slot, prev_poses, new_poses, num_fields_dev)
     torch.ops.ngm355.fields_repose_(positions, orientations, anchor_slot, prev_poses, new_poses, num_fields_dev, num_fields,
                                     bool(advance_prev))
+
+
+# ------------------------------------------------------------------------------------------------
+# covering a keyframe's depth with new fields (include/ngm_hip.h ngm_cover_depth)
+# ------------------------------------------------------------------------------------------------
+def cover_cell(radius: float) -> float:
+    """The grid's edge 2 r / sqrt 3 (rm.py:299: the cube inscribed in a field's sphere), formed in double and rounded to
+    float32 once -- what torch makes of the reference's Python scalar when it meets a float32 tensor."""
+    import math
+    return float(torch.tensor(2.0 * float(radius) / math.sqrt(3.0), dtype=torch.float64).to(torch.float32))
+
+
+@_op("cover_depth")
+def _cover_depth_op(depth: torch.Tensor, c2w: torch.Tensor, shift: torch.Tensor, field_positions: Optional[torch.Tensor],
+                    field_ids: Optional[torch.Tensor], num_active: int, intrinsics: List[float], radius: float, cell: float,
+                    max_new: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """depth: an (H, W) float32 view whose rows are dense (stride(0) == W stride(1)); intrinsics = fx, fy, cx, cy"""
+    L = K.lib()
+    h, w = int(depth.shape[0]), int(depth.shape[1])
+    wsb = L.ngm_cover_depth_workspace(h, w, int(num_active), int(max_new))
+    if wsb < 0:
+        raise K.NgmError(f"cover_depth: {h} x {w} pixels, {num_active} active fields, max_new {max_new} refused "
+                         f"(height * width < 2^31, 1 <= max_new <= {K.NGM_COVER_MAX_NEW})", code=int(wsb))
+    ws = torch.empty(wsb, device=depth.device, dtype=torch.uint8)
+    new_positions = torch.zeros(max_new, 3, device=depth.device, dtype=torch.float32)
+    counts = torch.zeros(4, device=depth.device, dtype=torch.int32)
+    fx, fy, cx, cy = intrinsics
+    a = K.CoverDepthArgs(depth.data_ptr(), c2w.data_ptr(), shift.data_ptr(), _ptr(field_positions), _ptr(field_ids),
+                         new_positions.data_ptr(), counts.data_ptr(), int(depth.stride(1)),
+                         0 if field_positions is None else int(field_positions.shape[0]), int(num_active), h, w, int(max_new),
+                         fx, fy, cx, cy, radius, cell)
+    K.check(L.ngm_cover_depth(C.byref(a), ws.data_ptr(), wsb, _stream()), "ngm_cover_depth")
+    return new_positions, counts
+
+
+@_cover_depth_op.register_fake
+def _(depth, c2w, shift, field_positions, field_ids, num_active, intrinsics, radius, cell, max_new):
+    return depth.new_empty(max_new, 3, dtype=torch.float32), depth.new_empty(4, dtype=torch.int32)
+
+
+COVER_STATUS = {0: "ok", 1: "more than max_new new cells", 2: "a cell index outside (-2^20, 2^20)"}
+
+
+def cover_depth(depth_or_rgbd, c2w, shift, field_positions, radius, fx, fy, cx, cy, max_new, field_ids=None, num_active=None,
+                cell=None):
+    """Where new fields go so that a keyframe's depth is covered (torch.ops.ngm355.cover_depth, ngm_cover_depth;
+    NeuralGraphMap._extend_global_map_dict, rm.py:265-345): on the current stream, no host synchronisation.
+    depth_or_rgbd: (H, W) float32 depth or (H, W, 4) float32 r g b depth (read in place, no copy); c2w (4, 4) and shift (3)
+    float32 DEVICE tensors; field_positions (rows, 3) float32 or None; the active fields are its first num_active rows
+    (default: all), or with field_ids (int64, device) the rows it names, entries < 0 or >= rows skipped.  cell: the grid's
+    edge, default cover_cell(radius).
+    Returns new_positions (max_new, 3) float32 and counts (4,) int32 = num_new, status, uncovered valid pixels, valid pixels:
+    status 0 = rows [0, num_new) hold the centres of the new cells in ascending (i, j, k) order (the other rows are zero);
+    1 = more than max_new (num_new = the number needed, no row written); 2 = a cell index outside (-2^20, 2^20)."""
+    def need(cond, msg, exc=ValueError):
+        if not cond:
+            raise exc("cover_depth: " + msg)
+    _require_gpu(depth_or_rgbd, c2w, shift, field_positions, field_ids)
+    img = depth_or_rgbd
+    need(isinstance(img, torch.Tensor) and img.dtype == torch.float32, "the image must be a float32 tensor", TypeError)
+    need(img.dim() == 2 or (img.dim() == 3 and img.shape[2] == 4), f"the image must be (H, W) or (H, W, 4), got {tuple(img.shape)}")
+    depth = img if img.dim() == 2 else img[..., 3]
+    h, w = depth.shape
+    need(h >= 1 and w >= 1, "the image has no pixels")
+    if not (depth.stride(1) >= 1 and depth.stride(0) == w * depth.stride(1)):      # rows must follow each other densely
+        depth = depth.contiguous()
+    for name, t, shape in (("c2w", c2w, (4, 4)), ("shift", shift, (3,))):
+        need(isinstance(t, torch.Tensor) and t.dtype == torch.float32, f"{name} must be a float32 device tensor", TypeError)
+        need(tuple(t.shape) == shape and t.is_contiguous(), f"{name} must be a contiguous {shape} tensor, got {tuple(t.shape)}")
+    rows = 0
+    if field_positions is not None:
+        need(field_positions.dtype == torch.float32, "field_positions must be float32", TypeError)
+        need(field_positions.dim() == 2 and field_positions.shape[1] == 3 and field_positions.is_contiguous(),
+             f"field_positions must be a contiguous (rows, 3) tensor, got {tuple(field_positions.shape)}")
+        rows = field_positions.shape[0]
+    if field_ids is not None:
+        need(field_ids.dtype == torch.int64, "field_ids must be int64", TypeError)
+        need(field_ids.dim() == 1 and field_ids.is_contiguous(), "field_ids must be a contiguous 1-D tensor")
+        need(num_active is None or num_active == field_ids.shape[0], "num_active and field_ids disagree")
+        num_active = field_ids.shape[0]
+        if rows == 0:
+            field_ids, num_active = None, 0
+    elif num_active is None:
+        num_active = rows
+    num_active = int(num_active)
+    need(0 <= num_active and (field_ids is not None or num_active <= rows), f"num_active {num_active} outside [0, {rows}]")
+    if num_active == 0:
+        field_ids = None
+    need(0 < float(radius) < float("inf"), "radius must be finite and > 0")
+    cell = cover_cell(radius) if cell is None else float(cell)              # from the double, as the reference forms it
+    radius = float(radius)
+    need(cell > 0 and cell != float("inf"), "cell must be finite and > 0")
+    need(isinstance(max_new, int) and max_new >= 1, f"max_new must be an integer >= 1, got {max_new!r}")
+    return torch.ops.ngm355.cover_depth(depth, c2w, shift, field_positions, field_ids, num_active,
+                                        [float(fx), float(fy), float(cx), float(cy)], radius, cell, max_new)

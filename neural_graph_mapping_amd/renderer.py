@@ -468,6 +468,87 @@ class NeuralGraphRenderer:
         ops.fields_repose_(pos, quat, self._anchor["slot"], store.slot_c2w_prev, store.slot_c2w, num_fields_dev=nfd,
                            advance_prev=True)
 
+    # -- new fields from a keyframe's depth (rm.py:265-345) -----------------------------------------
+    COVER_DEFAULT_MAX_NEW = 4096           # cover_depth(max_new=None) without reserved rows
+
+    def cover_depth(self, depth_or_rgbd, c2w, active_field_ids=None, shift=None, generator=None, max_new=None, camera=None):
+        """Where NeuralGraphMap._extend_global_map_dict (rm.py:265-345) would put new fields for this keyframe: back-project
+        the depth, drop the points within field_radius of an active field, snap the rest to a grid of edge 2 r / sqrt 3
+        shifted by `shift`, drop the cells that hold an active field's centre, one field at the centre of every cell left.
+        One ngm_cover_depth call on the current stream, no host synchronisation.
+        depth_or_rgbd: (H, W) depth or (H, W, 4) r g b depth (a KeyframeStore slot is read in place); c2w (4, 4), on the
+        device.  active_field_ids: int64 ids of the active fields (None: every field; entries < 0 or past the map are
+        skipped, so padded lists pass).  shift=None draws torch.empty(3, device=...).uniform_(0.0, cell, generator=generator)
+        on the device: the reference's own draw, from torch's generator.  max_new=None: the free reserved rows (at least 1),
+        COVER_DEFAULT_MAX_NEW without a reservation.
+        Returns (new_positions (max_new, 3) float32, counts (4,) int32 = num_new, status, uncovered valid pixels, valid
+        pixels), see ops.cover_depth.  Deviations from the reference: pixels with a non-finite depth or world point are
+        skipped (a lost pose adds nothing); its _bb_min / _bb_max, written and never read, are not kept."""
+        cam = camera or self._camera
+        fx, fy, cx, cy, _ = cam.get_pinhole_camera_parameters(0.0)
+        rs, md = self._reserved, self._global_map_dict
+        dev = depth_or_rgbd.device
+        num = 0 if md is None else md["num"]
+        if rs is not None:
+            pos, free = rs["positions"], rs["max"] - num
+        else:
+            pos, free = (None if md is None else md["positions"].contiguous()), None
+        if max_new is None:
+            max_new = self.COVER_DEFAULT_MAX_NEW if free is None else max(free, 1)
+        cell = ops.cover_cell(self._field_radius)
+        if shift is None:
+            shift = torch.empty(3, device=dev).uniform_(0.0, cell, generator=generator)
+        ids = None
+        if active_field_ids is not None:
+            ids = torch.as_tensor(active_field_ids, dtype=torch.int64).reshape(-1).to(dev).contiguous()
+            if rs is not None:                     # rows at or past `num` are reserved, not fields
+                ids = torch.where(ids < num, ids, torch.full_like(ids, -1))
+        c2w = c2w.to(device=dev, dtype=torch.float32).contiguous()
+        shift = shift.to(device=dev, dtype=torch.float32).contiguous()
+        return ops.cover_depth(depth_or_rgbd, c2w, shift, pos, self._field_radius, fx, fy, cx, cy, int(max_new), field_ids=ids,
+                               num_active=None if ids is not None else num, cell=cell)
+
+    def extend_map(self, depth_or_rgbd, frame_id, c2w, store=None, active_field_ids=None, shift=None, generator=None,
+                   camera=None):
+        """NeuralGraphMap._extend_global_map_dict (rm.py:265-345): cover this keyframe's depth with new fields and anchor
+        them to it.  cover_depth, then ONE read-back of its 16-byte counts -- the number of fields and the `num`-row views
+        of the map are host state, and an append whose count never leaves the device is a different change --, then
+        add_fields(num_new, positions=...) with identity orientations (reserved rows: the one append launch; without a
+        reservation add_fields(num_new) and set_field_poses of the concatenation), then, with `store`,
+        anchor_fields(store, [frame_id] * num_new, field_ids=new ids) (rm.py:335, 343; frame_id must be a keyframe of it).
+        Returns range(num_prev, num_prev + num_new); an empty range touches nothing.  More new fields than there is room
+        for (reserved rows, or NGM_COVER_MAX_NEW), or a cell index outside (-2^20, 2^20), raises ValueError and changes
+        nothing.  Legal between replays of a capture_training graph, exactly as add_fields is."""
+        if store is not None:
+            store.slot_of(frame_id)                # ValueError before anything happens
+        md = self._global_map_dict
+        num_prev = 0 if md is None else md["num"]
+        room = None if self._reserved is None else self._reserved["max"] - num_prev
+        new_positions, counts = self.cover_depth(depth_or_rgbd, c2w, active_field_ids=active_field_ids, shift=shift,
+                                                 generator=generator, camera=camera)
+        num_new, status = counts[:2].tolist()      # the one read-back
+        if status == 2:
+            raise ValueError("extend_map: a point of the depth image lies more than 2^20 grid cells from the origin")
+        if status == 1 or (room is not None and num_new > room):
+            left = f"{room} reserved rows are free" if room is not None else f"cover_depth's default max_new is {new_positions.shape[0]}"
+            raise ValueError(f"extend_map: {num_new} new fields needed but {left}")
+        if num_new == 0:
+            return range(num_prev, num_prev)
+        new_pos = new_positions[:num_new]
+        if self._reserved is not None:
+            self.add_fields(num_new, positions=new_pos)
+        else:
+            quat = torch.zeros(num_new, 4, device=new_pos.device)
+            quat[:, 0] = 1.0
+            old = None if md is None else (md["positions"], md["orientations"])
+            self.add_fields(num_new)
+            self.set_field_poses(new_pos.clone() if old is None else torch.cat((old[0], new_pos)),
+                                 quat if old is None else torch.cat((old[1], quat)))
+        new_ids = range(num_prev, num_prev + num_new)
+        if store is not None:
+            self.anchor_fields(store, [frame_id] * num_new, field_ids=list(new_ids))
+        return new_ids
+
     # -- checkpoint interchange (rm.py:2147-2173) ------------------------------------------------
     def save_model(self, path: str) -> None:
         """torch.save of {map_dict, all_fields_params, state_dict}: the reference's checkpoint layout
