@@ -23,6 +23,7 @@
 // one channel of the blend straight into the (nx, ny, nz) volume marching cubes reads: no point array, no (P, 4) output.
 #include "ngm_field.h"
 #include "ngm_launch.h"
+#include "ngm_scan.h"
 #include "ngm_workspace.h"
 
 #include <algorithm>
@@ -116,28 +117,7 @@ __device__ __forceinline__ float wave_max_f(float v) { return -wave_min_f(-v); }
 // One workgroup of 1024 threads (the map is a few hundred to a few ten thousand centres): bounding box -> cell size / grid
 // dimensions (coarsened until the grid fits max_cells) -> per-cell counts -> exclusive scan -> centres grouped by cell.
 // The order of the centres inside a cell is whatever the atomics give: k_knn_assign breaks distance ties by field index,
-// so its result does not depend on it.
-// exclusive scan of arr[0 .. n) in place by one workgroup of 1024 threads, arr[n] = total: contiguous segments per thread,
-// block scan of the segment sums (sscan: 1024 ints of LDS)
-__device__ __forceinline__ void block_exclusive_scan_1024(int* arr, int n, int* sscan) {
-  const int t = threadIdx.x;
-  const int per = (n + 1023) / 1024, b0 = min(n, t * per), b1 = min(n, b0 + per);
-  int sum = 0;
-  for (int i = b0; i < b1; ++i) sum += arr[i];
-  sscan[t] = sum;
-  __syncthreads();
-  for (int d = 1; d < 1024; d <<= 1) {
-    const int v = (t >= d) ? sscan[t - d] : 0;
-    __syncthreads();
-    sscan[t] += v;
-    __syncthreads();
-  }
-  int run = sscan[t] - sum;
-  for (int i = b0; i < b1; ++i) { const int cnt = arr[i]; arr[i] = run; run += cnt; }
-  if (t == 1023) arr[n] = sscan[1023];
-  __threadfence();
-  __syncthreads();
-}
+// so its result does not depend on it.  The exclusive scans are ngm_scan.h's workgroup_scan_inplace.
 
 // Candidate list of sub-cell e of the extended grid (the grid plus one ring): the centres closer to its box than the mask radius (a
 // little more: the points are binned in fp32).  Four out of five samples of an image are nowhere near a field and fall
@@ -172,7 +152,6 @@ __device__ __forceinline__ int knn_near_visit(const KnnArgs& a, const KnnGridHdr
 // kernels below on the whole device (a map of 40 000 centres: 2 ms -> a fraction of that)
 __global__ __launch_bounds__(1024) void k_knn_grid(KnnArgs a) {
   __shared__ float red[6][16];
-  __shared__ int sscan[1024];
   __shared__ KnnGridHdr h;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
@@ -224,7 +203,9 @@ __global__ __launch_bounds__(1024) void k_knn_grid(KnnArgs a) {
   for (int f = t; f < a.NF; f += 1024) atomicAdd(&a.cell_start[cell_of(f)], 1);
   __threadfence();
   __syncthreads();
-  block_exclusive_scan_1024(a.cell_start, nc, sscan);
+  workgroup_scan_inplace(a.cell_start, nc, true);
+  __threadfence();
+  __syncthreads();
   for (int f = t; f < a.NF; f += 1024) {
     const int cidx = cell_of(f);
     const int slot = a.cell_start[cidx] + atomicAdd(&a.cell_fill[cidx], 1);
@@ -237,7 +218,9 @@ __global__ __launch_bounds__(1024) void k_knn_grid(KnnArgs a) {
   for (int e = t; e < ne; e += 1024) a.near_start[e] = knn_near_visit(a, h, e, false);
   __threadfence();
   __syncthreads();
-  block_exclusive_scan_1024(a.near_start, ne, sscan);
+  workgroup_scan_inplace(a.near_start, ne, true);
+  __threadfence();
+  __syncthreads();
   for (int e = t; e < ne; e += 1024) (void)knn_near_visit(a, h, e, true);
 }
 // the candidate lists of a large map, on the whole device: count -> scan (one workgroup) -> fill
@@ -247,9 +230,8 @@ __global__ __launch_bounds__(256) void k_knn_near_count(KnnArgs a) {
   for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < ne; e += gridDim.x * blockDim.x) a.near_start[e] = knn_near_visit(a, h, e, false);
 }
 __global__ __launch_bounds__(1024) void k_knn_near_scan(KnnArgs a) {
-  __shared__ int sscan[1024];
   const KnnGridHdr h = *a.grid;
-  block_exclusive_scan_1024(a.near_start, knn_near_cells(h), sscan);
+  workgroup_scan_inplace(a.near_start, knn_near_cells(h), true);
 }
 __global__ __launch_bounds__(256) void k_knn_near_fill(KnnArgs a) {
   const KnnGridHdr h = *a.grid;
@@ -516,12 +498,7 @@ __global__ void k_knn_offsets(KnnArgs a) {
       for (int r = 0; r < KNN_COUNT_REPL; ++r) { c += a.counts[(int64_t)r * a.NF + f]; a.counts[(int64_t)r * a.NF + f] = 0; }   // summed, and ready for the next block
     }
     const int t = (c + KNN_TILE - 1) / KNN_TILE;
-    int sc = c, st = t;                  // inclusive wave scans
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int oc = __shfl_up(sc, d, 64), ot = __shfl_up(st, d, 64);
-      if (lane >= d) { sc += oc; st += ot; }
-    }
+    const int sc = wave_inclusive_scan(c, lane), st = wave_inclusive_scan(t, lane);
     if (f < a.NF) { a.seg_off[f] = so + sc - c; a.tile_off[f] = to + st - t; a.cursor[f] = 0; }
     so += __shfl(sc, 63, 64); to += __shfl(st, 63, 64);
   }

@@ -3,8 +3,8 @@
 //   probability proportional to its area, then a uniform point in it)
 //     k_face_area       : fp32 triangle area per face, stored as fp64; 0 for a face with a non-finite vertex or an index
 //                         outside [0, V)
-//     k_scan_*          : inclusive fp64 scan over the faces, three passes (chunk sums, one workgroup over the chunk sums with
-//                         a carry, chunks again): GT meshes have millions of faces
+//     k_scan_*          : inclusive fp64 scan over the faces, the three passes of ngm_scan.h (chunk sums, one workgroup over the
+//                         chunk sums with a carry, chunks again): GT meshes have millions of faces
 //     k_surface_sample  : one thread per sample: Philox block `sample index` of stream MESH_STREAM_SURFACE, words 0 and 1 a
 //                         53-bit uniform that picks the face by binary search in the scan, words 2 and 3 the point in it
 //   exact nearest point between two clouds (evaluation.py:75-130: scipy.spatial.KDTree build + query)
@@ -20,6 +20,7 @@
 // index that reaches memory is checked (face indices against V) or clamped (cell indices).
 #include "ngm_device.h"
 #include "ngm_launch.h"
+#include "ngm_scan.h"
 #include "ngm_workspace.h"
 
 #include <algorithm>
@@ -30,94 +31,8 @@ constexpr uint32_t MESH_STREAM_SURFACE = 0x54470006u;      // next to the TSMV_S
 
 __device__ __forceinline__ bool me_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
-// ---- scans ------------------------------------------------------------------------------------------------------------
-// Three passes over chunks of SCAN_CHUNK elements, one workgroup of SCAN_T threads per chunk, SCAN_PER contiguous elements
-// per thread: (1) chunk sums, (2) exclusive scan of the chunk sums by ONE workgroup (1024 per round, carried), (3) the chunks
-// again with their offsets.  The length is n_host, or *n_dev where the host does not know it (the grid's cell count): the
-// launch covers the host's upper bound, chunks beyond the length do nothing.  INCLUSIVE = false also leaves a[n] = total.
-constexpr int SCAN_T = 256, SCAN_PER = 8, SCAN_CHUNK = SCAN_T * SCAN_PER;
-
-template <typename T>
-__device__ __forceinline__ T scan_block_exclusive(T v, T* lds, T* total) {
-  const int t = threadIdx.x;
-  lds[t] = v;
-  __syncthreads();
-  for (int d = 1; d < SCAN_T; d <<= 1) {
-    const T o = (t >= d) ? lds[t - d] : T(0);
-    __syncthreads();
-    lds[t] += o;
-    __syncthreads();
-  }
-  *total = lds[SCAN_T - 1];
-  const T r = lds[t] - v;
-  __syncthreads();
-  return r;
-}
-
-template <typename T>
-__global__ __launch_bounds__(SCAN_T) void k_scan_reduce(const T* a, const int* n_dev, int64_t n_host, T* partial) {
-  __shared__ T lds[SCAN_T];
-  const int64_t n = n_dev ? (int64_t)*n_dev : n_host;
-  const int64_t b0 = (int64_t)blockIdx.x * SCAN_CHUNK + (int64_t)threadIdx.x * SCAN_PER;
-  T s = T(0);
-#pragma unroll
-  for (int i = 0; i < SCAN_PER; ++i)
-    if (b0 + i < n) s += a[b0 + i];
-  T total;
-  (void)scan_block_exclusive(s, lds, &total);
-  if (threadIdx.x == 0) partial[blockIdx.x] = total;
-}
-
-template <typename T>
-__global__ __launch_bounds__(1024) void k_scan_partials(T* partial, int64_t nb) {
-  __shared__ T lds[1024];
-  const int t = threadIdx.x;
-  T carry = T(0);
-  for (int64_t base = 0; base < nb; base += 1024) {
-    const T v = (base + t < nb) ? partial[base + t] : T(0);
-    lds[t] = v;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-      const T o = (t >= d) ? lds[t - d] : T(0);
-      __syncthreads();
-      lds[t] += o;
-      __syncthreads();
-    }
-    if (base + t < nb) partial[base + t] = carry + (lds[t] - v);
-    carry += lds[1023];
-    __syncthreads();
-  }
-}
-
-template <typename T, bool INCLUSIVE>
-__global__ __launch_bounds__(SCAN_T) void k_scan_apply(T* a, const int* n_dev, int64_t n_host, const T* partial) {
-  __shared__ T lds[SCAN_T];
-  const int64_t n = n_dev ? (int64_t)*n_dev : n_host;
-  const int64_t b0 = (int64_t)blockIdx.x * SCAN_CHUNK + (int64_t)threadIdx.x * SCAN_PER;
-  T v[SCAN_PER];
-  T s = T(0);
-#pragma unroll
-  for (int i = 0; i < SCAN_PER; ++i) { v[i] = (b0 + i < n) ? a[b0 + i] : T(0); s += v[i]; }
-  T total;
-  T run = partial[blockIdx.x] + scan_block_exclusive(s, lds, &total);
-#pragma unroll
-  for (int i = 0; i < SCAN_PER; ++i) {
-    if (b0 + i < n) {
-      if (INCLUSIVE) { run += v[i]; a[b0 + i] = run; }
-      else { a[b0 + i] = run; run += v[i]; if (b0 + i == n - 1) a[n] = run; }
-    }
-  }
-  if (!INCLUSIVE && n == 0 && blockIdx.x == 0 && threadIdx.x == 0) a[0] = T(0);
-}
-
-template <typename T, bool INCLUSIVE>
-static void launch_scan(T* a, const int* n_dev, int64_t n_max, T* partial, hipStream_t st) {
-  const int64_t nb = std::max<int64_t>((n_max + SCAN_CHUNK - 1) / SCAN_CHUNK, 1);
-  hipLaunchKernelGGL(k_scan_reduce<T>, dim3((unsigned)nb), dim3(SCAN_T), 0, st, a, n_dev, n_max, partial);
-  hipLaunchKernelGGL(k_scan_partials<T>, dim3(1), dim3(1024), 0, st, partial, nb);
-  hipLaunchKernelGGL((k_scan_apply<T, INCLUSIVE>), dim3((unsigned)nb), dim3(SCAN_T), 0, st, a, n_dev, n_max, partial);
-}
-static int64_t scan_partials(int64_t n_max) { return std::max<int64_t>((n_max + SCAN_CHUNK - 1) / SCAN_CHUNK, 1); }
+// the device-wide scans of ngm_scan.h, 2048-element chunks: fp64 areas (inclusive), int cell counts, int64 child counts
+constexpr int ME_SCAN_PER = 8;
 
 // ---- surface sampler --------------------------------------------------------------------------------------------------
 struct SurfArgs {
@@ -194,7 +109,7 @@ __global__ __launch_bounds__(256) void k_surface_sample(SurfArgs a) {
 // workspace: the areas / their scan, the scan's chunk sums
 static void surf_layout(int64_t F, double** cum, double** partial, WsArena& ws) {
   *cum = ws.take<double>(F);
-  *partial = ws.take<double>(scan_partials(F) + 1);
+  *partial = ws.take<double>(scan_partial_count<ME_SCAN_PER>(F) + 1);
 }
 int64_t ngm_surface_sample_bytes(int64_t num_faces) {
   double *cum, *partial;
@@ -210,7 +125,7 @@ int ngm_launch_surface_sample(const float* verts, int64_t V, const int64_t* face
   if (!ws.covers(workspace_bytes)) return NGM_E_WORKSPACE;
   if (N == 0) return 0;
   hipLaunchKernelGGL(k_face_area, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, st, a);
-  launch_scan<double, true>(a.cum, nullptr, F, partial, st);
+  launch_scan<double, ME_SCAN_PER, true>(a.cum, nullptr, F, partial, st);
   hipLaunchKernelGGL(k_surface_sample, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, a);
   return 0;
 }
@@ -412,7 +327,7 @@ static void np_layout(NpArgs& a, WsArena& ws) {
   a.part = ws.take<float>(6 * NP_BBOX_BLOCKS);
   a.cell_start = ws.take<int>((int64_t)a.max_cells + 1);
   a.cell_fill = ws.take<int>(a.max_cells);
-  a.scan_part = ws.take<int>(scan_partials(a.max_cells) + 1);
+  a.scan_part = ws.take<int>(scan_partial_count<ME_SCAN_PER>(a.max_cells) + 1);
   a.sorted = ws.take<float4>(a.M);
 }
 int64_t ngm_nearest_point_bytes(int64_t M, int64_t N) {
@@ -428,7 +343,7 @@ static void np_build_grid(const NpArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(k_np_header, dim3(1), dim3(256), 0, st, a);
   hipLaunchKernelGGL(k_np_clear, dim3((unsigned)std::min((a.max_cells + 256) / 256, 4096)), dim3(256), 0, st, a);
   hipLaunchKernelGGL(k_np_count, dim3(ref_blocks), dim3(256), 0, st, a);
-  launch_scan<int, false>(a.cell_start, &a.hdr->ncells, a.max_cells, a.scan_part, st);
+  launch_scan<int, ME_SCAN_PER, false>(a.cell_start, &a.hdr->ncells, a.max_cells, a.scan_part, st);
   hipLaunchKernelGGL(k_np_fill, dim3(ref_blocks), dim3(256), 0, st, a);
 }
 int ngm_launch_nearest_point(const float* refs, int64_t M, const float* queries, int64_t N, float* dist, int64_t* index, void* workspace,
@@ -634,7 +549,7 @@ static SubLayout sub_layout(int64_t F, WsArena& ws) {
   l.level = ws.take<int>(F);
   l.vscan = ws.take<int64_t>(F + 1);
   l.fscan = ws.take<int64_t>(F + 1);
-  l.partial = ws.take<int64_t>(scan_partials(F) + 1);
+  l.partial = ws.take<int64_t>(scan_partial_count<ME_SCAN_PER>(F) + 1);
   return l;
 }
 int64_t ngm_mesh_subdivide_bytes(int64_t F) { return ws_bytes(sub_layout, F); }
@@ -650,8 +565,8 @@ int ngm_launch_mesh_subdivide_count(const float* verts, int64_t V, const int64_t
   a.verts = verts; a.faces = faces; a.V = V; a.F = F; a.level = l.level; a.vscan = l.vscan; a.fscan = l.fscan; a.totals = totals;
   a.max_edge = max_edge; a.max_iter = max_iter;
   hipLaunchKernelGGL(k_sub_level, dim3((unsigned)((F + SUB_T - 1) / SUB_T)), dim3(SUB_T), 0, st, a);
-  launch_scan<int64_t, false>(l.vscan, nullptr, F, l.partial, st);
-  launch_scan<int64_t, false>(l.fscan, nullptr, F, l.partial, st);
+  launch_scan<int64_t, ME_SCAN_PER, false>(l.vscan, nullptr, F, l.partial, st);
+  launch_scan<int64_t, ME_SCAN_PER, false>(l.fscan, nullptr, F, l.partial, st);
   hipLaunchKernelGGL(k_sub_totals, dim3(1), dim3(64), 0, st, a);
   return 0;
 }

@@ -165,6 +165,20 @@ def grid_in_lds_bytes(NF):
     return ((NF + 3) & ~3) * 4 + NF * 16 + (max_cells + 1) * 4
 
 
+def grid_cells(pos, cell=1.1547005):
+    """cells of the uniform grid k_knn_grid lays over the centres (its header arithmetic in fp32; `cell`: 1.1547005 field radii,
+    the requested edge when no mask radius is given): the length of its first exclusive scan"""
+    NF, c = pos.shape[0], np.float32(cell)
+    max_cells = min(max(8 * NF, 512), 1 << 18)
+    lo, hi = pos.numpy().astype(np.float32).min(0), pos.numpy().astype(np.float32).max(0)
+    for _ in range(200):
+        n = [int(np.float32(np.float32(hi[d] - lo[d]) / c)) + 1 for d in range(3)]
+        if n[0] * n[1] * n[2] <= max_cells and (n[0] + 2) * (n[1] + 2) * (n[2] + 2) <= 4 * max_cells:
+            break
+        c = np.float32(c * np.float32(1.26))
+    return n[0] * n[1] * n[2]
+
+
 def smallest_nf_beyond(fits):
     nf = 1
     while fits(nf):
@@ -375,6 +389,7 @@ LAYOUTS = {
     "near_inline_2048": lambda: _layout(cover_lattice(2048, seed=4), 2048, 4),
     "near_kernels_2049": lambda: _layout(cover_lattice(2049, seed=5), 4096, 5),
     "global_histograms_38401": lambda: _layout(cover_lattice(nf_global_histograms(), seed=6), 4096, 6),
+    "scan_round_1025": lambda: _layout(cover_lattice(1025, seed=13, dims=(5, 5, 41)), 2048, 13),
     "clusters20": lambda: _layout(two_clusters(7), 2048, 7, near=1.5),
     "sparse50": lambda: _layout(sparse_box(8), 2048, 8, near=1.0),
     "single_field": lambda: _layout(_ONE.clone(), 512, 9, near=1.5),

@@ -99,8 +99,8 @@ def test_a_every_k_instance_on_the_exact_cover_lattice(K_):
 
 
 # ------------------------------------------------------------------------------------------------ B: every assignment path
-B_CASES = ["lds_edge_below", "grid_not_in_lds", "near_inline_2048", "near_kernels_2049", "global_histograms_38401", "clusters20",
-           "sparse50", "single_field", "identical5", "collinear40", "coplanar40"]
+B_CASES = ["lds_edge_below", "grid_not_in_lds", "near_inline_2048", "near_kernels_2049", "global_histograms_38401", "scan_round_1025",
+           "clusters20", "sparse50", "single_field", "identical5", "collinear40", "coplanar40"]
 
 
 @pytest.mark.parametrize("K_", [2, 11])
@@ -109,6 +109,8 @@ def test_b_every_assignment_path(name, K_):
     """grid_not_in_lds: 1 261 fields, the smallest map whose grid (52 NF + 4 bytes) no longer fits the 64 KB the assignment keeps
     it in (lds_edge_below: 1 260, the last that does); near_kernels_2049: candidate lists by the three device-wide kernels
     (near_inline_2048: the last map one workgroup lists); global_histograms_38401: 4 NF > 150 KB, per-pair global atomics;
+    scan_round_1025: a 5 x 5 x 41 lattice, 1 025 cells, one past a round of the one-workgroup scan of the cell counts (the other
+    maps' grids have 1 331, 2 197 and 39 304 cells, 149 to 392 past a round; the candidate lists' lengths are multiples of 8);
     clusters20 / sparse50: the coarsened grid, phase B over several rings; one field, five identical centres (every distance
     ties: the lowest indices win), 40 collinear and 40 coplanar centres: grids of one cell, one row, one plane"""
     assert Q.nf_grid_not_in_lds() == 1261 and Q.nf_global_histograms() == 38401

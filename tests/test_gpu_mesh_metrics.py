@@ -373,10 +373,11 @@ def test_guard_bands_around_outputs_and_workspaces(test_mesh):
         for n in (1, 63, 257, 5000):
             Mh.sample_surface(v, f, n, 1)
         Mh.sample_surface(*uv_sphere(1.0, n_lat=33, n_lon=63), 1000, 2)         # 4158 faces: three chunks of the scan
+        Mh.sample_surface(*uv_sphere(1.0, n_lat=32, n_lon=32), 1000, 3)         # 2048 faces: exactly one chunk, stored as vectors
         for name in ("1x1", "63x65", "64x64", "1000x1", "line", "outlier", "nonfinite_refs", "no_finite_ref", "coincident"):
             q, r = CASES[name]()
             Mh.nearest_distances(dev(np.asarray(q, np.float32)), dev(np.asarray(r, np.float32)))
-    assert len(raws) >= 3 * 5 + 3 * 9
+    assert len(raws) >= 3 * 6 + 3 * 9
 
 
 # ------------------------------------------------------------------------------------------------ dispatcher and renderer

@@ -92,9 +92,9 @@ def check_against_mirror(verts, faces, max_edge, max_iter=10, attrs=None, label=
 
 
 # ------------------------------------------------------------------------------------------------ against the closed form
-@pytest.mark.parametrize("num_faces", [1, 63, 64, 65, 5000])
+@pytest.mark.parametrize("num_faces", [1, 63, 64, 65, 2047, 2048, 2049, 5000])
 def test_against_the_mirror_face_counts_and_mixed_levels(num_faces):
-    """1, 63, 64, 65 faces; 5000: more than one chunk (2048) of the scans.  Edges from a few centimetres to most of a metre at
+    """1, 63, 64, 65 faces; 2047, 2048, 2049: one below, at and one above a chunk (2048) of the scans; 5000: more than one chunk.  Edges from a few centimetres to most of a metre at
     max_edge 0.1: levels 0 to 3 mixed in one mesh, every one of them present from 63 faces on"""
     verts, faces = SH.random_mesh(num_faces, 500 + num_faces, lo=0.03, hi=0.25)
     (v, f, parent), want = check_against_mirror(verts, faces, 0.1, label=f"F={num_faces}")

@@ -85,6 +85,8 @@ def test_thresholds_of_the_assignment_paths():
     assert Q.nf_grid_not_in_lds() == 1261              # 52 NF + 4 bytes of histogram, centres and 8 NF + 1 cell offsets > 64 KB
     assert Q.grid_in_lds_bytes(1260) == 65524 and Q.grid_in_lds_bytes(1261) > 65536
     assert Q.nf_global_histograms() == 38401           # 4 NF > 150 KB
+    # the grid's exclusive scan works in rounds of 1024 cells: one cell in the second round
+    assert Q.grid_cells(Q.LAYOUTS["scan_round_1025"]()[0]) == 1025
 
 
 @pytest.mark.parametrize("spacing", [0.5, 1.0, 1.5])
