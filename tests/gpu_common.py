@@ -94,6 +94,56 @@ def grad_close_per_field(a, b, tol=2e-3, name=""):
     assert worst < tol, (name, "per field", errs)
 
 
+def ray_close(a, b, name="", restated=None, margin=None, floor=4 * 2.0 ** -23, rays=None, cap=None):
+    """`grad_close` ray by ray.  With d_r = max |a - b| over ray r (leading dimension), s_r = max |b| over that ray and s = max
+    |b| over all compared rays, ray r is allowed  margin * E32 * s_r + floor * s:  the error E32 of the fp32 torch restatement
+    `restated` of the same operation against the same reference, times a margin, relative to THAT ray's scale -- one
+    normalisation per tensor lets a ray of large values hide a ray of small ones -- plus a floor of a few ulp of the tensor's
+    scale.  E32 is measured in the same form: the smallest E with r_r <= E s_r + (floor / margin) s on every ray, so a ray whose
+    reference cancels to nothing (a variance of 1e-19, a gradient through a transmittance of 1e-7) neither sets the bar nor
+    is held to a relative error no fp32 evaluation has there.
+    `cap` = (rtol, atol, per_tensor): the bar the suite already holds this tensor to, in that bar's own form -- rtol * s_r (per_tensor:
+    rtol * max |b| of the WHOLE tensor) + atol; a ray is allowed the smaller of the two.  margin = None: the cap alone.
+    `rays`: bool mask of the rays compared (None = all).  A ray with a NaN or an infinity in `a` has an infinite error.
+    The worst ray is the one with the largest d_r / allowance.  Recorded in MARGINS, both relative to that ray's own scale s_r
+    (absolute where s_r = 0): err = d_r / s_r, the measured error, and tol = allowance / s_r, the bar that binds on it (the
+    name says which of the two it is).  Does NOT assert: the caller asserts err < tol once every tensor of its case is
+    recorded.  -> (err, tol)"""
+    a, b = a.detach().cpu().double(), b.detach().cpu().double()
+    assert a.shape == b.shape, (name, a.shape, b.shape)
+    assert bool(torch.isfinite(b).all()), (name, "the reference is not finite")
+    whole = float(b.abs().max()) if b.numel() else 0.0
+    if rays is not None:
+        a, b = a[rays], b[rays]
+        restated = None if restated is None else restated[rays]
+    tag, err, tol = name + "[per ray", 0.0, floor
+    if b.numel():
+        N = b.shape[0]
+        d = (a - b).abs().reshape(N, -1).max(-1).values
+        d = torch.where(torch.isfinite(a).reshape(N, -1).all(-1), d, torch.full_like(d, float("inf")))     # (max() may skip a NaN)
+        s = b.abs().reshape(N, -1).max(-1).values
+        group = float(s.max())
+        derived = torch.full_like(s, float("inf"))
+        if margin is not None:
+            r = (restated.detach().cpu().double() - b).abs().reshape(N, -1).max(-1).values
+            e32 = float(torch.where(s > 0, (r - floor / margin * group).clamp_min(0.0) / s.clamp_min(1e-300), torch.zeros_like(s)).max())
+            derived = margin * e32 * s + floor * group
+            tag += f"; fp32 torch {e32:.2e} x {margin:g} + floor"
+        capped = torch.full_like(s, float("inf"))
+        if cap is not None:
+            capped = cap[0] * (torch.full_like(s, whole) if cap[2] else s) + cap[1]
+        allowed = torch.minimum(derived, capped)
+        ratio = torch.where(d > 0, d / allowed.clamp_min(1e-300), torch.zeros_like(d))
+        i = int(ratio.argmax())
+        unit = float(s[i]) if float(s[i]) > 0 else 1.0
+        err, tol = float(d[i]) / unit, float(allowed[i]) / unit
+        if err == 0.0 and tol == 0.0:                    # an all-zero reference met exactly (nothing is allowed, nothing is off)
+            tol = floor
+        tag += f"; worst ray {i} of scale {float(s[i]):.2e}: {'earlier bar' if float(capped[i]) < float(derived[i]) else 'derived bar'} binds, err / bar {float(ratio[i]):.2f}"
+    MARGINS.append(dict(test=_test_id(), name=tag + "]", err=err, tol=tol))
+    return err, tol
+
+
 def nll_branch_targets(t, pred64, scale, gen):
     """Targets that put `photometric_loss: gaussian_nll` on its NLL branch (mean colour NLL <= 2, losses.py:34-35), built from
     the oracle's fp64 prediction `pred64` of the same rays and draws: target colour = C + scale sqrt(V) z, z ~ U(-1, 1), so the

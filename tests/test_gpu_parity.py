@@ -573,12 +573,15 @@ def test_quadrature_backward_vs_oracle(mode, lead, S):
     depths = dists * 0.9
     dC, dD, dT = torch.randn(*lead, 3), torch.randn(*lead), torch.randn(*lead)
     co, go = colors.clone().requires_grad_(), geoms.clone().requires_grad_()
-    Co, Do, _, _, To, _ = O.quadrature(mode, co, go, dists, depths, 20.0)
+    outs_o = O.quadrature(mode, co, go, dists, depths, 20.0)
+    Co, Do, _, _, To, _ = outs_o
     ((Co * dC).sum() + (Do * dD).sum() + (To * dT).sum()).backward()
     rc = K.render_cfg(geometry_mode=mode, geometry_factor=20.0)
     cg, gg = colors.to(DEV).requires_grad_(), geoms.to(DEV).requires_grad_()
-    Cg, Dg, _, _, Tg, _ = ops.quadrature(rc, cg, gg, dists.to(DEV), depths.to(DEV))
-    close(Cg, Co.detach(), 1e-5, 2e-6)
+    outs_g = ops.quadrature(rc, cg, gg, dists.to(DEV), depths.to(DEV))
+    Cg, Dg, _, _, Tg, _ = outs_g
+    for a, b in zip(outs_g, outs_o):                 # colour, depth, both variances, termination probability, weights
+        close(a.detach(), b.detach(), 1e-5, 2e-6)
     ((Cg * dC.to(DEV)).sum() + (Dg * dD.to(DEV)).sum() + (Tg * dT.to(DEV)).sum()).backward()
     grad_close(cg.grad, co.grad, 1e-5, "d_colors")
     grad_close(gg.grad, go.grad, 2e-5, "d_geoms")
@@ -598,13 +601,16 @@ def test_quadrature_backward_neighbour_modes_vs_oracle(mode, lead, S):
     dC, dD, dT = torch.randn(*lead, 3), torch.randn(*lead), torch.randn(*lead)
     co, go = colors.clone().requires_grad_(), geoms.clone().requires_grad_()
     io = isds.clone().requires_grad_() if isds is not None else None
-    Co, Do, _, _, To, _ = O.quadrature(mode, co, go, dists, depths, 20.0, io)
+    outs_o = O.quadrature(mode, co, go, dists, depths, 20.0, io)
+    Co, Do, _, _, To, _ = outs_o
     ((Co * dC).sum() + (Do * dD).sum() + (To * dT).sum()).backward()
     rc = K.render_cfg(geometry_mode=mode, geometry_factor=20.0)
     cg, gg = colors.to(DEV).requires_grad_(), geoms.to(DEV).requires_grad_()
     ig = isds.to(DEV).requires_grad_() if isds is not None else None
-    Cg, Dg, _, _, Tg, _ = ops.quadrature(rc, cg, gg, dists.to(DEV), depths.to(DEV), ig)
-    close(Cg, Co.detach(), 1e-5, 2e-6)
+    outs_g = ops.quadrature(rc, cg, gg, dists.to(DEV), depths.to(DEV), ig)
+    Cg, Dg, _, _, Tg, _ = outs_g
+    for a, b in zip(outs_g, outs_o):                 # colour, depth, both variances, termination probability, weights
+        close(a.detach(), b.detach(), 1e-5, 2e-6)
     ((Cg * dC.to(DEV)).sum() + (Dg * dD.to(DEV)).sum() + (Tg * dT.to(DEV)).sum()).backward()
     grad_close(cg.grad, co.grad, 1e-5, "d_colors")
     grad_close(gg.grad, go.grad, 5e-5, "d_geoms")
