@@ -1,14 +1,17 @@
 """End-to-end smoke of the drop-in path on one MI355X: keyframe store -> training-target sampler -> fused
 training step (forward, losses, backward, sparse Adam) -> kNN-blended render -> PSNR.
 
-    python examples/fit_synthetic.py [--iters 300] [--device-iteration | --live [--grow [--cover]] [--loop-closure]] [--mesh-metrics [--cull]]
-                                     [--frame-metrics]
+    python examples/fit_synthetic.py [--iters 300] [--device-iteration | --single-view | --live [--grow [--cover]] [--loop-closure]]
+                                     [--mesh-metrics [--cull]] [--frame-metrics]
 
 A synthetic RGB-D "scan" of a textured wall with a sphere in front of it is observed from a few keyframes; fields
 on a grid in front of the cameras are trained exactly as NeuralGraphMap._optimization_iteration would
 (rm.py:1123-1221), with every tensor operation of the hot path running in the HIP kernels.
 --device-iteration trains through NeuralGraphRenderer.capture_training instead: targets drawn on the device and consumed at
 their fixed capacity, sampler + training step replayed as one captured graph per iteration (no host synchronisation).
+--single-view trains in the reference's `update_mode: single_view` through NeuralGraphRenderer.capture_training_sv: the
+keyframes form a frame stack, odd iterations draw their targets from the newest frame and even iterations from a random stored
+one (a device write into the graph's `slot` between replays), sampler + training step again one captured graph.
 --live runs the mapping loop's shape instead of a frozen scene: a new current frame every five iterations, keyframes added
 to a KeyframeStore while training, the observed fields recomputed per frame on the device -- and still ONE capture.
 --live --grow also GROWS the map while that one graph keeps replaying: the renderer reserves rows for the whole map
@@ -105,8 +108,10 @@ def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0, g
     extend_map on that keyframe's depth (the reference's _extend_global_map_dict), anchored to it; the reservation is larger,
     since the number of fields is then the scene's and the grid's business.
     loop_closure (with "live"): the fields are anchored to the keyframes; after the last keyframe all keyframe poses are
-    perturbed rigidly and the map is re-posed on the device between two replays of the one graph."""
-    if loop not in ("torch", "device", "materialize", "live"):
+    perturbed rigidly and the map is re-posed on the device between two replays of the one graph.
+    "single_view" -- capture_training_sv over the keyframes as a frame stack: odd iterations read the newest frame, even
+    iterations a random stored one (torch.randint on the device into `slot`), rm.py:1130-1149."""
+    if loop not in ("torch", "device", "materialize", "live", "single_view"):
         raise ValueError(loop)
     if (grow or loop_closure) and loop != "live":
         raise ValueError("grow and loop_closure go with the live loop")
@@ -162,6 +167,10 @@ def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0, g
 
     losses, closure = [], None
     step = r.capture_training(cur, c2ws, store, cid, 32, 256, seed=jitter_seed, camera=cam) if loop == "device" else None
+    if loop == "single_view":
+        slot = torch.zeros(1, dtype=torch.int32, device=dev)
+        slot_gen = torch.Generator(device=dev).manual_seed(0)
+        step = r.capture_training_sv(store, c2ws, cur, 32, 256, num_points=min(50000, H * W), seed=jitter_seed, camera=cam, slot=slot)
     if loop == "live":
         from neural_graph_mapping_amd.keyframes import KeyframeStore
         ks = KeyframeStore(len(eyes) + 1, H, W, device=dev)
@@ -203,6 +212,12 @@ def main(iters=300, device="cuda:0", quiet=False, loop="torch", jitter_seed=0, g
             out = step()
             assert step.graph is graph                              # one capture serves every frame and keyframe
         elif loop == "device":
+            out = step()
+        elif loop == "single_view":
+            if it % 2 == 1:
+                slot.fill_(len(eyes) - 1)                           # the newest frame
+            else:
+                slot.copy_(torch.randint(0, len(eyes), (1,), device=dev, generator=slot_gen, dtype=torch.int32))
             out = step()
         elif loop == "materialize":
             tgt = r.sample_target_mv_device(cur, c2ws, store, cid, 32, 256, camera=cam, seed=0, iteration=it).materialize()
@@ -262,6 +277,8 @@ if __name__ == "__main__":
     ap.add_argument("--iters", type=int, default=300)
     ap.add_argument("--device-iteration", action="store_true",
                     help="train through capture_training: device-drawn targets, one captured graph per iteration")
+    ap.add_argument("--single-view", action="store_true",
+                    help="train through capture_training_sv: single-view targets from a frame stack, one captured graph per iteration")
     ap.add_argument("--live", action="store_true",
                     help="one captured graph across changing frames and keyframes (KeyframeStore + observed_fields_device)")
     ap.add_argument("--grow", action="store_true",
@@ -277,7 +294,7 @@ if __name__ == "__main__":
     ap.add_argument("--frame-metrics", action="store_true",
                     help="score keyframe 0 with PSNR, SSIM and depth L1 on the device (evaluate_frame)")
     a = ap.parse_args()
-    loop = "live" if a.live else "device" if a.device_iteration else "torch"
+    loop = "live" if a.live else "device" if a.device_iteration else "single_view" if a.single_view else "torch"
     res = main(a.iters, loop=loop, grow=a.grow, loop_closure=a.loop_closure, mesh_metrics=a.mesh_metrics, cull=a.cull,
                frame_metrics=a.frame_metrics, cover=a.cover)
     if a.cover:                                                    # the two maps differ by construction: no bar, both numbers

@@ -765,6 +765,82 @@ int ngm_target_sv_rays(int32_t F, int32_t R, const float* field_pos_cam, float r
                        const int64_t* segments, const float* image, int32_t height, int32_t width, float fx, float fy, float cx,
                        float cy, const ngm_target_out* out, void* stream);
 
+/* ---- single-view training-target sampler, whole, on the device (opt-in; additive to ABI 11) -----------------------------
+ * _sample_target_sv (rm.py:1461-1583) with every draw made on the device from Philox4x32-10 (NOT torch's stream): no host
+ * synchronisation, fixed output capacity, no data-dependent shape, the number of rows left in device memory -- so a captured
+ * graph draws fresh single-view targets at every replay, and the counted step takes `out` as it takes ngm_target_sample_mv's.
+ * In the reference's order (Philox offset = iteration throughout):
+ *   1. points: num_points pixels uniformly without replacement among those with depth != 0: key_p = (word 0 of block
+ *      ctr = linear pixel p, stream 0x54470007) << 32 | p, the num_points smallest keys (the radix select of
+ *      ngm_target_observed_fields: the SET is deterministic, the order of `pixels` is not, and nothing below depends on it).
+ *      Fewer valid pixels than num_points: all of them (the reference's multinomial would raise); none: *count = 0.
+ *      Back-projection (camera.py:374-390, OpenGL): x = ((col - cx) * d) / fx, y = ((-(row - cy)) * d) / fy, z = -d; the
+ *      points' AABB is their exact min / max.
+ *   2. candidates: per entry of active_field_ids the centre in the camera frame (R^T (p - t), products summed left to
+ *      right), the sphere AABB against the points' AABB (geometry.py:26-42), then hits = the number of points whose segment
+ *      origin -> point crosses the sphere (ngm_target_sv_intersect's arithmetic; integer counts, no hit matrix in memory).
+ *      A field is a candidate when it is in the box and hits >= num_rays.  Entries < 0 or >= the field count in force are
+ *      skipped (hits 0), so a fixed-length list padded with -1 works; the other entries must be duplicate-free.
+ *   3. fields: at most T = num_train_fields candidates: all of them in the order of active_field_ids -- else the T smallest
+ *      of key_g = (word 0 of block ctr = field id g, stream 0x54470008) << 32 | g, in key order.  subset_fields = their
+ *      positions in the candidate list (0, 1, ... when no draw was needed), -1 past them.
+ *      Sharding (world_size W, rank r): every rank makes the same draw; rows are made only for drawn fields with
+ *      g % W == r, in draw order.  capacity >= min(T, num_active, #{id in [0, num_fields): id % W == r}) is required.
+ *   4. rays: per row, num_rays of the field's hit points uniformly without replacement: for the hit point at pixel p
+ *      key = (word 0 of block ctr = (g << 32 | p), stream 0x54470009) << 32 | p, the num_rays smallest, ray k = the k-th
+ *      smallest.  A row depends on (seed, iteration, frame, g) only: not on its index, the rank or the other fields.
+ *   5. targets: ngm_target_sv_rays' arithmetic per ray (near / far not clamped, rgb_mask = depth_mask = gt < far,
+ *      term_mask = 1); out->c2ws (when given) receives the frame's pose in every ray slot.
+ *   6. rows past *count: field_ids = -1, masks 0, zeros elsewhere (segments -1).
+ * Frame stack: num_slots >= 1 frames in rgbd (num_slots,H,W,4) / c2w (num_slots,4,4); the frame read is
+ * clamp(*slot_dev, 0, num_slots - 1), slot 0 when slot_dev is NULL.  num_fields_dev (or NULL): the count in force is
+ * clamp(*num_fields_dev, 0, num_fields), as in the *_grow entry points.  iteration >= 0: this iteration; < 0: *iteration_dev
+ * is read, and advanced by one by the last kernel, after every read of it.
+ * Replay of recorded draws (world_size 1): pixels_in (num_points linear pixel indices, used in the given order, entries
+ * outside [0, H*W) unused) replaces draw 1; subset_fields_in (T positions in the candidate list) replaces draw 3 when there
+ * are more than T candidates; segments_in (capacity, num_rays) indices into pixels_in replaces draw 4 (needs pixels_in).
+ * 1 <= num_points <= NGM_SV_MAX_POINTS, num_train_fields and num_rays <= NGM_TARGET_MAX_DRAW, H*W < 2^31.
+ * `hits` of a field outside the points' box is 0: its segments are not tested, as in the reference.
+ * No float atomics; bitwise repeatable from call to call.  15 launches (6 with pixels_in).
+ * Workspace: 8 bytes per pixel of the frame (the pixel keys) + 16 bytes per point + 28 bytes per active entry + the ray keys,
+ * capacity x num_points x 8 bytes -- 12.8 MB at 32 rows x 50 000 points, but 1 GiB at the largest sizes this entry point
+ * accepts (2048 rows x 65 536 points): a caller with a large num_train_fields should size num_points with that in mind and
+ * keep the workspace between calls. */
+#define NGM_SV_MAX_POINTS 65536
+typedef struct ngm_target_sample_sv_args {
+  const float* rgbd;                /* (num_slots,H,W,4) frames [r,g,b,depth]                              */
+  const float* c2w;                 /* DEVICE (num_slots,4,4) row-major camera poses, read at run time     */
+  const int32_t* slot_dev;          /* device (1) or NULL                                                  */
+  const int64_t* active_field_ids;  /* (num_active)                                                        */
+  const float* field_positions;     /* (>= num_fields, 3)                                                  */
+  const int32_t* num_fields_dev;    /* device (1) or NULL                                                  */
+  int32_t num_slots, height, width;
+  int32_t num_active, num_fields;
+  int32_t num_points, num_train_fields, num_rays, capacity;
+  int32_t world_size, rank;
+  int32_t reserved0;
+  float fx, fy, cx, cy;             /* intrinsics at pixel centre 0                                        */
+  float radius;                     /* _field_radius                                                       */
+  int32_t reserved1;
+  uint64_t seed;
+  int64_t iteration;
+  int64_t* iteration_dev;
+  const int64_t* pixels_in;         /* (num_points) or NULL                                                */
+  const int64_t* subset_fields_in;  /* (num_train_fields) or NULL                                          */
+  const int64_t* segments_in;       /* (capacity,num_rays) or NULL                                         */
+  int64_t* field_ids;               /* out (capacity)                                                      */
+  int32_t* count;                   /* out (1): rows                                                       */
+  int64_t* pixels;                  /* out (num_points): chosen linear pixel indices, -1 past *num_used    */
+  int32_t* num_used;                /* out (1): valid chosen pixels                                        */
+  int32_t* hits;                    /* out (num_active): crossing segments per entry, 0 for skipped ones   */
+  int32_t* num_candidates;          /* out (1)                                                             */
+  int64_t* subset_fields;           /* out (num_train_fields): positions in the candidate list, -1 padded  */
+  int64_t* segments;                /* out (capacity,num_rays): the chosen points as linear pixel indices  */
+} ngm_target_sample_sv_args;
+int64_t ngm_target_sample_sv_workspace(int32_t height, int32_t width, int32_t num_active, int32_t num_points, int32_t capacity);
+int ngm_target_sample_sv(const ngm_target_sample_sv_args* a, const ngm_target_out* out, void* workspace,
+                         int64_t workspace_bytes, void* stream);
+
 /* ---- mesh extraction -------------------------------------------------------------------
  * Marching cubes on a dense grid of field values: replaces the pytorch3d.ops.marching_cubes call of
  * NeuralGraphMap._extract_mesh (rm.py:2255-2298; the grid itself is filled by ngm_field_eval_knn, rm.py:2255-2261).

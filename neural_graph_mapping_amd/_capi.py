@@ -161,6 +161,44 @@ class ObservedFields(C.Structure):
                 ("num_used", C.c_void_p)]
 
 
+NGM_SV_MAX_POINTS = 65536                      # include/ngm_hip.h: points one ngm_target_sample_sv call may draw
+
+
+class TargetSampleSv(C.Structure):
+    """ngm_target_sample_sv_args"""
+    _fields_ = [("rgbd", f32p), ("c2w", f32p), ("slot_dev", C.c_void_p), ("active_field_ids", C.c_void_p),
+                ("field_positions", f32p), ("num_fields_dev", C.c_void_p), ("num_slots", C.c_int32), ("height", C.c_int32),
+                ("width", C.c_int32), ("num_active", C.c_int32), ("num_fields", C.c_int32), ("num_points", C.c_int32),
+                ("num_train_fields", C.c_int32), ("num_rays", C.c_int32), ("capacity", C.c_int32), ("world_size", C.c_int32),
+                ("rank", C.c_int32), ("reserved0", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("radius", C.c_float), ("reserved1", C.c_int32), ("seed", C.c_uint64),
+                ("iteration", C.c_int64), ("iteration_dev", C.c_void_p), ("pixels_in", C.c_void_p),
+                ("subset_fields_in", C.c_void_p), ("segments_in", C.c_void_p), ("field_ids", C.c_void_p), ("count", C.c_void_p),
+                ("pixels", C.c_void_p), ("num_used", C.c_void_p), ("hits", C.c_void_p), ("num_candidates", C.c_void_p),
+                ("subset_fields", C.c_void_p), ("segments", C.c_void_p)]
+
+
+def target_sample_sv_plan(num_active, num_fields, num_train_fields, num_rays, num_points, world_size=1, rank=0):
+    """Host-side row capacity of ngm_target_sample_sv, known before anything runs: min(T, len(active_field_ids), fields of
+    [0, num_fields) with id % world_size == rank).  Raises on bad input."""
+    for name, v in (("len(active_field_ids)", num_active), ("num_fields", num_fields), ("num_train_fields", num_train_fields),
+                    ("num_rays_per_field", num_rays), ("num_points", num_points), ("world_size", world_size), ("rank", rank)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise TypeError(f"target_sample_sv: {name} must be an int, got {type(v).__name__}")
+    if not 1 <= num_rays <= NGM_TARGET_MAX_DRAW:
+        raise ValueError(f"target_sample_sv: num_rays_per_field must be in [1, {NGM_TARGET_MAX_DRAW}], got {num_rays}")
+    if not 1 <= num_points <= NGM_SV_MAX_POINTS:
+        raise ValueError(f"target_sample_sv: num_points must be in [1, {NGM_SV_MAX_POINTS}], got {num_points}")
+    if not 0 <= num_train_fields <= NGM_TARGET_MAX_DRAW:
+        raise ValueError(f"target_sample_sv: num_train_fields must be in [0, {NGM_TARGET_MAX_DRAW}], got {num_train_fields}")
+    if num_active < 0 or num_fields < 0:
+        raise ValueError("target_sample_sv: len(active_field_ids) and num_fields must be >= 0")
+    if world_size < 1 or not 0 <= rank < world_size:
+        raise ValueError(f"target_sample_sv: need 0 <= rank < world_size, got rank={rank}, world_size={world_size}")
+    owned = (num_fields - rank + world_size - 1) // world_size if num_fields > rank else 0
+    return min(num_train_fields, num_active, owned)
+
+
 def target_sample_mv_live_plan(max_current, num_fields, num_train_fields, num_rays, world_size=1, rank=0):
     """Host-side sizes of ngm_target_sample_mv_live: (max_observed, max_random, capacity) = (min(T // 2, max_current),
     min(T, num_fields), min(min(T, num_fields), fields of this rank)): what target_sample_mv_plan gives for every count
@@ -351,6 +389,10 @@ def lib():
     L.ngm_target_observed_fields_grow_workspace.restype = i64
     L.ngm_target_observed_fields_grow.argtypes = [P(ObservedFields), vp, vp, i64, vp]
     L.ngm_target_observed_fields_grow.restype = C.c_int
+    L.ngm_target_sample_sv_workspace.argtypes = [i32, i32, i32, i32, i32]
+    L.ngm_target_sample_sv_workspace.restype = i64
+    L.ngm_target_sample_sv.argtypes = [P(TargetSampleSv), P(TargetOut), vp, i64, vp]
+    L.ngm_target_sample_sv.restype = C.c_int
     L.ngm_marching_cubes_workspace.argtypes = [i32, i32, i32]
     L.ngm_marching_cubes_workspace.restype = i64
     L.ngm_marching_cubes_count.argtypes = [vp, i32, i32, i32, f32, vp, vp, i64, vp]
@@ -423,6 +465,7 @@ EXPORTED = ["ngm_abi_version", "ngm_last_error", "ngm_device_info", "ngm_permuto
             "ngm_target_observed_fields", "ngm_field_counts_add",
             "ngm_fields_append", "ngm_fields_repose", "ngm_target_sample_mv_grow_workspace", "ngm_target_sample_mv_grow",
             "ngm_target_observed_fields_grow_workspace", "ngm_target_observed_fields_grow",
+            "ngm_target_sample_sv_workspace", "ngm_target_sample_sv",
             "ngm_render_fwd_counted", "ngm_render_bwd_counted", "ngm_render_bwd_adam_counted",
             "ngm_peer_mailbox_bytes", "ngm_peer_alloc", "ngm_peer_free", "ngm_ipc_export", "ngm_ipc_open", "ngm_ipc_close", "ngm_loss_exchange", "ngm_peer_set_timeout",
             "ngm_marching_cubes_workspace", "ngm_marching_cubes_count", "ngm_marching_cubes_emit", "ngm_marching_cubes_tables",

@@ -679,6 +679,46 @@ int ngm_target_sv_rays(int32_t F, int32_t R, const float* field_pos_cam, float r
   return check_launch("ngm_target_sv_rays");
 }
 
+// rows a rank can need: min(T, num_active, its fields among num_fields)
+static int64_t target_sample_sv_rows(const ngm_target_sample_sv_args* a) {
+  const int64_t owned = a->num_fields > a->rank ? ((int64_t)a->num_fields - a->rank + a->world_size - 1) / a->world_size : 0;
+  int64_t rows = a->num_train_fields < a->num_active ? a->num_train_fields : a->num_active;
+  return rows < owned ? rows : owned;
+}
+int64_t ngm_target_sample_sv_workspace(int32_t height, int32_t width, int32_t num_active, int32_t num_points, int32_t capacity) {
+  if (height < 1 || width < 1 || (int64_t)height * width > INT32_MAX || num_active < 0 || num_points < 1 ||
+      num_points > NGM_SV_MAX_POINTS || capacity < 0 || capacity > NGM_TARGET_MAX_DRAW)
+    return -1;
+  return ngm_target_sample_sv_bytes(height, width, num_active, num_points, capacity);
+}
+int ngm_target_sample_sv(const ngm_target_sample_sv_args* a, const ngm_target_out* out, void* workspace, int64_t workspace_bytes,
+                         void* stream) {
+  if (!a || !out) return fail(NGM_E_INVALID, "ngm_target_sample_sv: NULL argument");
+  if (a->num_slots < 1 || a->height < 1 || a->width < 1 || (int64_t)a->height * a->width > INT32_MAX || a->num_active < 0 ||
+      a->num_fields < 0 || a->num_train_fields < 0 || a->num_rays < 1 || a->capacity < 0 || a->world_size < 1 || a->rank < 0 ||
+      a->rank >= a->world_size || a->num_points < 1 || !(a->radius >= 0.f))
+    return fail(NGM_E_INVALID, "ngm_target_sample_sv: bad sizes (num_slots, H, W, num_points, num_rays >= 1, H x W < 2^31, "
+                               "0 <= rank < world_size, radius >= 0, nothing negative)");
+  if (a->num_points > NGM_SV_MAX_POINTS || a->num_train_fields > NGM_TARGET_MAX_DRAW || a->num_rays > NGM_TARGET_MAX_DRAW ||
+      a->capacity > NGM_TARGET_MAX_DRAW)
+    return fail(NGM_E_INVALID, "ngm_target_sample_sv: num_points <= NGM_SV_MAX_POINTS; num_train_fields, num_rays and capacity <= "
+                               "NGM_TARGET_MAX_DRAW");
+  if (a->capacity < target_sample_sv_rows(a))
+    return fail(NGM_E_INVALID, "ngm_target_sample_sv: capacity must be >= min(num_train_fields, num_active, fields of this rank)");
+  if ((a->segments_in && !a->pixels_in) || ((a->pixels_in || a->subset_fields_in || a->segments_in) && a->world_size != 1))
+    return fail(NGM_E_INVALID, "ngm_target_sample_sv: segments_in needs pixels_in; recorded draws are for world_size 1");
+  if (!a->rgbd || !a->c2w || (a->num_active > 0 && (!a->active_field_ids || !a->hits)) || (a->num_fields > 0 && !a->field_positions) ||
+      !a->count || !a->pixels || !a->num_used || !a->num_candidates || (a->num_train_fields > 0 && !a->subset_fields) ||
+      (a->capacity > 0 && (!a->field_ids || !a->segments)) || (a->iteration < 0 && !a->iteration_dev))
+    return fail(NGM_E_INVALID, "ngm_target_sample_sv: NULL array (iteration < 0 needs iteration_dev)");
+  if (a->capacity > 0 && (!out->ijs || !out->near || !out->far || !out->gt || !out->rgbds || !out->rgb_mask || !out->depth_mask ||
+                          !out->term_probs || !out->term_mask))
+    return fail(NGM_E_INVALID, "ngm_target_sample_sv: NULL output array");
+  if (ngm_launch_target_sample_sv(*a, *out, workspace, workspace_bytes, (hipStream_t)stream))
+    return fail(NGM_E_WORKSPACE, "ngm_target_sample_sv: workspace too small");
+  return check_launch("ngm_target_sample_sv");
+}
+
 int ngm_debug_last_bwd_variant(void) { return g_last_bwd.variant; }
 int ngm_debug_last_matmul(int which) { return (which >= 0 && which < 3) ? g_last_fwd[which].matmul : -1; }
 int ngm_debug_last_fwd_one_tile(void) { return g_last_fwd[NGM_FWD_RENDER].one_tile; }

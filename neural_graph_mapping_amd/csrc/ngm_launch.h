@@ -289,6 +289,9 @@ int ngm_launch_target_sample_mv(const ngm_keyframes& kf, const ngm_target_sample
 int64_t ngm_target_observed_fields_bytes(int height, int width);
 int ngm_launch_target_observed_fields(const ngm_observed_fields& a, void* workspace, int64_t workspace_bytes, hipStream_t st,
                                       const int32_t* num_fields_dev = nullptr);
+int64_t ngm_target_sample_sv_bytes(int height, int width, int num_active, int num_points, int capacity);
+int ngm_launch_target_sample_sv(const ngm_target_sample_sv_args& a, const ngm_target_out& o, void* workspace, int64_t workspace_bytes,
+                                hipStream_t st);
 int ngm_launch_fields_append(const ngm_fields_append_args& a, hipStream_t st);
 int ngm_launch_fields_repose(const ngm_fields_repose_args& a, hipStream_t st);
 int ngm_launch_field_counts_add(const int64_t* field_ids, const int32_t* count, int rows, int num_fields, int64_t* training_iterations,

@@ -119,6 +119,14 @@ __global__ void k_target_rays(ngm_keyframes kf, int F, int R, const float* __res
 //   geometry.LineSegments.closest_points / intersects_spheres (geometry.py:67-105) with p1 = 0: t = clamp(c.p / |p|^2, 0, 1)
 //   (|p|^2 == 0 -> 1), closest = p t, hit = |c - closest|^2 <= r^2.  One thread per (field, point); 50 000 points x up
 //   to a few hundred fields of byte output: HBM-bound.
+// the one segment-sphere test of the single-view samplers (r2 = radius * radius)
+__device__ __forceinline__ bool target_sv_hit(float cx, float cy, float cz, float px, float py, float pz, float r2) {
+  float sq = (px * px + py * py) + pz * pz;
+  if (sq == 0.0f) sq = 1.0f;
+  const float t = fminf(fmaxf(((cx * px + cy * py) + cz * pz) / sq, 0.0f), 1.0f);
+  const float ex = cx - px * t, ey = cy - py * t, ez = cz - pz * t;
+  return (ex * ex + ey * ey) + ez * ez <= r2;
+}
 __global__ void k_target_sv_intersect(int F, int64_t N, const float* __restrict__ pos_c, const float* __restrict__ points, float radius,
                                       uint8_t* __restrict__ hit) {
   const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -126,11 +134,28 @@ __global__ void k_target_sv_intersect(int F, int64_t N, const float* __restrict_
   if (n >= N) return;
   const float px = points[3 * n], py = points[3 * n + 1], pz = points[3 * n + 2];
   const float cx = pos_c[3 * f], cy = pos_c[3 * f + 1], cz = pos_c[3 * f + 2];
-  float sq = (px * px + py * py) + pz * pz;
-  if (sq == 0.0f) sq = 1.0f;
-  const float t = fminf(fmaxf(((cx * px + cy * py) + cz * pz) / sq, 0.0f), 1.0f);
-  const float ex = cx - px * t, ey = cy - py * t, ez = cz - pz * t;
-  hit[(int64_t)f * N + n] = ((ex * ex + ey * ey) + ez * ez <= radius * radius) ? 1 : 0;
+  hit[(int64_t)f * N + n] = target_sv_hit(cx, cy, cz, px, py, pz, radius * radius) ? 1 : 0;
+}
+// One ray of rm.py:1536-1561: pixel (i, j) of `image` against the field centre (pcx, pcy, pcz) in the camera frame -> output
+// row `idx` of o.  Shared by k_target_sv_rays and the device sampler's k_tssv_rows.
+__device__ __forceinline__ void target_sv_ray_one(float pcx, float pcy, float pcz, float radius, int64_t i, int64_t j,
+                                                  const float* __restrict__ image, int width, float fx, float fy, float cx, float cy,
+                                                  const ngm_target_out& o, int64_t idx) {
+  o.ijs[2 * idx] = i; o.ijs[2 * idx + 1] = j;
+  const float dx = ((float)j - cx) / fx, dy = ((float)i - cy) / fy;
+  const float nrm = fmaxf(sqrtf(dx * dx + dy * dy + 1.0f), 1e-12f);
+  const float gx = dx / nrm, gy = (-dy) / nrm, gz = -1.0f / nrm;
+  const float center = pcx * gx + pcy * gy + pcz * gz;
+  const float nearv = center - radius, farv = center + radius;
+  const float4 px = reinterpret_cast<const float4*>(image)[i * (int64_t)width + j];
+  const float gt = px.w / (1.0f / nrm);
+  const bool dm = gt < farv;
+  o.near[idx] = nearv; o.far[idx] = farv; o.gt[idx] = gt;
+  reinterpret_cast<float4*>(o.rgbds)[idx] = px;
+  o.rgb_mask[idx] = dm ? 1 : 0;
+  o.depth_mask[idx] = dm ? 1 : 0;
+  o.term_probs[idx] = dm ? 1.0f : 0.0f;
+  o.term_mask[idx] = 1;
 }
 // k_target_sv_rays: per sampled segment: pixel, direction, near / far from the field sphere (NOT clamped at 0 here,
 // rm.py:1543-1544), RGB-D target, ray distance of the depth, masks (rm.py:1536-1561)
@@ -142,21 +167,7 @@ __global__ void k_target_sv_rays(int F, int R, const float* __restrict__ pos_c, 
   const int f = (int)(idx / R);
   const int64_t sgm = segments[idx];
   const int64_t i = pts_ijs[2 * sgm], j = pts_ijs[2 * sgm + 1];
-  o.ijs[2 * idx] = i; o.ijs[2 * idx + 1] = j;
-  const float dx = ((float)j - cx) / fx, dy = ((float)i - cy) / fy;
-  const float nrm = fmaxf(sqrtf(dx * dx + dy * dy + 1.0f), 1e-12f);
-  const float gx = dx / nrm, gy = (-dy) / nrm, gz = -1.0f / nrm;
-  const float center = pos_c[3 * f] * gx + pos_c[3 * f + 1] * gy + pos_c[3 * f + 2] * gz;
-  const float nearv = center - radius, farv = center + radius;
-  const float4 px = reinterpret_cast<const float4*>(image)[i * (int64_t)width + j];
-  const float gt = px.w / (1.0f / nrm);
-  const bool dm = gt < farv;
-  o.near[idx] = nearv; o.far[idx] = farv; o.gt[idx] = gt;
-  reinterpret_cast<float4*>(o.rgbds)[idx] = px;
-  o.rgb_mask[idx] = dm ? 1 : 0;
-  o.depth_mask[idx] = dm ? 1 : 0;
-  o.term_probs[idx] = dm ? 1.0f : 0.0f;
-  o.term_mask[idx] = 1;
+  target_sv_ray_one(pos_c[3 * f], pos_c[3 * f + 1], pos_c[3 * f + 2], radius, i, j, image, width, fx, fy, cx, cy, o, idx);
   (void)height;
 }
 int ngm_launch_target_sv_intersect(int F, int64_t N, const float* pos_c, const float* points, float radius, uint8_t* hit, hipStream_t st) {
@@ -616,17 +627,42 @@ static obs_ws obs_layout(int64_t pixels, WsArena& ws) {
   return t;
 }
 
-__global__ __launch_bounds__(OBS_THREADS) void k_obs_keys(ngm_observed_fields a, obs_ws w) {
-  const int64_t n = (int64_t)a.height * a.width;
+// What the pixel draw needs (k_obs_keys / k_obs_hist / k_obs_collect): shared by ngm_target_observed_fields and the
+// single-view sampler, which differ in the stream id and in where the frame lies (a slot of a frame stack there).
+struct obs_sel {
+  const float* rgbd;            // (num_slots, n, 4)
+  const int32_t* slot_dev;      // device, or NULL: slot 0
+  int num_slots;
+  int64_t n;                    // H x W
+  int num_points;
+  uint32_t stream;
+  uint64_t seed;
+  int64_t frame;                // >= 0, or < 0: *frame_dev
+  const int64_t* frame_dev;
+  const int64_t* subset_in;
+  int64_t* pixels;
+};
+__device__ __forceinline__ const float* obs_frame(const obs_sel& a) {
+  if (!a.slot_dev) return a.rgbd;
+  return a.rgbd + (int64_t)min(max(*a.slot_dev, 0), a.num_slots - 1) * a.n * 4;
+}
+static obs_sel obs_sel_of(const ngm_observed_fields& a) {
+  return obs_sel{a.rgbd, nullptr, 1, (int64_t)a.height * a.width, a.num_points, TSMV_STREAM_PIXELS, a.seed, a.frame, a.frame_dev, a.subset_in,
+                 a.pixels};
+}
+
+__global__ __launch_bounds__(OBS_THREADS) void k_obs_keys(obs_sel a, obs_ws w) {
+  const int64_t n = a.n;
   const int64_t gid = (int64_t)blockIdx.x * OBS_THREADS + threadIdx.x, gsz = (int64_t)gridDim.x * OBS_THREADS;
   if (gid < OBS_PASSES * 256) w.hist[gid] = 0;            // the grid has at least OBS_PASSES workgroups (see the launch)
   if (gid < 4) w.counters[gid] = 0;
-  const uint64_t frame = (uint64_t)(a.frame >= 0 ? a.frame : *a.frame_dev);     // advanced by k_obs_fields, after every read
+  const uint64_t frame = (uint64_t)(a.frame >= 0 ? a.frame : *a.frame_dev);     // advanced by a later launch, after every read
+  const float* rgbd = obs_frame(a);
   for (int64_t i = gid; i < n; i += gsz) {
     uint64_t key = TSMV_EXCLUDED;
-    if (a.rgbd[4 * i + 3] != 0.0f) {
+    if (rgbd[4 * i + 3] != 0.0f) {
       uint32_t q[4];
-      philox_block(a.seed, frame, (uint64_t)i, TSMV_STREAM_PIXELS, q);
+      philox_block(a.seed, frame, (uint64_t)i, a.stream, q);
       key = ((uint64_t)q[0] << 32) | (uint32_t)i;
     }
     w.keys[i] = key;
@@ -665,7 +701,7 @@ __device__ __forceinline__ obs_state obs_state_block(const obs_ws& w, int passes
   return *sst;
 }
 
-__global__ __launch_bounds__(OBS_THREADS) void k_obs_hist(ngm_observed_fields a, obs_ws w, int pass) {
+__global__ __launch_bounds__(OBS_THREADS) void k_obs_hist(obs_sel a, obs_ws w, int pass) {
   __shared__ int sh[OBS_PASSES * 256];
   __shared__ int local[256];
   __shared__ obs_state sst;
@@ -674,7 +710,7 @@ __global__ __launch_bounds__(OBS_THREADS) void k_obs_hist(ngm_observed_fields a,
   const int shift = s.shift - 8;                          // this pass' digit
   local[threadIdx.x] = 0;                                 // OBS_THREADS == 256
   __syncthreads();
-  const int64_t n = (int64_t)a.height * a.width, gsz = (int64_t)gridDim.x * OBS_THREADS;
+  const int64_t n = a.n, gsz = (int64_t)gridDim.x * OBS_THREADS;
   for (int64_t i = (int64_t)blockIdx.x * OBS_THREADS + threadIdx.x; i < n; i += gsz) {
     const uint64_t key = w.keys[i];
     if (key == TSMV_EXCLUDED || (pass > 0 && (key >> (shift + 8)) != s.prefix)) continue;
@@ -685,11 +721,11 @@ __global__ __launch_bounds__(OBS_THREADS) void k_obs_hist(ngm_observed_fields a,
   if (v) atomicAdd(&w.hist[256 * pass + threadIdx.x], v);
 }
 
-__global__ __launch_bounds__(OBS_THREADS) void k_obs_collect(ngm_observed_fields a, obs_ws w) {
+__global__ __launch_bounds__(OBS_THREADS) void k_obs_collect(obs_sel a, obs_ws w) {
   __shared__ int sh[OBS_PASSES * 256];
   __shared__ obs_state sst;
   const int64_t gid = (int64_t)blockIdx.x * OBS_THREADS + threadIdx.x, gsz = (int64_t)gridDim.x * OBS_THREADS;
-  const int64_t n = (int64_t)a.height * a.width;
+  const int64_t n = a.n;
   if (a.subset_in) {                                      // recorded draws: out-of-range entries become -1 (unused)
     for (int64_t i = gid; i < a.num_points; i += gsz) {
       const int64_t p = a.subset_in[i];
@@ -812,13 +848,9 @@ __global__ __launch_bounds__(OBS_FIELD_THREADS) void k_obs_fields(ngm_observed_f
   }
 }
 
-int64_t ngm_target_observed_fields_bytes(int height, int width) { return ws_bytes(obs_layout, (int64_t)height * width); }
-int ngm_launch_target_observed_fields(const ngm_observed_fields& a, void* workspace, int64_t workspace_bytes, hipStream_t st,
-                                      const int32_t* num_fields_dev) {
-  WsArena ws(workspace);
-  const obs_ws w = obs_layout((int64_t)a.height * a.width, ws);
-  if (!workspace || !ws.covers(workspace_bytes)) return NGM_E_WORKSPACE;
-  const int64_t n = (int64_t)a.height * a.width;
+// the pixel draw: keys + 8 histogram passes + collect, or with subset_in the copy alone
+static void obs_launch_select(const obs_sel& a, const obs_ws& w, hipStream_t st) {
+  const int64_t n = a.n;
   int blocks = (int)((n + OBS_THREADS - 1) / OBS_THREADS);
   blocks = blocks < OBS_PASSES ? OBS_PASSES : blocks > OBS_MAX_BLOCKS ? OBS_MAX_BLOCKS : blocks;
   if (!a.subset_in) {
@@ -827,7 +859,398 @@ int ngm_launch_target_observed_fields(const ngm_observed_fields& a, void* worksp
   }
   hipLaunchKernelGGL(k_obs_collect, dim3(a.subset_in ? (a.num_points + OBS_THREADS - 1) / OBS_THREADS : blocks), dim3(OBS_THREADS), 0, st,
                      a, w);
+}
+
+int64_t ngm_target_observed_fields_bytes(int height, int width) { return ws_bytes(obs_layout, (int64_t)height * width); }
+int ngm_launch_target_observed_fields(const ngm_observed_fields& a, void* workspace, int64_t workspace_bytes, hipStream_t st,
+                                      const int32_t* num_fields_dev) {
+  WsArena ws(workspace);
+  const obs_ws w = obs_layout((int64_t)a.height * a.width, ws);
+  if (!workspace || !ws.covers(workspace_bytes)) return NGM_E_WORKSPACE;
+  obs_launch_select(obs_sel_of(a), w, st);
   hipLaunchKernelGGL(k_obs_fields, dim3(1), dim3(OBS_FIELD_THREADS), 0, st, a, w, num_fields_dev);
+  return 0;
+}
+
+// ---- the single-view sampler, whole, on the device (ngm_target_sample_sv, include/ngm_hip.h) ------------------------------
+// No host synchronisation, no hit matrix in memory:
+//   k_obs_keys / k_obs_hist x 8 / k_obs_collect  the pixel draw (stream ..07), or the copy of pixels_in
+//   k_tssv_points  one thread per chosen pixel: back-projection into the workspace, min / max / valid count per workgroup
+//                  (partials, reduced by their readers: no float atomics); zeroes `hits`; keeps the iteration for the others
+//   k_tssv_box     one workgroup, once per call: the box and the valid count from the partials; camera-frame centre and box test
+//                  per active field, the fields in the box compacted into the workspace (ballot + prefix)
+//   k_tssv_count   one lane per point; the fields in the box pass through LDS in tiles of 256 and every wave tests them
+//                  against its 64 points: ballot + popcount into an LDS count, then one integer atomic per (workgroup, field)
+//   k_tssv_draw    one workgroup: candidates in the order of active_field_ids (ballot + prefix), the field draw
+//                  (tsmv_k_smallest over the candidates' keys, positions recovered by binary search), the owner filter
+//   k_tssv_rows    one workgroup per row: re-tests the row's field against the points, forms the ray keys in the workspace,
+//                  tsmv_k_smallest for the num_rays smallest, then target_sv_ray_one per ray; rows past the count are padding;
+//                  advances the iteration counter (every read of it was in an earlier launch)
+// tsmv_k_smallest ends in an O(k^2) rank sort: at num_rays = 512 each of the 512 threads reads 512 keys from LDS (the same
+// address across a wave: broadcasts), about as much as one pass over 50 000 keys costs; rows run side by side on their CUs.
+constexpr uint32_t TSSV_STREAM_PIXELS = 0x54470007u, TSSV_STREAM_FIELDS = 0x54470008u, TSSV_STREAM_RAYS = 0x54470009u;
+constexpr int TSSV_PT_THREADS = 256, TSSV_DRAW_THREADS = 1024, TSSV_ROW_THREADS = 512;
+
+struct __align__(16) tssv_pt { float x, y, z; int pix; };        // pix < 0: unused slot
+struct __align__(16) tssv_part { float mn[3], mx[3]; int count, pad; };
+struct __align__(16) tssv_box { float lo[3], hi[3]; int have, n_in; };   // have: valid points; n_in: entries of `inbox`
+struct __align__(16) tssv_in { float x, y, z; int k; };          // k: position in active_field_ids
+
+struct tssv_ws {
+  obs_ws sel;
+  int64_t* hdr;        // [0] iteration of this call
+  tssv_pt* pts;        // num_points
+  tssv_part* part;     // one per workgroup of k_tssv_points
+  tssv_box* box;       // 1: the points' AABB, the valid points, the fields in the box
+  tssv_in* inbox;      // num_active: camera-frame centres of the fields in the box
+  int* cand;          // num_active: candidate -> position in active_field_ids
+  uint64_t* fkeys;     // num_active: field keys by candidate
+  uint64_t* rkeys;     // capacity x num_points: ray keys
+};
+static int tssv_pt_blocks(int num_points) { return (num_points + TSSV_PT_THREADS - 1) / TSSV_PT_THREADS; }
+static tssv_ws tssv_layout(int64_t pixels, int num_active, int num_points, int capacity, WsArena& ws) {
+  tssv_ws t;
+  t.sel = obs_layout(pixels, ws);
+  t.hdr = ws.take<int64_t>(2);
+  t.pts = ws.take<tssv_pt>(num_points);
+  t.part = ws.take<tssv_part>(tssv_pt_blocks(num_points));
+  t.box = ws.take<tssv_box>(1);
+  t.inbox = ws.take<tssv_in>(num_active);
+  t.cand = ws.take<int>(num_active);
+  t.fkeys = ws.take<uint64_t>(num_active);
+  t.rkeys = ws.take<uint64_t>((int64_t)capacity * num_points);
+  return t;
+}
+
+__device__ __forceinline__ int tssv_slot(const ngm_target_sample_sv_args& a) {
+  return a.slot_dev ? min(max(*a.slot_dev, 0), a.num_slots - 1) : 0;
+}
+
+__global__ __launch_bounds__(TSSV_PT_THREADS) void k_tssv_points(ngm_target_sample_sv_args a, tssv_ws w) {
+  __shared__ float wmin[3 * (TSSV_PT_THREADS / 64)], wmax[3 * (TSSV_PT_THREADS / 64)];
+  __shared__ int wcnt[TSSV_PT_THREADS / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int i = blockIdx.x * TSSV_PT_THREADS + tid;
+  const int64_t n = (int64_t)a.height * a.width;
+  if (blockIdx.x == 0 && tid == 0) w.hdr[0] = a.iteration >= 0 ? a.iteration : *a.iteration_dev;
+  for (int k = i; k < a.num_active; k += gridDim.x * TSSV_PT_THREADS) a.hits[k] = 0;
+  const int used = a.pixels_in ? a.num_points : min(w.sel.counters[0], a.num_points);
+  const float* rgbd = a.rgbd + (int64_t)tssv_slot(a) * n * 4;
+  float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+  bool ok = false;
+  if (i < a.num_points) {
+    int64_t p = -1;
+    if (i < used) p = a.pixels[i];
+    else a.pixels[i] = -1;                                 // slots past the chosen pixels (never with pixels_in)
+    ok = p >= 0 && p < n;
+    tssv_pt pt = {0.f, 0.f, 0.f, -1};
+    if (ok) {                                              // camera.py:374-390, OpenGL: k_obs_fields' arithmetic
+      const int r = (int)(p / a.width), c = (int)(p - (int64_t)r * a.width);
+      const float d = rgbd[4 * p + 3];
+      pt.x = (((float)c - a.cx) * d) / a.fx;
+      pt.y = ((-((float)r - a.cy)) * d) / a.fy;
+      pt.z = -d;
+      pt.pix = (int)p;
+      mn[0] = mx[0] = pt.x; mn[1] = mx[1] = pt.y; mn[2] = mx[2] = pt.z;
+    }
+    w.pts[i] = pt;
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    for (int o = 32; o > 0; o >>= 1) {
+      mn[k] = fminf(mn[k], __shfl_xor(mn[k], o));
+      mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], o));
+    }
+    if (lane == 0) { wmin[3 * wv + k] = mn[k]; wmax[3 * wv + k] = mx[k]; }
+  }
+  const uint64_t bal = __ballot(ok);
+  if (lane == 0) wcnt[wv] = __popcll(bal);
+  __syncthreads();
+  if (tid == 0) {
+    tssv_part q;
+    q.count = 0; q.pad = 0;
+    for (int k = 0; k < 3; ++k) { q.mn[k] = INFINITY; q.mx[k] = -INFINITY; }
+    for (int v = 0; v < TSSV_PT_THREADS / 64; ++v) {
+      q.count += wcnt[v];
+      for (int k = 0; k < 3; ++k) { q.mn[k] = fminf(q.mn[k], wmin[3 * v + k]); q.mx[k] = fmaxf(q.mx[k], wmax[3 * v + k]); }
+    }
+    w.part[blockIdx.x] = q;
+  }
+}
+
+// once per call: the points' box and count from the partials, and the active fields that are in force and in the box, with their
+// camera-frame centres, compacted in the order of active_field_ids (ballot + prefix)
+__global__ __launch_bounds__(TSSV_DRAW_THREADS) void k_tssv_box(ngm_target_sample_sv_args a, tssv_ws w, int pt_blocks) {
+  __shared__ float red[6][TSSV_DRAW_THREADS / 64];
+  __shared__ int redc[TSSV_DRAW_THREADS / 64], wave_cnt[TSSV_DRAW_THREADS / 64];
+  __shared__ float box[6];
+  __shared__ int s_have;
+  constexpr int NW = TSSV_DRAW_THREADS / 64;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+  int cnt = 0;
+  for (int b = tid; b < pt_blocks; b += TSSV_DRAW_THREADS) {       // exact min / max: the order of the partials does not matter
+    const tssv_part q = w.part[b];
+    cnt += q.count;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { mn[k] = fminf(mn[k], q.mn[k]); mx[k] = fmaxf(mx[k], q.mx[k]); }
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    for (int o = 32; o > 0; o >>= 1) {
+      mn[k] = fminf(mn[k], __shfl_xor(mn[k], o));
+      mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], o));
+    }
+    if (lane == 0) { red[k][wv] = mn[k]; red[3 + k][wv] = mx[k]; }
+  }
+  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+  if (lane == 0) redc[wv] = cnt;
+  __syncthreads();
+  if (tid < 6) {
+    float v = red[tid][0];
+    for (int q = 1; q < NW; ++q) v = tid < 3 ? fminf(v, red[tid][q]) : fmaxf(v, red[tid][q]);
+    box[tid] = v;
+  }
+  if (tid == 6) {
+    int have = 0;
+    for (int q = 0; q < NW; ++q) have += redc[q];
+    s_have = have;
+  }
+  __syncthreads();
+  const int have = s_have;
+  const float* T = a.c2w + 16 * (int64_t)tssv_slot(a);
+  const float r = a.radius;
+  const int nf = a.num_fields_dev ? min(max(*a.num_fields_dev, 0), a.num_fields) : a.num_fields;      // block-uniform
+  int base = 0;
+  for (int k0 = 0; k0 < a.num_active && have > 0; k0 += TSSV_DRAW_THREADS) {
+    const int k = k0 + tid;
+    bool in_box = false;
+    Cam3 c = {0.f, 0.f, 0.f};
+    if (k < a.num_active) {
+      const int64_t id = a.active_field_ids[k];
+      if (id >= 0 && id < nf) {
+        c = world_to_cam(T, a.field_positions[3 * id], a.field_positions[3 * id + 1], a.field_positions[3 * id + 2]);
+        in_box = c.x - r <= box[3] && c.y - r <= box[4] && c.z - r <= box[5] && c.x + r >= box[0] && c.y + r >= box[1] &&
+                 c.z + r >= box[2];
+      }
+    }
+    const uint64_t bal = __ballot(in_box);
+    if (lane == 0) wave_cnt[wv] = __popcll(bal);
+    __syncthreads();
+    int off = base, tot = 0;
+    for (int q = 0; q < NW; ++q) {
+      off += q < wv ? wave_cnt[q] : 0;
+      tot += wave_cnt[q];
+    }
+    if (in_box) w.inbox[off + __popcll(bal & ((1ull << lane) - 1ull))] = tssv_in{c.x, c.y, c.z, k};
+    base += tot;
+    __syncthreads();
+  }
+  if (tid == 0) {
+    tssv_box q;
+    for (int k = 0; k < 3; ++k) { q.lo[k] = box[k]; q.hi[k] = box[3 + k]; }
+    q.have = have; q.n_in = base;
+    *w.box = q;
+    *a.num_used = have;
+  }
+}
+
+__global__ __launch_bounds__(TSSV_PT_THREADS) void k_tssv_count(ngm_target_sample_sv_args a, tssv_ws w) {
+  __shared__ float tx[TSSV_PT_THREADS], ty[TSSV_PT_THREADS], tz[TSSV_PT_THREADS];
+  __shared__ int tk[TSSV_PT_THREADS], tc[TSSV_PT_THREADS];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int n_in = min(max(w.box->n_in, 0), a.num_active);          // block-uniform; 0 without valid points
+  if (n_in == 0) return;                                  // `hits` is all zero already
+  const int i = blockIdx.x * TSSV_PT_THREADS + tid;
+  tssv_pt pt = {0.f, 0.f, 0.f, -1};
+  if (i < a.num_points) pt = w.pts[i];
+  const bool valid = pt.pix >= 0;
+  const float r2 = a.radius * a.radius;
+  for (int q0 = 0; q0 < n_in; q0 += TSSV_PT_THREADS) {
+    const int nt = min(TSSV_PT_THREADS, n_in - q0);
+    if (tid < nt) {
+      const tssv_in f = w.inbox[q0 + tid];
+      tx[tid] = f.x; ty[tid] = f.y; tz[tid] = f.z; tk[tid] = f.k;
+    }
+    tc[tid] = 0;
+    __syncthreads();
+    for (int q = 0; q < nt; ++q) {
+      const bool h = valid && target_sv_hit(tx[q], ty[q], tz[q], pt.x, pt.y, pt.z, r2);
+      const uint64_t bal = __ballot(h);
+      if (lane == 0 && bal) atomicAdd(&tc[q], __popcll(bal));           // LDS; one global atomic per (workgroup, field) below
+    }
+    __syncthreads();
+    if (tid < nt && tc[tid]) atomicAdd(&a.hits[tk[tid]], tc[tid]);
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(TSSV_DRAW_THREADS) void k_tssv_draw(ngm_target_sample_sv_args a, tssv_ws w) {
+  __shared__ uint64_t sel[NGM_TARGET_MAX_DRAW], scratch[NGM_TARGET_MAX_DRAW];
+  __shared__ int drawn[NGM_TARGET_MAX_DRAW];
+  __shared__ int hist[256], st[4], wave_cnt[TSSV_DRAW_THREADS / 64];
+  __shared__ int s_rows;
+  constexpr int NW = TSSV_DRAW_THREADS / 64;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const uint64_t it = (uint64_t)w.hdr[0];
+  const int A = a.num_active, T = a.num_train_fields, R = a.num_rays;
+  // 1. candidates in the order of active_field_ids (hits are counted only for fields in force and in the box)
+  int base = 0;
+  for (int k0 = 0; k0 < A; k0 += TSSV_DRAW_THREADS) {
+    const int k = k0 + tid;
+    const bool is_c = k < A && a.hits[k] >= R;
+    const uint64_t bal = __ballot(is_c);
+    if (lane == 0) wave_cnt[wv] = __popcll(bal);
+    __syncthreads();
+    int off = base, tot = 0;
+    for (int q = 0; q < NW; ++q) {
+      off += q < wv ? wave_cnt[q] : 0;
+      tot += wave_cnt[q];
+    }
+    if (is_c) w.cand[off + __popcll(bal & ((1ull << lane) - 1ull))] = k;
+    base += tot;
+    __syncthreads();
+  }
+  const int nc = base, n_draw = min(nc, T);
+  if (tid == 0) *a.num_candidates = nc;
+  for (int i = tid; i < T; i += TSSV_DRAW_THREADS) {
+    drawn[i] = -1;
+    a.subset_fields[i] = -1;
+  }
+  __syncthreads();
+  // 2. the fields: all candidates, the recorded positions, or the T smallest keys in key order
+  if (nc <= T) {
+    for (int i = tid; i < nc; i += TSSV_DRAW_THREADS) { drawn[i] = w.cand[i]; a.subset_fields[i] = i; }
+  } else if (a.subset_fields_in) {
+    for (int i = tid; i < T; i += TSSV_DRAW_THREADS) {
+      const int64_t c = a.subset_fields_in[i];
+      if (c >= 0 && c < nc) { drawn[i] = w.cand[c]; a.subset_fields[i] = c; }
+    }
+  } else {
+    for (int c = tid; c < nc; c += TSSV_DRAW_THREADS) {
+      const uint64_t g = (uint64_t)a.active_field_ids[w.cand[c]];
+      uint32_t q[4];
+      philox_block(a.seed, it, g, TSSV_STREAM_FIELDS, q);
+      w.fkeys[c] = ((uint64_t)q[0] << 32) | (uint32_t)g;
+    }
+    __syncthreads();
+    tsmv_k_smallest(w.fkeys, nc, T, sel, scratch, hist, st);
+    for (int c = tid; c < nc; c += TSSV_DRAW_THREADS) {   // the rank of candidate c among the chosen keys, if it is one
+      const uint64_t key = w.fkeys[c];
+      int lo = 0, hi = T;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (sel[mid] < key) lo = mid + 1; else hi = mid;
+      }
+      if (lo < T && sel[lo] == key) { drawn[lo] = w.cand[c]; a.subset_fields[lo] = c; }
+    }
+  }
+  __syncthreads();
+  // 3. owner filter, draw order kept
+  if (tid == 0) {
+    int n = 0;
+    for (int i = 0; i < n_draw; ++i) {
+      if (drawn[i] < 0) continue;
+      const int64_t g = a.active_field_ids[drawn[i]];
+      if (g % a.world_size == a.rank && n < a.capacity) a.field_ids[n++] = g;
+    }
+    s_rows = n;
+    *a.count = n;
+    if (a.capacity == 0 && a.iteration < 0) *a.iteration_dev = (int64_t)it + 1;      // no k_tssv_rows launch then
+  }
+  __syncthreads();
+  for (int i = s_rows + tid; i < a.capacity; i += TSSV_DRAW_THREADS) a.field_ids[i] = -1;
+}
+
+__device__ __forceinline__ void tssv_zero_ray(const ngm_target_out& o, int64_t idx) {
+  if (o.c2ws) {
+    float4* dst = reinterpret_cast<float4*>(o.c2ws + 16 * idx);
+    dst[0] = dst[1] = dst[2] = dst[3] = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  o.ijs[2 * idx] = 0; o.ijs[2 * idx + 1] = 0;
+  o.near[idx] = 0.f; o.far[idx] = 0.f; o.gt[idx] = 0.f;
+  reinterpret_cast<float4*>(o.rgbds)[idx] = make_float4(0.f, 0.f, 0.f, 0.f);
+  o.rgb_mask[idx] = 0; o.depth_mask[idx] = 0; o.term_probs[idx] = 0.f; o.term_mask[idx] = 0;
+}
+
+__global__ __launch_bounds__(TSSV_ROW_THREADS) void k_tssv_rows(ngm_target_sample_sv_args a, ngm_target_out o, tssv_ws w) {
+  __shared__ uint64_t sel[NGM_TARGET_MAX_DRAW], scratch[NGM_TARGET_MAX_DRAW];
+  __shared__ int hist[256], st[4];
+  const int row = blockIdx.x, tid = threadIdx.x, R = a.num_rays;
+  const uint64_t it = (uint64_t)w.hdr[0];
+  const int cnt = min(max(*a.count, 0), a.capacity);
+  if (row == 0 && tid == 0 && a.iteration < 0) *a.iteration_dev = (int64_t)it + 1;
+  if (row >= cnt) {                                       // block-uniform
+    for (int k = tid; k < R; k += TSSV_ROW_THREADS) {
+      tssv_zero_ray(o, (int64_t)row * R + k);
+      a.segments[(int64_t)row * R + k] = -1;
+    }
+    return;
+  }
+  const int64_t n = (int64_t)a.height * a.width;
+  const int slot = tssv_slot(a);
+  const float* T = a.c2w + 16 * (int64_t)slot;
+  const float* image = a.rgbd + (int64_t)slot * n * 4;
+  const int64_t g = a.field_ids[row];
+  const Cam3 c = world_to_cam(T, a.field_positions[3 * g], a.field_positions[3 * g + 1], a.field_positions[3 * g + 2]);
+  if (!a.segments_in) {
+    const float r2 = a.radius * a.radius;
+    uint64_t* keys = w.rkeys + (int64_t)row * a.num_points;
+    for (int i = tid; i < a.num_points; i += TSSV_ROW_THREADS) {
+      const tssv_pt pt = w.pts[i];
+      uint64_t key = TSMV_EXCLUDED;
+      if (pt.pix >= 0 && target_sv_hit(c.x, c.y, c.z, pt.x, pt.y, pt.z, r2)) {
+        uint32_t q[4];
+        philox_block(a.seed, it, ((uint64_t)g << 32) | (uint32_t)pt.pix, TSSV_STREAM_RAYS, q);
+        key = ((uint64_t)q[0] << 32) | (uint32_t)pt.pix;
+      }
+      keys[i] = key;
+    }
+    __syncthreads();
+    tsmv_k_smallest(keys, a.num_points, R, sel, scratch, hist, st);
+  }
+  for (int k = tid; k < R; k += TSSV_ROW_THREADS) {
+    const int64_t idx = (int64_t)row * R + k;
+    int64_t p = -1;
+    if (a.segments_in) {
+      const int64_t s = a.segments_in[idx];
+      if (s >= 0 && s < a.num_points) p = w.pts[s].pix;
+    } else {
+      p = (int64_t)(sel[k] & 0xFFFFFFFFull);
+    }
+    if (p < 0 || p >= n) {                                // a recorded draw that names an unused point
+      tssv_zero_ray(o, idx);
+      a.segments[idx] = -1;
+      continue;
+    }
+    a.segments[idx] = p;
+    if (o.c2ws) {
+      float4* dst = reinterpret_cast<float4*>(o.c2ws + 16 * idx);
+      const float4* src = reinterpret_cast<const float4*>(T);
+      dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2]; dst[3] = src[3];
+    }
+    const int64_t i = p / a.width, j = p - i * a.width;
+    target_sv_ray_one(c.x, c.y, c.z, a.radius, i, j, image, a.width, a.fx, a.fy, a.cx, a.cy, o, idx);
+  }
+}
+
+int64_t ngm_target_sample_sv_bytes(int height, int width, int num_active, int num_points, int capacity) {
+  return ws_bytes(tssv_layout, (int64_t)height * width, num_active, num_points, capacity);
+}
+int ngm_launch_target_sample_sv(const ngm_target_sample_sv_args& a, const ngm_target_out& o, void* workspace, int64_t workspace_bytes,
+                                hipStream_t st) {
+  WsArena ws(workspace);
+  const int64_t n = (int64_t)a.height * a.width;
+  const tssv_ws w = tssv_layout(n, a.num_active, a.num_points, a.capacity, ws);
+  if (!workspace || !ws.covers(workspace_bytes)) return NGM_E_WORKSPACE;
+  obs_launch_select(obs_sel{a.rgbd, a.slot_dev, a.num_slots, n, a.num_points, TSSV_STREAM_PIXELS, a.seed, a.iteration, a.iteration_dev,
+                            a.pixels_in, a.pixels}, w.sel, st);
+  const int pb = tssv_pt_blocks(a.num_points);
+  hipLaunchKernelGGL(k_tssv_points, dim3(pb), dim3(TSSV_PT_THREADS), 0, st, a, w);
+  hipLaunchKernelGGL(k_tssv_box, dim3(1), dim3(TSSV_DRAW_THREADS), 0, st, a, w, pb);
+  if (a.num_active > 0) hipLaunchKernelGGL(k_tssv_count, dim3(pb), dim3(TSSV_PT_THREADS), 0, st, a, w);
+  hipLaunchKernelGGL(k_tssv_draw, dim3(1), dim3(TSSV_DRAW_THREADS), 0, st, a, w);
+  if (a.capacity > 0) hipLaunchKernelGGL(k_tssv_rows, dim3(a.capacity), dim3(TSSV_ROW_THREADS), 0, st, a, o, w);
   return 0;
 }
 

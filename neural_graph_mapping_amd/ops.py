@@ -1388,6 +1388,122 @@ def target_observed_fields(rgbd, c2w, field_positions, fx, fy, cx, cy, radius, n
     return dict(current_field_ids=ids_out, current_count=count_out, pixels=pixels, num_used=used)
 
 
+# ------------------------------------------------------------------------------------------------
+# single-view training-target sampler, whole, on the device (include/ngm_hip.h ngm_target_sample_sv)
+# ------------------------------------------------------------------------------------------------
+TARGET_SAMPLE_SV_OUT = ("ijs", "c2ws", "near", "far", "gt", "field_ids", "rgbds", "rgb_mask", "depth_mask", "term_probs",
+                        "term_mask", "count", "pixels", "num_used", "hits", "num_candidates", "subset_fields", "segments")
+
+
+def _target_sample_sv_empty(device, num_active, capacity, num_train_fields, num_rays, num_points):
+    """the unwritten outputs of torch.ops.ngm355.target_sample_sv in TARGET_SAMPLE_SV_OUT order -- all a fake implementation
+    returns"""
+    f32, i64, i32, b = torch.float32, torch.int64, torch.int32, torch.bool
+    cap, R = capacity, num_rays
+    shapes = [((cap, R, 2), i64), ((cap, R, 4, 4), f32), ((cap, R), f32), ((cap, R), f32), ((cap, R), f32), ((cap,), i64),
+              ((cap, R, 4), f32), ((cap, R), b), ((cap, R), b), ((cap, R), f32), ((cap, R), b), ((1,), i32),
+              ((num_points,), i64), ((1,), i32), ((num_active,), i32), ((1,), i32), ((num_train_fields,), i64), ((cap, R), i64)]
+    return [torch.empty(shape, dtype=dt, device=device) for shape, dt in shapes]
+
+
+@_op("target_sample_sv", mutates_args=("iteration_dev",))
+def _target_sample_sv_op(rgbd: torch.Tensor, c2w: torch.Tensor, slot: Optional[torch.Tensor], active_field_ids: torch.Tensor,
+                         field_positions: torch.Tensor, num_fields_dev: Optional[torch.Tensor],
+                         iteration_dev: Optional[torch.Tensor], pixels_in: Optional[torch.Tensor],
+                         subset_fields_in: Optional[torch.Tensor], segments_in: Optional[torch.Tensor], intrinsics: List[float],
+                         radius: float, num_fields: int, num_points: int, num_train_fields: int, num_rays: int, capacity: int,
+                         seed: int, iteration: int, world_size: int, rank: int) -> List[torch.Tensor]:
+    """TARGET_SAMPLE_SV_OUT, every per-row array at `capacity` (rows past count: padding); rgbd (S,H,W,4), c2w (S,4,4)"""
+    dev = rgbd.device
+    S, H, W = rgbd.shape[0], rgbd.shape[1], rgbd.shape[2]
+    A = active_field_ids.shape[0]
+    outs = _target_sample_sv_empty(dev, A, capacity, num_train_fields, num_rays, num_points)
+    o = dict(zip(TARGET_SAMPLE_SV_OUT, outs))
+    ws_bytes = K.lib().ngm_target_sample_sv_workspace(H, W, A, num_points, capacity)
+    if ws_bytes < 0:
+        raise K.NgmError("ngm_target_sample_sv_workspace: bad sizes")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    a = K.TargetSampleSv()
+    a.rgbd, a.c2w = C.cast(rgbd.data_ptr(), K.f32p), C.cast(c2w.data_ptr(), K.f32p)
+    a.field_positions = C.cast(field_positions.data_ptr(), K.f32p)
+    a.slot_dev, a.active_field_ids, a.num_fields_dev = _ptr(slot), _ptr(active_field_ids), _ptr(num_fields_dev)
+    a.num_slots, a.height, a.width, a.num_active, a.num_fields = S, H, W, A, num_fields
+    a.num_points, a.num_train_fields, a.num_rays, a.capacity = num_points, num_train_fields, num_rays, capacity
+    a.world_size, a.rank = world_size, rank
+    a.fx, a.fy, a.cx, a.cy = intrinsics
+    a.radius, a.seed, a.iteration, a.iteration_dev = float(radius), int(seed), int(iteration), _ptr(iteration_dev)
+    a.pixels_in, a.subset_fields_in, a.segments_in = _ptr(pixels_in), _ptr(subset_fields_in), _ptr(segments_in)
+    for k in ("field_ids", "count", "pixels", "num_used", "hits", "num_candidates", "subset_fields", "segments"):
+        setattr(a, k, o[k].data_ptr())
+    out = K.TargetOut()
+    for k in ("ijs", "c2ws", "near", "far", "gt", "rgbds", "rgb_mask", "depth_mask", "term_probs", "term_mask"):
+        setattr(out, k, o[k].data_ptr())
+    K.check(K.lib().ngm_target_sample_sv(C.byref(a), C.byref(out), _ptr(ws), ws_bytes, _stream()), "ngm_target_sample_sv")
+    return outs
+
+
+@_target_sample_sv_op.register_fake
+def _(rgbd, c2w, slot, active_field_ids, field_positions, num_fields_dev, iteration_dev, pixels_in, subset_fields_in, segments_in,
+      intrinsics, radius, num_fields, num_points, num_train_fields, num_rays, capacity, seed, iteration, world_size, rank):
+    return _target_sample_sv_empty(rgbd.device, active_field_ids.shape[0], capacity, num_train_fields, num_rays, num_points)
+
+
+def target_sample_sv(rgbd, c2w, active_field_ids, field_positions, fx, fy, cx, cy, radius, num_fields, num_train_fields,
+                     num_rays_per_field, num_points=50000, seed=0, iteration=None, iteration_dev=None, world_size=1, rank=0,
+                     slot=None, num_fields_dev=None, capacity=None, pixels_in=None, subset_fields_in=None, segments_in=None):
+    """_sample_target_sv (rm.py:1461-1583) with the draws on the device, no host synchronisation, fixed shapes
+    (torch.ops.ngm355.target_sample_sv; include/ngm_hip.h ngm_target_sample_sv is the contract).  rgbd (H, W, 4) with c2w
+    (4, 4), or a frame stack (S, H, W, 4) / (S, 4, 4) with slot = a one-element int32 device tensor naming the frame read.
+    active_field_ids (A,) int64, duplicate-free; entries < 0 or past the field count are skipped.  iteration=None:
+    iteration_dev (one-element int64 device tensor) is read and advanced by one inside the call.  num_fields_dev: the count in
+    force is read on the device (reserved rows; num_fields is the capacity then).  capacity: rows of the outputs, at least
+    (and by default) K.target_sample_sv_plan(...).  pixels_in / subset_fields_in / segments_in replay recorded draws
+    (world_size 1).  Returns a dict keyed by TARGET_SAMPLE_SV_OUT; `count` (int32, device) rows are valid."""
+    def need(cond, msg, exc=ValueError):
+        if not cond:
+            raise exc("target_sample_sv: " + msg)
+    for name, t, dt in (("rgbd", rgbd, torch.float32), ("c2w", c2w, torch.float32), ("field_positions", field_positions, torch.float32),
+                        ("active_field_ids", active_field_ids, torch.int64)):
+        need(isinstance(t, torch.Tensor), f"{name} must be a tensor", TypeError)
+        need(t.dtype == dt, f"{name} must be {dt}, got {t.dtype}", TypeError)
+        need(t.is_contiguous(), f"{name} must be contiguous")
+    if rgbd.dim() == 3:
+        need(slot is None, "slot needs a frame stack: rgbd (S, H, W, 4) and c2w (S, 4, 4)")
+        rgbd, c2w = rgbd[None], c2w[None]
+    need(rgbd.dim() == 4 and rgbd.shape[3] == 4 and min(rgbd.shape[:3]) >= 1, f"rgbd must be ([S,] H, W, 4), got {tuple(rgbd.shape)}")
+    need(tuple(c2w.shape) == (rgbd.shape[0], 4, 4), f"c2w must be ({rgbd.shape[0]}, 4, 4) for this rgbd, got {tuple(c2w.shape)}")
+    need(active_field_ids.dim() == 1, f"active_field_ids must be 1-D, got shape {tuple(active_field_ids.shape)}")
+    num_fields, T, R, num_points = int(num_fields), int(num_train_fields), int(num_rays_per_field), int(num_points)
+    need(field_positions.dim() == 2 and field_positions.shape[1] == 3 and field_positions.shape[0] >= num_fields,
+         f"field_positions must be (>= num_fields = {num_fields}, 3), got {tuple(field_positions.shape)}")
+    rows = K.target_sample_sv_plan(active_field_ids.shape[0], num_fields, T, R, num_points, int(world_size), int(rank))
+    capacity = rows if capacity is None else int(capacity)
+    need(rows <= capacity <= K.NGM_TARGET_MAX_DRAW, f"capacity must be in [{rows}, {K.NGM_TARGET_MAX_DRAW}], got {capacity}")
+    for name, t in (("slot", slot), ("num_fields_dev", num_fields_dev)):
+        if t is not None:
+            _check_device_count("target_sample_sv", name, t)
+    if iteration_dev is not None:
+        need(isinstance(iteration_dev, torch.Tensor) and iteration_dev.dtype == torch.int64 and iteration_dev.numel() == 1,
+             "iteration_dev must be a one-element int64 tensor", TypeError)
+    need(iteration is not None or iteration_dev is not None, "iteration=None needs iteration_dev (the device counter)")
+    need(iteration is None or int(iteration) >= 0, f"iteration must be >= 0, got {iteration}")
+    need(0 <= int(seed) < 2 ** 63, f"seed must be in [0, 2^63), got {seed}")
+    for name, t, shape in (("pixels_in", pixels_in, (num_points,)), ("subset_fields_in", subset_fields_in, (T,)),
+                           ("segments_in", segments_in, (capacity, R))):
+        if t is not None:
+            need(isinstance(t, torch.Tensor) and t.dtype == torch.int64, f"{name} must be an int64 tensor", TypeError)
+            need(tuple(t.shape) == shape and t.is_contiguous(), f"{name} must be a contiguous {shape} tensor, got {tuple(t.shape)}")
+            need(int(world_size) == 1, "recorded draws are for world_size 1")
+    need(segments_in is None or pixels_in is not None, "segments_in indexes pixels_in: give both")
+    _require_gpu(rgbd, c2w, active_field_ids, field_positions, slot, num_fields_dev, iteration_dev, pixels_in, subset_fields_in,
+                 segments_in)
+    outs = torch.ops.ngm355.target_sample_sv(rgbd, c2w, slot, active_field_ids, field_positions, num_fields_dev, iteration_dev,
+                                             pixels_in, subset_fields_in, segments_in, [float(fx), float(fy), float(cx), float(cy)],
+                                             float(radius), num_fields, num_points, T, R, capacity, int(seed),
+                                             -1 if iteration is None else int(iteration), int(world_size), int(rank))
+    return dict(zip(TARGET_SAMPLE_SV_OUT, outs))
+
+
 def field_counts_add(field_ids, count, training_iterations, num_fields):
     """training_iterations[field_ids[i]] += 1 for i < count (device int32, or None: every row), skipping -1: one launch
     (ngm_field_counts_add), no synchronisation."""

@@ -75,6 +75,42 @@ class LiveDeviceTarget(DeviceTarget):
         return d
 
 
+class SvDeviceTarget(DeviceTarget):
+    """The DeviceTarget of sample_target_sv_device (ngm_target_sample_sv): the multi-view draw fields (subset_observed,
+    subset_random, offsets, frame_cids, u_xy) are None; the single-view draws are attributes, all device tensors at fixed
+    shapes: pixels (num_points,) linear pixel indices with -1 past num_used (1,), hits (A,) crossing segments per entry of
+    active_field_ids, num_candidates (1,), subset_fields (T,) positions in the candidate list with -1 past them, segments
+    (capacity, R) the rays' points as linear pixel indices (-1 in padding rows)."""
+
+    def __new__(cls, o: dict, world_size: int, rgbd, slot, num_train_fields: int):
+        self = super().__new__(cls, o["ijs"], o["c2ws"], o["near"], o["far"], o["gt"], o["field_ids"], o["rgbds"], o["rgb_mask"],
+                               o["depth_mask"], o["term_probs"], o["term_mask"], o["count"], None, None, None, None, None,
+                               int(world_size))
+        for k in ("pixels", "num_used", "hits", "num_candidates", "subset_fields", "segments"):
+            setattr(self, k, o[k])
+        self._rgbd, self._slot, self._num_train_fields = rgbd, slot, int(num_train_fields)
+        return self
+
+    def draws(self) -> dict:
+        """The draws in the conventions of sample_target_sv(draws=...): subset_points = indices into torch.nonzero(depth),
+        subset_fields = positions in the candidate list, segments = indices into the point list; replaying them there
+        reproduces this target.  Reads the frame as it is NOW (and synchronises).  Single process only."""
+        if self.world_size != 1:
+            raise ValueError("DeviceTarget.draws(): a sharded target holds only its own rank's fields")
+        img = self._rgbd
+        if img.dim() == 4:
+            img = img[0 if self._slot is None else min(max(int(self._slot.item()), 0), img.shape[0] - 1)]
+        n = int(self.count.item())
+        pixels = self.pixels[self.pixels >= 0]                 # after a replay unused entries (-1) may lie between used ones
+        valid = torch.nonzero(img[..., 3].reshape(-1)).squeeze(1)              # ascending = the row order of torch.nonzero(depth)
+        where = torch.full((img.shape[0] * img.shape[1],), -1, dtype=torch.int64, device=pixels.device)
+        where[pixels] = torch.arange(pixels.shape[0], device=pixels.device)
+        seg = self.segments[:n]
+        seg = torch.where(seg >= 0, where[seg.clamp_min(0)], seg)              # -1: a recorded draw that named an unused point
+        return dict(subset_points=torch.searchsorted(valid, pixels), segments=seg,
+                    subset_fields=self.subset_fields[:min(int(self.num_candidates.item()), self._num_train_fields)])
+
+
 class Camera:
     """Pinhole intrinsics with the reference's pixel-centre convention (camera.py:15-116)."""
 
@@ -1148,6 +1184,86 @@ class NeuralGraphRenderer:
                       field_ids=ids, rgbds=o["rgbds"], rgb_mask=o["rgb_mask"], depth_mask=o["depth_mask"],
                       term_probs=o["term_probs"], term_mask=o["term_mask"])
 
+    def sample_target_sv_device(self, rgbd, c2w, active_field_ids, num_train_fields, num_rays_per_field, num_points: int = 50000,
+                                seed: int = 0, iteration: Optional[int] = None, world_size: int = 1, rank: int = 0,
+                                camera: Optional[Camera] = None, slot: Optional[torch.Tensor] = None,
+                                draws: Optional[dict] = None) -> DeviceTarget:
+        """sample_target_sv with every draw made on the device (ngm_target_sample_sv: no host synchronisation, no
+        data-dependent shape, no hit matrix in memory), so it can be captured in a graph.  Same distribution as the
+        reference's sampler, NOT the same random numbers: Philox4x32-10 keyed by (seed, iteration) -- the points by pixel,
+        the fields by field id, the rays of field g by (g, pixel) -- so a row depends on (seed, iteration, frame, g) only.
+        rgbd (H, W, 4) with c2w (4, 4), or a frame stack (S, H, W, 4) / (S, 4, 4) with slot (one-element int32 device tensor):
+        the frame clamp(slot, 0, S - 1) is read, so a captured graph changes frames by a 4-byte device write.
+        active_field_ids (A,) int64, duplicate-free; entries < 0 or past the number of fields are skipped (a fixed-length
+        buffer padded with -1 works).  iteration=None: the renderer's device iteration counter is read and advanced by the
+        call (call once outside a capture first); an int uses that iteration and leaves the counter alone.
+        world_size / rank: every rank makes the same draw; rows are made only for drawn fields with id % world_size == rank.
+        With reserved rows (reserve_fields) the reserved positions are read and the number of fields comes from the device.
+        draws=dict(pixels=, subset_fields=, segments=): recorded draws instead (pixels: num_points linear pixel indices in
+        order; subset_fields: T positions in the candidate list, used when there are more than T candidates; segments:
+        (rows, R) indices into pixels); any of them may be missing, segments needs pixels.
+        Returns an SvDeviceTarget with min(T, A, fields of this rank) rows, `count` of them valid."""
+        cam = camera or self._camera
+        dev = self._device
+        counter = None
+        if iteration is None:
+            if self._target_iter_dev is None:
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("sample_target_sv_device: call it once outside the graph capture first (or pass "
+                                       "iteration=...): the device iteration counter must exist before the capture")
+                self._target_iter_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+            counter = self._target_iter_dev
+        act = active_field_ids if active_field_ids.device == torch.device(dev) else active_field_ids.to(dev)
+        if act.dtype != torch.int64:
+            act = act.long()
+        rs = self._reserved
+        positions = self._global_map_dict["positions"].contiguous() if rs is None else rs["positions"]
+        num_fields = int(self._global_map_dict["num"] if rs is None else rs["max"])
+        T, R = int(num_train_fields), int(num_rays_per_field)
+        d = {k: (None if v is None else v.to(dev).long().contiguous()) for k, v in (draws or {}).items()}
+        capacity = K.target_sample_sv_plan(act.shape[0], num_fields, T, R, int(num_points), int(world_size), int(rank))
+        seg = d.get("segments")
+        if seg is not None and seg.shape[0] < capacity:                   # recorded rows: the fields that survived
+            seg = torch.cat([seg, seg.new_zeros(capacity - seg.shape[0], seg.shape[1])])
+        fx, fy, cx, cy, _ = cam.get_pinhole_camera_parameters(0.0)
+        o = ops.target_sample_sv(rgbd, c2w, act.contiguous(), positions, fx, fy, cx, cy, self._field_radius + 0.0, num_fields, T, R,
+                                 num_points=num_points, seed=seed, iteration=iteration, iteration_dev=counter,
+                                 world_size=world_size, rank=rank, slot=slot,
+                                 num_fields_dev=None if rs is None else rs["num_fields_dev"], capacity=capacity,
+                                 pixels_in=d.get("pixels"), subset_fields_in=d.get("subset_fields"), segments_in=seg)
+        return SvDeviceTarget(o, world_size, rgbd, slot, T)
+
+    def capture_training_sv(self, rgbd, c2w, active_field_ids, num_train_fields, num_rays_per_field, num_points: int = 50000,
+                            seed=0, camera: Optional[Camera] = None, world_size: int = 1, rank: int = 0, *,
+                            slot: Optional[torch.Tensor] = None):
+        """capture_training for `update_mode: single_view`: sample_target_sv_device(iteration=None) followed by the counted
+        optimization_iteration on its target, as ONE captured graph.  Returns a callable like capture_training's (`.target`,
+        `.graph`).  rgbd, c2w, active_field_ids and slot are READ IN PLACE at every replay: write a new frame into the
+        stack, rewrite `slot` or the (fixed-length, -1 padded) active_field_ids between replays freely; their shapes and
+        storage, the number of fields and the stacked parameters must stay (the same host check, the same "capture again"
+        error) -- or, after reserve_fields, the reservation, and add_fields between replays is legal."""
+        why = self.counted_step_unsupported()
+        if why is not None:
+            raise RuntimeError(f"capture_training_sv: {why} is outside the counted step (optimization_iteration would fall "
+                               "back to DeviceTarget.materialize(), which synchronises)")
+        named = dict(rgbd=rgbd, c2w=c2w, active_field_ids=active_field_ids)
+        if slot is not None:
+            named["slot"] = slot
+        for n, t in named.items():
+            if not t.is_cuda or not t.is_contiguous():
+                raise ValueError(f"capture_training_sv: {n} must be a contiguous device tensor (it is read in place at every replay)")
+        if active_field_ids.dtype != torch.int64:
+            raise TypeError("capture_training_sv: active_field_ids must be int64")
+        if slot is not None and slot.dtype != torch.int32:
+            raise TypeError("capture_training_sv: slot must be int32")
+
+        def sample():
+            return self.sample_target_sv_device(rgbd, c2w, active_field_ids, num_train_fields, num_rays_per_field,
+                                                num_points=num_points, seed=seed, iteration=None, world_size=world_size, rank=rank,
+                                                camera=camera, slot=slot)
+        return self._capture_sampled("capture_training_sv", named, sample, self._reserved is not None,
+                                     self._global_map_dict["num"], seed)
+
     # -- eval path: render_image / PSNR (rm.py:402-437, 1966-2000; evaluation.py:46-56) ----------
     def eval_num_samples(self) -> int:
         """rm.py:199-207: derived from the training sample spacing unless configured."""
@@ -1662,6 +1778,18 @@ class NeuralGraphRenderer:
         num_fields = self._global_map_dict["num"]
         grow = self._reserved is not None and current_count is not None      # the graph reads num_fields_dev
 
+        def sample():
+            return self.sample_target_mv_device(current_field_ids, c_c2w, nc_rgbd, frame_cid_to_ncid, num_train_fields,
+                                                num_rays_per_field, num_fields=None if grow else num_fields, camera=camera, seed=seed,
+                                                iteration=None, world_size=world_size, rank=rank, current_count=current_count,
+                                                num_frames=num_frames)
+        return self._capture_sampled("capture_training", named, sample, grow, num_fields, seed)
+
+    def _capture_sampled(self, caller: str, named: dict, sample, grow: bool, num_fields: int, seed):
+        """What capture_training and capture_training_sv share: `sample()` (a device sampler with iteration=None, returning a
+        DeviceTarget) + the counted step as one graph through _capture, the warm-up that leaves the iteration counter where
+        it was, and the replay check over `named` (the caller's inputs, read in place), the field poses, the stacked
+        parameters and -- grow -- the reservation."""
         def watched():
             ts = dict(named, positions=self._global_map_dict["positions"], orientations=self._global_map_dict["orientations"])
             ts.update({"param " + n: v for n, v in self._model.all_fields_params.items()})
@@ -1687,13 +1815,8 @@ class NeuralGraphRenderer:
             return seen
         for n in ("positions", "orientations"):
             if not self._global_map_dict[n].is_contiguous():
-                raise ValueError(f"capture_training: the field {n} must be contiguous (read in place at every replay)")
+                raise ValueError(f"{caller}: the field {n} must be contiguous (read in place at every replay)")
 
-        def sample():
-            return self.sample_target_mv_device(current_field_ids, c_c2w, nc_rgbd, frame_cid_to_ncid, num_train_fields,
-                                                num_rays_per_field, num_fields=None if grow else num_fields, camera=camera, seed=seed,
-                                                iteration=None, world_size=world_size, rank=rank, current_count=current_count,
-                                                num_frames=num_frames)
         if self.track_training_iterations:
             self._training_iterations()                       # must exist before the capture
         # once outside the capture, on a side stream: creates the device counters, the workspace and the gradient buffers
@@ -1703,7 +1826,7 @@ class NeuralGraphRenderer:
             it0 = None if self._target_iter_dev is None else self._target_iter_dev.clone()
             probe = sample()
             if probe.ijs.shape[0] == 0:
-                raise ValueError("capture_training: this rank's capacity is 0 (it owns none of the fields that can be drawn: "
+                raise ValueError(f"{caller}: this rank's capacity is 0 (it owns none of the fields that can be drawn: "
                                  "fewer fields than ranks); there is no step to capture -- call optimization_iteration, "
                                  "which runs the idle iteration for such a rank")
             self.optimization_iteration(probe, seed=seed, update=False)
@@ -1720,7 +1843,7 @@ class NeuralGraphRenderer:
         def forward():
             step.target = sample()
             return self._iteration_forward(step.target, None, None, seed, advance=True, count=step.target.count)
-        run = self._capture("capture_training", step, forward)
+        run = self._capture(caller, step, forward)
         if run.graph is None:
             run.target = None
             return run
@@ -1730,7 +1853,7 @@ class NeuralGraphRenderer:
             now = watched()
             if now != seen or (not grow and self._global_map_dict["num"] != num_fields):
                 changed = sorted(n for n in now if now[n] != seen.get(n)) or ["number of fields"]
-                raise RuntimeError(f"capture_training: {changed} changed shape or storage since the capture; the graph "
+                raise RuntimeError(f"{caller}: {changed} changed shape or storage since the capture; the graph "
                                    "reads the captured addresses -- capture again")
             return run()
         replay.graph, replay.target = run.graph, step.target
